@@ -117,7 +117,7 @@ trace_shade_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
             if (lane == 0) {
                 l_ctl[0] = (uint32_t)__popcll(hit_mask);
                 if (!ok) l_ctl[1] = 1u;
-                l_ctl[2] = (kOneSurfaceSampleMajor && one_surface) ? 1u : 0u;
+                l_ctl[2] = one_surface ? 1u : 0u;
             }
             if (COUNT) t_ph1 += wall_clock64() - t_mark;
         }
@@ -273,7 +273,7 @@ __global__ void __launch_bounds__(64) primary_kernel(DeviceScene S, TileSpec ts,
     chunk_base = __builtin_amdgcn_readfirstlane(chunk_base);
     const uint32_t first_idx = __builtin_amdgcn_readfirstlane(hit_mask ? __shfl(pr.best_idx, __ffsll((long long)hit_mask) - 1) : 0u);
     const bool one_surface = ballot(hit && pr.best_idx != first_idx) == 0ull;
-    uint32_t flags = (kOneSurfaceSampleMajor && one_surface) ? 1u : 0u;
+    uint32_t flags = one_surface ? 1u : 0u;
     if (!ok) {   // a hard primary direction: the whole tile goes to the reference re-render
         flags |= 2u;
         if (lane == 0) {

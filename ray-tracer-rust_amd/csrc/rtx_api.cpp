@@ -36,7 +36,7 @@ thread_local int g_last_hip_error = 0;
 struct DeviceState {
     std::mutex mu;
     bool uploaded = false;
-    void *nodes = nullptr, *primary_nodes = nullptr, *wide = nullptr, *ref_nodes = nullptr, *tris = nullptr, *shade = nullptr, *samples = nullptr, *lights = nullptr, *thr = nullptr, *planes = nullptr, *light_boxes = nullptr;
+    void *nodes = nullptr, *primary_nodes = nullptr, *ref_nodes = nullptr, *tris = nullptr, *shade = nullptr, *samples = nullptr, *lights = nullptr, *thr = nullptr, *planes = nullptr, *light_boxes = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint8_t *d_out = nullptr;
@@ -130,20 +130,13 @@ int upload_all(RtxScene *scene, DeviceState &st)
 {
     const rtx::PreparedScene &p = scene->prep;
     int rc;
-    const float inflate = RTX_CULL_INFLATED ? p.cull_delta : 0.0f;
+    const float inflate = p.cull_delta;   // the culling planes move outwards: rtx_traverse.hpp, box_mask
     if ((rc = upload_vec(&st.nodes, rtx::nodes_in_device_order(p.nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
     if (!p.primary_nodes.empty() &&
         (rc = upload_vec(&st.primary_nodes, rtx::nodes_in_device_order(p.primary_nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
-    if (!p.wide.empty()) {   // A/B builds only (scene_prep.h: kBuildWideTree); boxes moved outwards like the binary stream's
-        std::vector<rtx::WideNode> w = p.wide;
-        for (rtx::WideNode &n : w)
-            for (int c = 0; c < 4; ++c)
-                for (int a = 0; a < 3; ++a) { n.box[c][a] -= inflate; n.box[c][3 + a] += inflate; }
-        if ((rc = upload_vec(&st.wide, w)) != RTX_OK) return rc;
-    }
     if (!p.ref_nodes.empty() &&
         (rc = upload_vec(&st.ref_nodes, rtx::nodes_in_device_order(p.ref_nodes), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
-    // one record of zeros behind the primitive records: a leaf's loop touches the record after the one it tests (load_tri_at)
+    // one spare record of zeros behind the primitive records (no walk requests the record after the one it tests any more)
     if ((rc = upload_vec(&st.tris, p.tris, sizeof(rtx::TriRec))) != RTX_OK) return rc;
     if ((rc = upload_vec(&st.shade, p.shade)) != RTX_OK) return rc;
     if ((rc = upload_vec(&st.samples, p.samples)) != RTX_OK) return rc;
@@ -165,7 +158,7 @@ int upload_all(RtxScene *scene, DeviceState &st)
 // what upload_all allocated so far goes back when it fails half way (the caller may retry: nothing may leak)
 void release_uploads(DeviceState &st)
 {
-    void **bufs[] = {&st.nodes, &st.primary_nodes, &st.wide, &st.ref_nodes, &st.tris, &st.shade, &st.samples, &st.lights, &st.thr, &st.planes, &st.light_boxes,
+    void **bufs[] = {&st.nodes, &st.primary_nodes, &st.ref_nodes, &st.tris, &st.shade, &st.samples, &st.lights, &st.thr, &st.planes, &st.light_boxes,
                      reinterpret_cast<void **>(&st.d_counters)};
     for (void **b : bufs) {
         if (*b) (void)hipFree(*b);
@@ -194,8 +187,8 @@ rtx::DeviceScene device_scene(const RtxScene *scene, const DeviceState &st)
     rtx::DeviceScene S;
     S.nodes = static_cast<const rtx::NodeRec *>(st.nodes);
     S.primary_nodes = static_cast<const rtx::NodeRec *>(st.primary_nodes ? st.primary_nodes : st.nodes);
-    S.wide = static_cast<const rtx::WideNode *>(st.wide);
-    S.n_wide = static_cast<uint32_t>(p.wide.size());
+    S.wide = nullptr;
+    S.n_wide = 0u;
     S.ref_nodes = static_cast<const rtx::NodeRec *>(st.ref_nodes);
     S.n_ref_nodes = static_cast<uint32_t>(p.ref_nodes.size());
     S.tris = static_cast<const rtx::TriRec *>(st.tris);
@@ -398,7 +391,7 @@ void rtx_scene_destroy(RtxScene *scene)
         DeviceGuard g(kv.first);
         if (g.status() != hipSuccess) continue;
         if (st.stream) (void)hipStreamSynchronize(st.stream);
-        void *bufs[] = {st.nodes, st.primary_nodes, st.wide, st.ref_nodes, st.tris, st.shade, st.samples, st.lights, st.thr, st.planes, st.light_boxes, st.d_out, st.d_counters, st.d_redo,
+        void *bufs[] = {st.nodes, st.primary_nodes, st.ref_nodes, st.tris, st.shade, st.samples, st.lights, st.thr, st.planes, st.light_boxes, st.d_out, st.d_counters, st.d_redo,
                         st.ws.hits, st.ws.pix_slot, st.ws.tiles, st.ws.chunks, st.ws.results, st.ws.acc, st.ws.ctr, st.ws.buckets, st.ws.cut};
         for (void *b : bufs) if (b) (void)hipFree(b);
         if (st.h_stage) (void)hipHostFree(st.h_stage);

@@ -7,20 +7,18 @@
 
 #include "scene_prep.h"
 
-// The library's node stream is uploaded with its planes moved outwards by PreparedScene::cull_delta and the
-// multiply-based box test then needs no widening of its own (rtx_traverse.hpp: box_mask); 0 = exact boxes + widening.
-#ifndef RTX_CULL_INFLATED
-#define RTX_CULL_INFLATED 1
-#endif
-
 namespace rtx {
 
 // Everything the kernel reads, resident in HBM for the life of the upload.
 // Passed by value (kernarg segment -> SGPRs).
 struct DeviceScene {
+    // (the node streams are uploaded with their planes moved outwards by PreparedScene::cull_delta: the multiply-based box
+    //  test then needs no widening of its own, rtx_traverse.hpp: box_mask)
     const NodeRec  *nodes;         // (n_nodes + 1) x 32 B, pre-order with skip links; last = zeroed sentinel
     const NodeRec  *primary_nodes; // the same tree, the same size, nearest-to-the-eye child first: the primary rays' stream (= nodes when there is none)
-    const WideNode *wide;          // A/B builds only (scene_prep.h: kBuildWideTree), else NULL: n_wide x 128 B, the tree with four children per node
+    const void     *wide;          // unused (NULL), as is n_wide below: the four-child tree's slots.  They stay because the
+                                   // kernels' register allocation depends on the argument layout (without them the SGPR
+                                   // spill counts of probe_kernel and shade_tiles_kernel move by up to 12 either way)
     const NodeRec  *ref_nodes;     // (n_ref_nodes + 1) x 32 B: the reference's own tree, or NULL
     const TriRec   *tris;          // n_tris x 64 B, leaf order
     const ShadeRec *shade;         // n_tris x 32 B, caller order
@@ -69,9 +67,9 @@ struct HitRec {          // 48 B
     float p[3], n[3], rgb[3], pad[3];
 };
 static_assert(sizeof(TileDesc) == 16 && sizeof(HitRec) == 48, "stream record sizes");
-// One entry of a tile's cut: the record range [begin, end) of the node stream that holds a subtree (wide build: begin =
-// byte offset of a wide node), and a copy of the subtree's ROOT record — a chunk tests the roots of its tile's cut out
-// of LDS and fetches from the stream only below a root it passes.
+// One entry of a tile's cut: the record range [begin, end) of the node stream that holds a subtree, and a copy of the
+// subtree's ROOT record — a chunk tests the roots of its tile's cut out of LDS and fetches from the stream only below a
+// root it passes.
 struct CutEntry {
     uint32_t begin, end;
     NodeDev  root;
@@ -91,7 +89,7 @@ struct StreamWorkspace {
     float    *acc;       // tiles x 64 x 3 running sums, only when nb_ray > 1
     uint32_t *ctr;       // hit count, chunk count, chunk cursor
     uint32_t *buckets;   // probe pipeline: tile order by cost class (layout: order_tiles_kernel)
-    CutEntry *cut;       // tiles x kMaxCut entries (A/B forms; the whole-stream form keeps two words of answers in a tile's
+    CutEntry *cut;       // tiles x kMaxCut entries (read by the ablation library; the whole-stream form keeps two words of answers in a tile's
                          // first entry), then — cut_stream_offset — tiles x kCutStreamRecords node records: the tiles' cuts
                          // as streams; written by probe_kernel, walked by shade_tiles_kernel
 };
@@ -108,10 +106,7 @@ __host__ __device__ inline size_t cut_stream_offset(size_t tiles)      // bytes 
     return (tiles * kMaxCut * sizeof(CutEntry) + 63u) & ~static_cast<size_t>(63u);
 }
 struct StreamWorkspaceBytes { size_t hits, pix_slot, tiles, chunks, results, acc, ctr, buckets, cut; };
-// 1: the kernels walk the four-child form of the tree (rtx_traverse.hpp: walk_wide) instead of the binary stream.  Same
-// bytes, measured slower on every configuration: kept as a build switch for A/B runs only.
-// (RTX_WIDE_WALK: default 0 in scene_prep.h, which also decides whether the four-child tree is built at all)
-// Supported range of the A/B switch.  Above: a job stages its tile's cut with ONE word per work-item of its 512
+// Supported range of RTX_MAX_CUT.  Above: a job stages its tile's cut with ONE word per work-item of its 512
 // (rtx_kernel.hip: cut_word), so kCutWords * kMaxCut <= 512 — the build of round 2's cut-size sweep that printed no bench
 // line (profiles/r02/h_ab_cut_size_with_roots_in_lds.log, "build 5" = 64 entries of the ten-word CutEntry = 640 words) left
 // entries 51..63 of every cut unstaged and walked whatever LDS held; the same sweep before the roots moved into the

@@ -33,12 +33,6 @@ namespace rtx {
 
 namespace {
 
-// phase-2 ray numbering for tiles whose hit pixels all lie on one triangle (see the kernel); a switch so
-// that the profile can show what it is worth
-#ifndef RTX_ONE_SURFACE_SAMPLE_MAJOR
-#define RTX_ONE_SURFACE_SAMPLE_MAJOR 1
-#endif
-constexpr bool kOneSurfaceSampleMajor = RTX_ONE_SURFACE_SAMPLE_MAJOR != 0;
 // LDS hit record of the fused kernel: p_hit xyz, normal xyz, colour rgb, 3 spare floats
 constexpr uint32_t kHitStride = 12u;
 // Hit records of a tile whose hit pixels all lie on ONE triangle (the ground, walls: nine tiles in ten of the default
@@ -46,9 +40,6 @@ constexpr uint32_t kHitStride = 12u;
 // 792 bytes instead of 3072, written by probe_kernel and read by the tile's job (a 4096 x 4096 frame: 0.38 GB each way).
 // The job word says which form it is (the descriptor arrives with the records, not before them).  compact_hit_word: where
 // word k of the full form (record k / 12, word k % 12) lies in the compact one; kNone: a padding word (zero).
-#ifndef RTX_COMPACT_HITS
-#define RTX_COMPACT_HITS 1
-#endif
 __device__ __forceinline__ uint32_t compact_hit_word(uint32_t record, uint32_t word)
 {
     return word < 3u ? record * 3u + word : (word < 9u ? 192u + word - 3u : kNone);
@@ -88,13 +79,11 @@ __device__ __forceinline__ bool tile_pixel(const DeviceScene &S, const TileSpec 
 // consecutively, blocks row by row — consecutive tile numbers (what one XCD is dealt: probe_kernel's workgroups, the
 // runs of shade_tiles_kernel's order) are then a compact patch of the frame, not a strip eight pixels high, and their
 // rays meet the same part of the scene.  The blocks of the right and lower edge are padded: a tile outside the frame
-// has no pixel (tile_pixel) and ends as a tile without a hit.  0: row-major (the single-kernel ablation variants).
-#ifndef RTX_TILE_BLOCKS
-#define RTX_TILE_BLOCKS 1
-#endif
+// has no pixel (tile_pixel) and ends as a tile without a hit.  (tile_xy with blocks = false: row-major, the single-kernel
+// ablation variants.)
 __host__ __device__ inline uint32_t numbered_tiles(uint32_t tiles_x, uint32_t tiles_y)
 {
-    return RTX_TILE_BLOCKS ? ((tiles_x + 7u) / 8u) * ((tiles_y + 7u) / 8u) * 64u : tiles_x * tiles_y;
+    return ((tiles_x + 7u) / 8u) * ((tiles_y + 7u) / 8u) * 64u;
 }
 __device__ __forceinline__ void tile_xy(uint32_t tile_id, uint32_t tiles_x, bool blocks, uint32_t &tx, uint32_t &ty)
 {
@@ -227,34 +216,6 @@ __device__ __forceinline__ void shadow_result_grey(const float *__restrict__ l_h
     // (they start at +0.0 and only grow), so the ordered accumulation needs no test
     const float c = FAST_DIV ? div_denom(h[6] * lnd, dd) : (h[6] * lnd) / dd.d;
     if (s.valid) l_res[__umul24(s.hp, res_stride) + s.si] = lit ? c : 0.0f;
-}
-
-// A FULL tile numbered sample-major (64 hit pixels of one surface — nearly every tile of the ground): chunk c is light
-// sample c for the 64 pixels, lane l carries pixel l in every chunk.  The lane's hit record stays in registers for the
-// whole job (h[0..2] p_hit, h[3..5] normal, h[6] red) and the ray number needs no division.  (Reading the other tiles'
-// records per chunk into the same registers, to spare the general loop the copies where the two ways meet: +3 %.)
-__device__ __forceinline__ ShadowRay shadow_ray_from(const float (&h)[7], const float *__restrict__ l_light, bool valid, uint32_t hp, uint32_t si)
-{
-    ShadowRay s;
-    s.hp = hp;
-    s.si = si;
-    const float *lp = l_light + __umul24(3u, si);
-    const float vx = lp[0] - h[0], vy = lp[1] - h[1], vz = lp[2] - h[2];             // p - orig
-    float dist_light, sx, sy, sz;
-    s.not_hard = length_and_direction(vx, vy, vz, dist_light, sx, sy, sz);            // main.rs:202; Ray::new, main.rs:201 -> ray.rs:15
-    s.ray = make_ray_bare(valid, h[0], h[1], h[2], sx, sy, sz);
-    s.ray.limit = dist_light;
-    s.valid = valid;
-    return s;
-}
-__device__ __forceinline__ void shadow_result_grey_from(const float (&h)[7], float *__restrict__ l_res, uint32_t res_stride,
-                                                        const ShadowRay &s, const DenomDiv &dd)
-{
-    const LaneRay &r = s.ray;
-    const float lnd = fabsf(h[3] * r.dx + h[4] * r.dy + h[5] * r.dz);               // main.rs:207
-    const bool lit = r.best_idx == kNone;
-    const float c = div_denom(h[6] * lnd, dd);                                       // main.rs:211
-    if (s.valid) l_res[__umul24(s.hp, res_stride) + s.si] = lit ? c : 0.0f;          // (see shadow_result_grey)
 }
 
 __device__ __forceinline__ void store_pixel(const DeviceScene &S, const float *__restrict__ thr, uint8_t *__restrict__ out,
@@ -396,21 +357,6 @@ __device__ __forceinline__ uint32_t cost_class(unsigned long long cost)
 constexpr uint32_t kChunkFixedCost = 8u;
 
 
-// independent wavefronts (tiles) per workgroup of probe_kernel: 1, 4 and 8 measured the same (m_ab_probewaves.log)
-// 1: probe_kernel's primary walk on the four-child form of the tree (measured: the scheduling pass of one share of an
-// 8-way 1080p frame 0.090 -> 0.087 ms, of the 1M-triangle soup 2.95 -> 2.80 ms, but big_bunny 4096x4096 0.294 -> 0.311 ms
-// and the ground-only frame 0.051 -> 0.054 ms: tiles that walk next to nothing pay for four boxes per step.  Off.)
-#ifndef RTX_PROBE_WIDE
-#define RTX_PROBE_WIDE 0
-#endif
-#ifndef RTX_PROBE_XCD
-#define RTX_PROBE_XCD 1
-#endif
-#ifndef RTX_PROBE_WAVES
-#define RTX_PROBE_WAVES 1
-#endif
-// 1: the probing walk of a tile of a scene without cuts (probe_kernel: the tile's hit pixels towards light sample 0, for the
-// cost estimate) is the shading pass's chunk 0 where the tile is full and numbered sample-major; its answers are kept.
 // Cut form: a tile whose cut has at least this many entries — a tile that walks — draws its chunks as well (0: none do).
 // Round 2 measured this a loss (+1 % on big_bunny 1080p: the walks were slower then and the jobs that never draw paid for
 // the loop's shape); with the hand-written box step it is -2.3 % there (six interleaved rounds) and -0.5 % at 4096x4096;
@@ -418,38 +364,21 @@ constexpr uint32_t kChunkFixedCost = 8u;
 #ifndef RTX_CUT_DRAW_MIN
 #define RTX_CUT_DRAW_MIN 1
 #endif
-#ifndef RTX_CUT_STREAM        // 1: a chunk steps its tile's cut as a stream of records (walk_cut_stream); 0: out of LDS (walk_cut)
-#define RTX_CUT_STREAM 1
-#endif
-// the entry form of a tile's cut (CutEntry, staged in LDS by a job) is read by the A/B forms only: the LDS walk, the wide
-// walk, the ablation library's variants
-#if RTX_ABLATION || RTX_WIDE_WALK || !RTX_CUT_STREAM
+// the entry form of a tile's cut (CutEntry, staged in LDS by a job) is read by the ablation library's variants only
+#if RTX_ABLATION
 #define kCutEntriesUsed true
 #else
 #define kCutEntriesUsed false
 #endif
+// independent wavefronts (tiles) per workgroup of probe_kernel: 1, 4 and 8 measured the same (m_ab_probewaves.log)
+constexpr uint32_t kProbeWaves = 1u;
 // Wavefronts per SIMD probe_kernel's register allocation must allow: a 4096 x 4096 frame's 262,144 one-wavefront workgroups
 // are bound by how many of them are resident (the probing walk of cut tiles brought the kernel to 106 scalar registers: 7)
 #ifndef RTX_PROBE_WAVES_PER_SIMD
 #define RTX_PROBE_WAVES_PER_SIMD 8
 #endif
-#ifndef RTX_PROBE_CUT_TILES           // 1: one-surface tiles with a cut are probed by a real walk of light sample 0 (probe_kernel)
-#define RTX_PROBE_CUT_TILES 1
-#endif
-#ifndef RTX_PROBE_MIX                 // the tile's weight from that walk alone (0), the larger of walk and proxy (1), half the proxy + the walk (2)
-#define RTX_PROBE_MIX 2
-#endif
-#ifndef RTX_PROBE_VISIT_SCALE         // a record of that walk in the units of the cut's proxy
+#ifndef RTX_PROBE_VISIT_SCALE         // a record of the probing walk of a cut tile (probe_cut_walk) in the units of the cut's proxy
 #define RTX_PROBE_VISIT_SCALE 6u
-#endif
-#ifndef RTX_COST_MIXED_TILES_TWICE
-#define RTX_COST_MIXED_TILES_TWICE 1
-#endif
-#ifndef RTX_WHOLE_DRAW_CHUNKS
-#define RTX_WHOLE_DRAW_CHUNKS 1
-#endif
-#ifndef RTX_KEEP_PROBING_WALK
-#define RTX_KEEP_PROBING_WALK 1
 #endif
 
 // ---- the cut of a tile ------------------------------------------------------------------------------------------
@@ -548,88 +477,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 #include "rtx_j1_ablation.hpp"
 #endif
 
-// Breadth-first descent of the wide tree with the shaft test, one frontier node per work-item; the frontier of a level
-// lives in registers (lane l holds its l-th node), the next one is gathered through 64 words of LDS.  A frontier
-// node's four child boxes are tested against the shaft.  A node with a LEAF child that meets the shaft becomes an
-// entry of the cut itself (the rays test the leaf's box when they walk that node — a leaf has no record of its own);
-// otherwise its inner children that meet the shaft form the next frontier, and a node none of whose children meets the
-// shaft is dropped.  Invariant: entries written + frontier nodes <= kMaxCut, so a level is one pass of the wavefront;
-// when the next level would break it, the frontier's live nodes become entries as they are and the descent stops.
-// Returns the number of entries written to `out` (byte offsets of wide nodes); *weight = a proxy of what one chunk's
-// walk of the cut will fetch.
-__device__ __forceinline__ uint32_t shaft_cut_wide(const WideNode *__restrict__ wide, const Shaft &sh,
-                                                   CutEntry *__restrict__ out, uint32_t *__restrict__ l_front, uint32_t lane,
-                                                   uint32_t &weight)
-{
-    uint32_t my = 0u, my_size = 0u, n_front = 1u, n_out = 0u, w = 0u;
-    for (;;) {
-        const bool have = lane < n_front;
-        bool meets[4] = {false, false, false, false}, leaf[4] = {false, false, false, false};
-        uint32_t ref[4] = {0u, 0u, 0u, 0u}, aux[4] = {0u, 0u, 0u, 0u};
-        if (have) {
-            const WideNode *nd = reinterpret_cast<const WideNode *>(reinterpret_cast<const char *>(wide) + my);
-#pragma unroll
-            for (uint32_t c = 0; c < 4u; ++c) {
-                NodeDev bx;
-                bx.lox = nd->box[c][0]; bx.loy = nd->box[c][1]; bx.loz = nd->box[c][2];
-                bx.hix = nd->box[c][3]; bx.hiy = nd->box[c][4]; bx.hiz = nd->box[c][5];
-                ref[c] = nd->ref[c];
-                aux[c] = nd->aux[c];
-                leaf[c] = (ref[c] >> 31) != 0u;
-                meets[c] = !(leaf[c] && aux[c] == 0u) && shaft_meets(sh, bx);   // an empty slot never does
-            }
-        }
-        const bool with_leaf = (meets[0] && leaf[0]) || (meets[1] && leaf[1]) || (meets[2] && leaf[2]) || (meets[3] && leaf[3]);
-        const bool live = meets[0] || meets[1] || meets[2] || meets[3];
-        const bool expand = live && !with_leaf;
-        const uint32_t kids = expand ? (uint32_t)meets[0] + (uint32_t)meets[1] + (uint32_t)meets[2] + (uint32_t)meets[3] : 0u;
-        const unsigned long long m_live = ballot(live), m_entry = ballot(with_leaf);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        // exclusive prefix of `kids` over the lanes, and its total
-        uint32_t before = 0u, total = 0u;
-#pragma unroll
-        for (uint32_t k = 1; k <= 4u; ++k) {
-            const unsigned long long mk = ballot(kids >= k);
-            before += (uint32_t)__popcll(mk & below);
-            total += (uint32_t)__popcll(mk);
-        }
-        const uint32_t n_entry = (uint32_t)__popcll(m_entry);
-        if (n_out + n_entry + total > kMaxCut) {      // stop here: the live nodes of this level are the rest of the cut
-            if (live) {
-                out[n_out + (uint32_t)__popcll(m_live & below)] = CutEntry{my, 0u, NodeDev{}};
-                w += 4u + 6u * (32u - (uint32_t)__clz((int)my_size));
-            }
-            n_out += (uint32_t)__popcll(m_live);
-            break;
-        }
-        if (with_leaf) {
-            out[n_out + (uint32_t)__popcll(m_entry & below)] = CutEntry{my, 0u, NodeDev{}};
-            w += 4u + 6u * (32u - (uint32_t)__clz((int)my_size));
-        }
-        n_out += n_entry;
-        if (total == 0u) break;
-        if (expand) {
-            uint32_t slot = before;
-#pragma unroll
-            for (uint32_t c = 0; c < 4u; ++c)
-                if (meets[c]) {
-                    l_front[slot] = ref[c];
-                    l_front[64u + slot] = aux[c];
-                    ++slot;
-                }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        n_front = total;
-        my = l_front[lane];
-        my_size = l_front[64u + lane];
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    weight = wave_sum(w);
-    return n_out;
-}
-
 // probe_kernel's probing walk of a one-surface tile with a cut: the tile's hit pixels towards one light point, through the
 // cut's entry form in LDS; returns the records the walk fetched.  (Inlined: as a CALLED function — to keep its registers
 // out of probe_kernel's, which every tile of a frame pays for — one bench run in three FAILED on the GPU box; not pursued.)
@@ -650,10 +497,13 @@ __device__ __forceinline__ uint32_t probe_cut_walk(const NodeRec RTX_CONSTANT *n
     return (uint32_t)(probe.node_visits + probe.tri_visits);
 }
 
-// The same descent over the binary stream (what librtx.so ships; the wide form above is kept for A/B, DESIGN.md section
-// 4): one stream record per work-item, its own box against the shaft; a leaf that meets it becomes an entry, an inner
-// node's two children (the next record, and the one its `info` names) join the next frontier.  Entries are record
-// ranges [begin, end) of the stream.
+// Breadth-first descent of the stream with the shaft test, one frontier node per work-item; the frontier of a level lives
+// in registers (lane l holds its l-th node), the next one is gathered through LDS: one stream record per work-item, its
+// own box against the shaft; a leaf that meets it becomes an entry, an inner node's two children (the next record, and
+// the one its `info` names) join the next frontier.  Invariant: entries written + frontier nodes <= kMaxCut, so a level
+// is one pass of the wavefront; when the next level would break it, the frontier's live nodes become entries as they are
+// and the descent stops.  Entries are record ranges [begin, end) of the stream.  Returns the number of entries written;
+// weight = a proxy of what one chunk's walk of the cut will fetch.
 __device__ __forceinline__ uint32_t shaft_cut_binary(const NodeDev *__restrict__ nodes, uint32_t root, const Shaft &sh,
                                                      CutEntry *__restrict__ out, NodeDev *__restrict__ out_stream,
                                                      uint32_t *__restrict__ l_front, CutEntry *__restrict__ l_entries,
@@ -727,34 +577,31 @@ __device__ __forceinline__ uint32_t shaft_cut_binary(const NodeDev *__restrict__
 // WHOLE: the scene does not cut per tile (S.n_nodes > S.cut_max_nodes: shade_tiles_kernel's whole-stream form follows) — an
 // instantiation of its own, so that each carries one probing walk only (the kernel is short of scalar registers)
 template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE>
-__global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD) probe_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
+__global__ void __launch_bounds__(64 * kProbeWaves, RTX_PROBE_WAVES_PER_SIMD) probe_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
                                                    uint32_t r, StreamWorkspace W, uint8_t *__restrict__ out,
                                                    uint32_t *__restrict__ queue, unsigned long long *__restrict__ counters)
 {
     const NodeRec RTX_CONSTANT *nodes = (const NodeRec RTX_CONSTANT *)S.nodes;
     const TriRec RTX_CONSTANT *tris = (const TriRec RTX_CONSTANT *)S.tris;
-    // one wavefront per tile, RTX_PROBE_WAVES independent wavefronts per workgroup (no barrier; LDS only inside shaft_cut)
-    __shared__ uint32_t l_front_all[RTX_PROBE_WAVES][128];   // the cut's next frontier: node, subtree size
-    __shared__ CutEntry l_entries_all[RTX_PROBE_WAVES][kMaxCut];   // the tile's cut in its entry form, for the probing walk
+    // one wavefront per tile, kProbeWaves independent wavefronts per workgroup (no barrier; LDS only inside shaft_cut_binary
+    // and the probing walk)
+    __shared__ uint32_t l_front_all[kProbeWaves][128];           // the cut's next frontier
+    __shared__ CutEntry l_entries_all[kProbeWaves][kMaxCut];     // the tile's cut in its entry form, for the probing walk
 #if RTX_ABLATION
-    __shared__ __align__(16) uint32_t l_j1_block[RTX_PROBE_WAVES][kJ1BlockWords];   // RTX_J1=2: a block of 64 primitive records
+    __shared__ __align__(16) uint32_t l_j1_block[kProbeWaves][kJ1BlockWords];   // RTX_J1=2: a block of 64 primitive records
 #endif
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_in_group = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t *const l_front = l_front_all[wave_in_group];
-#if RTX_PROBE_XCD
     // workgroups b, b + 8, ... share an XCD (MI355X_MICROARCH.md, workgroup dispatch): the XCDs are dealt runs of 64
     // consecutive tile numbers — one 64 x 64 pixel block each — so that an L2 serves neighbouring tiles' walks.  (One
     // contiguous eighth of the frame per XCD was 25-35 % slower: the upper half of a frame is sky.)
-    static_assert(RTX_PROBE_WAVES == 1, "the XCD mapping assumes one tile per workgroup");
+    static_assert(kProbeWaves == 1u, "the XCD mapping assumes one tile per workgroup");
     const uint32_t k = blockIdx.x >> 3;
     const uint32_t tile_id = ((((k >> 6) << 3) + (blockIdx.x & 7u)) << 6) + (k & 63u);
-#else
-    const uint32_t tile_id = blockIdx.x * RTX_PROBE_WAVES + wave_in_group;
-#endif
     if (tile_id >= n_tiles) return;
     uint32_t px, py, ly, tile_x, tile_y;
-    tile_xy(tile_id, tiles_x, RTX_TILE_BLOCKS != 0, tile_x, tile_y);
+    tile_xy(tile_id, tiles_x, true, tile_x, tile_y);
     const bool in_frame = tile_pixel(S, ts, tile_x, tile_y, lane, px, py, ly);
     WaveCounters wc;
     float dx, dy, dz;
@@ -763,14 +610,7 @@ __global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD
 #if RTX_EXPERIMENT_PROBE_PHASES   // timing experiment only: a tile's primary walk and its cut's descent, 10 ns ticks, in the
     const unsigned long long pp_t0 = wall_clock64();   // descriptor's spare word (low / high half); tools/probe_phases.py
 #endif
-#if RTX_WIDE_WALK || RTX_PROBE_WIDE
-    // (A/B builds: the PRIMARY walk on the four-child form of the tree, rtx_traverse.hpp: walk_wide.  A primary walk is one
-    //  wavefront's chain of dependent fetches, ~0.3 us per step, and the longest of them — a silhouette tile's, 42 us — is
-    //  the length of this pass for one GPU's share of a frame, tools/probe_phases.py; see RTX_PROBE_WIDE for what it gave.)
-    const bool ok = hit_wide<COUNT, FAST, SPHERES, false>((const WideNode RTX_CONSTANT *)S.wide, S.n_wide, tris, S.shade, nullptr, 0u, pr, wc,
-                                                          S.n_global, false);                                  // main.rs:187
-    (void)nodes;
-#elif RTX_ABLATION
+#if RTX_ABLATION
     const bool ok = (S.j1_mode == 2u || S.j1_mode == 3u)
         ? j1_closest_hit_blocks<COUNT>(S.j1_mode, S.tris, S.shade, S.n_prims, pr, wc, lane, l_j1_block[wave_in_group])
         : closest_hit<COUNT, FAST, SPHERES>((const NodeRec RTX_CONSTANT *)S.primary_nodes, tris, S.shade, S.n_nodes, pr, wc, S.n_global);   // main.rs:187
@@ -794,7 +634,7 @@ __global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD
         was_redo = old.flags & 2u;
         counted = old.pad;
     }
-    uint32_t flags = (kOneSurfaceSampleMajor && one_surface) ? 1u : 0u;
+    uint32_t flags = one_surface ? 1u : 0u;   // bit 0: the tile's shadow rays are numbered sample-major (shade_tiles_kernel)
     if (!ok || was_redo) flags |= 2u;
     if (!ok && !was_redo && lane == 0) {
         queue[kQueueHeader + atomicAdd(&queue[kQueueRedoCount], 1u)] = tile_id;
@@ -804,7 +644,7 @@ __global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD
         }
     }
     float hx = 0.0f, hy = 0.0f, hz = 0.0f;
-    const bool compact = RTX_COMPACT_HITS && one_surface && n_hit != 0u && (!SPHERES || S.shade[first_idx].kind == 0u);
+    const bool compact = one_surface && n_hit != 0u && (!SPHERES || S.shade[first_idx].kind == 0u);
     if (compact) flags |= kTileCompactHits;
     if (hit) {
         const ShadeRec sh = S.shade[pr.best_idx];
@@ -847,10 +687,6 @@ __global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD
         shaft_constraint(sh, 4u, ohz, lb[5] - ohz, S.shaft_delta);
         shaft_constraint(sh, 5u, olz, lb[2] - olz, S.shaft_delta);
         uint32_t weight = 0u;
-#if RTX_WIDE_WALK
-        if (S.n_wide != 0u)
-            n_cut = shaft_cut_wide(S.wide, sh, W.cut + (size_t)tile_id * kMaxCut, l_front, lane, weight);
-#else
         // the tree proper: behind the root and the global triangles' leaf when there are any (scene_prep.cpp)
         const uint32_t root = S.n_global != 0u ? 2u : 0u;
         if (!WHOLE && root < S.n_nodes) {
@@ -865,15 +701,14 @@ __global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD
             // late, are the frame's tail.  (Keeping the walk's answers as the shading pass's chunk 0, as the whole-stream form
             // does, was measured too: the shading pass's general loop pays more for the case than a walk in a hundred saves.
             // Skipping the walk in wavefronts already at work for 6 / 12 / 25 us — tiles beside the silhouette — as well: no.)
-            if (RTX_PROBE_CUT_TILES && n_cut != 0u && (flags & 1u)) {
+            if (n_cut != 0u && (flags & 1u)) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 const uint32_t walked_weight = RTX_PROBE_VISIT_SCALE *
                     probe_cut_walk<FAST, SPHERES>(nodes, tris, S.shade, reinterpret_cast<const uint32_t *>(l_entries_all[wave_in_group]), n_cut,
                                                   S.n_global, S.light_points + 3u * (r * S.nb_light), hit, hx, hy, hz);
-                weight = RTX_PROBE_MIX == 1 ? (weight > walked_weight ? weight : walked_weight)
-                       : RTX_PROBE_MIX == 2 ? weight / 2u + walked_weight : walked_weight;
+                weight = weight / 2u + walked_weight;   // (half the proxy + the walk; the walk alone, and the larger of the two: no better)
             }
         } else if (WHOLE && root < S.n_nodes) {
             // A scene of many small primitives (BASELINE configs[4]): nearly every tile's shaft meets thousands of leaves, a
@@ -894,7 +729,7 @@ __global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD
             // In a FULL tile numbered sample-major these 64 rays ARE the shading pass's chunk 0 — hit pixel `lane` towards
             // light sample 0, the same origin, light point and normalisation — so their answers are kept (two words where
             // a cut would lie) and shade_tiles_kernel does not walk that chunk again: one walk in a hundred.
-            if (RTX_KEEP_PROBING_WALK && walked && n_hit == 64u && (flags & 1u)) {
+            if (walked && n_hit == 64u && (flags & 1u)) {
                 const unsigned long long occluded = ballot(sr.best_idx != kNone);
                 if (lane == 0) {
                     uint32_t *kept = reinterpret_cast<uint32_t *>(W.cut + (size_t)tile_id * kMaxCut);
@@ -904,13 +739,12 @@ __global__ void __launch_bounds__(64 * RTX_PROBE_WAVES, RTX_PROBE_WAVES_PER_SIMD
                 flags |= kTileChunk0Kept;
             }
         }
-#endif
         cost = (unsigned long long)(kChunkFixedCost + weight) * n_chunks;
         // A tile numbered pixel-major — hit pixels on several primitives: the mesh's own surface and its silhouette — takes
         // about twice as long as a one-surface tile of the same proxy (its rays start INSIDE the boxes they walk; measured per
         // cost class with tools/tile_timeline.py: x1.9 ... x2.5), and the order and the splitting should know: the costliest
         // tiles of a frame are of this kind, and one of them started late is the frame's tail.
-        if (RTX_COST_MIXED_TILES_TWICE && !(flags & 1u) && n_cut != 0u) cost *= 2u;
+        if (!(flags & 1u) && n_cut != 0u) cost *= 2u;
     }
     // A tile without a hit is finished here (main.rs:235: the sums stay as they are), a queued tile belongs to the
     // reference re-render: neither is scheduled for shade_tiles_kernel (cost class kNone).
@@ -972,9 +806,6 @@ constexpr uint32_t kOrderHist = kCostBuckets, kOrderCursor = 2u * kCostBuckets, 
 // own compute units ask for next.  Group g's k-th claim is job ((k / run) * 8 + g) * run + k % run of the order: every
 // group still goes through the order costliest first, and a group whose share is used up draws from the next group's
 // ([kOrderClaim + g]: claims of group g, zeroed with the histogram).  Speed only: any workgroup may run any job.
-#ifndef RTX_XCD_QUEUES
-#define RTX_XCD_QUEUES 1
-#endif
 #ifndef RTX_CLAIM_RUN_LOG
 #define RTX_CLAIM_RUN_LOG 10      // runs of 16 / 64 / 256 / 1024 / 4096 jobs: the 1M-triangle soup -1.7 / -2.3 / -3.5 / -4.3 / -3.7 %
 #endif
@@ -1099,19 +930,13 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
     if (key != kNone) {
         const uint32_t lg = parts_log[key];
         uint32_t *dst = W.buckets + kOrderList + start[key] + (slot << lg);
-        const uint32_t form = (RTX_COMPACT_HITS && (W.tiles[i].flags & kTileCompactHits)) ? 1u << kJobCompactShift : 0u;
+        const uint32_t form = (W.tiles[i].flags & kTileCompactHits) ? 1u << kJobCompactShift : 0u;
         for (uint32_t p = 0; p < (1u << lg); ++p) dst[p] = i | (p << kJobTileBits) | (lg << kJobPartsShift) | form;
     }
 }
 
 // Without the primary phase the kernel fits the 64 VGPRs of 8 wavefronts per SIMD (4 workgroups per CU): 53 VGPRs, no
 // scratch in the shipped build; when it first went in, 8 per SIMD measured 2.22 ms against 2.28 ms at 6 (C3).
-#ifndef RTX_PLANE_SHORTCUT
-#define RTX_PLANE_SHORTCUT 1
-#endif
-#ifndef RTX_SHADE_LEAN_STEP
-#define RTX_SHADE_LEAN_STEP 1
-#endif
 #ifndef RTX_SHADE_WAVES_PER_SIMD
 #define RTX_SHADE_WAVES_PER_SIMD 8
 #endif
@@ -1124,23 +949,11 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
 // are long chains of dependent scalar loads: 8, i.e. 64 vector and 78 scalar registers; at 6 the 1M-triangle soup takes
 // 20 % longer); the cut form, whose frames are mostly chunks that walk little or nothing, does better with the registers
 // of 6 (fewer scalar registers spilled to lanes: -3 % on big_bunny 4096x4096, -7 % on the ground-only frame, 1080p equal).
-#ifndef RTX_SHADE_PRIORITY
-#define RTX_SHADE_PRIORITY 1
-#endif
-#ifndef RTX_OPEN_GROUND_LOOP
-#define RTX_OPEN_GROUND_LOOP 1
-#endif
-// 1: the general chunk loop, too, works on a full tile's registers (hit record, the origin's part of the ground's
-// certificate).  At the 64 vector registers of 8 wavefronts per SIMD that keeps nine of them alive across the walk and ten
-// in scratch; with the registers the open-ground loop's alone, one: big_bunny 4096x4096 -1.2 %, the ground-only frame
-// -1.7 %, one share of an 8-way 1080p frame -2.6 %, the 1080p frame +0.5 % (four interleaved rounds,
-// profiles/r02/j_ab_full_tile_registers.log).
-#ifndef RTX_FULL_TILE_GENERAL
-#define RTX_FULL_TILE_GENERAL 0
-#endif
-#ifndef RTX_FULL_TILE_PATH
-#define RTX_FULL_TILE_PATH 1
-#endif
+// (A full tile's registers — hit record, the origin's part of the ground's certificate — are the open-ground loop's
+//  alone.  With the general chunk loop working on them too, the 64 vector registers of 8 wavefronts per SIMD keep nine of
+//  them alive across the walk and ten in scratch instead of one: big_bunny 4096x4096 -1.2 %, the ground-only frame
+//  -1.7 %, one share of an 8-way 1080p frame -2.6 %, the 1080p frame +0.5 % for the form kept (four interleaved rounds,
+//  profiles/r02/j_ab_full_tile_registers.log).)
 // (The cut form at 6 was 3-7 % faster than at 8 while a cheap job was bound by its serial stretches; since the open
 //  ground's chunks are bound by their vector instructions — the loop of their own below — 8 is, although ten vector
 //  registers then live in scratch: big_bunny 4096x4096 -4.6 %, the ground-only frame -2 %, one share of an 8-way 1080p
@@ -1149,6 +962,8 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
 #ifndef RTX_SHADE_CUT_WAVES_PER_SIMD
 #define RTX_SHADE_CUT_WAVES_PER_SIMD 8
 #endif
+// s_setprio of a job's serial stretches (its loads into LDS, the ordered sums, the store); its ray loops run at 0
+constexpr int kShadePriority = 1;
 template <bool COUNT, bool FAST, int NW, bool SPHERES, bool WHOLE>
 __global__ void __launch_bounds__(64 * NW, COUNT ? 1 : (WHOLE ? RTX_SHADE_WAVES_PER_SIMD : RTX_SHADE_CUT_WAVES_PER_SIMD))
 shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x, uint32_t n_tiles, uint32_t r,
@@ -1170,15 +985,11 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
     if (S.j1_mode == 1u && threadIdx.x < 2u) l_j1_win[threadIdx.x] = 0u;               // "no window" until a job stages one
 #endif
 
-#if RTX_WIDE_WALK
-    const WideNode RTX_CONSTANT *wide = (const WideNode RTX_CONSTANT *)S.wide;
-#else
     const NodeRec RTX_CONSTANT *nodes = (const NodeRec RTX_CONSTANT *)S.nodes;
-#endif
     const TriRec RTX_CONSTANT *tris = (const TriRec RTX_CONSTANT *)S.tris;
     // the first global triangle's plane, fetched once (rtx_traverse.hpp: plane_rules_out)
     const TriRec RTX_CONSTANT *planes = (const TriRec RTX_CONSTANT *)S.planes;
-    const bool have_plane = RTX_PLANE_SHORTCUT && planes != nullptr;
+    const bool have_plane = planes != nullptr;
     TriRec plane0 = {};
     if (have_plane) {
         plane0.v0[0] = planes->v0[0]; plane0.v0[1] = planes->v0[1]; plane0.v0[2] = planes->v0[2];
@@ -1189,9 +1000,6 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     WaveCounters wc;
-#if !RTX_WIDE_WALK
-    constexpr bool whole_tree = WHOLE;
-#endif
     const float denom = (float)(S.nb_ray * S.nb_light);                              // main.rs:211
     const DenomDiv denom_d = denom_div(denom);
     static_assert(sizeof(HitRec) == kHitStride * sizeof(float), "the LDS hit record is the HBM hit record");
@@ -1210,7 +1018,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
     bool have_ahead = false;
     // (the whole-stream form only — scenes whose records do not fit an XCD's L2; measured on one box, interleaved, runs of 16:
     //  the 1M-triangle soup -1.7 %, and with the cut form big_bunny 4096x4096 -0.4 %, 1080p +2 %, the ground-only frame +10 %)
-    constexpr bool xcd_queues = RTX_XCD_QUEUES != 0 && WHOLE;
+    constexpr bool xcd_queues = WHOLE;
     const uint32_t group0 = blockIdx.x & 7u;
     uint32_t groups_done = 0u, g_ahead = 0u;      // (state of the work-item that claims the jobs)
     // the light points are the same for every job of a launch (main.rs:194-196: sample i of primary ray r): when one batch
@@ -1241,20 +1049,18 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
         __syncthreads();
         const uint32_t job = __builtin_amdgcn_readfirstlane(l_ctl[3]);
         if (job == kNone) break;
-#if RTX_SHADE_PRIORITY
         // A job's short serial stretches (its loads into LDS, the ordered sums, the store) are what the other wavefronts
         // of its workgroup wait for at barriers: they issue ahead of the other workgroups' ray loops on the same SIMD
-        __builtin_amdgcn_s_setprio(RTX_SHADE_PRIORITY);
-#endif
+        __builtin_amdgcn_s_setprio(kShadePriority);
 #if RTX_EXPERIMENT_PHASES       // timing experiment only: where a job of a tile with an empty cut spends its time (100 MHz ticks)
         unsigned long long ph_t[6] = {(unsigned long long)wall_clock64(), 0, 0, 0, 0, 0};
 #endif
         // part `part` of 2^parts_log of the tile: its hit records [h0, h0 + n_hit), the pixels they belong to, and (part 0)
         // the tile's pixels without a hit
         const uint32_t tile_id = job & kJobTileMask, part = (job >> kJobTileBits) & 7u, parts_log = (job >> kJobPartsShift) & 3u;
-        const bool compact = RTX_COMPACT_HITS && ((job >> kJobCompactShift) & 1u) != 0u;
+        const bool compact = ((job >> kJobCompactShift) & 1u) != 0u;
         uint32_t tile_x, tile_y;
-        tile_xy(tile_id, tiles_x, RTX_TILE_BLOCKS != 0, tile_x, tile_y);
+        tile_xy(tile_id, tiles_x, true, tile_x, tile_y);
         // A whole tile's job requests everything it needs from HBM at once — the tile's descriptor, all 64 of its hit-record
         // slots, its pixel slots, its cut list — and sorts it out when it is there: waiting for the descriptor first, to ask
         // only for the records that exist, made two dependent round trips in front of every such job.  A PART of a tile
@@ -1288,7 +1094,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
             reinterpret_cast<const char *>(W.cut) + cut_stream_offset(n_tiles)) + (size_t)tile_id * kCutStreamRecords;
         // whole-stream form: chunk 0 of a full sample-major tile was walked by probe_kernel (its probing walk); the answers
         // lie where a cut would (words 0 and 1: work-items 0 and 1 of wavefront 0, which is the wavefront that has chunk 0)
-        const bool chunk0_kept = WHOLE && RTX_KEEP_PROBING_WALK != 0 && (tflags & kTileChunk0Kept) != 0u && parts_log == 0u &&
+        const bool chunk0_kept = WHOLE && (tflags & kTileChunk0Kept) != 0u && parts_log == 0u &&
                                  n_hit == 64u && sample_major;
         const uint32_t kept_lo = __builtin_amdgcn_readlane(cut_word, 0), kept_hi = __builtin_amdgcn_readlane(cut_word, 1);
         if (!skip) {
@@ -1334,16 +1140,11 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                 const bool grey_tile = ballot(hit && !(cr == cg && cg == cb && cr >= 0.0f && a0 == a1 && a1 == a2)) == 0ull;
                 if (lane == 0) l_ctl[2] = grey_tile ? 1u : 0u;   // read behind the barrier that publishes the light points
             }
-            // a full tile numbered sample-major keeps each lane's hit record in registers (shadow_ray_full); cut form only:
-            // the whole-stream form has no registers to spare
-            const bool full_tile = RTX_FULL_TILE_PATH != 0 && !WHOLE && sample_major && n_hit == 64u;
+            // a full tile numbered sample-major: the open-ground loop below keeps each lane's hit record in registers; cut
+            // form only: the whole-stream form has no registers to spare
+            const bool full_tile = !WHOLE && sample_major && n_hit == 64u;
             float my_hit[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
             PlaneOrigin my_plane = {0.0f, 0.0f};          // the origin's part of the ground's certificate (plane_rules_out)
-            if (RTX_FULL_TILE_GENERAL && full_tile) {
-#pragma unroll
-                for (uint32_t k = 0; k < 7u; ++k) my_hit[k] = l_hit[kHitStride * lane + k];
-                if (have_plane) my_plane = plane_origin(plane0, my_hit[0], my_hit[1], my_hit[2]);
-            }
             if (n_hit != 0u) {                                                        // else main.rs:235
                 for (uint32_t b0 = 0; b0 < S.nb_light; b0 += batch) {                 // main.rs:193, in batches that fit LDS
                     const uint32_t bc = (S.nb_light - b0 < batch) ? S.nb_light - b0 : batch;
@@ -1351,7 +1152,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                         for (uint32_t k = threadIdx.x; k < 3u * bc; k += 64u * NW)
                             l_light[k] = S.light_points[3u * (r * S.nb_light + b0) + k]; // main.rs:194-196 (hoisted to the host)
                     }
-                    if (((WHOLE && RTX_WHOLE_DRAW_CHUNKS != 0) || RTX_CUT_DRAW_MIN != 0) && threadIdx.x == 0) l_ctl[0] = 0u;   // chunks drawn so far (behind the first NW)
+                    if ((WHOLE || RTX_CUT_DRAW_MIN != 0) && threadIdx.x == 0) l_ctl[0] = 0u;   // chunks drawn so far (behind the first NW)
                     __syncthreads();   // (also publishes the grey flag)
                     // A tile with an empty cut is through its rays in 10 us: the next job's position in the list is requested
                     // now, by the work-item that claims the jobs, and turned into a job id when the ordered sums start —
@@ -1380,9 +1181,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                     // it from the next integer (checked exhaustively for the domain, ray < 8320, div <= 128).  The
                     // general 32-bit division costs three quarter-rate multiplies and a dozen more instructions.
                     const float inv_div = 1.0f / (float)div;
-#if RTX_SHADE_PRIORITY
                     __builtin_amdgcn_s_setprio(0);
-#endif
                     // The chunks of a full grey tile of the open ground — no subtree in its cut, the ground the only global
                     // triangle — in a loop of their own: ray, the ground's certificate, the sample's contribution; nothing
                     // of the walk is in it (no copies into the general loop's registers, none of its spilled scalars).  A
@@ -1391,13 +1190,15 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                     // ground-only frame, 81 % of big_bunny 4096x4096.
                     uint32_t c_first = wave * 64u;
                     uint32_t first_entry = 0u;        // the cut's entry this wavefront's next walk begins with (walk_cut)
-#if RTX_OPEN_GROUND_LOOP && !RTX_WIDE_WALK
                     if (!WHOLE && full_tile && grey_tile && n_cut == 0u && have_plane && S.n_global == 1u && denom_d.usable) {
-#if !RTX_FULL_TILE_GENERAL      // the registers are this loop's alone: loaded here, dead behind it
+                        // A full tile numbered sample-major: chunk c is light sample c for the 64 pixels, lane l carries pixel l
+                        // in every chunk, and the ray number needs no division.  The lane's hit record (my_hit[0..2] p_hit,
+                        // [3..5] normal, [6] red) and the origin's part of the ground's certificate (my_plane) stay in registers
+                        // that are this loop's alone: loaded here, dead behind it.  (Reading the other tiles' records per chunk
+                        // into the same registers, to spare the general loop the copies where the two ways meet: +3 %.)
 #pragma unroll
                         for (uint32_t k = 0; k < 7u; ++k) my_hit[k] = l_hit[kHitStride * lane + k];
                         my_plane = plane_origin(plane0, my_hit[0], my_hit[1], my_hit[2]);
-#endif
                         // The four words of the plane record this loop reads, as values of their own: the record came in with
                         // one eight-word scalar load, the register allocator treats it as one eight-register value, and when
                         // it spills that value around the walk (any change to the walk's registers decides that) this loop
@@ -1413,7 +1214,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                             if (!length_and_direction(vx, vy, vz, dist_light, sx, sy, sz)) break;    // main.rs:201-202
                             // (the certificate's "magnitude" half: these origins lie on the ground, "moving away" certifies
                             //  none of them; a tile above the ground falls to the general loop and the whole certificate)
-                            const float sd = __builtin_fmaf(sz, pn2, __builtin_fmaf(sy, pn1, sx * pn0));           // plane_magnitude
+                            const float sd = __builtin_fmaf(sz, pn2, __builtin_fmaf(sy, pn1, sx * pn0));           // plane_rules_out's sd
                             if (ballot(!(my_plane.lhs < fabsf(sd) - pkd)) != 0ull) break;
                             const float lnd = fabsf(my_hit[3] * sx + my_hit[4] * sy + my_hit[5] * sz);            // main.rs:207
                             // main.rs:211 by div_denom's short steps (the loop is entered with a usable divisor; a chunk with
@@ -1426,36 +1227,25 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                             l_res[__umul24(lane, res_stride) + sample] = __builtin_fmaf(__builtin_fmaf(-dd_, q1, x), dy_, q1);
                         }
                     }
-#endif
                     // A wavefront DRAWS its next chunk (a counter in LDS) instead of being dealt every NW-th, in the whole-stream
                     // form and in tiles of the cut form that walk.  Walks differ in length by an order of magnitude (a chunk in
                     // the open: a dozen records; one whose rays all end in the mesh: fifty to two hundred — the split by outcome
                     // in DESIGN.md section 4), and a job ends when its slowest wavefront does: the 1M-triangle soup -7 %.
-                    constexpr bool kDrawWhole = WHOLE && RTX_WHOLE_DRAW_CHUNKS != 0;
-                    const bool kDrawChunks = kDrawWhole || (RTX_CUT_DRAW_MIN != 0 && n_cut >= RTX_CUT_DRAW_MIN);
+                    const bool kDrawChunks = WHOLE || (RTX_CUT_DRAW_MIN != 0 && n_cut >= RTX_CUT_DRAW_MIN);
                     for (uint32_t c0 = c_first; c0 < total; ) {
-                        ShadowRay sr;
-                        if (RTX_FULL_TILE_GENERAL && full_tile) {   // chunk = light sample c0 / 64 of the tile's 64 pixels
-                            sr = shadow_ray_from(my_hit, l_light, true, lane, c0 >> 6);
-                        } else {
-                            const bool valid = c0 + lane < total;
-                            const uint32_t quo = (uint32_t)(((float)(c0 + lane) + 0.5f) * inv_div);
-                            const uint32_t rem = (c0 + lane) - __umul24(quo, div);
-                            sr = shadow_ray_at(l_hit, l_light, valid, valid ? quo : 0u, valid ? rem : 0u, sample_major);
-                        }
+                        const bool valid = c0 + lane < total;
+                        const uint32_t quo = (uint32_t)(((float)(c0 + lane) + 0.5f) * inv_div);
+                        const uint32_t rem = (c0 + lane) - __umul24(quo, div);
+                        ShadowRay sr;   // (declared, then assigned: as an initialisation the walk's registers are allocated differently)
+                        sr = shadow_ray_at(l_hit, l_light, valid, valid ? quo : 0u, valid ? rem : 0u, sample_major);
                         const bool no_ground = have_plane &&
-                            ((RTX_FULL_TILE_GENERAL && full_tile) ? ballot(!plane_rules_out(plane0, my_plane, sr.ray.dx, sr.ray.dy, sr.ray.dz)) == 0ull
-                                       : ballot(sr.ray.active && !plane_rules_out(plane0, sr.ray.ox, sr.ray.oy, sr.ray.oz, sr.ray.dx, sr.ray.dy, sr.ray.dz)) == 0ull);
+                            ballot(sr.ray.active && !plane_rules_out(plane0, sr.ray.ox, sr.ray.oy, sr.ray.oz, sr.ray.dx, sr.ray.dy, sr.ray.dz)) == 0ull;
                         // A chunk with nothing to walk — no subtree in the tile's cut, and the ground (the only global triangle)
                         // ruled out from its plane — is lit; what is left of the walk's own prologue is its refusal of hard
                         // directions (closest_hit: such a tile is re-rendered against the reference's tree).  Three of four
                         // chunks of a frame of the default scene are of this kind.
                         bool ok;
-#if RTX_WIDE_WALK
-                        ray_cull_constants(sr.ray);
-                        ok = hit_wide<COUNT, FAST, SPHERES, true>(wide, S.n_wide, tris, S.shade, l_cut, n_cut, sr.ray, wc, S.n_global, no_ground);   // main.rs:204
-#else
-                        const bool nothing_to_walk = n_cut == 0u && !whole_tree && (S.n_global == 0u || (S.n_global == 1u && no_ground));
+                        const bool nothing_to_walk = n_cut == 0u && !WHOLE && (S.n_global == 0u || (S.n_global == 1u && no_ground));
                         if (WHOLE && chunk0_kept && c0 == 0u && b0 == 0u) {   // probe_kernel has walked these rays: its answers
                             const unsigned long long occluded = ((unsigned long long)kept_hi << 32) | kept_lo;
                             sr.ray.best_idx = ((occluded >> lane) & 1ull) ? 0u : kNone;
@@ -1465,27 +1255,21 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                         } else {
                             ray_cull_constants(sr.ray);                              // main.rs:204
 #if RTX_ABLATION
-                            if (whole_tree && S.j1_mode == 1u)
+                            if (WHOLE && S.j1_mode == 1u)
                                 ok = j1_any_hit_whole_vec<COUNT, SPHERES>(S.nodes, nodes, tris, S.shade, S.n_nodes, l_j1_win, sr.ray, wc, S.n_global, no_ground);
                             else
 #endif
-                            if (whole_tree)
-                                ok = any_hit<COUNT, FAST, SPHERES, RTX_SHADE_LEAN_STEP != 0>(nodes, tris, S.shade, S.n_nodes, sr.ray, wc, S.n_global, no_ground);
+                            if (WHOLE)
+                                ok = any_hit<COUNT, FAST, SPHERES, true>(nodes, tris, S.shade, S.n_nodes, sr.ray, wc, S.n_global, no_ground);
 #if RTX_ABLATION
                             else if (S.j1_mode == 1u)
                                 ok = j1_any_hit_cut_vec<COUNT, SPHERES>(S.nodes, nodes, tris, S.shade, l_cut, n_cut, l_j1_win, sr.ray, wc, S.n_global, no_ground);
 #endif
                             else
-#if RTX_CUT_STREAM
-                                ok = any_hit_cut_stream<COUNT, FAST, SPHERES, RTX_SHADE_LEAN_STEP != 0>(nodes, tris, S.shade, cut_stream, n_cut, sr.ray, wc, S.n_global, no_ground, first_entry);
-#else
-                                ok = any_hit_cut<COUNT, FAST, SPHERES, RTX_SHADE_LEAN_STEP != 0>(nodes, tris, S.shade, l_cut, n_cut, sr.ray, wc, S.n_global, no_ground, first_entry);
-#endif
+                                ok = any_hit_cut_stream<COUNT, FAST, SPHERES, true>(nodes, tris, S.shade, cut_stream, n_cut, sr.ray, wc, S.n_global, no_ground, first_entry);
                         }
-#endif
                         if (!ok && lane == 0) l_ctl[1] = 1u;
-                        if (RTX_FULL_TILE_GENERAL && grey_tile && full_tile) shadow_result_grey_from(my_hit, l_res, res_stride, sr, denom_d);
-                        else if (grey_tile) shadow_result_grey<!WHOLE>(l_hit, l_res, res_stride, sr, denom_d);   // (whole-stream form: no registers to spare, +0.7 %)
+                        if (grey_tile) shadow_result_grey<!WHOLE>(l_hit, l_res, res_stride, sr, denom_d);   // (whole-stream form: no registers to spare, +0.7 %)
                         else shadow_result(l_hit, l_res, res_stride, sr);
                         if (kDrawChunks) {
                             uint32_t drawn = 0u;
@@ -1495,9 +1279,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                             c0 += 64u * NW;
                         }
                     }
-#if RTX_SHADE_PRIORITY
-                    __builtin_amdgcn_s_setprio(RTX_SHADE_PRIORITY);
-#endif
+                    __builtin_amdgcn_s_setprio(kShadePriority);
                     __syncthreads();
 #if RTX_EXPERIMENT_PHASES
                     ph_t[3] = wall_clock64();
@@ -1642,11 +1424,7 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
 #define RTX_SHADE_NW 8
 #endif
     constexpr int NW = RTX_SHADE_NW;     // wavefronts per workgroup of shade_tiles_kernel
-#if RTX_WIDE_WALK
-    const bool whole = false;
-#else
     const bool whole = S.n_nodes > S.cut_max_nodes;
-#endif
     const uint32_t batch = S.nb_light < kMaxLightBatch ? (S.nb_light ? S.nb_light : 1u) : kMaxLightBatch;
 #if RTX_ABLATION
     const size_t lds_bytes = (static_cast<size_t>(lds_floats(batch)) + (S.j1_mode == 1u ? kJ1WindowWords : 0u)) * sizeof(float);
@@ -1683,9 +1461,8 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
         hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(256), 0, stream, d_redo, r == 0u ? 0u : kQueueNextTile,
                            r == 0u ? kQueueHeader : kQueueNextTile + 1u, W.buckets, 3u * kCostBuckets);
         hipLaunchKernelGGL(whole ? (probe_kernel<COUNT, FAST, SPHERES, true>) : (probe_kernel<COUNT, FAST, SPHERES, false>),
-                           dim3(RTX_PROBE_XCD ? 512u * ((n_tiles + 511u) / 512u) : (n_tiles + RTX_PROBE_WAVES - 1u) / RTX_PROBE_WAVES),
-                           dim3(64 * RTX_PROBE_WAVES), 0, stream, S, ts, tiles_x, n_tiles,
-                           r, W, d_out, d_redo, d_counters);
+                           dim3(512u * ((n_tiles + 511u) / 512u)), dim3(64 * kProbeWaves), 0, stream,   // whole runs of 64 tile numbers, 8 XCDs
+                           S, ts, tiles_x, n_tiles, r, W, d_out, d_redo, d_counters);
         hipLaunchKernelGGL(count_classes_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, W);
         hipLaunchKernelGGL(order_tiles_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, W, grid, split_share());
         if (ev && r == 0u && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;   // end of the scheduling pass
@@ -1698,7 +1475,7 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL((reference_tiles_kernel<COUNT, SPHERES>), dim3(n_tiles < 1024u ? n_tiles : 1024u), dim3(64), 0, stream,
-                       S, ts, tiles_x, d_out, d_redo, d_counters, RTX_TILE_BLOCKS != 0);
+                       S, ts, tiles_x, d_out, d_redo, d_counters, true);
     return hipGetLastError();
 }
 
@@ -1797,17 +1574,9 @@ hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t 
 #define RTX_SW_STR(x) RTX_SW_STR2(x)
 #define RTX_SW(x) " " #x "=" RTX_SW_STR(x)
 extern "C" __attribute__((used, visibility("hidden"))) const char rtx_build_switches_text[] = "rtx-build-switches:"
-    RTX_SW(RTX_ASM_NODE_LOAD) RTX_SW(RTX_ASM_TRI_LOAD) RTX_SW(RTX_ASM_WALK)
-    RTX_SW(RTX_CLAIM_RUN_LOG) RTX_SW(RTX_COMPACT_HITS) RTX_SW(RTX_COST_MIXED_TILES_TWICE) RTX_SW(RTX_CULL_FMA) RTX_SW(RTX_CULL_INFLATED)
-    RTX_SW(RTX_CULL_PACKED) RTX_SW(RTX_CUT_DRAW_MIN) RTX_SW(RTX_CUT_RING) RTX_SW(RTX_CUT_STREAM) RTX_SW(RTX_CUT_UNION_MIN) RTX_SW(RTX_FULL_TILE_GENERAL) RTX_SW(RTX_FULL_TILE_PATH)
-    RTX_SW(RTX_LIGHTWARD_ORDER) RTX_SW(RTX_LIGHT_BATCH) RTX_SW(RTX_MAX_CUT) RTX_SW(RTX_PRUNE_CLOSEST)
-    RTX_SW(RTX_OCTANT_STEP) RTX_SW(RTX_ONE_SURFACE_SAMPLE_MAJOR) RTX_SW(RTX_OPEN_GROUND_LOOP)
-    RTX_SW(RTX_PACKED_WAVES_PER_SIMD) RTX_SW(RTX_KEEP_PROBING_WALK) RTX_SW(RTX_PLANE_SHORTCUT) RTX_SW(RTX_PRIMARY_STREAM) RTX_SW(RTX_PROBE_CUT_TILES) RTX_SW(RTX_PROBE_MIX) RTX_SW(RTX_PROBE_VISIT_SCALE) RTX_SW(RTX_PROBE_WAVES) RTX_SW(RTX_PROBE_WAVES_PER_SIMD)
-    RTX_SW(RTX_PROBE_WIDE) RTX_SW(RTX_PROBE_XCD) RTX_SW(RTX_SHADE_CUT_WAVES_PER_SIMD) RTX_SW(RTX_WHOLE_DRAW_CHUNKS)
-    RTX_SW(RTX_SHADE_LEAN_STEP) RTX_SW(RTX_SHADE_NW) RTX_SW(RTX_SHADE_PRIORITY)
-    RTX_SW(RTX_SHADE_WAVES_PER_SIMD) RTX_SW(RTX_SKIP_ROOT_TEST) RTX_SW(RTX_SPLIT_SCALE_MIN) RTX_SW(RTX_SPLIT_SHARE_PERCENT)
-    RTX_SW(RTX_TILE_BLOCKS) RTX_SW(RTX_TILE_PARTS_MAX) RTX_SW(RTX_TRIANGLE_EARLY_OUT)
-    RTX_SW(RTX_TRI_BOX_FIRST) RTX_SW(RTX_TRI_TOUCH_NEXT) RTX_SW(RTX_WALK_INTEGER_FLAGS) RTX_SW(RTX_WALK_SINGLE_EXIT)
-    RTX_SW(RTX_WAVES_PER_SIMD) RTX_SW(RTX_WIDE_WALK) RTX_SW(RTX_XCD_QUEUES)
+    RTX_SW(RTX_CLAIM_RUN_LOG) RTX_SW(RTX_CUT_DRAW_MIN) RTX_SW(RTX_CUT_UNION_MIN) RTX_SW(RTX_LIGHT_BATCH) RTX_SW(RTX_MAX_CUT)
+    RTX_SW(RTX_PACKED_WAVES_PER_SIMD) RTX_SW(RTX_PROBE_VISIT_SCALE) RTX_SW(RTX_PROBE_WAVES_PER_SIMD)
+    RTX_SW(RTX_SHADE_CUT_WAVES_PER_SIMD) RTX_SW(RTX_SHADE_NW) RTX_SW(RTX_SHADE_WAVES_PER_SIMD)
+    RTX_SW(RTX_SPLIT_SCALE_MIN) RTX_SW(RTX_SPLIT_SHARE_PERCENT) RTX_SW(RTX_TILE_PARTS_MAX) RTX_SW(RTX_WAVES_PER_SIMD)
     RTX_SW(RTX_EXPERIMENT_TIMELINE) RTX_SW(RTX_EXPERIMENT_PHASES) RTX_SW(RTX_EXPERIMENT_PROBE_PHASES) RTX_SW(RTX_ABLATION);
 #undef RTX_SW

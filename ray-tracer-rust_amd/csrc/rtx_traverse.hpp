@@ -15,9 +15,9 @@
 //   reference's "lit" test — equivalent to testing the closest one, see candidate_occludes.
 //
 //   Inner-node culling only has to be CONSERVATIVE (never reject a box the exact test accepts):
-//   slab_fast() replaces the six IEEE divisions by multiplications with 1/d and widens the
-//   interval by 2^-20 relative + 2^-100 absolute, which covers the <= 3*2^-24 relative
-//   difference between fl(a*fl(1/d)) and fl(a/d) (DESIGN.md "Conservative culling").
+//   the multiply-based test (slab_fast_fma, box_mask, advance_to_leaf) replaces the six IEEE
+//   divisions by multiplications with 1/d and widens the interval, or moves the planes outwards,
+//   by more than fl(a*fl(1/d)) and fl(a/d) can differ (DESIGN.md "Conservative culling").
 //
 //   All of the above holds for rays whose direction components are regular (non-zero, normal,
 //   finite).  Rays with a zero component are outside it — the reference's result then depends on
@@ -76,26 +76,14 @@ __device__ __forceinline__ bool slab_exact(float lox, float loy, float loz, floa
 }
 
 // Conservative superset of slab_exact for rays whose direction components are all finite and of
-// magnitude >= 2^-60 (so 1/d is finite and no product is NaN).  ix,iy,iz = 1/d (IEEE division).
-//   exact   q = fl(fl(p-o)/d)          mine  t = fl(fl(p-o)*fl(1/d)),  |t-q| <= 3*2^-24 |q| (+ underflow)
+// magnitude >= 2^-60 (so 1/d is finite and no product is NaN).  ix,iy,iz = 1/d.
+//   exact   q = fl(fl(p-o)/d)          multiplied  t = fl(fl(p-o)*fl(1/d)),  |t-q| <= 3*2^-24 |q| (+ underflow)
 // near/far per axis = min/max of the two products (same planes as the sign-of-d selection), entry =
 // max of nears, exit = min of fars; the exact test passes only if every near <= every far and every
 // far > 0, so rejecting only when entry exceeds exit by more than the widening, or exit is clearly
 // negative, never rejects a box the exact test accepts (also covers its origin-inside shortcut:
 // then every near <= 0 <= every far).
-__device__ __forceinline__ bool slab_fast(float lox, float loy, float loz, float hix, float hiy, float hiz,
-                                          float ox, float oy, float oz, float ix, float iy, float iz)
-{
-    const float ax = (lox - ox) * ix, bx = (hix - ox) * ix;
-    const float ay = (loy - oy) * iy, by = (hiy - oy) * iy;
-    const float az = (loz - oz) * iz, bz = (hiz - oz) * iz;
-    const float t_in = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-    const float t_out = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-    const float slack = __builtin_fmaf(fabsf(t_in) + fabsf(t_out), 0x1p-20f, 0x1p-100f);
-    return !(t_in - t_out > slack) && !(t_out < -0x1p-100f);   // written so that a NaN can only accept
-}
-
-// slab_fast with one fused multiply-add per plane: t = fma(plane, 1/d, -(o*(1/d))).  Culling only — no pixel
+// Here with one fused multiply-add per plane: t = fma(plane, 1/d, -(o*(1/d))).  Culling only — no pixel
 // value depends on these numbers — so a fused operation is allowed here.  Against the exact quotient q:
 //   t = T(1+e_r)(1+e_f) - (o/d)(1+e_r) e_m,  T = (plane-o)/d,   |t - q| <= 4*2^-24 |t| + 1.01*2^-24 |o/d|
 // (e_r: rounding of 1/d, e_m: of o*(1/d), e_f: of the fma).  The second term does not shrink with t, so the
@@ -318,7 +306,7 @@ __device__ __forceinline__ void ray_cull_constants(LaneRay &r)
 {
     // Culling only: v_rcp_f32 (1 ulp, e_r <= 2^-23 instead of 2^-24) replaces the ten-instruction IEEE division.
     // The bound of slab_fast_fma becomes 5*2^-24 |t| + 1.01*2^-24 |o/d|, still three times inside its widening
-    // (slab_fast: 6*2^-24 against 16*2^-24).  Regular directions only reach these values: 2^-60 <= |d| <= 2.
+    // (6*2^-24 against 16*2^-24).  Regular directions only reach these values: 2^-60 <= |d| <= 2.
     r.ix = __builtin_amdgcn_rcpf(r.dx); r.iy = __builtin_amdgcn_rcpf(r.dy); r.iz = __builtin_amdgcn_rcpf(r.dz);
     const float px = r.ox * r.ix, py = r.oy * r.iy, pz = r.oz * r.iz;
     r.nx = -px; r.ny = -py; r.nz = -pz;
@@ -333,55 +321,15 @@ __device__ __forceinline__ LaneRay make_ray(bool active, float ox, float oy, flo
     return r;
 }
 
-#ifndef RTX_CULL_FMA
-#define RTX_CULL_FMA 1
-#endif
-
-// slab_fast_fma with the six plane distances as three packed fused multiply-adds (v_pk_fma_f32: two IEEE f32 fmas per
-// instruction, each half rounded like the scalar one).  The pairs are the adjacent registers of the node record.
-typedef float pk2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bool slab_fast_fma_packed(const NodeRec &n, const LaneRay &r)
-{
-    const pk2 ixy = {r.ix, r.iy}, nxy = {r.nx, r.ny}, izz = {r.iz, r.iz}, nzz = {r.nz, r.nz};
-    const pk2 a = __builtin_elementwise_fma(pk2{n.bmin[0], n.bmin[1]}, ixy, nxy);   // near/far of x, y: low planes
-    const pk2 b = __builtin_elementwise_fma(pk2{n.bmax[0], n.bmax[1]}, ixy, nxy);   //                   high planes
-    const pk2 c = __builtin_elementwise_fma(pk2{n.bmin[2], n.bmax[2]}, izz, nzz);   // z: low, high
-    const float t_in = fmaxf(fmaxf(fminf(a.x, b.x), fminf(a.y, b.y)), fminf(c.x, c.y));
-    const float t_out = fminf(fminf(fmaxf(a.x, b.x), fmaxf(a.y, b.y)), fmaxf(c.x, c.y));
-    const float slack = __builtin_fmaf(fabsf(t_in) + fabsf(t_out), 0x1p-20f, r.slack0);
-    return !(t_in - t_out > slack) && !(t_out < r.behind);   // written so that a NaN can only accept
-}
-
-// The same test as the wave's vote: the lanes whose ray may pass the box.  Each comparison is voted on its own —
-// a vote on a compare IS the compare's lane mask, while a vote on the AND of two compares costs two more vector
-// instructions (the compiler rebuilds a per-lane integer and compares it again) — and the masks are combined by
-// the scalar unit.
-__device__ __forceinline__ unsigned long long slab_fast_fma_packed_mask(const NodeRec &n, const LaneRay &r)
-{
-    const pk2 ixy = {r.ix, r.iy}, nxy = {r.nx, r.ny}, izz = {r.iz, r.iz}, nzz = {r.nz, r.nz};
-    const pk2 a = __builtin_elementwise_fma(pk2{n.bmin[0], n.bmin[1]}, ixy, nxy);
-    const pk2 b = __builtin_elementwise_fma(pk2{n.bmax[0], n.bmax[1]}, ixy, nxy);
-    const pk2 c = __builtin_elementwise_fma(pk2{n.bmin[2], n.bmax[2]}, izz, nzz);
-    const float t_in = fmaxf(fmaxf(fminf(a.x, b.x), fminf(a.y, b.y)), fminf(c.x, c.y));
-    const float t_out = fminf(fminf(fmaxf(a.x, b.x), fmaxf(a.y, b.y)), fmaxf(c.x, c.y));
-    const float slack = __builtin_fmaf(fabsf(t_in) + fabsf(t_out), 0x1p-20f, r.slack0);
-    // "exit clearly behind the origin": against -slack instead of the ray constant -1.00001 E — slack >= E(1 - 2^-24),
-    // still eight times the absolute error term, and the negation is an operand modifier, not an instruction.
-    // (Tried and dropped, both measured slower on one box with interleaved runs although they remove six of the
-    //  sixteen vector instructions of this test: choosing each axis' near plane on the scalar unit for wavefronts whose
-    //  rays share an octant, +30 %; reading (near, far) from one of eight pre-swapped copies of the stream, +4..10 %.
-    //  The walk is a chain of dependent steps — scalar load, test, vote, branch — and at eight wavefronts per SIMD its
-    //  length costs as much as the instruction count.)
-    return ballot(!(t_in - t_out > slack)) & ballot(!(t_out < -slack));   // a NaN can only accept
-}
-
 // Packed f32 arithmetic does not pay in this kernel: with six single v_fma_f32 the frame is 4.5 % FASTER than with the
 // three v_pk_fma_f32 (same box, interleaved runs; 19 instead of 16 vector instructions per node), and packing the
 // cross and dot products of the triangle test — by the compiler (SLP) or by hand over a pair-ordered record — made it
-// 7-9 % slower.  The packed forms stay selectable.
-#ifndef RTX_CULL_PACKED
-#define RTX_CULL_PACKED 0
-#endif
+// 7-9 % slower.
+// (Tried and dropped with the packed form, both measured slower on one box with interleaved runs although they remove
+//  six of the sixteen vector instructions of the test: choosing each axis' near plane on the scalar unit for wavefronts
+//  whose rays share an octant, +30 %; reading (near, far) from one of eight pre-swapped copies of the stream, +4..10 %.
+//  The walk is a chain of dependent steps — scalar load, test, vote, branch — and at eight wavefronts per SIMD its
+//  length costs as much as the instruction count.)
 // (Requesting both possible successors of a node as soon as the node is there, so that the scalar-memory latency
 //  runs under the test, was measured 25 % slower — same box, interleaved runs: the scalar unit and its cache, one per
 //  compute unit, are as loaded as the vector units here, 0.75 G scalar against 0.92 G vector instructions per frame.)
@@ -389,14 +337,8 @@ __device__ __forceinline__ unsigned long long slab_fast_fma_packed_mask(const No
 __device__ __forceinline__ bool box_pass(bool use_fast, const NodeRec &n, const LaneRay &r)
 {
     if (use_fast) {
-#if RTX_CULL_FMA && RTX_CULL_PACKED
-        return slab_fast_fma_packed(n, r);
-#elif RTX_CULL_FMA
         return slab_fast_fma(n.bmin[0], n.bmin[1], n.bmin[2], n.bmax[0], n.bmax[1], n.bmax[2], r.ix, r.iy, r.iz,
                              r.nx, r.ny, r.nz, r.slack0, r.behind);
-#else
-        return slab_fast(n.bmin[0], n.bmin[1], n.bmin[2], n.bmax[0], n.bmax[1], n.bmax[2], r.ox, r.oy, r.oz, r.ix, r.iy, r.iz);
-#endif
     }
     return slab_exact(n.bmin[0], n.bmin[1], n.bmin[2], n.bmax[0], n.bmax[1], n.bmax[2], r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
 }
@@ -404,35 +346,21 @@ __device__ __forceinline__ bool box_pass(bool use_fast, const NodeRec &n, const 
 // lanes (of any kind, with or without a ray) whose box test passes
 __device__ __forceinline__ unsigned long long box_mask(bool use_fast, const NodeRec &n, const LaneRay &r)
 {
-#if RTX_CULL_FMA && RTX_CULL_PACKED
-    if (use_fast) return slab_fast_fma_packed_mask(n, r);
-#elif RTX_CULL_FMA
-    if (use_fast) {   // the same with six single fused multiply-adds
+    if (use_fast) {   // slab_fast_fma's plane distances, each comparison voted on its own
         const float ax = __builtin_fmaf(n.bmin[0], r.ix, r.nx), bx = __builtin_fmaf(n.bmax[0], r.ix, r.nx);
         const float ay = __builtin_fmaf(n.bmin[1], r.iy, r.ny), by = __builtin_fmaf(n.bmax[1], r.iy, r.ny);
         const float az = __builtin_fmaf(n.bmin[2], r.iz, r.nz), bz = __builtin_fmaf(n.bmax[2], r.iz, r.nz);
         const float t_in = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
         const float t_out = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-#if RTX_CULL_INFLATED
         // The planes in the stream lie delta = 2^-19 M further out than the box's (M: largest coordinate magnitude of
         // scene and eye; scene_prep: cull_delta).  In position units the fast distance of a plane is off by at most
         // 3*2^-24 |P - o| + 1.01*2^-24 |o| and the exact quotient by 2*2^-24 |p - o|, together < 11.01*2^-24 M < delta:
         // every fast near lies below the exact near, every fast far above the exact far, and the plain comparisons
         // reject nothing the exact test accepts — no per-test widening, three instructions fewer per node.
         return ballot(!(t_in > t_out)) & ballot(!(t_out < 0.0f));
-#else
-        const float slack = __builtin_fmaf(fabsf(t_in) + fabsf(t_out), 0x1p-20f, r.slack0);
-        return ballot(!(t_in - t_out > slack)) & ballot(!(t_out < -slack));
-#endif
     }
-#endif
     return ballot(box_pass(use_fast, n, r));
 }
-
-#ifndef RTX_TRIANGLE_EARLY_OUT
-#define RTX_TRIANGLE_EARLY_OUT 1
-#endif
-constexpr bool kTriangleEarlyOut = RTX_TRIANGLE_EARLY_OUT != 0;
 
 // The triangles of one leaf against the ray of every lane: Triangle::intersect (triangle.rs:66-94), the leaf
 // rule x < 1.0 -> None (bvh.rs:64-67), the leaf's own box (bvh.rs:52, exact arithmetic) and the tie rule.
@@ -508,31 +436,16 @@ __device__ __forceinline__ bool length_and_direction(float vx, float vy, float v
 }
 
 // A whole 64-byte primitive record with one scalar load, its byte offset in a scalar register (see load_node_at).
-#ifndef RTX_ASM_TRI_LOAD
-#define RTX_ASM_TRI_LOAD 1
-#endif
-// RTX_TRI_TOUCH_NEXT: with the record, one word of the NEXT record is requested (and thrown away): a leaf tests its
-// records one after another, each a dependent fetch of a line of its own, and in a scene whose records do not fit the
-// L2s (BASELINE configs[4]) each of them is a miss of several hundred cycles; this way the next one is on its way — into
-// L2 and the scalar cache — while the current one is tested.  The array has one spare record at its end (rtx_api.cpp).
-// (It paid -1 % on the 1M-triangle soup when it went in; since the primitive record's own box is tested first it costs
-//  1.4 % there — the box test leaves the next fetch less to hide behind — and nothing on the OBJ scenes: off.
+// (Requesting one word of the NEXT record with it, so that a leaf's dependent fetches overlap, paid -1 % on the
+//  1M-triangle soup when it went in; since the primitive record's own box is tested first it costs 1.4 % there — the box
+//  test leaves the next fetch less to hide behind — and nothing on the OBJ scenes: removed.
 //  profiles/r03/xj_ab_older_switches_again.log)
-#ifndef RTX_TRI_TOUCH_NEXT
-#define RTX_TRI_TOUCH_NEXT 0
-#endif
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ TriRec load_tri_at(const TriRec RTX_CONSTANT *base, uint32_t index)
 {
     u32x16 v;
     const uint32_t byte_offset = index << 6;
-#if RTX_TRI_TOUCH_NEXT
-    uint32_t touched;
-    asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dword %1, %2, %3 offset:0x40\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(v), "=&s"(touched) : "s"(base), "s"(byte_offset));
-#else
     asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(base), "s"(byte_offset));
-#endif
     TriRec t;
     t.v0[0] = __uint_as_float(v[0]); t.v0[1] = __uint_as_float(v[1]); t.v0[2] = __uint_as_float(v[2]);
     t.e1[0] = __uint_as_float(v[3]); t.e1[1] = __uint_as_float(v[4]); t.e1[2] = __uint_as_float(v[5]);
@@ -589,9 +502,6 @@ __device__ __forceinline__ TriRec load_tri_vec(const TriRec RTX_CONSTANT *base, 
 }
 #endif
 
-#ifndef RTX_TRI_BOX_FIRST      // 1: shadow walks test a primitive record's own box before the primitive; 2: all walks; 0: none
-#define RTX_TRI_BOX_FIRST 1
-#endif
 template <bool COUNT, bool ANYHIT = false, bool FAST_OK = false, bool VEC = false>
 __device__ __forceinline__ void leaf_triangles(const TriRec RTX_CONSTANT *__restrict__ tris,
                                                const ShadeRec *__restrict__ shade, uint32_t first, uint32_t count,
@@ -600,30 +510,26 @@ __device__ __forceinline__ void leaf_triangles(const TriRec RTX_CONSTANT *__rest
 {
     const bool was_active = r.active;
     for (uint32_t k = 0; k < count; ++k) {
-#if RTX_ABLATION && RTX_ASM_TRI_LOAD
+#if RTX_ABLATION
         const TriRec rec = VEC ? load_tri_vec(tris, first + k) : load_tri_at(tris, first + k);
         const TriRec *tr = &rec;
-#elif RTX_ASM_TRI_LOAD
+#else
         const TriRec rec = load_tri_at(tris, first + k);
         const TriRec *tr = &rec;
-#else
-        const TriRec RTX_CONSTANT *tr = tris + (first + k);
 #endif
         const float v0x = tr->v0[0], v0y = tr->v0[1], v0z = tr->v0[2];
         const float e1x = tr->e1[0], e1y = tr->e1[1], e1z = tr->e1[2];
         const float e2x = tr->e2[0], e2y = tr->e2[1], e2z = tr->e2[2];
         if (COUNT) { wc.tri_tests += n_active; wc.tri_visits += 1; }
-#if RTX_TRI_BOX_FIRST
         // The record's own box first (a candidate must pass it anyway: own_box_passes), for half of what the first part of the
         // primitive test costs: a record whose box no walking ray passes is not tested at all.  (Culling only: the
         // multiply-based test in its self-widening form — these boxes are the exact ones, not moved outwards like the
         // stream's.  Only when few rays are left: the count and its branch cost more than the test saves.)
-        if ((ANYHIT || RTX_TRI_BOX_FIRST == 2) && FAST_OK && !VEC) {
+        if (ANYHIT && FAST_OK && !VEC) {   // shadow walks only
             // (the record's box is the exact one, not moved outwards like the stream's: the test widens itself, slab_fast_fma)
             if ((ballot(slab_fast_fma(tr->bmin[0], tr->bmin[1], tr->bmin[2], tr->bmax[0], tr->bmax[1], tr->bmax[2], r.ix, r.iy, r.iz,
                                       r.nx, r.ny, r.nz, r.slack0, r.behind)) & alive) == 0ull) continue;
         }
-#endif
         const float pvx = r.dy * e2z - r.dz * e2y;                                   // :69
         const float pvy = r.dz * e2x - r.dx * e2z;
         const float pvz = r.dx * e2y - r.dy * e2x;
@@ -636,8 +542,7 @@ __device__ __forceinline__ void leaf_triangles(const TriRec RTX_CONSTANT *__rest
         // no lane can hit this triangle any more: skip the second half of the test for the whole wavefront
         // (one vote per comparison, combined by the scalar unit; `alive` may still hold lanes that found their
         //  occluder in this leaf — a superset only makes the skip rarer)
-        if (kTriangleEarlyOut &&
-            (ballot(!(fabsf(det) < 0.00001f)) & ballot(!(u < 0.0f)) & ballot(!(u > 1.0f)) & alive) == 0ull) continue;
+        if ((ballot(!(fabsf(det) < 0.00001f)) & ballot(!(u < 0.0f)) & ballot(!(u > 1.0f)) & alive) == 0ull) continue;
         const float qvx = tvy * e1z - tvz * e1y;                                     // :84
         const float qvy = tvz * e1x - tvx * e1z;
         const float qvz = tvx * e1y - tvy * e1x;
@@ -703,18 +608,6 @@ __device__ __forceinline__ void leaf_spheres(const TriRec RTX_CONSTANT *__restri
 // only emits the form with a 64-bit address it first assembles with four scalar instructions, and the scalar unit —
 // one per compute unit — is as loaded as the vector units in this loop.  The wait is part of the statement: the
 // compiler does not count a load it has not issued itself.
-#ifndef RTX_ASM_NODE_LOAD
-#define RTX_ASM_NODE_LOAD 1
-#endif
-#ifndef RTX_SKIP_ROOT_TEST
-#define RTX_SKIP_ROOT_TEST 1
-#endif
-#ifndef RTX_WALK_INTEGER_FLAGS
-#define RTX_WALK_INTEGER_FLAGS 1
-#endif
-#ifndef RTX_WALK_SINGLE_EXIT
-#define RTX_WALK_SINGLE_EXIT 1
-#endif
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ NodeRec load_node_at(const NodeRec RTX_CONSTANT *base, uint32_t index)
 {
@@ -749,8 +642,8 @@ __device__ __forceinline__ NodeRec load_node_at(const NodeRec RTX_CONSTANT *base
 // carry 2^-100 for flushed products.  The kernel evaluates this next to the ray's set-up, for the FIRST global
 // triangle only, and tells the walk to leave that triangle out when every one of its lanes is certified.
 // The part of the certificate that depends on the ray's ORIGIN only (a full tile's lane keeps its origin for a whole
-// job: rtx_kernel.hip, shadow_ray_full): lhs = (|s_n| + k A_n)(1 + 2^-19), and s_n itself where |s_n| > k A_n, else 0
-// (a zero makes "moving away" false).
+// job: rtx_kernel.hip, the open-ground loop of shade_tiles_kernel): lhs = (|s_n| + k A_n)(1 + 2^-19), and s_n itself
+// where |s_n| > k A_n, else 0 (a zero makes "moving away" false).
 struct PlaneOrigin { float lhs, sn; };
 __device__ __forceinline__ PlaneOrigin plane_origin(const TriRec &g, float ox, float oy, float oz)
 {
@@ -771,13 +664,8 @@ __device__ __forceinline__ bool plane_rules_out(const TriRec &g, const PlaneOrig
     const bool away = po.sn * sd > 0.0f && fabsf(sd) > kd;
     return magnitude || away;
 }
-// (the "magnitude" half alone — all there is for an origin ON the plane, whose PlaneOrigin::sn is 0; for any other
-//  origin it certifies less, never more)
-__device__ __forceinline__ bool plane_magnitude(const TriRec &g, const PlaneOrigin &po, float dx, float dy, float dz)
-{
-    const float sd = __builtin_fmaf(dz, g.e1[2], __builtin_fmaf(dy, g.e1[1], dx * g.e1[0]));
-    return po.lhs < fabsf(sd) - g.bmin[0];
-}
+// (The "magnitude" half alone is all there is for an origin ON the plane, whose PlaneOrigin::sn is 0; for any other
+//  origin it certifies less, never more: shade_tiles_kernel's open-ground loop evaluates only that half.)
 __device__ __forceinline__ bool plane_rules_out(const TriRec &g, float ox, float oy, float oz, float dx, float dy, float dz)
 {
     return plane_rules_out(g, plane_origin(g, ox, oy, oz), dx, dy, dz);
@@ -813,23 +701,13 @@ __device__ __forceinline__ bool plane_rules_out(const TriRec &g, float ox, float
 // taken apart inside the assembly text, and the steps need words 0-5 as vector operands and 6, 7 on the scalar unit.
 // On return: info = the leaf's info word (bit 31 set) and link = its record count, off = the leaf's offset — or info = 0
 // and off >= end.  `visits` counts the records fetched (COUNT builds only).
-#ifndef RTX_ASM_WALK
-#define RTX_ASM_WALK 1
-#endif
-#ifndef RTX_OCTANT_STEP
-#define RTX_OCTANT_STEP 1
-#endif
 // the octant of the walking lanes' directions (bit a: component a negative), 8 when they differ; ix, iy, iz = 1/d, regular
 __device__ __forceinline__ uint32_t walk_octant(const LaneRay &r, unsigned long long alive)
 {
-#if RTX_OCTANT_STEP
     const unsigned long long mx = ballot(r.ix < 0.0f) & alive, my = ballot(r.iy < 0.0f) & alive, mz = ballot(r.iz < 0.0f) & alive;
     const bool uniform = (mx == 0ull || mx == alive) && (my == 0ull || my == alive) && (mz == 0ull || mz == alive);
     // (readfirstlane: the compiler otherwise forms this wave-uniform integer with vector selects and hands the assembly a vector register)
     return __builtin_amdgcn_readfirstlane(uniform ? (mx != 0ull ? 1u : 0u) | (my != 0ull ? 2u : 0u) | (mz != 0ull ? 4u : 0u) : 8u);
-#else
-    return 8u;
-#endif
 }
 // PRUNE (closest-hit walks): a box is also left out when every walking lane enters it BEYOND the lane's closest hit so
 // far.  The reference never prunes by distance — it takes the minimum over every candidate (bvh.rs:86-132) — but a
@@ -839,9 +717,6 @@ __device__ __forceinline__ uint32_t walk_octant(const LaneRay &r, unsigned long 
 // (a candidate's t and a box's entry are formed by different roundings of the same geometry: ulps apart at most).  One
 // vector instruction per record (exit = min(exit, far)); what it saves is every record behind the first surface a tile's
 // primary rays meet.
-#ifndef RTX_PRUNE_CLOSEST
-#define RTX_PRUNE_CLOSEST 1
-#endif
 template <bool COUNT, bool PRUNE = false>
 __device__ __forceinline__ void advance_to_leaf(const NodeRec RTX_CONSTANT *__restrict__ nodes, uint32_t &off, uint32_t end,
                                                 unsigned long long alive, const LaneRay &r, uint32_t oct, uint32_t &link,
@@ -1007,8 +882,8 @@ __device__ __forceinline__ unsigned long long walk_range_fast(const NodeRec RTX_
     for (;;) {
         uint32_t link, info, visits = 0u;
         // (closest-hit walks: boxes entered beyond the closest hit so far are left out — advance_to_leaf, PRUNE)
-        advance_to_leaf<COUNT, !ANYHIT && RTX_PRUNE_CLOSEST != 0>(nodes, off, end_off, alive, r, oct, link, info, visits,
-                                                                  r.best_t * (1.0f + 0x1p-16f));
+        advance_to_leaf<COUNT, !ANYHIT>(nodes, off, end_off, alive, r, oct, link, info, visits,
+                                        r.best_t * (1.0f + 0x1p-16f));
         if (COUNT) { wc.box_tests += n_active * visits; wc.node_visits += visits; }
         if (info == 0u) break;
         if (SPHERES && (info & kSphereFlag))
@@ -1036,16 +911,9 @@ __device__ __forceinline__ unsigned long long walk_range(const NodeRec RTX_CONST
                                                          unsigned long long &n_active, WaveCounters &wc,
                                                          uint32_t oct_known = kNone)
 {
-#if RTX_ASM_WALK && RTX_CULL_FMA && RTX_CULL_INFLATED && !RTX_CULL_PACKED
     if (USE_FAST) return walk_range_fast<COUNT, SPHERES, ANYHIT>(nodes, tris, shade, i, end, r, alive, n_active, wc, oct_known);
-#endif
     while (i < end) {
-#if RTX_ASM_NODE_LOAD
         const NodeRec cur = load_node_at(nodes, i);
-#else
-        const NodeRec cur = load_node(nodes + i);
-#endif
-#if RTX_WALK_INTEGER_FLAGS
         // The step's two conditions as 0/1 integers in scalar registers, combined by integer instructions: as booleans
         // the compiler turns each into a lane mask and back (s_cselect_b64, s_and_b64 with exec, ...), and the scalar
         // unit is as loaded as the vector units here.  (s_and_b64 sets SCC when its result is not zero.)
@@ -1054,11 +922,6 @@ __device__ __forceinline__ unsigned long long walk_range(const NodeRec RTX_CONST
         uint32_t any_u;
         asm("s_and_b64 vcc, %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(any_u) : "s"(hits), "s"(alive) : "vcc", "scc");
         const bool visit = (leaf_u & any_u) != 0u, onward = (leaf_u | any_u) != 0u;
-#else
-        const bool leaf = (cur.info & kLeafFlag) != 0u;
-        const bool any = (box_mask(USE_FAST, cur, r) & alive) != 0ull;
-        const bool visit = leaf && any, onward = any || leaf;
-#endif
         if (COUNT) { wc.box_tests += n_active; wc.node_visits += 1; }
         if (visit) {
             if (SPHERES && (cur.info & kSphereFlag))
@@ -1067,16 +930,11 @@ __device__ __forceinline__ unsigned long long walk_range(const NodeRec RTX_CONST
                 leaf_triangles<COUNT, ANYHIT, USE_FAST>(tris, shade, cur.info & kLeafIndexMask, cur.link, r, alive, n_active, wc);
             if (ANYHIT) {   // lanes that found an occluder have left the walk (r.active); so does a wavefront without lanes
                 alive = ballot(r.active);
-#if RTX_WALK_SINGLE_EXIT
                 if (alive == 0ull) i = end - 1u;        // the step below ends the walk: the loop keeps ONE exit test
-#else
-                if (alive == 0ull) break;
-#endif
                 if (COUNT) n_active = __popcll(alive);
             }
         }
         // after a leaf (visited or not) and into a passed inner node: next record in pre-order; else skip the subtree
-#if RTX_WALK_INTEGER_FLAGS
         if (LEAN) {   // the same select with SCC taken from the OR itself (one scalar instruction less per record); only
                       // where the kernel has scalar registers to spare: probe_kernel, at 103, does not build with it
             uint32_t next;
@@ -1085,9 +943,6 @@ __device__ __forceinline__ unsigned long long walk_range(const NodeRec RTX_CONST
         } else {
             i = onward ? i + 1u : cur.link;
         }
-#else
-        i = onward ? i + 1u : cur.link;
-#endif
     }
     return alive;
 }
@@ -1104,8 +959,8 @@ __device__ __forceinline__ void walk_stream(const NodeRec RTX_CONSTANT *__restri
     // The root's own test is skipped when the root is an inner node (a stream of more than one record): culling
     // only has to be a superset, and nothing is lost — a candidate passes its own box, hence (section 2 of
     // DESIGN.md) every enclosing box, the root's included.  One node in thirteen on the default scene.
-    uint32_t i = (RTX_SKIP_ROOT_TEST && n_nodes > 1u) ? 1u : 0u;
-    if (RTX_SKIP_ROOT_TEST && n_global != 0u) {
+    uint32_t i = n_nodes > 1u ? 1u : 0u;
+    if (n_global != 0u) {
         // the "global" triangles (scene_prep.cpp: as large as the scene, i.e. the ground) sit in the leaf at node 1:
         // tested here without its box test, then the walk starts at the root of the tree proper
         leaf_triangles<COUNT, ANYHIT, USE_FAST>(tris, shade, first_global, n_global - first_global, r, alive, n_active, wc);
@@ -1159,158 +1014,12 @@ __device__ __forceinline__ bool any_hit(const NodeRec RTX_CONSTANT *__restrict__
     return closest_hit<COUNT, FAST, SPHERES, true, LEAN>(nodes, tris, shade, n_nodes, r, wc, n_global, first_global_ruled_out);
 }
 
-// ---- the wide walk (A/B builds only: -DRTX_WIDE_WALK=1 / -DRTX_PROBE_WIDE=1; librtx.so walks the binary stream) -------
-// Measured slower than the binary walk in every form that was tried, kept for comparison.
-// The same tree with FOUR children per node (scene_prep.h: WideNode).  A step fetches one
-// 128-byte node with two scalar loads, tests its four child boxes in one stretch of vector code, votes once per child
-// and then handles the children whose vote is not empty: a leaf child's primitives are tested on the spot, an inner
-// child goes onto the wave's stack — the 64 lanes of ONE vector register, written and read by lane number, so a push
-// and a pop are two instructions and touch no memory.  The reference never prunes by distance, so the order of the
-// visits is free; what matters is the cost of the step's scalar skeleton (the scalar unit serves the whole compute unit,
-// four wavefronts' vector units wait on it): the binary walk paid about fifteen scalar instructions per BOX — its
-// fetch, wait, votes, leaf test and successor select — this one pays them per FOUR boxes, and a walk is a third as many
-// dependent steps long.  Same candidate set: every child box is the box of a node of the binary tree, i.e. a box that
-// contains the exact boxes of the leaves below it.
-__device__ __forceinline__ void load_wide_at(const WideNode RTX_CONSTANT *base, uint32_t byte_offset, u32x16 &a, u32x16 &b)
-{
-    asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx16 %1, %2, %3 offset:0x40\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(a), "=&s"(b) : "s"(base), "s"(byte_offset));
-}
-
-// lanes whose ray may pass the (moved-out, see box_mask) box: ONE vote — entry, not before the origin, <= exit
-template <bool USE_FAST>
-__device__ __forceinline__ unsigned long long wide_child_mask(uint32_t ulox, uint32_t uloy, uint32_t uloz, uint32_t uhix,
-                                                              uint32_t uhiy, uint32_t uhiz, const LaneRay &r)
-{
-    const float lox = __uint_as_float(ulox), loy = __uint_as_float(uloy), loz = __uint_as_float(uloz);
-    const float hix = __uint_as_float(uhix), hiy = __uint_as_float(uhiy), hiz = __uint_as_float(uhiz);
-    if (USE_FAST) {
-        const float ax = __builtin_fmaf(lox, r.ix, r.nx), bx = __builtin_fmaf(hix, r.ix, r.nx);
-        const float ay = __builtin_fmaf(loy, r.iy, r.ny), by = __builtin_fmaf(hiy, r.iy, r.ny);
-        const float az = __builtin_fmaf(loz, r.iz, r.nz), bz = __builtin_fmaf(hiz, r.iz, r.nz);
-        const float t_in = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-        const float t_out = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-        return ballot(!(fmaxf(t_in, 0.0f) > t_out));      // = !(t_in > t_out) && !(t_out < 0); a NaN can only accept
-    }
-    return ballot(slab_exact(lox, loy, loz, hix, hiy, hiz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz));
-}
-
-// The walk below the wide node at byte offset `entry`; returns the lanes still walking (see walk_range).
-// A step: pop a wide node, fetch it, test its four boxes, then sort the children whose vote is not empty by kind —
-// inner children are pushed (by predication, no branch: a push is a select on the lane number), leaf children are
-// queued in four scalar registers and their primitives tested right away, in ONE loop with one call site.  An any-hit
-// walk whose lanes have all found their occluder empties stack and queue instead of leaving the loops.  Everything that
-// steers the loops is a 0/1 integer in a scalar register (cf. walk_range).
-template <bool COUNT, bool SPHERES, bool ANYHIT, bool USE_FAST>
-__device__ __forceinline__ unsigned long long walk_wide(const WideNode RTX_CONSTANT *__restrict__ wide,
-                                                        const TriRec RTX_CONSTANT *__restrict__ tris,
-                                                        const ShadeRec *__restrict__ shade, uint32_t entry, LaneRay &r,
-                                                        unsigned long long alive, unsigned long long &n_active,
-                                                        WaveCounters &wc)
-{
-    const uint32_t lane_id = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    uint32_t stack = entry;   // lane k: byte offset of the k-th pending wide node; lane 0 = entry
-    uint32_t sp = 1u;         // wave-uniform
-    do {
-        --sp;
-        const uint32_t x = __builtin_amdgcn_readlane(stack, sp);
-        u32x16 a, b;
-        load_wide_at(wide, x, a, b);
-        const unsigned long long m0 = wide_child_mask<USE_FAST>(a[0], a[1], a[2], a[3], a[4], a[5], r);
-        const unsigned long long m1 = wide_child_mask<USE_FAST>(a[6], a[7], a[8], a[9], a[10], a[11], r);
-        const unsigned long long m2 = wide_child_mask<USE_FAST>(a[12], a[13], a[14], a[15], b[0], b[1], r);
-        const unsigned long long m3 = wide_child_mask<USE_FAST>(b[2], b[3], b[4], b[5], b[6], b[7], r);
-        if (COUNT) { wc.box_tests += 4ull * n_active; wc.node_visits += 1; }
-        // p = a walking lane passes the child's box; leaf children go to the queue (q0 first), inner ones to the stack
-        uint32_t q0 = 0u, q1 = 0u, q2 = 0u, q3 = 0u, nq = 0u;
-#define RTX_WIDE_SORT(mask, ref)                                                                                          \
-        {                                                                                                                \
-            uint32_t p;                                                                                                  \
-            asm("s_and_b64 vcc, %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(p) : "s"(mask), "s"(alive) : "vcc", "scc");       \
-            const uint32_t is_leaf = (ref) >> 31, pl = p & is_leaf, pi = p & ~is_leaf;                                   \
-            const uint32_t slot = pi ? sp : 64u;                                                                         \
-            stack = lane_id == slot ? (ref) : stack;                                                                     \
-            sp += pi;                                                                                                    \
-            q3 = pl ? q2 : q3; q2 = pl ? q1 : q2; q1 = pl ? q0 : q1; q0 = pl ? (ref) : q0;                               \
-            nq += pl;                                                                                                    \
-        }
-        RTX_WIDE_SORT(m0, b[8])
-        RTX_WIDE_SORT(m1, b[9])
-        RTX_WIDE_SORT(m2, b[10])
-        RTX_WIDE_SORT(m3, b[11])
-#undef RTX_WIDE_SORT
-        while (nq != 0u) {
-            const uint32_t leaf = q0;
-            q0 = q1; q1 = q2; q2 = q3;
-            --nq;
-            const uint32_t first = leaf & kWideLeafFirstMask, count = (leaf >> kWideLeafCountShift) & 31u;
-            if (SPHERES && (leaf & kSphereFlag))
-                leaf_spheres<COUNT, ANYHIT>(tris, shade, first, count, r, n_active, wc);
-            else
-                leaf_triangles<COUNT, ANYHIT, USE_FAST>(tris, shade, first, count, r, alive, n_active, wc);
-            if (ANYHIT) {   // lanes that found an occluder have left the walk; so does a wavefront without lanes
-                alive = ballot(r.active);
-                if (alive == 0ull) { sp = 0u; nq = 0u; }
-                if (COUNT) n_active = __popcll(alive);
-            }
-        }
-    } while (sp != 0u);
-    return alive;
-}
-
-// One closest-hit (ANYHIT: any-hit) traversal of the wide tree; the rules of closest_hit above apply (false and no
-// trace when an active lane's direction is hard; the exact box test when one is soft).  cut: NULL = the whole tree,
-// else LDS words, n_cut pairs whose first word is the byte offset of a wide node the walk starts from (shaft_cut_wide).
-template <bool COUNT, bool FAST, bool SPHERES, bool ANYHIT>
-__device__ __forceinline__ bool hit_wide(const WideNode RTX_CONSTANT *__restrict__ wide, uint32_t n_wide,
-                                         const TriRec RTX_CONSTANT *__restrict__ tris,
-                                         const ShadeRec *__restrict__ shade, const uint32_t *__restrict__ cut,
-                                         uint32_t n_cut, LaneRay &r, WaveCounters &wc, uint32_t n_global,
-                                         bool first_global_ruled_out)
-{
-    unsigned long long alive = ballot(r.active);
-    const unsigned long long regular = ballot(fabsf(r.dx) >= 0x1p-60f) & ballot(fabsf(r.dx) <= 2.0f) &
-                                       ballot(fabsf(r.dy) >= 0x1p-60f) & ballot(fabsf(r.dy) <= 2.0f) &
-                                       ballot(fabsf(r.dz) >= 0x1p-60f) & ballot(fabsf(r.dz) <= 2.0f);
-    const bool all_regular = (alive & ~regular) == 0ull;          // direction classes: see closest_hit
-    if (!all_regular && ballot(r.active && direction_is_hard(r.dx, r.dy, r.dz)) != 0ull) return false;
-    unsigned long long n_active = 0;
-    if (COUNT) n_active = __popcll(alive);
-    const bool use_fast = FAST && all_regular;
-    if (n_global != 0u) {   // the global triangles (the ground): every walk tests them, without a box test
-        const uint32_t first = (use_fast && first_global_ruled_out) ? 1u : 0u;
-        if (use_fast) leaf_triangles<COUNT, ANYHIT, true>(tris, shade, first, n_global - first, r, alive, n_active, wc);
-        else leaf_triangles<COUNT, ANYHIT, false>(tris, shade, first, n_global - first, r, alive, n_active, wc);
-        if (ANYHIT) {
-            alive = ballot(r.active);
-            if (alive == 0ull) return true;
-            if (COUNT) n_active = __popcll(alive);
-        }
-    }
-    if (n_wide == 0u) return true;
-    if (cut == nullptr) {
-        if (use_fast) (void)walk_wide<COUNT, SPHERES, ANYHIT, true>(wide, tris, shade, 0u, r, alive, n_active, wc);
-        else (void)walk_wide<COUNT, SPHERES, ANYHIT, false>(wide, tris, shade, 0u, r, alive, n_active, wc);
-        return true;
-    }
-    for (uint32_t k = 0; k < n_cut; ++k) {
-        const uint32_t entry = __builtin_amdgcn_readfirstlane(cut[kCutWords * k]);
-        if (use_fast) alive = walk_wide<COUNT, SPHERES, ANYHIT, true>(wide, tris, shade, entry, r, alive, n_active, wc);
-        else alive = walk_wide<COUNT, SPHERES, ANYHIT, false>(wide, tris, shade, entry, r, alive, n_active, wc);
-        if (ANYHIT && alive == 0ull) break;
-    }
-    return true;
-}
-
 // The shadow walk of a chunk whose tile carries a CUT of the tree (rtx_kernel.hip: shaft_cut): the subtrees — record
 // ranges [begin, end) of the stream, at most kMaxCut of them — that the tile's shaft towards the light can touch.
 // Every box a ray of the tile passes lies in one of them (or holds one), so walking the ranges one after another
 // visits a superset of the candidates the whole-stream walk would find among the occluders, and an any-hit result does
 // not depend on the order.  The upper levels of the tree, which the hundred chunks of a tile would otherwise descend a
 // hundred times, are walked once per tile.  cut: LDS, (begin, end) pairs.
-#ifndef RTX_CUT_RING
-#define RTX_CUT_RING 1
-#endif
 template <bool COUNT, bool SPHERES, bool USE_FAST, bool LEAN>
 __device__ __forceinline__ void walk_cut(const NodeRec RTX_CONSTANT *__restrict__ nodes,
                                          const TriRec RTX_CONSTANT *__restrict__ tris,
@@ -1332,10 +1041,10 @@ __device__ __forceinline__ void walk_cut(const NodeRec RTX_CONSTANT *__restrict_
     //  exit costs five scalar instructions per record there, this nesting three, the whole-stream walk none.)
     const uint32_t oct = USE_FAST ? walk_octant(r, alive) : kNone;   // once per chunk (advance_to_leaf); later walkers are among these lanes
     // The entries are walked in a ring that begins where the wavefront's previous walk ENDED — the entry in which its last
-    // ray found an occluder (RTX_CUT_RING).  The order is free (any-hit), and while a triangle rarely occludes the next
+    // ray found an occluder.  The order is free (any-hit), and while a triangle rarely occludes the next
     // light point's ray as well (profiles/r03/y_*), the PART of the mesh that does is the same for all of a tile's chunks:
     // walks that end with every ray occluded are half of a frame's record fetches.
-    uint32_t k = (RTX_CUT_RING && first_entry < n_cut) ? first_entry : 0u;
+    uint32_t k = first_entry < n_cut ? first_entry : 0u;
     for (uint32_t j = 0; j < n_cut; ++j, k = (k + 1u == n_cut) ? 0u : k + 1u) {
         const uint32_t *e = cut + kCutWords * k;
         NodeRec root;   // NodeDev order: lo.x lo.y hi.x hi.y lo.z hi.z link info
@@ -1392,20 +1101,17 @@ __device__ __forceinline__ void walk_cut_stream(const NodeRec RTX_CONSTANT *__re
         if ((box_mask(USE_FAST, all, r) & alive) == 0ull) return;
     }
     const uint32_t oct = USE_FAST ? walk_octant(r, alive) : kNone;
-    uint32_t start = __builtin_amdgcn_readfirstlane((RTX_CUT_RING && first_entry < n_cut) ? first_entry << 5 : 0u);
+    uint32_t start = __builtin_amdgcn_readfirstlane(first_entry < n_cut ? first_entry << 5 : 0u);
     uint32_t off = start, end_off = __builtin_amdgcn_readfirstlane(n_cut << 5);
     for (;;) {
         while (off < end_off) {
             uint32_t link, info;
-#if RTX_ASM_WALK && RTX_CULL_FMA && RTX_CULL_INFLATED && !RTX_CULL_PACKED
             if (USE_FAST) {
                 uint32_t visits = 0u;
                 advance_to_leaf<COUNT, false>(cut, off, end_off, alive, r, oct, link, info, visits, 0.0f);
                 if (COUNT) { wc.box_tests += n_active * visits; wc.node_visits += visits; }
                 if (info == 0u) break;
-            } else
-#endif
-            {
+            } else {
                 const NodeRec cur = load_node_at(cut, off >> 5);
                 if (COUNT) { wc.box_tests += n_active; wc.node_visits += 1; }
                 if ((box_mask(USE_FAST, cur, r) & alive) == 0ull) { off += 32u; continue; }

@@ -330,8 +330,8 @@ public:
     // depth_cap: levels the tree may have.  A range that could not be finished within the cap by halving is halved
     // from there on (median split along its widest centroid axis) instead of split by the SAH.
     TreeBuilder(std::vector<Prim> &prims, std::vector<NodeRec> &nodes, uint32_t leaf_max, double box_cost,
-                uint32_t depth_cap = 64u, const float *light = nullptr, bool near_first = false)
-        : prims_(prims), nodes_(nodes), leaf_max_(leaf_max), box_cost_(box_cost), depth_cap_(depth_cap), light_(light), near_first_(near_first) {}
+                uint32_t depth_cap = 64u, const float *light = nullptr)
+        : prims_(prims), nodes_(nodes), leaf_max_(leaf_max), box_cost_(box_cost), depth_cap_(depth_cap), light_(light) {}
 
     uint32_t leaves = 0, max_leaf = 0, depth = 0;
 
@@ -407,7 +407,7 @@ public:
             return d2;
         };
         const bool first_is_nearer = mean_dist2(begin, mid) < mean_dist2(mid, end);
-        if (first_is_nearer == near_first_) return mid;                       // already in the wanted order
+        if (!first_is_nearer) return mid;                                     // already in the wanted order
         std::rotate(prims_.begin() + begin, prims_.begin() + mid, prims_.begin() + end);
         return begin + (end - mid);
     }
@@ -478,138 +478,10 @@ private:
     uint32_t leaf_max_;
     double box_cost_;
     uint32_t depth_cap_;
-    const float *light_;   // NULL: children in the order the split made them
-    bool near_first_;      // the child nearer to *light_ first (else second)
+    const float *light_;   // NULL: children in the order the split made them; else the child nearer to *light_ second
 };
 
 }  // namespace
-
-// The binary tree with grandchildren pulled up: starting from a node's two children, the inner child with the largest
-// box is replaced by its own two children until four slots are used or only leaves remain.  Visiting order is free
-// (the reference never prunes by distance), so the slots keep the order in which they were filled.  A leaf of more
-// than kWideLeafMax records (RTX_ACCEL_BRUTE, a large leaf_max) becomes a subtree of its own over runs of its records.
-uint32_t wide_nodes_build(const std::vector<NodeRec> &nodes, uint32_t root, const float *prim_boxes, std::vector<WideNode> &out)
-{
-    out.clear();
-    if (root >= nodes.size()) return 0;
-    // a child to be: a node of the binary tree, or a run [first, first + count) of a large leaf's records
-    struct Kid {
-        bool run;
-        uint32_t bin;                // !run
-        uint32_t first, count, flags;// run (flags: kSphereFlag or 0)
-        float lo[3], hi[3];
-    };
-    auto kid_of_node = [&](uint32_t i) {
-        Kid k{};
-        const NodeRec &n = nodes[i];
-        std::memcpy(k.lo, n.bmin, 12);
-        std::memcpy(k.hi, n.bmax, 12);
-        if ((n.info & kLeafFlag) && n.link > kWideLeafMax) {
-            k.run = true; k.first = n.info & kLeafIndexMask; k.count = n.link; k.flags = n.info & kSphereFlag;
-        } else {
-            k.run = false; k.bin = i;
-        }
-        return k;
-    };
-    auto kid_of_run = [&](uint32_t first, uint32_t count, uint32_t flags) {
-        Kid k{};
-        k.run = true; k.first = first; k.count = count; k.flags = flags;
-        for (int a = 0; a < 3; ++a) { k.lo[a] = FLT_MAX; k.hi[a] = -FLT_MAX; }
-        for (uint32_t i = first; i < first + count; ++i)
-            for (int a = 0; a < 3; ++a) {
-                k.lo[a] = std::fmin(k.lo[a], prim_boxes[6 * static_cast<size_t>(i) + a]);
-                k.hi[a] = std::fmax(k.hi[a], prim_boxes[6 * static_cast<size_t>(i) + 3 + a]);
-            }
-        return k;
-    };
-    auto is_leaf = [&](const Kid &k) { return k.run ? k.count <= kWideLeafMax : (nodes[k.bin].info & kLeafFlag) != 0u; };
-    auto area = [&](const Kid &k) {
-        const double dx = double(k.hi[0]) - k.lo[0], dy = double(k.hi[1]) - k.lo[1], dz = double(k.hi[2]) - k.lo[2];
-        return dx * dy + dy * dz + dz * dx;
-    };
-    // the two children an inner kid splits into
-    auto split = [&](const Kid &k, Kid &x, Kid &y) {
-        if (k.run) {
-            const uint32_t half = ((k.count / 2u + kWideLeafMax - 1u) / kWideLeafMax) * kWideLeafMax;   // whole runs to the left
-            const uint32_t left = std::min(std::max(half, kWideLeafMax), k.count - 1u);
-            x = kid_of_run(k.first, left, k.flags);
-            y = kid_of_run(k.first + left, k.count - left, k.flags);
-        } else {
-            x = kid_of_node(k.bin + 1u);
-            y = kid_of_node(nodes[k.bin].info);
-        }
-    };
-    bool far_point = true;
-    for (int a = 0; a < 3; ++a)
-        far_point = far_point && std::fabs(nodes[root].bmin[a]) < 0x1p90f && std::fabs(nodes[root].bmax[a]) < 0x1p90f;
-    struct Todo { Kid kid; uint32_t wide, level; };
-    std::vector<Todo> todo;
-    uint32_t depth = 0;
-    out.emplace_back();
-    todo.push_back({kid_of_node(root), 0u, 1u});
-    while (!todo.empty()) {
-        const Todo t = todo.back();
-        todo.pop_back();
-        if (t.level > depth) depth = t.level;
-        Kid kids[4];
-        uint32_t n = 0;
-        if (is_leaf(t.kid)) {
-            kids[n++] = t.kid;                                   // only the root can be a leaf here
-        } else {
-            split(t.kid, kids[0], kids[1]);
-            n = 2;
-            while (n < 4u) {
-                int best = -1;
-                double best_area = -1.0;
-                for (uint32_t k = 0; k < n; ++k)
-                    if (!is_leaf(kids[k]) && area(kids[k]) > best_area) { best_area = area(kids[k]); best = int(k); }
-                if (best < 0) break;
-                const Kid b = kids[best];
-                split(b, kids[best], kids[n]);
-                ++n;
-            }
-        }
-        WideNode w;
-        for (uint32_t c = 0; c < 4u; ++c) {
-            if (c < n) {
-                const Kid &k = kids[c];
-                for (int a = 0; a < 3; ++a) { w.box[c][a] = k.lo[a]; w.box[c][3 + a] = k.hi[a]; }
-                if (is_leaf(k)) {
-                    const uint32_t first = k.run ? k.first : (nodes[k.bin].info & kLeafIndexMask);
-                    const uint32_t count = k.run ? k.count : nodes[k.bin].link;
-                    const uint32_t flags = k.run ? k.flags : (nodes[k.bin].info & kSphereFlag);
-                    w.ref[c] = kLeafFlag | flags | (count << kWideLeafCountShift) | first;
-                    w.aux[c] = count;
-                } else {
-                    const uint32_t child = static_cast<uint32_t>(out.size());
-                    out.emplace_back();
-                    w.ref[c] = child * static_cast<uint32_t>(sizeof(WideNode));
-                    w.aux[c] = 0;                                // filled in below
-                    todo.push_back({k, child, t.level + 1u});
-                }
-            } else {
-                // a leaf of no record.  Its box is a point far outside the scene, which no ray passes unless its three
-                // direction components are equal to the last bit — and then nothing is tested; in a scene that large
-                // itself, the first child's box (the slot then costs an empty turn of the leaf loop when that child passes)
-                if (far_point) for (int a = 0; a < 6; ++a) w.box[c][a] = 0x1p100f;
-                else std::memcpy(w.box[c], w.box[0], sizeof w.box[c]);
-                w.ref[c] = kLeafFlag;
-                w.aux[c] = 0;
-            }
-        }
-        out[t.wide] = w;
-    }
-    // subtree sizes: children were appended after their parent, so a reverse sweep sees them first
-    std::vector<uint32_t> size(out.size(), 1u);
-    for (size_t i = out.size(); i-- > 0;)
-        for (uint32_t c = 0; c < 4u; ++c)
-            if (!(out[i].ref[c] & kLeafFlag)) {
-                const uint32_t child = out[i].ref[c] / static_cast<uint32_t>(sizeof(WideNode));
-                out[i].aux[c] = size[child];
-                size[i] += size[child];
-            }
-    return depth;
-}
 
 int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
 {
@@ -744,24 +616,12 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
 
         // after a tree is built: inner nodes of the library's stream name their second child in `info` (the first one
         // is the next record; the walks only look at bit 31 of an inner node's info, the cut's descent follows both).
-        // A/B builds (kBuildWideTree) also restate the tree proper — behind the root and the global triangles' leaf when
-        // there are any — with four children per node.
         auto finish_tree = [&]() {
             for (size_t i = 0; i < s.nodes.size(); ++i)
                 if (!(s.nodes[i].info & kLeafFlag)) {
                     const NodeRec &first = s.nodes[i + 1];
                     s.nodes[i].info = (first.info & kLeafFlag) ? static_cast<uint32_t>(i) + 2u : first.link;
                 }
-            s.wide.clear();
-            s.wide_depth = 0;
-            if (!kBuildWideTree) return;
-            const uint32_t proper = s.n_global != 0u ? 2u : 0u;
-            std::vector<float> order_boxes(6 * static_cast<size_t>(n_prims));     // primitive boxes in leaf order
-            for (uint32_t i = 0; i < n_prims; ++i) {
-                std::memcpy(&order_boxes[6 * static_cast<size_t>(i)], prims[i].lo, 12);
-                std::memcpy(&order_boxes[6 * static_cast<size_t>(i) + 3], prims[i].hi, 12);
-            }
-            s.wide_depth = wide_nodes_build(s.nodes, proper, order_boxes.data(), s.wide);
         };
         s.nodes.clear();
         s.primary_nodes.clear();
@@ -837,10 +697,8 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
             }
             // centre of the light points (the first primary ray's): orders the children of every node (TreeBuilder)
             float light_c[3] = {0.0f, 0.0f, 0.0f};
-            bool light_ok = RTX_LIGHTWARD_ORDER != 0 && d.nb_light_sample != 0u;
-            if (RTX_LIGHTWARD_ORDER == 2) {          // A/B: the child nearer to the EYE first (what pruned primary walks would like)
-                std::memcpy(light_c, d.eye, 12);
-            } else if (light_ok) {
+            bool light_ok = d.nb_light_sample != 0u;
+            if (light_ok) {
                 double acc[3] = {0, 0, 0};
                 for (uint32_t i = 0; i < d.nb_light_sample; ++i)
                     for (int k = 0; k < 3; ++k) acc[k] += s.light_points[3 * static_cast<size_t>(i) + k];
@@ -849,9 +707,8 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
                     light_ok = light_ok && std::isfinite(light_c[k]);
                 }
             }
-            auto build_tree = [&](uint32_t depth_cap) {
-                s.nodes.clear();
-                TreeBuilder tb(prims, s.nodes, leaf_max, box_cost, depth_cap, light_ok ? light_c : nullptr, RTX_LIGHTWARD_ORDER == 2);
+            {
+                TreeBuilder tb(prims, s.nodes, leaf_max, box_cost, 64u, light_ok ? light_c : nullptr);
                 if (s.n_global) {
                     Box g;
                     g.reset();
@@ -883,26 +740,11 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
                     s.max_leaf_tris = tb.max_leaf;
                     s.depth = tb.depth;
                 }
-            };
-            build_tree(64u);
+            }
             finish_tree();
             s.primary_nodes.clear();
-            if (RTX_PRIMARY_STREAM && s.n_global < n_prims)
+            if (s.n_global < n_prims)
                 stream_nearest_first(s.nodes, s.n_global != 0u ? 2u : 0u, d.eye, s.primary_nodes);
-            if (kBuildWideTree && s.wide_depth > kMaxWideDepth) {
-                // the walk's stack holds 3 pending children per wide level: a tree that deep (a pathological scene) is
-                // rebuilt balanced, which halves its levels when the children are pulled up
-                uint32_t halvings = 0;
-                while ((1ull << halvings) < n_prims) ++halvings;
-                build_tree(halvings + 3u);
-                finish_tree();
-                s.primary_nodes.clear();      // (A/B builds: the wide walk has no second stream)
-                if (s.wide_depth > kMaxWideDepth) return RTX_ERR_INTERNAL;
-            }
-        }
-        if (kBuildWideTree) {
-            if (static_cast<uint64_t>(s.wide.size()) * sizeof(WideNode) >= (1ull << 31)) return RTX_ERR_UNSUPPORTED;
-            if (s.wide_depth > kMaxWideDepth) return RTX_ERR_INTERNAL;     // (RTX_ACCEL_BRUTE: log4(n / 16) levels)
         }
         s.tris.resize(n_prims);
         std::vector<uint32_t> pos_of(n_prims);

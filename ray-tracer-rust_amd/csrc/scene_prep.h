@@ -47,38 +47,6 @@ inline std::vector<NodeDev> nodes_in_device_order(const std::vector<NodeRec> &v,
                          v[i].bmin[2] - inflate, v[i].bmax[2] + inflate, v[i].link, v[i].info};
     return out;
 }
-// The four-child form of the tree exists in A/B builds only (-DRTX_WIDE_WALK=1: every walk on it; -DRTX_PROBE_WIDE=1:
-// probe_kernel's primary walk): measured slower than the binary stream on every configuration.
-// librtx.so neither builds nor uploads it, and none of its limits (depth, 25-bit record index) binds the product.
-#ifndef RTX_WIDE_WALK
-#define RTX_WIDE_WALK 0
-#endif
-#ifndef RTX_PROBE_WIDE
-#define RTX_PROBE_WIDE 0
-#endif
-constexpr bool kBuildWideTree = (RTX_WIDE_WALK != 0) || (RTX_PROBE_WIDE != 0);
-
-// One WIDE node (A/B builds, see above): four children tested per step, 32 dwords, fetched with two scalar 64-byte
-// loads.  Made from the binary tree above by pulling grandchildren up (wide_nodes_build), so every child box is the box
-// of a binary node (or of a run of a large leaf's primitives) — a superset chain over the same exact leaf boxes — and
-// the walk keeps its pending children on a small wave-uniform stack.
-//   box[c]  lo.x lo.y lo.z hi.x hi.y hi.z of child c (on the device moved outwards by cull_delta, like NodeDev)
-//   ref[c]  inner child: byte offset of its wide node (a multiple of 128, bit 31 clear)
-//           leaf child:  kLeafFlag | (kSphereFlag) | records << kWideLeafCountShift | first primitive record
-//                        (1..16 records: a larger leaf of the binary tree is cut into runs under wide nodes of its own)
-//           empty slot:  a leaf of 0 records; its box is a point far outside the scene (2^100 on every axis), which
-//                        practically no ray passes — and if one does, nothing is tested
-//   aux[c]  inner child: wide nodes of its subtree (the cut's cost proxy); leaf child: records
-struct WideNode {
-    float    box[4][6];
-    uint32_t ref[4];
-    uint32_t aux[4];
-};
-static_assert(sizeof(WideNode) == 128, "WideNode must be 128 bytes");
-constexpr uint32_t kWideLeafCountShift = 25u, kWideLeafMax = 16u, kWideLeafFirstMask = (1u << kWideLeafCountShift) - 1u;
-constexpr uint32_t kWideStackLanes = 64u;   // the walk's stack lives in the 64 lanes of one vector register:
-constexpr uint32_t kMaxWideDepth = 20u;     // one entry + at most 3 more per level below it (prepare_scene rebuilds a deeper tree balanced)
-static_assert(1u + 3u * kMaxWideDepth <= kWideStackLanes, "stack bound");
 constexpr uint32_t kLeafFlag = 0x80000000u;
 constexpr uint32_t kSphereFlag = 0x40000000u;
 constexpr uint32_t kLeafIndexMask = 0x3FFFFFFFu;
@@ -106,14 +74,6 @@ struct ShadeRec {
     float    rgb[3];      // Color
     uint32_t kind;        // 0 triangle, 1 sphere
 };
-// 1: the builder orders the children of every node far-from-the-light first (scene_prep.cpp: lightward_second)
-#ifndef RTX_LIGHTWARD_ORDER
-#define RTX_LIGHTWARD_ORDER 1
-#endif
-// 1: a second stream of the same tree for the primary rays, nearest-to-the-eye child first (PreparedScene::primary_nodes)
-#ifndef RTX_PRIMARY_STREAM
-#define RTX_PRIMARY_STREAM 1
-#endif
 static_assert(sizeof(ShadeRec) == 32, "ShadeRec must be 32 bytes");
 
 struct PreparedScene {
@@ -130,9 +90,6 @@ struct PreparedScene {
     // this way; `nodes` puts the child farther from the LIGHT first, which is what the shadow walks want.  Same records,
     // same leaves (a leaf names its run of the primitive array), other order and links.  Empty: `nodes` serves both.
     std::vector<NodeRec>  primary_nodes;
-    std::vector<WideNode> wide;        // A/B builds only (kBuildWideTree): the same tree with four children per node (may be
-                                       // empty: a scene of global triangles only); wide[0] is the root.  Else empty.
-    uint32_t wide_depth = 0;           // levels of wide nodes
     std::vector<NodeRec>  ref_nodes;   // the reference's own tree as a stream (empty when not built)
     std::vector<TriRec>   tris;        // primitive records (triangles and spheres) in leaf order
     std::vector<ShadeRec> shade;       // in caller order
@@ -154,19 +111,15 @@ struct PreparedScene {
     std::vector<TriRec>   global_planes;
 };
 constexpr uint32_t kMaxGlobalPrims = 8u;
-// the walk addresses primitive records by 32-bit byte offsets, 64 B each; an A/B build's wide leaf ref holds a 25-bit index
-constexpr uint64_t kMaxPrimitives = kBuildWideTree ? (1ull << 25) : (1ull << 26);
+// the walk addresses primitive records by 32-bit byte offsets, 64 B each
+constexpr uint64_t kMaxPrimitives = 1ull << 26;
 
 // Returns RTX_OK or a negative RtxError.
 int prepare_scene(const RtxSceneDesc &desc, PreparedScene &out);
 
-// Four-child nodes from the binary stream `nodes` (pre-order, inner.info = second child) below record `root`; returns
-// the number of wide levels.  A root that is a leaf gives one wide node with one child.
-// prim_boxes: n x {lo xyz, hi xyz} of the primitive records in leaf order (to bound the runs of a large leaf).
 // `nodes` (pre-order, inner.info = second child) with the children of every inner node below record `root` in the order
 // that puts the one nearer to `point` first; records before `root` are kept as they are.
 void stream_nearest_first(const std::vector<NodeRec> &nodes, uint32_t root, const float *point, std::vector<NodeRec> &out);
-uint32_t wide_nodes_build(const std::vector<NodeRec> &nodes, uint32_t root, const float *prim_boxes, std::vector<WideNode> &out);
 
 // ---- pieces with their own tests ----
 void camera_new(const float eye[3], const float look_at[3], const float up[3],

@@ -57,8 +57,9 @@ def test_product_library_has_one_pipeline_and_reads_no_environment(rtx):
 def test_shipped_library_was_built_with_the_default_switches():
     """The kernel sources carry compile-time switches for A/B builds (tools/ab_build.sh puts those builds under
     gpurun_out/, never over the product).  librtx.so states what it was built with — rtx_build_switches_text, every
-    switch and its value — and that text must equal what the sources give with NO -D at all, and name every switch the
-    sources define: an experiment build in the product's place fails here."""
+    switch and its value — and that text must equal what the sources give with NO -D at all, and name exactly the
+    switches the sources define (at most 20: a closed experiment leaves the sources with its switch): an experiment build
+    in the product's place fails here, and so does a stale name in the text."""
     csrc = os.path.join(ROOT, "ray-tracer-rust_amd", "csrc")
     blob = open(os.path.join(ROOT, "ray-tracer-rust_amd", "librtx.so"), "rb").read()
     shipped = set(m.decode() for m in re.findall(rb"rtx-build-switches:[ -~]*", blob))
@@ -73,9 +74,11 @@ def test_shipped_library_was_built_with_the_default_switches():
     defined = set()
     for f in ("rtx_device.h", "rtx_traverse.hpp", "rtx_kernel.hip", "scene_prep.h", "rtx_ablation_kernels.hpp", "rtx_traverse_ablation.hpp"):
         src = open(os.path.join(csrc, f)).read()
-        defined |= set(re.findall(r"^#ifndef (RTX_[A-Z0-9_]+)$", src, re.M))
+        defined |= set(re.findall(r"^#ifndef (RTX_[A-Z0-9_]+)[ \t]*(?://.*)?$", src, re.M))
         defined |= set(re.findall(r"^#\s*(?:if|elif)[^\n]*\b(RTX_EXPERIMENT_[A-Z0-9_]+)", src, re.M))
     assert defined <= named, "switches missing from rtx_build_switches_text: %s" % sorted(defined - named)
+    assert defined == named, "rtx_build_switches_text names switches the sources do not define: %s" % sorted(named - defined)
+    assert len(named) <= 20, sorted(named)
     assert " RTX_ABLATION=0" in shipped
     abl = open(os.path.join(ROOT, "ray-tracer-rust_amd", "librtx_ablation.so"), "rb").read()
     assert b" RTX_ABLATION=1" in abl

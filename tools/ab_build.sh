@@ -4,7 +4,7 @@
 # benched ROUNDS times, interleaved.  Every variant has its own object directory and library under gpurun_out/ab/ and is
 # loaded through RTX_PY_LIB: the product's obj/ and librtx.so are never touched.  Each build's compiler output and each
 # bench run's stderr are kept (gpurun_out/ab/build_<i>.log, run_<i>.err): a variant that prints no line has said why.
-#   tools/ab_build.sh "" "-DRTX_SCALAR_RAY_NUMBERING=0"
+#   tools/ab_build.sh "" "-DRTX_CLAIM_RUN_LOG=8"
 #   WORKLOADS="c3 c2" ROUNDS=3 tools/ab_build.sh "" "-DRTX_SHADE_WAVES_PER_SIMD=6"
 set -u
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Development tool: the record fetches of one counted frame for several builds of librtx.so (EXTRA= flag strings), on one
 # box.  Builds live under gpurun_out/ab/ and are loaded through RTX_PY_LIB (the product's files are not touched).
-#   WORKLOADS="c3 c5" tools/count_builds.sh "" "-DRTX_HOME_FIRST=0"
+#   WORKLOADS="c3 c5" tools/count_builds.sh "" "-DRTX_CUT_UNION_MIN=0"
 set -u
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 CSRC="$ROOT/ray-tracer-rust_amd/csrc"
