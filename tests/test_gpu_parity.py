@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 from PIL import Image
 
+from gpu_forms import render_both
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,7 +55,7 @@ def test_gpu_matches_golden(rtx, samples_seeded, samples_half, name):
     ref, case = golden(name)
     T = samples_seeded if case["table"] == "seed" else samples_half
     with rtx.default_scene([model(o) for o in case["objs"]], case["width"], case["height"], T) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_rays"] == case["width"] * case["height"]
     assert st["primary_hits"] == case["primary_hits"]          # integer: bit-exact
     assert st["rays"] == case["r_total"]
@@ -65,10 +67,10 @@ def test_gpu_brute_force_equals_bvh_and_oracle(rtx, orc, samples_seeded):
     match the oracle's faithful BVH on a 64x64 crop that has bunny, ground and shadow."""
     W = H = 64
     with rtx.default_scene([model("big_bunny.obj")], W, H, samples_seeded) as s:
-        a, sa = s.render_rows(stats=True)
+        a, sa = render_both(s)
     with rtx.default_scene([model("big_bunny.obj")], W, H, samples_seeded, accel=rtx.ACCEL_BRUTE) as s:
         assert s.info()["n_nodes"] == 1
-        b, sb = s.render_rows(stats=True)
+        b, sb = render_both(s)
     assert np.array_equal(a, b)
     assert sa["primary_hits"] == sb["primary_hits"] and sb["tri_tests"] >= sa["tri_tests"]
     ref, ost = orc.default_scene(["big_bunny.obj"], W, H, samples_seeded).render_rows(mode=orc.MODE_BVH)
@@ -187,7 +189,7 @@ def test_nb_ray_two(rtx, orc, samples_seeded):
     tris, rgb = orc.default_primitives(["big_bunny.obj"])
     ref, ost = orc.Scene(W, H, tris, rgb, samples_seeded, nb_ray=2, nb_light_sample=20).render_rows(mode=orc.MODE_BVH)
     with rtx.Scene(W, H, tris, rgb, samples_seeded, nb_ray=2, nb_light_sample=20) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_rays"] == 2 * W * H and st["primary_hits"] == ost["primary_hits"]
     assert st["shadow_rays"] == ost["shadow_rays"]
     assert_image_close(img, ref, "nb_ray=2")
@@ -233,7 +235,7 @@ def test_hits_closer_than_one_are_ignored(rtx, orc, samples_seeded):
     ref, ost, otri = orc.Scene(W, H, tris, rgb, samples_seeded, **kw).render_rows(mode=orc.MODE_BVH, want_tri=True)
     assert (otri[otri != 0xFFFFFFFF] == 1).all() and ost["primary_hits"] > 0
     with rtx.Scene(W, H, tris, rgb, samples_seeded, **kw) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"]
     assert_image_close(img, ref, "t<1 scene")
     assert img[..., 0].max() == 0        # nothing red
@@ -378,7 +380,7 @@ def test_random_soups_including_degenerate_rays(rtx, orc, samples_seeded, sample
     ref, ost, otri = orc.Scene(W, H, tris, rgb, T, **kw).render_rows(mode=orc.MODE_BVH, want_tri=True)
     assert ost["nonfinite_t"] == 0 and ost["primary_hits"] > 100
     with rtx.Scene(W, H, tris, rgb, T, **kw) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"]
     nz = assert_image_close(img, ref, "soup seed %d" % seed)
     assert nz == 0
@@ -392,7 +394,7 @@ def test_synthetic_soup_with_reference_tree(rtx, orc, samples_seeded):
     ref, ost = orc.Scene(W, H, tris, rgb, samples_seeded, nb_light_sample=24).render_rows(mode=orc.MODE_BVH)
     with rtx.Scene(W, H, tris, rgb, samples_seeded, nb_light_sample=24) as s:
         assert s.info()["n_ref_nodes"] == 2 * len(tris) - 1
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"] and st["redo_tiles"] == 0
     assert assert_image_close(img, ref, "synthetic 20k") == 0
 
@@ -408,7 +410,7 @@ def test_synthetic_soup_beyond_reference_tree(rtx, orc, samples_seeded):
     ref, ost = osc.render_rows(mode=orc.MODE_LEAFBOX)
     with rtx.Scene(W, H, tris, rgb, samples_seeded, nb_light_sample=8) as s:
         assert s.info()["n_ref_nodes"] == 0
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"] and st["redo_tiles"] == 0
     assert assert_image_close(img, ref, "synthetic 60k") == 0
 

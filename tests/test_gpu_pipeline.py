@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from gpu_forms import CUT_FRAME, cut_scenes, render_both
 from test_host_spheres import mixed_scene
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +44,7 @@ def test_several_primary_rays_with_tiles_queued_for_the_reference_walk(rtx, orc,
     W = H = 40
     ref, ost = orc.Scene(W, H, tris, rgb, T, nb_ray=nb_ray, nb_light_sample=nb_light, **AXIS).render_rows(mode=orc.MODE_BVH)
     with rtx.Scene(W, H, tris, rgb, T, nb_ray=nb_ray, nb_light_sample=nb_light, **AXIS) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
         again = s.render_rows()                               # the workspace is reused by the next launch
     assert st["redo_tiles"] > 0 and st["redo_tiles"] <= (W // 8) * (H // 8)       # queued once, not once per ray
     assert st["primary_rays"] == nb_ray * W * H and st["primary_hits"] == ost["primary_hits"]
@@ -57,7 +58,7 @@ def test_light_batches_and_partial_tiles(rtx, orc, samples_seeded):
     kw = dict(AXIS, nb_light_sample=150)
     ref, ost = orc.Scene(W, H, tris, rgb, samples_seeded, **kw).render_rows(mode=orc.MODE_BVH)
     with rtx.Scene(W, H, tris, rgb, samples_seeded, **kw) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
         rows = np.concatenate([s.render_rows(0, 5), s.render_rows(5, 16)])          # launches that start off the tile grid
     assert st["primary_hits"] == ost["primary_hits"]
     assert np.array_equal(img, ref) and np.array_equal(rows, ref)
@@ -69,12 +70,12 @@ def test_no_light_samples_and_empty_scene_view(rtx, orc, samples_seeded):
     tris, rgb = soup(43, 60)
     W = H = 24
     with rtx.Scene(W, H, tris, rgb, samples_seeded, **dict(AXIS, nb_light_sample=0)) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] > 0 and st["shadow_rays"] == 0 and not img.any()
     away = dict(AXIS, look_at=(0.0, 0.0, 1.0), nb_light_sample=8)
     ref, ost = orc.Scene(W, H, tris, rgb, samples_seeded, **away).render_rows(mode=orc.MODE_BVH)
     with rtx.Scene(W, H, tris, rgb, samples_seeded, **away) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert ost["primary_hits"] == 0 == st["primary_hits"] and np.array_equal(img, ref)
 
 
@@ -85,7 +86,7 @@ def test_mixed_arms_several_primary_rays_zero_table(rtx, orc):
     W = H = 32
     ref, ost = orc.Scene(W, H, tris, rgb, T, spheres=spheres, sphere_rgb=srgb, kinds=kinds, **kw).render_rows(mode=orc.MODE_BVH)
     with rtx.Scene(W, H, tris, rgb, T, spheres=spheres, sphere_rgb=srgb, kinds=kinds, **kw) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"] and st["redo_tiles"] > 0
     assert np.array_equal(img, ref)
 
@@ -161,7 +162,7 @@ def test_scenes_whose_triangles_are_all_or_partly_global(rtx, orc, samples_seede
         ref, ost = orc.Scene(W, H, t, c, samples_seeded, **kw).render_rows(mode=orc.MODE_BVH)
         with rtx.Scene(W, H, t, c, samples_seeded, **kw) as s:
             assert s.info()["n_global"] == want, name
-            img, st = s.render_rows(stats=True)
+            img, st = render_both(s)
         assert st["primary_hits"] == ost["primary_hits"] > 0 and np.array_equal(img, ref), name
 
 
@@ -202,7 +203,7 @@ def test_plane_shortcut_of_global_triangles(rtx, orc, samples_seeded, seed):
     ref, ost = orc.Scene(W, H, tris, rgb, samples_seeded, **kw).render_rows(mode=orc.MODE_BVH)
     with rtx.Scene(W, H, tris, rgb, samples_seeded, **kw) as s:
         assert s.info()["n_global"] == 1
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"] > 0.5 * W * H
     assert np.array_equal(img, ref)
 
@@ -210,41 +211,15 @@ def test_plane_shortcut_of_global_triangles(rtx, orc, samples_seeded, seed):
 _CUT_VS_WHOLE_CHILD = r"""
 import importlib, sys, hashlib, json
 import numpy as np
-sys.path.insert(0, %(root)r)
+sys.path[:0] = [%(root)r, %(tests)r]
 rtx = importlib.import_module('ray-tracer-rust_amd')
-F = np.float32
+import gpu_forms
 T = rtx.gen_samples()[:8192]
-
-def soup(seed, n, centre, extent, size):
-    g = np.random.default_rng(seed)
-    c = g.uniform(-extent, extent, (n, 1, 3)) + np.asarray(centre, F)
-    t = (c + g.uniform(-size, size, (n, 3, 3))).astype(F).reshape(n, 9)
-    return t, g.uniform(0.2, 1.0, (n, 3)).astype(F)
-
-out = {}
-# 1. the light INSIDE the mesh: the light's box overlaps every tile's hit box, shafts run in every direction
-t, c = soup(1, 3000, (0, 0, 0), 40, 2.5)
-out['light inside'] = dict(tris=t, rgb=c, eye=(0, 10, 150), look_at=(0, 0, 0), distance=90.0,
-                           light_tri=np.array([-3, 1, -3, 3, 1, -3, 0, -2, 3], F), nb_light_sample=24)
-# 2. coordinates around one million: the margins of the shaft test are relative to the scene's magnitude
-t, c = soup(2, 2500, (1.0e6, 2.0e6, -1.5e6), 60, 4.0)
-floor = np.array([[1.0e6 - 500, 2.0e6 - 70, -1.5e6 + 500, 1.0e6 + 500, 2.0e6 - 70, -1.5e6 + 500, 1.0e6, 2.0e6 - 70, -1.5e6 - 800]], F)
-out['coordinates of a million'] = dict(tris=np.concatenate([t, floor]), rgb=np.concatenate([c, np.array([[0.5, 0.5, 0.5]], F)]),
-                                        eye=(1.0e6, 2.0e6 + 30, -1.5e6 + 260), look_at=(1.0e6, 2.0e6 - 20, -1.5e6), distance=100.0,
-                                        light_tri=np.array([1.0e6 - 15, 2.0e6 + 200, -1.5e6 - 10, 1.0e6 + 15, 2.0e6 + 200, -1.5e6 - 10, 1.0e6, 2.0e6 + 200, -1.5e6 + 12], F),
-                                        nb_light_sample=20)
-# 3. spheres among the triangles, and two primary rays per pixel
-t, c = soup(3, 1500, (0, 30, 0), 50, 3.0)
-g = np.random.default_rng(33)
-sph = np.concatenate([g.uniform(-50, 50, (200, 3)) + np.array([0, 30, 0]), g.uniform(0.5, 4.0, (200, 1))], axis=1).astype(F)
-floor = np.array([[-400, -25, 300, 400, -25, 300, 0, -25, -600]], F)
-out['spheres, two primary rays'] = dict(tris=np.concatenate([t, floor]), rgb=np.concatenate([c, np.array([[0.5, 0.5, 0.5]], F)]),
-                                         spheres=sph, sphere_rgb=g.uniform(0.2, 1.0, (200, 3)).astype(F),
-                                         eye=(0, 60, 220), look_at=(0, 20, 0), distance=110.0, nb_ray=2, nb_light_sample=16)
+W, H = gpu_forms.CUT_FRAME
 res = {}
-for name, kw in out.items():
+for name, kw in gpu_forms.cut_scenes().items():
     tris, rgb = kw.pop('tris'), kw.pop('rgb')
-    with rtx.Scene(160, 120, tris, rgb, T, **kw) as s:
+    with rtx.Scene(W, H, tris, rgb, T, **kw) as s:
         info = s.info()
         img, st = s.render_rows(stats=True)
     res[name] = dict(sha=hashlib.sha1(img.tobytes()).hexdigest(), hits=int(st['primary_hits']), rays=int(st['rays']),
@@ -253,16 +228,21 @@ print('RESULT', json.dumps(res))
 """
 
 
-def test_cut_and_whole_stream_walks_give_the_same_bytes():
+def test_cut_and_whole_stream_walks_give_the_same_bytes(rtx, orc, samples_seeded):
     """The per-tile shaft cut decides which subtrees a tile's shadow rays may see: a cut that is not
-    a superset would show as missing shadows.  The same scenes are rendered by librtx_ablation.so twice, each in a child
-    process — with the cuts, and with RTX_CUT_MAX_NODES=0, which makes every chunk walk the whole stream — and must give
-    the same bytes: the light inside the mesh (its box overlaps the tiles' hit boxes), coordinates around 10^6 (the
-    margins are relative), spheres with two primary rays per pixel."""
+    a superset would show as missing shadows.  The same scenes (tests/gpu_forms.py, cut_scenes) are rendered by
+    librtx_ablation.so twice, each in a child process — with the cuts, and with RTX_CUT_MAX_NODES=0, which makes every
+    chunk walk the whole stream — and must give the same bytes: the light inside the mesh (its box overlaps the tiles'
+    hit boxes), coordinates around 10^6 (the margins are relative), spheres with two primary rays per pixel.
+    Two equal walks could still share an error, so this process renders the three scenes with librtx.so (both counting
+    states) and with the oracle's faithful BVH as well: all four images must be the same bytes, whole frame.  (The
+    oracle meets no non-finite distance in any of the three, the scene at 10^6 included: asserted, so none needs a
+    mask.)"""
+    import hashlib
     import json
     import subprocess
     import sys
-    code = _CUT_VS_WHOLE_CHILD % dict(root=ROOT)
+    code = _CUT_VS_WHOLE_CHILD % dict(root=ROOT, tests=os.path.join(ROOT, "tests"))
     results = []
     for cut_max in (None, "0"):
         env = dict(os.environ, RTX_PY_ABLATION="1")
@@ -280,3 +260,20 @@ def test_cut_and_whole_stream_walks_give_the_same_bytes():
         assert a["hits"] == b["hits"] > 0 and a["rays"] == b["rays"] and a["lit"] > 0, (name, a, b)
         assert a["sha"] == b["sha"], (name, a, b)
         assert a["node_visits"] != b["node_visits"], "the two renders of %r walked the same records: one form ran twice" % name
+    T = samples_seeded[:8192]
+    assert np.array_equal(T, rtx.gen_samples()[:8192])          # the children's table
+    W, H = CUT_FRAME
+    scenes = cut_scenes()
+    assert set(scenes) == set(cut)
+    for name, kw in scenes.items():
+        tris, rgb = kw.pop("tris"), kw.pop("rgb")
+        assert len(tris) <= 3001
+        ref, ost = orc.Scene(W, H, tris, rgb, T, **kw).render_rows(mode=orc.MODE_BVH)
+        assert ost["nonfinite_t"] == 0, name
+        with rtx.Scene(W, H, tris, rgb, T, **kw) as s:
+            img, st = render_both(s)
+        assert st["primary_hits"] == ost["primary_hits"] == cut[name]["hits"], (name, st["primary_hits"], ost["primary_hits"], cut[name])
+        differing = int((img != ref).any(axis=2).sum())
+        print("%s: %d of %d pixels differ from the oracle" % (name, differing, W * H))
+        assert differing == 0, "%s: librtx.so differs from the oracle in %d pixels" % (name, differing)
+        assert hashlib.sha1(img.tobytes()).hexdigest() == hashlib.sha1(ref.tobytes()).hexdigest() == cut[name]["sha"], name

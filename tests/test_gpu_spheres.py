@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from gpu_forms import render_both
 from test_host_spheres import mixed_scene
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +52,7 @@ def test_known_answer_scene(rtx, orc, samples_seeded, accel):
     assert (otri == 1).sum() > 10 and (otri == 2).sum() > 10 and (otri == 4).sum() == 0
     with rtx.Scene(W, H, tris, rgb, samples_seeded, spheres=spheres, sphere_rgb=srgb, kinds=kinds, accel=accel,
                    **KAT) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"]
     same_image(img, ref, "sphere KAT scene accel=%d" % accel)
     ys, xs = np.nonzero(otri == 1)                      # the lit top of sphere 0 is green
@@ -74,7 +75,7 @@ def test_mixed_soups(rtx, orc, samples_seeded, samples_half, seed, table, nb_ray
     hit_kinds = kinds[otri[otri != 0xFFFFFFFF]]
     assert (hit_kinds == 1).sum() > 50 and (hit_kinds == 0).sum() > 50
     with rtx.Scene(W, H, tris, rgb, T, spheres=spheres, sphere_rgb=srgb, kinds=kinds, **kw) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
         if table == "zero":
             assert st["redo_tiles"] > 0
     assert st["primary_hits"] == ost["primary_hits"]
@@ -96,7 +97,7 @@ def test_spheres_only_and_no_reference_tree(rtx, orc, samples_seeded):
     assert np.array_equal(ref, ref_l) and ost["exact_ties"] == 0
     with rtx.Scene(W, H, none, none_rgb, samples_seeded, spheres=spheres, sphere_rgb=srgb, tie_rank=None, **kw) as s:
         assert s.info()["n_ref_nodes"] == 0
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
     assert st["primary_hits"] == ost["primary_hits"] > 100 and st["redo_tiles"] == 0
     same_image(img, ref, "spheres only")
 
@@ -113,7 +114,7 @@ def test_bunny_with_spheres_multi_tile_partition(rtx, orc, samples_seeded):
                                nb_light_sample=20).render_rows(mode=orc.MODE_BVH, want_tri=True)
     assert (otri >= len(tris)).sum() - (otri == 0xFFFFFFFF).sum() > 20          # sphere pixels
     with rtx.Scene(W, H, tris, rgb, samples_seeded, spheres=spheres, sphere_rgb=srgb, nb_light_sample=20) as s:
-        img, st = s.render_rows(stats=True)
+        img, st = render_both(s)
         frame = s.render_frame(devices=(0,), tile_rows=8)
     assert st["primary_hits"] == ost["primary_hits"]
     same_image(img, ref, "bunny + spheres")

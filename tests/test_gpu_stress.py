@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from gpu_forms import render_both
+
 pytestmark = pytest.mark.gpu
 F = np.float32
 
@@ -65,7 +67,7 @@ def test_random_scenes_match_the_oracle(rtx, orc, samples_seeded):
         if ost["nonfinite_t"]:
             continue                                            # outside the parity contract
         with rtx.Scene(W, H, tris, rgb, samples_seeded, **extra, **kw) as s:
-            img, st = s.render_rows(stats=True)
+            img, st = render_both(s)
         assert st["primary_hits"] == ost["primary_hits"], "scene %d: %r" % (k, kw)
         assert np.array_equal(img, ref), "scene %d: %d bytes differ (%dx%d, %d tris, %d spheres, %r)" % (
             k, int((img != ref).sum()), W, H, len(tris), len(spheres), kw)
