@@ -180,6 +180,62 @@ int rtx_render_tiles_device(RtxScene *scene, int device, uint32_t first_tile, ui
 uint32_t rtx_tiles_rows(const RtxScene *scene, uint32_t first_tile, uint32_t tile_stride, uint32_t tile_rows);
 size_t   rtx_tiles_bytes(const RtxScene *scene, uint32_t first_tile, uint32_t tile_stride, uint32_t tile_rows);
 
+/* ---- ray queries: rays the caller supplies ---------------------------------- */
+/* The reference's public traversal surface is BoundingVolumeHierarchy::intersect(&Ray) -> Option<HitInfo>
+ * (bounding_volume_hierarchy.rs:50-75,228), which render_pixel calls twice (main.rs:187,204).  These entry points are
+ * that call for a batch of rays — a bounce, a pick ray, an ambient-occlusion pass, a visibility test between two
+ * points — with the reference's semantics bit for bit.  They have kernels of their own and leave the render pipeline
+ * and its workspace alone.
+ *
+ * Outside the parity contract (the calls still terminate and return RTX_OK; the values are unspecified): rays with a
+ * non-finite origin or direction, a zero-length direction, or a hit whose t is not finite.  Finite origins may lie
+ * anywhere, far outside the scene included: a 64-ray group holding an origin with a coordinate beyond the scene's and
+ * the eye's largest walks with the exact box test (slower, same results). */
+#define RTX_NO_HIT 0xFFFFFFFFu
+typedef struct RtxRayHit {      /* 32 bytes */
+    uint32_t prim;              /* position in the Vec<Primitive>, RTX_NO_HIT = None                          */
+    float    t;                 /* the distance the leaf rule compared (bvh.rs:64-67): triangle.rs's t, sphere.rs's distance */
+    float    p_hit[3];          /* ray.origin + t * ray.direction (bvh.rs:69)                                  */
+    float    normal[3];         /* p.get_normal(p_hit): the triangle's unit normal / normalize(p_hit - origin) */
+} RtxRayHit;                    /* a miss writes prim = RTX_NO_HIT and zeros                                   */
+
+/* The walk is wave-uniform: a wavefront visits the union of its 64 rays' nodes, so by default a batch of at least a few
+ * thousand rays (DESIGN.md "Ray queries") is regrouped on the device first — sorted by direction class, direction octant
+ * and a Morton code of the origin — and traced in that order.  Results are written to the rays' own numbers and are the
+ * same bytes either way. */
+#define RTX_RAYS_KEEP_ORDER    1u  /* trace the rays in the caller's order: no regrouping pass                     */
+#define RTX_RAYS_FORCE_REGROUP 2u  /* DIAGNOSTIC: regroup whatever the batch size — how tools/trace_rays_timing.py and the
+                                      tests reach the regrouping pass with small batches; no result depends on it      */
+
+/* bvh.intersect(&Ray::new(origin, direction)) per ray: the minimum accepted t; hits with t < 1.0 are ignored
+ * (bvh.rs:64-67); on an exact tie the right-most leaf of the reference tree wins (tie_rank).  Colour is not returned:
+ * the caller indexes its own rgb with prim.  origins, directions: n_rays x 3 floats, host; a direction may have any
+ * length (Ray::new normalises).  NULL pointer, unknown flag or n_rays > 2^28: RTX_ERR_BAD_ARG; n_rays == 0: RTX_OK,
+ * no output written; no usable device: RTX_ERR_NO_DEVICE (there is no CPU fallback).
+ * stats may be NULL; when non-NULL the counted kernel form runs (same results) and the fields mean:
+ *   primary_rays = rays = n_rays, primary_hits = rays with a hit (rtx_occluded_rays: occluded rays), shadow_rays = 0,
+ *   box_tests / tri_tests / wave_node_visits / wave_tri_visits as for rendering,
+ *   redo_tiles = 64-RAY GROUPS traced with the literal reference traversal because one of their rays has a -0.0, NaN
+ *                or infinite direction component,
+ *   kernel_ms = device time of the call's kernels (regrouping included), total_ms = host wall time of the call. */
+int rtx_trace_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
+                   uint32_t flags, RtxRayHit *out_hits, RtxStats *stats);
+/* The decision of main.rs:201-231 per ray: the ray is Ray::new(origin, target - origin), D = distance(target, origin);
+ * it is occluded iff a closest hit exists and !(distance(origin, p_hit) > D).  out_occluded: n_rays bytes, 1 = occluded,
+ * 0 = lit.  Arguments, errors and stats as rtx_trace_rays. */
+int rtx_occluded_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
+                      uint32_t flags, uint8_t *out_occluded, RtxStats *stats);
+/* Device-resident variants, asynchronous on `stream` (a hipStream_t; NULL = the default stream), as
+ * rtx_render_tiles_device is: inputs and outputs are device pointers the caller owns (floats 4-byte aligned, d_hits
+ * 16-byte aligned: else RTX_ERR_BAD_ARG); the regrouping pass runs on the same stream in library-owned buffers, so
+ * device-resident query launches on one device must be ordered on one stream.  The host entry points above use the
+ * same buffers on the library's own stream; they wait (on the device, by an event) for the most recent device-resident
+ * query launch first, so they may be mixed with these freely. */
+int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
+                          uint32_t flags, void *d_hits, void *stream);
+int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
+                             uint32_t flags, void *d_occluded, void *stream);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

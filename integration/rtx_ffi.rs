@@ -82,6 +82,20 @@ pub struct RtxSceneInfo {
     pub sample_bytes: u64,
 }
 
+/// One closest hit of `rtx_trace_rays`: what `BoundingVolumeHierarchy::intersect` returns as `Option<HitInfo>`,
+/// flattened (`prim == RTX_NO_HIT` is `None`; colour is the caller's own `rgb[prim]`).
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxRayHit {
+    pub prim: u32,
+    pub t: f32,
+    pub p_hit: [f32; 3],
+    pub normal: [f32; 3],
+}
+pub const RTX_NO_HIT: u32 = 0xFFFF_FFFF;
+pub const RTX_RAYS_KEEP_ORDER: u32 = 1;
+pub const RTX_RAYS_FORCE_REGROUP: u32 = 2;
+
 /// Opaque handle (library-owned).
 #[repr(C)]
 pub struct RtxScene {
@@ -104,6 +118,14 @@ extern "C" {
                                    d_counters: *mut u64) -> c_int;
     pub fn rtx_tiles_rows(scene: *const RtxScene, first_tile: u32, tile_stride: u32, tile_rows: u32) -> u32;
     pub fn rtx_tiles_bytes(scene: *const RtxScene, first_tile: u32, tile_stride: u32, tile_rows: u32) -> usize;
+    pub fn rtx_trace_rays(scene: *mut RtxScene, device: c_int, n_rays: u32, origins: *const f32, directions: *const f32,
+                          flags: u32, out_hits: *mut RtxRayHit, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_occluded_rays(scene: *mut RtxScene, device: c_int, n_rays: u32, origins: *const f32, targets: *const f32,
+                             flags: u32, out_occluded: *mut u8, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_trace_rays_device(scene: *mut RtxScene, device: c_int, n_rays: u32, d_origins: *const c_void,
+                                 d_directions: *const c_void, flags: u32, d_hits: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn rtx_occluded_rays_device(scene: *mut RtxScene, device: c_int, n_rays: u32, d_origins: *const c_void,
+                                    d_targets: *const c_void, flags: u32, d_occluded: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn rtx_launch_timings(scene: *mut RtxScene, device: c_int, max_launches: c_int, schedule_ms: *mut f32,
                               shade_ms: *mut f32) -> c_int;
     pub fn rtx_strerror(err: c_int) -> *const c_char;

@@ -18,6 +18,7 @@
 
 #include "../../include/rtx.h"
 #include "rtx_device.h"
+#include "rtx_query.h"
 #include "scene_prep.h"
 
 namespace {
@@ -49,6 +50,15 @@ struct DeviceState {
     uint8_t *h_stage = nullptr;   // pinned
     size_t h_stage_cap = 0;
     size_t last_tiles = 0;        // tiles of the most recent launch (rtx_debug_tile_descs)
+    // ray queries (rtx_query.hip): device copies of the host entry points' arrays, the regrouping pass's (key, ray number)
+    // buffers and the sort's temporary storage; all grow-only, none shared with the render workspace
+    float *q_first = nullptr, *q_second = nullptr;
+    uint8_t *q_out = nullptr;
+    size_t q_first_cap = 0, q_second_cap = 0, q_out_cap = 0;
+    rtxq::SortBuffers q_sort{};
+    hipEvent_t q_sorted = nullptr;   // recorded behind a device-resident call that used q_sort on the CALLER's stream: a host
+                                     // call, which uses the same buffers on the library's stream, waits for it first
+    size_t q_keys_cap = 0, q_keys_sorted_cap = 0, q_index_cap = 0, q_index_sorted_cap = 0, q_temp_cap = 0;
     hipEvent_t ring[RTX_TIMING_RING][3] = {};   // launch start / end of the scheduling pass / launch end (rtx_launch_timings)
     unsigned long long launches = 0;
 };
@@ -341,6 +351,139 @@ int launch_on(RtxScene *scene, DeviceState &st, const rtx::TileSpec &ts, bool co
     return RTX_OK;
 }
 
+// ---- ray queries -------------------------------------------------------------------------------------------------------
+
+// The box the regrouping keys quantise origins in: the tree proper's root (beside the global triangles — the ground is
+// as large as the scene and would leave the mesh a handful of cells), else the stream's root.
+rtxq::KeyBox query_key_box(const rtx::PreparedScene &p)
+{
+    rtxq::KeyBox box{};
+    if (p.nodes.empty()) return box;
+    const rtx::NodeRec &root = p.nodes[(p.n_global != 0u && p.nodes.size() > 2u) ? 2u : 0u];
+    for (int a = 0; a < 3; ++a) {
+        const float extent = root.bmax[a] - root.bmin[a];
+        const float scale = static_cast<float>(1u << rtxq::kMortonBitsPerAxis) / extent;
+        box.lo[a] = root.bmin[a];
+        box.scale[a] = (extent > 0.0f && scale > 0.0f && scale < 0x1p100f) ? scale : 0.0f;   // (false for a NaN)
+    }
+    return box;
+}
+
+// the regrouping pass's buffers for n rays; caller holds st.mu and has the device current
+int ensure_query_sort(DeviceState &st, uint32_t n)
+{
+    const size_t words = static_cast<size_t>(n) * sizeof(uint32_t);
+    size_t temp = 0;
+    RTX_HIP(rtxq::sort_temp_bytes(n, &temp));
+    int rc;
+    if ((rc = grow_buffer(&st.q_sort.keys, &st.q_keys_cap, words)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(&st.q_sort.keys_sorted, &st.q_keys_sorted_cap, words)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(&st.q_sort.index, &st.q_index_cap, words)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(&st.q_sort.index_sorted, &st.q_index_sorted_cap, words)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(reinterpret_cast<char **>(&st.q_sort.temp), &st.q_temp_cap, temp ? temp : 16)) != RTX_OK) return rc;
+    st.q_sort.temp_bytes = st.q_temp_cap;
+    return RTX_OK;
+}
+
+static_assert(sizeof(RtxRayHit) == 32, "closest_kernel writes a hit as two 16-byte words");
+constexpr uint32_t kQueryFlags = RTX_RAYS_KEEP_ORDER | RTX_RAYS_FORCE_REGROUP;
+
+bool query_regroups(uint32_t n_rays, uint32_t flags)
+{
+    if (flags & RTX_RAYS_KEEP_ORDER) return false;
+    return n_rays >= rtxq::kRegroupMinRays || (flags & RTX_RAYS_FORCE_REGROUP) != 0u;
+}
+
+// key + sort + trace of one batch on `stream`; caller holds st.mu, has the device current and the scene uploaded
+int query_launch(RtxScene *scene, DeviceState &st, bool occlusion, uint32_t n_rays, const float *d_first,
+                 const float *d_second, uint32_t flags, void *d_out, unsigned long long *d_counters, hipStream_t stream)
+{
+    const bool regroup = query_regroups(n_rays, flags);
+    int rc;
+    if (regroup && (rc = ensure_query_sort(st, n_rays)) != RTX_OK) return rc;
+    const rtx::DeviceScene S = device_scene(scene, st);
+    RTX_HIP(rtxq::launch_query(S, occlusion, n_rays, d_first, d_second, query_key_box(scene->prep),
+                               scene->prep.cull_delta * 0x1p19f, regroup ? &st.q_sort : nullptr, d_out, d_counters, stream));
+    return RTX_OK;
+}
+
+// the host entry points: copy in, launch, copy out
+int query_host(RtxScene *scene, int device, bool occlusion, uint32_t n_rays, const float *first, const float *second,
+               uint32_t flags, void *out, RtxStats *stats)
+{
+    if (!scene || !first || !second || !out || (flags & ~kQueryFlags) || n_rays > rtxq::kMaxRays) return RTX_ERR_BAD_ARG;
+    const double t0 = wall_ms();
+    if (n_rays == 0u) {
+        if (stats) { std::memset(stats, 0, sizeof *stats); stats->total_ms = wall_ms() - t0; }
+        return RTX_OK;
+    }
+    DeviceState *st;
+    int rc = get_state(scene, device, &st);
+    if (rc != RTX_OK) return rc;
+    std::lock_guard<std::mutex> lk(st->mu);
+    DeviceGuard g(device);
+    RTX_HIP(g.status());
+    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
+    const size_t in_bytes = static_cast<size_t>(n_rays) * 3u * sizeof(float);
+    const size_t out_bytes = static_cast<size_t>(n_rays) * (occlusion ? 1u : sizeof(RtxRayHit));
+    if ((rc = grow_buffer(&st->q_first, &st->q_first_cap, in_bytes)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(&st->q_second, &st->q_second_cap, in_bytes)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(&st->q_out, &st->q_out_cap, out_bytes)) != RTX_OK) return rc;
+    if (st->q_sorted) RTX_HIP(hipStreamWaitEvent(st->stream, st->q_sorted, 0));   // a device-resident call may still be sorting
+    RTX_HIP(hipMemcpyAsync(st->q_first, first, in_bytes, hipMemcpyHostToDevice, st->stream));
+    RTX_HIP(hipMemcpyAsync(st->q_second, second, in_bytes, hipMemcpyHostToDevice, st->stream));
+    if (stats) RTX_HIP(hipMemsetAsync(st->d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st->stream));
+    RTX_HIP(hipEventRecord(st->ev0, st->stream));
+    if ((rc = query_launch(scene, *st, occlusion, n_rays, st->q_first, st->q_second, flags, st->q_out,
+                           stats ? st->d_counters : nullptr, st->stream)) != RTX_OK) {
+        (void)hipStreamSynchronize(st->stream);      // the copies above read the caller's arrays
+        return rc;
+    }
+    RTX_HIP(hipEventRecord(st->ev1, st->stream));
+    RTX_HIP(hipMemcpyAsync(out, st->q_out, out_bytes, hipMemcpyDeviceToHost, st->stream));
+    unsigned long long c[rtx::kNumCounters] = {0};
+    if (stats) RTX_HIP(hipMemcpyAsync(c, st->d_counters, sizeof c, hipMemcpyDeviceToHost, st->stream));
+    RTX_HIP(hipStreamSynchronize(st->stream));
+    if (stats) {
+        float ms = 0.0f;
+        RTX_HIP(hipEventElapsedTime(&ms, st->ev0, st->ev1));
+        std::memset(stats, 0, sizeof *stats);
+        stats->primary_rays = stats->rays = n_rays;
+        stats->primary_hits = c[0];
+        stats->box_tests = c[1];
+        stats->tri_tests = c[2];
+        stats->wave_node_visits = c[3];
+        stats->wave_tri_visits = c[4];
+        stats->redo_tiles = c[5];
+        stats->kernel_ms = ms;
+        stats->total_ms = wall_ms() - t0;
+    }
+    return RTX_OK;
+}
+
+int query_device(RtxScene *scene, int device, bool occlusion, uint32_t n_rays, const void *d_first, const void *d_second,
+                 uint32_t flags, void *d_out, void *stream)
+{
+    if (!scene || !d_first || !d_second || !d_out || (flags & ~kQueryFlags) || n_rays > rtxq::kMaxRays) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_first) | reinterpret_cast<uintptr_t>(d_second)) & 3u) return RTX_ERR_BAD_ARG;
+    if (!occlusion && (reinterpret_cast<uintptr_t>(d_out) & 15u)) return RTX_ERR_BAD_ARG;
+    if (n_rays == 0u) return RTX_OK;
+    DeviceState *st;
+    int rc = get_state(scene, device, &st);
+    if (rc != RTX_OK) return rc;
+    std::lock_guard<std::mutex> lk(st->mu);
+    DeviceGuard g(device);
+    RTX_HIP(g.status());
+    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
+    if ((rc = query_launch(scene, *st, occlusion, n_rays, static_cast<const float *>(d_first), static_cast<const float *>(d_second),
+                           flags, d_out, nullptr, static_cast<hipStream_t>(stream))) != RTX_OK) return rc;
+    if (query_regroups(n_rays, flags)) {     // the library's sort buffers are busy until this point of the caller's stream
+        if (!st->q_sorted) RTX_HIP(hipEventCreateWithFlags(&st->q_sorted, hipEventDisableTiming));
+        RTX_HIP(hipEventRecord(st->q_sorted, static_cast<hipStream_t>(stream)));
+    }
+    return RTX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,11 +535,14 @@ void rtx_scene_destroy(RtxScene *scene)
         if (g.status() != hipSuccess) continue;
         if (st.stream) (void)hipStreamSynchronize(st.stream);
         void *bufs[] = {st.nodes, st.primary_nodes, st.ref_nodes, st.tris, st.shade, st.samples, st.lights, st.thr, st.planes, st.light_boxes, st.d_out, st.d_counters, st.d_redo,
-                        st.ws.hits, st.ws.pix_slot, st.ws.tiles, st.ws.chunks, st.ws.results, st.ws.acc, st.ws.ctr, st.ws.buckets, st.ws.cut};
+                        st.ws.hits, st.ws.pix_slot, st.ws.tiles, st.ws.chunks, st.ws.results, st.ws.acc, st.ws.ctr, st.ws.buckets, st.ws.cut,
+                        st.q_first, st.q_second, st.q_out, st.q_sort.keys, st.q_sort.keys_sorted, st.q_sort.index, st.q_sort.index_sorted,
+                        st.q_sort.temp};
         for (void *b : bufs) if (b) (void)hipFree(b);
         if (st.h_stage) (void)hipHostFree(st.h_stage);
         if (st.ev0) (void)hipEventDestroy(st.ev0);
         if (st.ev1) (void)hipEventDestroy(st.ev1);
+        if (st.q_sorted) (void)hipEventDestroy(st.q_sorted);
         for (auto &slot : st.ring)
             for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e);
         if (st.stream) (void)hipStreamDestroy(st.stream);
@@ -615,6 +761,30 @@ int rtx_render_tiles_device(RtxScene *scene, int device, uint32_t first_tile, ui
                                     static_cast<hipStream_t>(stream), st->ring[st->launches % RTX_TIMING_RING]));
     if (ts.local_rows) ++st->launches;
     return RTX_OK;
+}
+
+int rtx_trace_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
+                   uint32_t flags, RtxRayHit *out_hits, RtxStats *stats)
+{
+    return query_host(scene, device, false, n_rays, origins, directions, flags, out_hits, stats);
+}
+
+int rtx_occluded_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
+                      uint32_t flags, uint8_t *out_occluded, RtxStats *stats)
+{
+    return query_host(scene, device, true, n_rays, origins, targets, flags, out_occluded, stats);
+}
+
+int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
+                          uint32_t flags, void *d_hits, void *stream)
+{
+    return query_device(scene, device, false, n_rays, d_origins, d_directions, flags, d_hits, stream);
+}
+
+int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
+                             uint32_t flags, void *d_occluded, void *stream)
+{
+    return query_device(scene, device, true, n_rays, d_origins, d_targets, flags, d_occluded, stream);
 }
 
 int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint64_t *out,

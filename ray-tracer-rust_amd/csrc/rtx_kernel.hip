@@ -118,23 +118,6 @@ __device__ __forceinline__ void primary_ray(const DeviceScene &S, bool in_frame,
     (void)length_and_direction(rx, ry, rz, rn, dx, dy, dz);                          // ray.rs:15: sqrt, three divisions (bit for bit)
 }
 
-// HitInfo.normal = p.get_normal(p_hit) (bvh.rs:72, mod.rs:80-87): the stored normal of a triangle (triangle.rs:29),
-// normalize(p_hit - origin) for a sphere (sphere.rs:93-95; the record holds the origin in its normal field)
-template <bool SPHERES>
-__device__ __forceinline__ void hit_normal(const ShadeRec &sh, float hx, float hy, float hz, float &nx, float &ny, float &nz)
-{
-    nx = sh.normal[0];
-    ny = sh.normal[1];
-    nz = sh.normal[2];
-    if (SPHERES && sh.kind != 0u) {
-        const float vx = hx - nx, vy = hy - ny, vz = hz - nz;
-        const float n = sqrtf(dot_zero_first(vx, vy, vz, vx, vy, vz));
-        nx = vx / n;
-        ny = vy / n;
-        nz = vz / n;
-    }
-}
-
 // One shadow ray of phase 2: ray number -> (compacted hit pixel, light sample), origin = the pixel's hit
 // point, direction = towards the light point (main.rs:194-202).
 struct ShadowRay {

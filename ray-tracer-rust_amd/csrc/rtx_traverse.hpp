@@ -178,6 +178,24 @@ __device__ __forceinline__ bool sphere_distance(const TriRec RTX_CONSTANT *sp, f
     return !behind && !outside && !both_behind;
 }
 
+// HitInfo.normal = p.get_normal(p_hit) (bvh.rs:72, mod.rs:80-87): the stored normal of a triangle (triangle.rs:29),
+// normalize(p_hit - origin) for a sphere (sphere.rs:93-95; the record holds the origin in its normal field)
+// (here, not in rtx_kernel.hip: the render kernels and the ray-query kernels of rtx_query.hip share it)
+template <bool SPHERES>
+__device__ __forceinline__ void hit_normal(const ShadeRec &sh, float hx, float hy, float hz, float &nx, float &ny, float &nz)
+{
+    nx = sh.normal[0];
+    ny = sh.normal[1];
+    nz = sh.normal[2];
+    if (SPHERES && sh.kind != 0u) {
+        const float vx = hx - nx, vy = hy - ny, vz = hz - nz;
+        const float n = sqrtf(dot_zero_first(vx, vy, vz, vx, vy, vz));
+        nx = vx / n;
+        ny = vy / n;
+        nz = vz / n;
+    }
+}
+
 // The literal reference traversal, for wavefronts that hold a ray with a zero / denormal / non-finite
 // direction component.  For such rays BoundingBox::intersect produces +-inf and NaN (0/0) terms and
 // the outcome depends on the tree: e.g. with d.y = -0.0 an ancestor box gives tymin=+inf, tymax=-inf

@@ -86,6 +86,18 @@ class SceneInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RayHit(C.Structure):
+    """RtxRayHit: one closest hit (prim == NO_HIT: a miss, everything else zero)."""
+    _fields_ = [("prim", C.c_uint32), ("t", C.c_float), ("p_hit", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+NO_HIT = 0xFFFFFFFF
+RAYS_KEEP_ORDER, RAYS_FORCE_REGROUP = 1, 2
+# the same 32 bytes as a numpy record: what Scene.trace_rays returns
+RAY_HIT_DTYPE = np.dtype([("prim", np.uint32), ("t", np.float32), ("p_hit", np.float32, 3), ("normal", np.float32, 3)])
+assert RAY_HIT_DTYPE.itemsize == C.sizeof(RayHit) == 32
+
+
 # every symbol include/rtx.h declares (tests check the export list against the header)
 _SIGS = {
     "rtx_abi_version": (C.c_int, []),
@@ -100,6 +112,10 @@ _SIGS = {
                                           C.c_size_t, C.c_void_p, C.c_void_p]),
     "rtx_tiles_rows": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "rtx_tiles_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rtx_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, C.POINTER(RayHit), C.POINTER(Stats)]),
+    "rtx_occluded_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, u8p, C.POINTER(Stats)]),
+    "rtx_trace_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtx_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -442,6 +458,53 @@ class Scene:
                                             C.c_void_p(stream) if stream else None,
                                             C.c_void_p(d_counters_ptr) if d_counters_ptr else None),
                "rtx_render_tiles_device")
+
+    # -- ray queries (GPU only): rays the caller supplies
+    @staticmethod
+    def _ray_flags(keep_order, force_regroup):
+        return (RAYS_KEEP_ORDER if keep_order else 0) | (RAYS_FORCE_REGROUP if force_regroup else 0)
+
+    @staticmethod
+    def _ray_arrays(first, second):
+        a = np.ascontiguousarray(first, dtype=np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(second, dtype=np.float32).reshape(-1, 3)
+        if len(a) != len(b):
+            raise ValueError("the two ray arrays disagree in length")
+        return a, b
+
+    def trace_rays(self, origins, directions, device=0, keep_order=False, stats=False, force_regroup=False):
+        """bvh.intersect(&Ray::new(origin, direction)) per ray -> structured array (RAY_HIT_DTYPE) of n records
+        {prim, t, p_hit, normal}; prim == NO_HIT is a miss.  Directions may have any length.  keep_order traces in the
+        given order (no regrouping pass); the results are the same bytes either way."""
+        o, d = self._ray_arrays(origins, directions)
+        out = np.zeros(len(o), RAY_HIT_DTYPE)
+        st = Stats()
+        _check(_lib.rtx_trace_rays(self._h, device, len(o), _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup),
+                                   out.ctypes.data_as(C.POINTER(RayHit)), C.byref(st) if stats else None), "rtx_trace_rays")
+        return (out, st.asdict()) if stats else out
+
+    def occluded_rays(self, origins, targets, device=0, keep_order=False, stats=False, force_regroup=False):
+        """The decision of main.rs:201-231 per (origin, target) pair -> uint8 [n], 1 = occluded, 0 = lit."""
+        o, t = self._ray_arrays(origins, targets)
+        out = np.zeros(len(o), np.uint8)
+        st = Stats()
+        _check(_lib.rtx_occluded_rays(self._h, device, len(o), _fp(o), _fp(t), self._ray_flags(keep_order, force_regroup),
+                                      out.ctypes.data_as(u8p), C.byref(st) if stats else None), "rtx_occluded_rays")
+        return (out, st.asdict()) if stats else out
+
+    def trace_rays_device(self, device, n_rays, d_origins_ptr, d_directions_ptr, d_hits_ptr, stream=None,
+                          keep_order=False, force_regroup=False):
+        """Asynchronous closest-hit launch on device buffers the caller owns (n x 3 float32 twice, n x 32 bytes out)."""
+        _check(_lib.rtx_trace_rays_device(self._h, device, n_rays, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
+                                          self._ray_flags(keep_order, force_regroup), C.c_void_p(d_hits_ptr),
+                                          C.c_void_p(stream) if stream else None), "rtx_trace_rays_device")
+
+    def occluded_rays_device(self, device, n_rays, d_origins_ptr, d_targets_ptr, d_occluded_ptr, stream=None,
+                             keep_order=False, force_regroup=False):
+        """Asynchronous occlusion launch on device buffers the caller owns (n x 3 float32 twice, n bytes out)."""
+        _check(_lib.rtx_occluded_rays_device(self._h, device, n_rays, C.c_void_p(d_origins_ptr), C.c_void_p(d_targets_ptr),
+                                             self._ray_flags(keep_order, force_regroup), C.c_void_p(d_occluded_ptr),
+                                             C.c_void_p(stream) if stream else None), "rtx_occluded_rays_device")
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
