@@ -10,15 +10,12 @@ import numpy as np
 import pytest
 
 import np_ref
+from query_sets import (F, H, LIGHT_POINT, NO_HIT, W, bits, bunny_random_sets, check_hits, expected_occlusion,
+                        oracle_hits)
 from test_gpu_spheres import KAT, kat_scene
 
 pytestmark = pytest.mark.gpu
-F = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NO_HIT = 0xFFFFFFFF
-LIGHT_POINT = (0.0, 300.0, -3.3)
-BOX_LO, BOX_HI = (-150.0, 5.0, -120.0), (120.0, 250.0, 120.0)
-W = H = 32
 
 
 @pytest.fixture(scope="module")
@@ -26,26 +23,6 @@ def rtx():
     mod = importlib.import_module("ray-tracer-rust_amd")
     assert mod.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
     return mod
-
-
-def unit(orc, d):
-    """Ray::new (ray.rs:12-17) by the oracle"""
-    out = np.zeros(3, F)
-    orc.lib().orc_ray_new(orc._fp(orc.f3(d)), orc._fp(out))
-    return out
-
-
-def oracle_hits(orc, osc, origins, directions, dtype):
-    """orc_closest_hit(o, Ray::new(d)) per ray as RtxRayHit records (the normal is left zero), and the unit directions"""
-    exp = np.zeros(len(origins), dtype)
-    units = np.zeros((len(origins), 3), F)
-    exp["prim"] = NO_HIT
-    for i, (o, d) in enumerate(zip(origins, directions)):
-        units[i] = unit(orc, d)
-        h = osc.closest_hit(o, units[i])
-        if h.hit:
-            exp["prim"][i], exp["t"][i], exp["p_hit"][i] = h.tri, h.t, list(h.p_hit)
-    return exp, units
 
 
 def primaries(orc, eye, look_at, up, distance, samples, scale=1.0):
@@ -63,20 +40,6 @@ def primaries(orc, eye, look_at, up, distance, samples, scale=1.0):
     return o, (d * F(scale)).astype(F)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
-
-
-def check_hits(got, exp, normals, what):
-    assert np.array_equal(got["prim"], exp["prim"]), "%s: primitives differ at %s" % (what, np.nonzero(got["prim"] != exp["prim"])[0][:8])
-    assert np.array_equal(bits(got["t"]), bits(exp["t"])), what + ": t differs"
-    assert np.array_equal(bits(got["p_hit"]), bits(exp["p_hit"])), what + ": p_hit differs"
-    hit = exp["prim"] != NO_HIT
-    if normals is not None:
-        assert np.array_equal(bits(got["normal"][hit]), bits(normals[exp["prim"][hit]])), what + ": a triangle's normal differs"
-    assert not got["t"][~hit].any() and not got["p_hit"][~hit].any() and not got["normal"][~hit].any(), what + ": a miss is not zeros"
-
-
 def trace_every_way(scene, o, d, exp, normals, what):
     """caller's order, default, forced regrouping x with / without statistics: the oracle's answer, the same bytes"""
     first = None
@@ -91,14 +54,6 @@ def trace_every_way(scene, o, d, exp, normals, what):
             first = got if first is None else first
             assert got.tobytes() == first.tobytes(), "%s: %s stats=%s differs from the first call" % (what, mode, stats)
     return first
-
-
-def expected_occlusion(exp, origins, targets):
-    """main.rs:202,220-221 on the oracle's closest hit, float32"""
-    o, t = np_ref._v(origins), np_ref._v(targets)
-    dist_light = np_ref._norm(np_ref._sub(t, o))
-    dist_hit = np_ref._norm(np_ref._sub(o, np_ref._v(exp["p_hit"])))
-    return ((exp["prim"] != NO_HIT) & ~(dist_hit > dist_light)).astype(np.uint8)
 
 
 def occluded_every_way(scene, o, t, want, what):
@@ -124,13 +79,7 @@ def bunny(rtx, orc, samples_seeded):
     lo = sets["primary"][2]["p_hit"].copy()
     ld = (np.asarray(LIGHT_POINT, F) - lo).astype(F)
     sets["to_light"] = (lo, ld) + oracle_hits(orc, osc, lo, ld, dt)
-    rng = np.random.default_rng(7)
-    ro = rng.uniform(BOX_LO, BOX_HI, size=(1500, 3)).astype(F)
-    rd = rng.normal(size=(1500, 3)).astype(F)
-    sets["random"] = (ro, rd) + oracle_hits(orc, osc, ro, rd, dt)
-    targets = rng.uniform(BOX_LO, BOX_HI, size=(1500, 3)).astype(F)
-    rt = (targets - ro).astype(F)
-    sets["random_targets"] = (ro, targets) + oracle_hits(orc, osc, ro, rt, dt)
+    sets.update(bunny_random_sets(orc, osc, dt))       # "random" and "random_targets"
     yield dict(scene=scene, osc=osc, sets=sets, normals=scene.normals(), ground=len(scene.tris) - 1)
     scene.close()
     osc.close()
