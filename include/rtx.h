@@ -236,6 +236,47 @@ int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const vo
 int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
                              uint32_t flags, void *d_occluded, void *stream);
 
+/* ---- shading rays the caller supplies ---------------------------------------- */
+/* render_pixel's body (main.rs:182-239) for a batch: per ray the closest hit, nb_light_sample shadow rays towards the
+ * scene's area light, the sequential f32 sum and Color::to_rgba — the colour the reference gives a pixel whose rays
+ * create_rays did not make: another camera model, a crop, a second bounce, a light-map bake, a picker.  Kernels of its
+ * own, beside the render pipeline and the ray queries.
+ *
+ * A "pixel" is nb_ray consecutive rays of the arrays (nb_ray is the scene's; the reference's value is 1): origins and
+ * directions hold n_pixels * nb_ray x 3 floats, host; a direction may have any length (Ray::new normalises).  Pixel p
+ * gets exactly what render_pixel computes when create_rays returns Ray::new(origins[p*nb_ray + r], directions[p*nb_ray
+ * + r]) for r = 0..nb_ray.  Each ray with a closest hit runs i = 0..nb_light_sample: the light point is the scene's
+ * light_points[r][i] (table entry (r*nb_ray + i) % n_samples, rtx_scene_light_points), the shadow ray is
+ * Ray::new(p_hit, p - p_hit), lnd = |normal . direction|, the decision is that of main.rs:218-232 (rtx_occluded_rays'),
+ * and avg += (colour * lnd) / (nb_ray * nb_light_sample) as f32, channel by channel in that order; an occluded sample
+ * adds nothing (the reference adds black / denom = +0.0), as in the render pipeline.  A pixel whose rays all miss is
+ * {0,0,0}, bytes 0,0,0, hits = 0.  Results do not depend on the tracing order: with or without the regrouping pass
+ * (the key is built from each pixel's ray 0) a pixel's 16 bytes are the same.
+ * Outside the parity contract, as for the ray queries: non-finite inputs, zero-length directions, non-finite t (the call
+ * still terminates with RTX_OK). */
+typedef struct RtxPixelShade {   /* 16 bytes, one 16-byte store */
+    float   linear[3];           /* render_pixel's avg_col (main.rs:182-239) for this pixel's rays */
+    uint8_t rgb8[3];             /* Color::to_rgba of it: the scene's gamma thresholds, as the frame's bytes */
+    uint8_t hits;                /* how many of the pixel's nb_ray rays had a closest hit, saturating at 255 */
+} RtxPixelShade;
+/* out_shade: n_pixels records.  out_hits: NULL, or n_pixels * nb_ray records, byte-identical to what rtx_trace_rays
+ * writes for the same rays.  flags: RTX_RAYS_KEEP_ORDER, RTX_RAYS_FORCE_REGROUP (the regrouping threshold counts
+ * pixels).  NULL scene / origins / directions / out_shade, unknown flag or n_pixels * nb_ray > 2^28: RTX_ERR_BAD_ARG;
+ * n_pixels == 0: RTX_OK, nothing written; no usable device: RTX_ERR_NO_DEVICE (there is no CPU fallback).
+ * stats may be NULL; when non-NULL the counted kernel form runs (same results) and the fields mean:
+ *   primary_rays = n_pixels * nb_ray, primary_hits = rays with a closest hit, shadow_rays = nb_light_sample *
+ *   primary_hits, rays = primary_rays + shadow_rays, box_tests / tri_tests / wave_node_visits / wave_tri_visits as for
+ *   rendering, redo_tiles = 64-LANE WALKS, primary or shadow, that took the literal reference traversal (a -0.0, NaN or
+ *   infinite direction component among their rays), kernel_ms / total_ms as rtx_trace_rays. */
+int rtx_shade_rays(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
+                   uint32_t flags, RtxPixelShade *out_shade, RtxRayHit *out_hits /* may be NULL */, RtxStats *stats);
+/* Device-resident variant, asynchronous on `stream`, as rtx_trace_rays_device is: device pointers the caller owns
+ * (floats 4-byte aligned; d_shade and, when given, d_hits 16-byte aligned: else RTX_ERR_BAD_ARG).  It uses the ray
+ * queries' regrouping buffers, so the same rule holds across all of them: device-resident query and shade launches on
+ * one device must be ordered on one stream, and the host entry points wait (by an event) for the most recent of them. */
+int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
+                          uint32_t flags, void *d_shade, void *d_hits /* may be NULL */, void *stream);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

@@ -92,6 +92,15 @@ pub struct RtxRayHit {
     pub p_hit: [f32; 3],
     pub normal: [f32; 3],
 }
+/// One pixel of `rtx_shade_rays`: `render_pixel`'s `avg_col` for the caller's rays, its `Color::to_rgba` bytes, and how
+/// many of the pixel's `nb_ray` rays had a closest hit (saturating at 255).
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxPixelShade {
+    pub linear: [f32; 3],
+    pub rgb8: [u8; 3],
+    pub hits: u8,
+}
 pub const RTX_NO_HIT: u32 = 0xFFFF_FFFF;
 pub const RTX_RAYS_KEEP_ORDER: u32 = 1;
 pub const RTX_RAYS_FORCE_REGROUP: u32 = 2;
@@ -126,6 +135,11 @@ extern "C" {
                                  d_directions: *const c_void, flags: u32, d_hits: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn rtx_occluded_rays_device(scene: *mut RtxScene, device: c_int, n_rays: u32, d_origins: *const c_void,
                                     d_targets: *const c_void, flags: u32, d_occluded: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn rtx_shade_rays(scene: *mut RtxScene, device: c_int, n_pixels: u32, origins: *const f32, directions: *const f32,
+                          flags: u32, out_shade: *mut RtxPixelShade, out_hits: *mut RtxRayHit, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_shade_rays_device(scene: *mut RtxScene, device: c_int, n_pixels: u32, d_origins: *const c_void,
+                                 d_directions: *const c_void, flags: u32, d_shade: *mut c_void, d_hits: *mut c_void,
+                                 stream: *mut c_void) -> c_int;
     pub fn rtx_launch_timings(scene: *mut RtxScene, device: c_int, max_launches: c_int, schedule_ms: *mut f32,
                               shade_ms: *mut f32) -> c_int;
     pub fn rtx_strerror(err: c_int) -> *const c_char;

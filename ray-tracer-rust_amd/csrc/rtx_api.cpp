@@ -19,6 +19,7 @@
 #include "../../include/rtx.h"
 #include "rtx_device.h"
 #include "rtx_query.h"
+#include "rtx_shade.h"
 #include "scene_prep.h"
 
 namespace {
@@ -484,6 +485,106 @@ int query_device(RtxScene *scene, int device, bool occlusion, uint32_t n_rays, c
     return RTX_OK;
 }
 
+// ---- shading caller-supplied rays (rtx_shade.hip) ----------------------------------------------------------------------
+
+static_assert(sizeof(RtxPixelShade) == 16, "shade_kernel writes a pixel as one 16-byte word");
+
+// n_pixels * nb_ray, or 0 when it is beyond what one batch may hold
+uint32_t shade_ray_count(const RtxScene *scene, uint32_t n_pixels)
+{
+    const uint64_t n = static_cast<uint64_t>(n_pixels) * scene->prep.nb_ray;
+    return n <= rtxq::kMaxRays ? static_cast<uint32_t>(n) : 0u;
+}
+
+// key + sort + shade of one batch on `stream`; caller holds st.mu, has the device current and the scene uploaded.  The
+// regrouping policy, its buffers, the key box and the origin bound are the ray queries' (query_launch); the unit is a pixel.
+int shade_launch(RtxScene *scene, DeviceState &st, uint32_t n_pixels, const float *d_origins, const float *d_directions,
+                 uint32_t flags, void *d_shade, void *d_hits, unsigned long long *d_counters, hipStream_t stream)
+{
+    const bool regroup = query_regroups(n_pixels, flags);
+    int rc;
+    if (regroup && (rc = ensure_query_sort(st, n_pixels)) != RTX_OK) return rc;
+    const rtx::DeviceScene S = device_scene(scene, st);
+    RTX_HIP(rtxs::launch_shade(S, n_pixels, d_origins, d_directions, query_key_box(scene->prep),
+                               scene->prep.cull_delta * 0x1p19f, regroup ? &st.q_sort : nullptr, d_shade, d_hits, d_counters,
+                               stream));
+    return RTX_OK;
+}
+
+// the host entry point: copy in, launch, copy out (staging and ordering as query_host)
+int shade_host(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions, uint32_t flags,
+               RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
+{
+    if (!scene || !origins || !directions || !out_shade || (flags & ~kQueryFlags)) return RTX_ERR_BAD_ARG;
+    const uint32_t n_rays = shade_ray_count(scene, n_pixels);
+    if (n_pixels != 0u && n_rays == 0u) return RTX_ERR_BAD_ARG;
+    const double t0 = wall_ms();
+    if (n_pixels == 0u) {
+        if (stats) { std::memset(stats, 0, sizeof *stats); stats->total_ms = wall_ms() - t0; }
+        return RTX_OK;
+    }
+    DeviceState *st;
+    int rc = get_state(scene, device, &st);
+    if (rc != RTX_OK) return rc;
+    std::lock_guard<std::mutex> lk(st->mu);
+    DeviceGuard g(device);
+    RTX_HIP(g.status());
+    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
+    const size_t in_bytes = static_cast<size_t>(n_rays) * 3u * sizeof(float);
+    const size_t shade_bytes = static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade);     // a multiple of 16: the hit
+    const size_t hit_bytes = out_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u;   // records behind stay aligned
+    if ((rc = grow_buffer(&st->q_first, &st->q_first_cap, in_bytes)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(&st->q_second, &st->q_second_cap, in_bytes)) != RTX_OK) return rc;
+    if ((rc = grow_buffer(&st->q_out, &st->q_out_cap, shade_bytes + hit_bytes)) != RTX_OK) return rc;
+    uint8_t *d_shade = st->q_out, *d_hits = out_hits ? st->q_out + shade_bytes : nullptr;
+    if (st->q_sorted) RTX_HIP(hipStreamWaitEvent(st->stream, st->q_sorted, 0));   // a device-resident call may still be sorting
+    RTX_HIP(hipMemcpyAsync(st->q_first, origins, in_bytes, hipMemcpyHostToDevice, st->stream));
+    RTX_HIP(hipMemcpyAsync(st->q_second, directions, in_bytes, hipMemcpyHostToDevice, st->stream));
+    if (stats) RTX_HIP(hipMemsetAsync(st->d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st->stream));
+    RTX_HIP(hipEventRecord(st->ev0, st->stream));
+    if ((rc = shade_launch(scene, *st, n_pixels, st->q_first, st->q_second, flags, d_shade, d_hits,
+                           stats ? st->d_counters : nullptr, st->stream)) != RTX_OK) {
+        (void)hipStreamSynchronize(st->stream);      // the copies above read the caller's arrays
+        return rc;
+    }
+    RTX_HIP(hipEventRecord(st->ev1, st->stream));
+    RTX_HIP(hipMemcpyAsync(out_shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st->stream));
+    if (out_hits) RTX_HIP(hipMemcpyAsync(out_hits, d_hits, hit_bytes, hipMemcpyDeviceToHost, st->stream));
+    unsigned long long c[rtx::kNumCounters] = {0};
+    if (stats) RTX_HIP(hipMemcpyAsync(c, st->d_counters, sizeof c, hipMemcpyDeviceToHost, st->stream));
+    RTX_HIP(hipStreamSynchronize(st->stream));
+    if (stats) {
+        float ms = 0.0f;
+        RTX_HIP(hipEventElapsedTime(&ms, st->ev0, st->ev1));
+        fill_stats(stats, scene, n_pixels, c, ms, wall_ms() - t0);
+    }
+    return RTX_OK;
+}
+
+int shade_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
+                 uint32_t flags, void *d_shade, void *d_hits, void *stream)
+{
+    if (!scene || !d_origins || !d_directions || !d_shade || (flags & ~kQueryFlags)) return RTX_ERR_BAD_ARG;
+    if (n_pixels != 0u && shade_ray_count(scene, n_pixels) == 0u) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_directions)) & 3u) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
+    if (n_pixels == 0u) return RTX_OK;
+    DeviceState *st;
+    int rc = get_state(scene, device, &st);
+    if (rc != RTX_OK) return rc;
+    std::lock_guard<std::mutex> lk(st->mu);
+    DeviceGuard g(device);
+    RTX_HIP(g.status());
+    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
+    if ((rc = shade_launch(scene, *st, n_pixels, static_cast<const float *>(d_origins), static_cast<const float *>(d_directions),
+                           flags, d_shade, d_hits, nullptr, static_cast<hipStream_t>(stream))) != RTX_OK) return rc;
+    if (query_regroups(n_pixels, flags)) {     // the library's sort buffers are busy until this point of the caller's stream
+        if (!st->q_sorted) RTX_HIP(hipEventCreateWithFlags(&st->q_sorted, hipEventDisableTiming));
+        RTX_HIP(hipEventRecord(st->q_sorted, static_cast<hipStream_t>(stream)));
+    }
+    return RTX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -785,6 +886,18 @@ int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const
                              uint32_t flags, void *d_occluded, void *stream)
 {
     return query_device(scene, device, true, n_rays, d_origins, d_targets, flags, d_occluded, stream);
+}
+
+int rtx_shade_rays(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
+                   uint32_t flags, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
+{
+    return shade_host(scene, device, n_pixels, origins, directions, flags, out_shade, out_hits, stats);
+}
+
+int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
+                          uint32_t flags, void *d_shade, void *d_hits, void *stream)
+{
+    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, d_shade, d_hits, stream);
 }
 
 int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint64_t *out,

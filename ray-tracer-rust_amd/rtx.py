@@ -98,6 +98,16 @@ RAY_HIT_DTYPE = np.dtype([("prim", np.uint32), ("t", np.float32), ("p_hit", np.f
 assert RAY_HIT_DTYPE.itemsize == C.sizeof(RayHit) == 32
 
 
+class PixelShade(C.Structure):
+    """RtxPixelShade: render_pixel's result for one pixel of caller-supplied rays."""
+    _fields_ = [("linear", C.c_float * 3), ("rgb8", C.c_uint8 * 3), ("hits", C.c_uint8)]
+
+
+# the same 16 bytes as a numpy record: what Scene.shade_rays returns
+PIXEL_SHADE_DTYPE = np.dtype([("linear", np.float32, 3), ("rgb8", np.uint8, 3), ("hits", np.uint8)])
+assert PIXEL_SHADE_DTYPE.itemsize == C.sizeof(PixelShade) == 16
+
+
 # every symbol include/rtx.h declares (tests check the export list against the header)
 _SIGS = {
     "rtx_abi_version": (C.c_int, []),
@@ -116,6 +126,10 @@ _SIGS = {
     "rtx_occluded_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, u8p, C.POINTER(Stats)]),
     "rtx_trace_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rtx_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtx_shade_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, C.POINTER(PixelShade),
+                                 C.POINTER(RayHit), C.POINTER(Stats)]),
+    "rtx_shade_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -289,6 +303,7 @@ class Scene:
         if self.kinds is not None and len(self.kinds) != len(self.tris) + len(self.spheres):
             raise ValueError("kinds must have one entry per primitive")
         self.n_prims = len(self.tris) + len(self.spheres)
+        self.nb_ray = int(nb_ray)
         if isinstance(tie_rank, str):
             if tie_rank != "reference":
                 raise ValueError(tie_rank)
@@ -505,6 +520,36 @@ class Scene:
         _check(_lib.rtx_occluded_rays_device(self._h, device, n_rays, C.c_void_p(d_origins_ptr), C.c_void_p(d_targets_ptr),
                                              self._ray_flags(keep_order, force_regroup), C.c_void_p(d_occluded_ptr),
                                              C.c_void_p(stream) if stream else None), "rtx_occluded_rays_device")
+
+    # -- shading rays the caller supplies (GPU only)
+    def shade_rays(self, origins, directions, device=0, keep_order=False, stats=False, force_regroup=False,
+                   want_hits=False):
+        """render_pixel's body (main.rs:182-239) per pixel of nb_ray consecutive rays -> structured array
+        (PIXEL_SHADE_DTYPE) of n / nb_ray records {linear, rgb8, hits}.  want_hits adds the rays' closest hits
+        (RAY_HIT_DTYPE, n records, what trace_rays returns); stats adds the statistics, last.  Directions may have any
+        length; keep_order shades in the given order (no regrouping pass): the same bytes either way."""
+        o, d = self._ray_arrays(origins, directions)
+        if len(o) % self.nb_ray:
+            raise ValueError("a pixel is nb_ray = %d consecutive rays" % self.nb_ray)
+        n = len(o) // self.nb_ray
+        out = np.zeros(n, PIXEL_SHADE_DTYPE)
+        hits = np.zeros(len(o), RAY_HIT_DTYPE) if want_hits else None
+        st = Stats()
+        _check(_lib.rtx_shade_rays(self._h, device, n, _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup),
+                                   out.ctypes.data_as(C.POINTER(PixelShade)),
+                                   hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None,
+                                   C.byref(st) if stats else None), "rtx_shade_rays")
+        res = (out,) + ((hits,) if want_hits else ()) + ((st.asdict(),) if stats else ())
+        return res if len(res) > 1 else out
+
+    def shade_rays_device(self, device, n_pixels, d_origins_ptr, d_directions_ptr, d_shade_ptr, d_hits_ptr=None,
+                          stream=None, keep_order=False, force_regroup=False):
+        """Asynchronous shading launch on device buffers the caller owns (n_pixels * nb_ray x 3 float32 twice,
+        n_pixels x 16 bytes out, optionally n_pixels * nb_ray x 32 bytes of hit records)."""
+        _check(_lib.rtx_shade_rays_device(self._h, device, n_pixels, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
+                                          self._ray_flags(keep_order, force_regroup), C.c_void_p(d_shade_ptr),
+                                          C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
+                                          C.c_void_p(stream) if stream else None), "rtx_shade_rays_device")
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
