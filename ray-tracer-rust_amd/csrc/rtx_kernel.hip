@@ -1214,7 +1214,11 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                     // form and in tiles of the cut form that walk.  Walks differ in length by an order of magnitude (a chunk in
                     // the open: a dozen records; one whose rays all end in the mesh: fifty to two hundred — the split by outcome
                     // in DESIGN.md section 4), and a job ends when its slowest wavefront does: the 1M-triangle soup -7 %.
-                    const bool kDrawChunks = WHOLE || (RTX_CUT_DRAW_MIN != 0 && n_cut >= RTX_CUT_DRAW_MIN);
+                    // (Not in the counted cut form: a wavefront's walk begins at the cut entry where its previous chunk found
+                    //  its occluder — first_entry — so with drawn chunks the records a chunk walks depend on which wavefront
+                    //  drew it, and box_tests / tri_tests / the visit counts of one frame differed from launch to launch by
+                    //  0.1 %, the bytes never.  Dealt chunks make RtxStats reproducible; the counted form is not timed.)
+                    const bool kDrawChunks = WHOLE || (!COUNT && RTX_CUT_DRAW_MIN != 0 && n_cut >= RTX_CUT_DRAW_MIN);
                     for (uint32_t c0 = c_first; c0 < total; ) {
                         const bool valid = c0 + lane < total;
                         const uint32_t quo = (uint32_t)(((float)(c0 + lane) + 0.5f) * inv_div);
