@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -26,54 +27,144 @@ namespace {
 
 thread_local int g_last_hip_error = 0;
 
-#define RTX_HIP(call)                                 \
-    do {                                              \
-        hipError_t e_ = (call);                       \
-        if (e_ != hipSuccess) {                       \
-            g_last_hip_error = static_cast<int>(e_);  \
-            return e_ == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP; \
-        }                                             \
+// the one mapping from a HIP result to the ABI's code; a failure is kept for rtx_last_hip_error
+int hip_rc(hipError_t e)
+{
+    if (e == hipSuccess) return RTX_OK;
+    g_last_hip_error = static_cast<int>(e);
+    return e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP;
+}
+
+#define RTX_HIP(call)                          \
+    do {                                       \
+        const int rc_ = hip_rc(call);          \
+        if (rc_ != RTX_OK) return rc_;         \
     } while (0)
 
-struct DeviceState {
-    std::mutex mu;
-    bool uploaded = false;
-    void *nodes = nullptr, *primary_nodes = nullptr, *ref_nodes = nullptr, *tris = nullptr, *shade = nullptr, *samples = nullptr, *lights = nullptr, *thr = nullptr, *planes = nullptr, *light_boxes = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint8_t *d_out = nullptr;
-    size_t d_out_cap = 0;
-    unsigned long long *d_counters = nullptr;
-    uint32_t *d_redo = nullptr;   // queue of tiles for reference_tiles_kernel
-    size_t d_redo_cap = 0;
-    rtx::StreamWorkspace ws{};    // streamed pipeline: intermediate products in HBM
-    rtx::StreamWorkspaceBytes ws_cap{};
-    uint8_t *h_stage = nullptr;   // pinned
-    size_t h_stage_cap = 0;
-    size_t last_tiles = 0;        // tiles of the most recent launch (rtx_debug_tile_descs)
-    // ray queries (rtx_query.hip): device copies of the host entry points' arrays, the regrouping pass's (key, ray number)
-    // buffers and the sort's temporary storage; all grow-only, none shared with the render workspace
-    float *q_first = nullptr, *q_second = nullptr;
-    uint8_t *q_out = nullptr;
-    size_t q_first_cap = 0, q_second_cap = 0, q_out_cap = 0;
-    rtxq::SortBuffers q_sort{};
-    hipEvent_t q_sorted = nullptr;   // recorded behind a device-resident call that used q_sort on the CALLER's stream: a host
-                                     // call, which uses the same buffers on the library's stream, waits for it first
-    size_t q_keys_cap = 0, q_keys_sorted_cap = 0, q_index_cap = 0, q_index_sorted_cap = 0, q_temp_cap = 0;
-    hipEvent_t ring[RTX_TIMING_RING][3] = {};   // launch start / end of the scheduling pass / launch end (rtx_launch_timings)
-    unsigned long long launches = 0;
-};
-
-// restores the caller's current device on scope exit
+// makes a device current; restores the caller's current device on scope exit
 class DeviceGuard {
 public:
-    explicit DeviceGuard(int dev) { ok_ = hipGetDevice(&prev_) == hipSuccess; err_ = hipSetDevice(dev); }
+    DeviceGuard() = default;
+    explicit DeviceGuard(int dev) { (void)set(dev); }
     ~DeviceGuard() { if (ok_) (void)hipSetDevice(prev_); }
+    hipError_t set(int dev) { ok_ = hipGetDevice(&prev_) == hipSuccess; return err_ = hipSetDevice(dev); }
     hipError_t status() const { return err_; }
 private:
     int prev_ = 0;
     bool ok_ = false;
     hipError_t err_ = hipSuccess;
+};
+
+// ---- owners ------------------------------------------------------------------------------------------------------------
+// Each holds one HIP handle and gives it back when it is destroyed, which needs the handle's device current.  They are
+// meant as members of DeviceState: its destructor is private, so that nothing but ReleaseOnDevice, which makes the
+// state's device current first, can run theirs.
+template <class T, hipError_t (*Free)(T)>
+class Owned {
+public:
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { (void)reset(); }
+    hipError_t reset()
+    {
+        const hipError_t e = h_ ? Free(h_) : hipSuccess;
+        h_ = nullptr;
+        return e;
+    }
+    T *put() { return &h_; }             // for the HIP call that creates the handle, while the owner is empty
+    operator T() const { return h_; }
+private:
+    T h_ = nullptr;
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+hipError_t alloc_device(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+hipError_t alloc_pinned(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+
+// Grow-only memory.  reserve(): nothing to do when it is large enough; otherwise free, then allocate — the contents are
+// not preserved, and after a failure the buffer is empty.
+template <hipError_t (*Alloc)(void **, size_t), hipError_t (*Free)(void *)>
+class GrowOnly {
+public:
+    int reserve(size_t bytes)
+    {
+        if (cap_ >= bytes) return RTX_OK;
+        cap_ = 0;
+        RTX_HIP(mem_.reset());
+        RTX_HIP(Alloc(mem_.put(), bytes));
+        cap_ = bytes;
+        return RTX_OK;
+    }
+    size_t capacity() const { return cap_; }
+    template <class T>
+    T *as() const { return static_cast<T *>(static_cast<void *>(mem_)); }
+private:
+    Owned<void *, Free> mem_;
+    size_t cap_ = 0;
+};
+using DeviceBuffer = GrowOnly<alloc_device, hipFree>;
+using PinnedBuffer = GrowOnly<alloc_pinned, hipHostFree>;
+
+struct Sized { DeviceBuffer &buffer; size_t bytes; };
+int reserve_all(std::initializer_list<Sized> list)
+{
+    for (const Sized &s : list) {
+        const int rc = s.buffer.reserve(s.bytes);
+        if (rc != RTX_OK) return rc;
+    }
+    return RTX_OK;
+}
+
+// What a scene keeps on one device.  The argument blocks the launchers read (rtx::DeviceScene, rtx::StreamWorkspace,
+// rtxq::SortBuffers) are built from these owners where a launch needs them.
+class DeviceState {
+public:
+    explicit DeviceState(int dev) : device(dev) {}
+    const int device;
+    bool uploaded = false;
+    size_t last_tiles = 0;               // tiles of the most recent launch (rtx_debug_tile_descs)
+    unsigned long long launches = 0;
+    // (destroyed from the last member to the first: the stream after the events and the memory)
+    Stream stream;
+    Event ev0, ev1;
+    Event ring[RTX_TIMING_RING][3];      // launch start / end of the scheduling pass / launch end (rtx_launch_timings)
+    Event q_sorted;                      // recorded behind a device-resident call that used q_sort on the CALLER's stream: a host
+                                         // call, which uses the same buffers on the library's stream, waits for it first
+    DeviceBuffer nodes, primary_nodes, ref_nodes, tris, shade, samples, lights, thr, planes, light_boxes;
+    DeviceBuffer d_out, d_counters;
+    DeviceBuffer d_redo;                 // queue of tiles for reference_tiles_kernel
+    PinnedBuffer h_stage;
+    struct { DeviceBuffer hits, pix_slot, tiles, chunks, results, acc, ctr, buckets, cut; } ws;   // streamed pipeline:
+                                                                                    // intermediate products in HBM
+    // ray queries and ray shading (rtx_query.hip, rtx_shade.hip): device copies of the host entry points' arrays, the
+    // regrouping pass's (key, ray number) buffers and the sort's temporary storage; none shared with the render workspace
+    DeviceBuffer q_first, q_second, q_out;
+    struct { DeviceBuffer keys, keys_sorted, index, index_sorted, temp; } q_sort;
+private:
+    ~DeviceState() = default;
+    friend struct ReleaseOnDevice;
+};
+
+// The one place a DeviceState and everything it owns is released — after an upload that failed half way and in
+// rtx_scene_destroy — with its own device current and the library's stream drained, whatever the caller had current.
+// A device that cannot be made current is skipped: the state is abandoned (leaked) on purpose, since its owners would
+// otherwise hand their handles to whatever device happens to be current.
+struct ReleaseOnDevice {
+    void operator()(DeviceState *st) const
+    {
+        DeviceGuard g(st->device);
+        if (g.status() != hipSuccess) return;
+        if (st->stream) (void)hipStreamSynchronize(st->stream);
+        delete st;
+    }
+};
+
+// a scene's place for one device: the lock outlives the state, which a failed upload takes away (the next call starts anew)
+struct DeviceSlot {
+    std::mutex mu;
+    std::unique_ptr<DeviceState, ReleaseOnDevice> st;
 };
 
 double wall_ms()
@@ -87,7 +178,7 @@ double wall_ms()
 struct RtxScene {
     rtx::PreparedScene prep;
     std::mutex mu;
-    std::map<int, std::unique_ptr<DeviceState>> dev;
+    std::map<int, DeviceSlot> dev;
 };
 
 namespace {
@@ -99,25 +190,30 @@ int device_count_quiet()
     return n < 0 ? 0 : n;
 }
 
-int get_state(RtxScene *scene, int device, DeviceState **out)
+int get_slot(RtxScene *scene, int device, DeviceSlot **out)
 {
     if (device < 0 || device >= device_count_quiet()) return RTX_ERR_NO_DEVICE;
     std::lock_guard<std::mutex> lk(scene->mu);
-    auto &slot = scene->dev[device];
-    if (!slot) slot.reset(new (std::nothrow) DeviceState);
-    if (!slot) return RTX_ERR_OOM;
-    *out = slot.get();
+    *out = &scene->dev[device];
     return RTX_OK;
+}
+
+// caller holds slot.mu
+int ensure_state(DeviceSlot &slot, int device)
+{
+    if (!slot.st) slot.st.reset(new (std::nothrow) DeviceState(device));
+    return slot.st ? RTX_OK : RTX_ERR_OOM;
 }
 
 // pad_bytes of zeros follow the data (the node stream carries one sentinel record)
 template <class T>
-int upload_vec(void **dst, const std::vector<T> &v, size_t pad_bytes = 0)
+int upload_vec(DeviceBuffer &dst, const std::vector<T> &v, size_t pad_bytes = 0)
 {
     const size_t bytes = v.size() * sizeof(T);
-    RTX_HIP(hipMalloc(dst, bytes + pad_bytes ? bytes + pad_bytes : 16));
-    if (bytes) RTX_HIP(hipMemcpy(*dst, v.data(), bytes, hipMemcpyHostToDevice));
-    if (pad_bytes) RTX_HIP(hipMemset(static_cast<char *>(*dst) + bytes, 0, pad_bytes));
+    const int rc = dst.reserve(bytes + pad_bytes ? bytes + pad_bytes : 16);
+    if (rc != RTX_OK) return rc;
+    if (bytes) RTX_HIP(hipMemcpy(dst.as<void>(), v.data(), bytes, hipMemcpyHostToDevice));
+    if (pad_bytes) RTX_HIP(hipMemset(dst.as<char>() + bytes, 0, pad_bytes));
     return RTX_OK;
 }
 
@@ -142,73 +238,81 @@ int upload_all(RtxScene *scene, DeviceState &st)
     const rtx::PreparedScene &p = scene->prep;
     int rc;
     const float inflate = p.cull_delta;   // the culling planes move outwards: rtx_traverse.hpp, box_mask
-    if ((rc = upload_vec(&st.nodes, rtx::nodes_in_device_order(p.nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
+    if ((rc = upload_vec(st.nodes, rtx::nodes_in_device_order(p.nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
     if (!p.primary_nodes.empty() &&
-        (rc = upload_vec(&st.primary_nodes, rtx::nodes_in_device_order(p.primary_nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
+        (rc = upload_vec(st.primary_nodes, rtx::nodes_in_device_order(p.primary_nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
     if (!p.ref_nodes.empty() &&
-        (rc = upload_vec(&st.ref_nodes, rtx::nodes_in_device_order(p.ref_nodes), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
+        (rc = upload_vec(st.ref_nodes, rtx::nodes_in_device_order(p.ref_nodes), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
     // one spare record of zeros behind the primitive records (no walk requests the record after the one it tests any more)
-    if ((rc = upload_vec(&st.tris, p.tris, sizeof(rtx::TriRec))) != RTX_OK) return rc;
-    if ((rc = upload_vec(&st.shade, p.shade)) != RTX_OK) return rc;
-    if ((rc = upload_vec(&st.samples, p.samples)) != RTX_OK) return rc;
-    if ((rc = upload_vec(&st.lights, p.light_points)) != RTX_OK) return rc;
-    if (!p.global_planes.empty() && (rc = upload_vec(&st.planes, p.global_planes)) != RTX_OK) return rc;
-    if ((rc = upload_vec(&st.light_boxes, p.light_boxes)) != RTX_OK) return rc;
-    RTX_HIP(hipMalloc(&st.thr, sizeof(p.gamma_thr)));
-    RTX_HIP(hipMemcpy(st.thr, p.gamma_thr, sizeof(p.gamma_thr), hipMemcpyHostToDevice));
-    RTX_HIP(hipMalloc(reinterpret_cast<void **>(&st.d_counters), rtx::kNumCounters * sizeof(unsigned long long)));
-    RTX_HIP(hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking));
-    RTX_HIP(hipEventCreate(&st.ev0));
-    RTX_HIP(hipEventCreate(&st.ev1));
+    if ((rc = upload_vec(st.tris, p.tris, sizeof(rtx::TriRec))) != RTX_OK) return rc;
+    if ((rc = upload_vec(st.shade, p.shade)) != RTX_OK) return rc;
+    if ((rc = upload_vec(st.samples, p.samples)) != RTX_OK) return rc;
+    if ((rc = upload_vec(st.lights, p.light_points)) != RTX_OK) return rc;
+    if (!p.global_planes.empty() && (rc = upload_vec(st.planes, p.global_planes)) != RTX_OK) return rc;
+    if ((rc = upload_vec(st.light_boxes, p.light_boxes)) != RTX_OK) return rc;
+    if ((rc = st.thr.reserve(sizeof(p.gamma_thr))) != RTX_OK) return rc;
+    RTX_HIP(hipMemcpy(st.thr.as<void>(), p.gamma_thr, sizeof(p.gamma_thr), hipMemcpyHostToDevice));
+    if ((rc = st.d_counters.reserve(rtx::kNumCounters * sizeof(unsigned long long))) != RTX_OK) return rc;
+    RTX_HIP(hipStreamCreateWithFlags(st.stream.put(), hipStreamNonBlocking));
+    RTX_HIP(hipEventCreate(st.ev0.put()));
+    RTX_HIP(hipEventCreate(st.ev1.put()));
     for (auto &slot : st.ring)
-        for (hipEvent_t &e : slot) RTX_HIP(hipEventCreate(&e));
+        for (Event &e : slot) RTX_HIP(hipEventCreate(e.put()));
     st.uploaded = true;
     return RTX_OK;
 }
 
-// what upload_all allocated so far goes back when it fails half way (the caller may retry: nothing may leak)
-void release_uploads(DeviceState &st)
+// Caller holds slot.mu, with a state in the slot.  An upload that fails half way takes the state out of the slot, and
+// with it everything allocated so far: nothing leaks, and the next call starts with uploaded == false.
+int ensure_uploaded(RtxScene *scene, DeviceSlot &slot)
 {
-    void **bufs[] = {&st.nodes, &st.primary_nodes, &st.ref_nodes, &st.tris, &st.shade, &st.samples, &st.lights, &st.thr, &st.planes, &st.light_boxes,
-                     reinterpret_cast<void **>(&st.d_counters)};
-    for (void **b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
-    if (st.ev0) { (void)hipEventDestroy(st.ev0); st.ev0 = nullptr; }
-    if (st.ev1) { (void)hipEventDestroy(st.ev1); st.ev1 = nullptr; }
-    for (auto &slot : st.ring)
-        for (hipEvent_t &e : slot)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (st.stream) { (void)hipStreamDestroy(st.stream); st.stream = nullptr; }
-}
-
-// caller holds st.mu and has the device current
-int ensure_uploaded(RtxScene *scene, DeviceState &st)
-{
-    if (st.uploaded) return RTX_OK;
-    const int rc = upload_all(scene, st);
-    if (rc != RTX_OK) release_uploads(st);
+    if (slot.st->uploaded) return RTX_OK;
+    const int rc = upload_all(scene, *slot.st);
+    if (rc != RTX_OK) slot.st.reset();
     return rc;
 }
+
+// The one way into an entry point that works on a device: the scene's slot for it, the slot's lock and a state in the
+// slot; from kCurrent on the device made current (the caller's comes back on scope exit), with kUploaded the scene's
+// uploads.  After rc == RTX_OK state() is good until a call that is handed the slot (launch_on) fails: a failed upload
+// takes the state out of the slot.
+class Entry {
+public:
+    enum Need { kLocked, kCurrent, kUploaded };
+    Entry(RtxScene *scene, int device, Need need)
+    {
+        if ((rc = get_slot(scene, device, &slot)) != RTX_OK) return;
+        lock_ = std::unique_lock<std::mutex>(slot->mu);
+        if ((rc = ensure_state(*slot, device)) != RTX_OK) return;
+        if (need >= kCurrent && (rc = make_current()) != RTX_OK) return;
+        if (need >= kUploaded) rc = ensure_uploaded(scene, *slot);
+    }
+    int make_current() { return hip_rc(guard_.set(slot->st->device)); }
+    DeviceState &state() const { return *slot->st; }
+    int rc = RTX_ERR_INTERNAL;
+    DeviceSlot *slot = nullptr;
+private:
+    std::unique_lock<std::mutex> lock_;
+    DeviceGuard guard_;
+};
 
 rtx::DeviceScene device_scene(const RtxScene *scene, const DeviceState &st)
 {
     const rtx::PreparedScene &p = scene->prep;
     rtx::DeviceScene S;
-    S.nodes = static_cast<const rtx::NodeRec *>(st.nodes);
-    S.primary_nodes = static_cast<const rtx::NodeRec *>(st.primary_nodes ? st.primary_nodes : st.nodes);
+    S.nodes = st.nodes.as<const rtx::NodeRec>();
+    S.primary_nodes = st.primary_nodes.capacity() ? st.primary_nodes.as<const rtx::NodeRec>() : S.nodes;
     S.wide = nullptr;
     S.n_wide = 0u;
-    S.ref_nodes = static_cast<const rtx::NodeRec *>(st.ref_nodes);
+    S.ref_nodes = st.ref_nodes.as<const rtx::NodeRec>();
     S.n_ref_nodes = static_cast<uint32_t>(p.ref_nodes.size());
-    S.tris = static_cast<const rtx::TriRec *>(st.tris);
-    S.shade = static_cast<const rtx::ShadeRec *>(st.shade);
-    S.samples = static_cast<const float2 *>(st.samples);
-    S.light_points = static_cast<const float *>(st.lights);
-    S.planes = static_cast<const rtx::TriRec *>(st.planes);
-    S.gamma_thr = static_cast<const float *>(st.thr);
-    S.light_boxes = static_cast<const float *>(st.light_boxes);
+    S.tris = st.tris.as<const rtx::TriRec>();
+    S.shade = st.shade.as<const rtx::ShadeRec>();
+    S.samples = st.samples.as<const float2>();
+    S.light_points = st.lights.as<const float>();
+    S.planes = st.planes.as<const rtx::TriRec>();
+    S.gamma_thr = st.thr.as<const float>();
+    S.light_boxes = st.light_boxes.as<const float>();
     S.shaft_delta = p.shaft_delta;
     S.n_nodes = static_cast<uint32_t>(p.nodes.size());
     S.n_samples = p.n_samples;
@@ -238,68 +342,20 @@ rtx::DeviceScene device_scene(const RtxScene *scene, const DeviceState &st)
     return S;
 }
 
-// device output buffer of at least `bytes`, pinned staging buffer of at least `stage_bytes` (0: none needed)
-int ensure_out(DeviceState &st, size_t bytes, size_t stage_bytes)
+// sizes the workspace of the streamed pipeline for a launch and gives its argument block; *used = false: the variant has none
+int reserve_stream_ws(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpec &ts, rtx::StreamWorkspace *ws, bool *used)
 {
-    if (st.d_out_cap < bytes) {
-        if (st.d_out) RTX_HIP(hipFree(st.d_out));
-        st.d_out = nullptr;
-        st.d_out_cap = 0;
-        RTX_HIP(hipMalloc(reinterpret_cast<void **>(&st.d_out), bytes));
-        st.d_out_cap = bytes;
-    }
-    if (st.h_stage_cap < stage_bytes) {
-        if (st.h_stage) RTX_HIP(hipHostFree(st.h_stage));
-        st.h_stage = nullptr;
-        st.h_stage_cap = 0;
-        RTX_HIP(hipHostMalloc(reinterpret_cast<void **>(&st.h_stage), stage_bytes, hipHostMallocDefault));
-        st.h_stage_cap = stage_bytes;
-    }
-    return RTX_OK;
-}
-
-// the redo queue of a launch (rtx_device.h); grows only
-int ensure_redo(DeviceState &st, size_t bytes)
-{
-    if (st.d_redo_cap >= bytes) return RTX_OK;
-    if (st.d_redo) RTX_HIP(hipFree(st.d_redo));
-    st.d_redo = nullptr;
-    st.d_redo_cap = 0;
-    RTX_HIP(hipMalloc(reinterpret_cast<void **>(&st.d_redo), bytes));
-    st.d_redo_cap = bytes;
-    return RTX_OK;
-}
-
-template <class T>
-int grow_buffer(T **ptr, size_t *cap, size_t bytes)
-{
-    if (*cap >= bytes) return RTX_OK;
-    if (*ptr) RTX_HIP(hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    RTX_HIP(hipMalloc(reinterpret_cast<void **>(ptr), bytes));
-    *cap = bytes;
-    return RTX_OK;
-}
-
-// workspace of the streamed pipeline for a launch; NULL result when the variant does not use it
-int ensure_stream_ws(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpec &ts, const rtx::StreamWorkspace **out)
-{
-    *out = nullptr;
-    if (!(kernel_variant() & (rtx::kVariantStream | rtx::kVariantProbe))) return RTX_OK;
+    *used = (kernel_variant() & (rtx::kVariantStream | rtx::kVariantProbe)) != 0u;
+    if (!*used) return RTX_OK;
     const rtx::StreamWorkspaceBytes need = rtx::stream_workspace_bytes(S, ts, kernel_variant());
-    int rc;
-    if ((rc = grow_buffer(&st.ws.hits, &st.ws_cap.hits, need.hits)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st.ws.pix_slot, &st.ws_cap.pix_slot, need.pix_slot)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st.ws.tiles, &st.ws_cap.tiles, need.tiles)) != RTX_OK) return rc;
-    if (need.chunks && (rc = grow_buffer(&st.ws.chunks, &st.ws_cap.chunks, need.chunks)) != RTX_OK) return rc;
-    if (need.results && (rc = grow_buffer(&st.ws.results, &st.ws_cap.results, need.results)) != RTX_OK) return rc;
-    if (need.acc && (rc = grow_buffer(&st.ws.acc, &st.ws_cap.acc, need.acc)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st.ws.ctr, &st.ws_cap.ctr, need.ctr)) != RTX_OK) return rc;
-    if (need.buckets && (rc = grow_buffer(&st.ws.buckets, &st.ws_cap.buckets, need.buckets)) != RTX_OK) return rc;
-    if (need.cut && (rc = grow_buffer(&st.ws.cut, &st.ws_cap.cut, need.cut)) != RTX_OK) return rc;
+    const int rc = reserve_all({{st.ws.hits, need.hits}, {st.ws.pix_slot, need.pix_slot}, {st.ws.tiles, need.tiles},
+                                {st.ws.chunks, need.chunks}, {st.ws.results, need.results}, {st.ws.acc, need.acc},
+                                {st.ws.ctr, need.ctr}, {st.ws.buckets, need.buckets}, {st.ws.cut, need.cut}});
+    if (rc != RTX_OK) return rc;
     st.last_tiles = need.tiles / sizeof(rtx::TileDesc);
-    *out = &st.ws;
+    *ws = rtx::StreamWorkspace{st.ws.hits.as<rtx::HitRec>(), st.ws.pix_slot.as<uint32_t>(), st.ws.tiles.as<rtx::TileDesc>(),
+                               st.ws.chunks.as<uint2>(), st.ws.results.as<float>(), st.ws.acc.as<float>(),
+                               st.ws.ctr.as<uint32_t>(), st.ws.buckets.as<uint32_t>(), st.ws.cut.as<rtx::CutEntry>()};
     return RTX_OK;
 }
 
@@ -314,13 +370,15 @@ uint32_t tiles_rows(uint32_t height, uint32_t first_tile, uint32_t tile_stride, 
     return static_cast<uint32_t>(rows);
 }
 
-void fill_stats(RtxStats *s, const RtxScene *scene, uint64_t pixels, const unsigned long long *c,
+// The one mapping from a counter block to RtxStats.  Rendering and shading: primary_rays = pixels * nb_ray and
+// nb_light_sample shadow rays per hit; the ray queries: their n rays and none.
+void fill_stats(RtxStats *s, uint64_t primary_rays, uint32_t shadow_rays_per_hit, const unsigned long long *c,
                 double kernel_ms, double total_ms)
 {
     std::memset(s, 0, sizeof *s);
-    s->primary_rays = pixels * scene->prep.nb_ray;
+    s->primary_rays = primary_rays;
     s->primary_hits = c[0];
-    s->shadow_rays = c[0] * scene->prep.nb_light_sample;
+    s->shadow_rays = c[0] * shadow_rays_per_hit;
     s->rays = s->primary_rays + s->shadow_rays;
     s->box_tests = c[1];
     s->tri_tests = c[2];
@@ -331,28 +389,49 @@ void fill_stats(RtxStats *s, const RtxScene *scene, uint64_t pixels, const unsig
     s->total_ms = total_ms;
 }
 
-// launch one device's share; caller holds st.mu and has the device current
-int launch_on(RtxScene *scene, DeviceState &st, const rtx::TileSpec &ts, bool count)
+// The one render launch, on `stream`: the redo queue and the streamed pipeline's workspace sized, `before()` (what the
+// caller puts on the stream once the buffers stand), the kernels, the launch's slot of the timing ring.  The per-tile
+// profile (d_wave_prof, ablation build) is the fused kernel's: no workspace, no slot.  Caller holds the slot's lock and
+// has the device current and the scene uploaded.  The redo queue is library-owned per device: launches on one device
+// must be ordered on one stream.
+template <class Before>
+int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpec &ts, uint8_t *d_out,
+                  unsigned long long *d_counters, unsigned long long *d_wave_prof, hipStream_t stream, Before before)
 {
-    int rc = ensure_uploaded(scene, st);
+    int rc;
+    if ((rc = st.d_redo.reserve(rtx::trace_redo_bytes(S, ts))) != RTX_OK) return rc;
+    rtx::StreamWorkspace ws{};
+    bool use_ws = false;
+    if (!d_wave_prof && (rc = reserve_stream_ws(st, S, ts, &ws, &use_ws)) != RTX_OK) return rc;
+    if ((rc = before()) != RTX_OK) return rc;
+    const Event *slot = st.ring[st.launches % RTX_TIMING_RING];
+    hipEvent_t phases[3] = {slot[0], slot[1], slot[2]};
+    RTX_HIP(rtx::launch_trace_shade(S, ts, d_out, st.d_redo.as<uint32_t>(), use_ws ? &ws : nullptr, d_counters, d_wave_prof,
+                                    kernel_variant(), stream, d_wave_prof ? nullptr : phases));
+    if (!d_wave_prof && ts.local_rows) ++st.launches;
+    return RTX_OK;
+}
+
+// launch one device's share into its d_out; caller holds slot.mu, with a state in the slot, and has the device current
+int launch_on(RtxScene *scene, DeviceSlot &slot, const rtx::TileSpec &ts, bool count)
+{
+    int rc = ensure_uploaded(scene, slot);
     if (rc != RTX_OK) return rc;
+    DeviceState &st = *slot.st;
     const size_t bytes = static_cast<size_t>(ts.local_rows) * scene->prep.width * 3u;
-    if ((rc = ensure_out(st, bytes ? bytes : 16, 0)) != RTX_OK) return rc;
-    const rtx::DeviceScene S = device_scene(scene, st);
-    if ((rc = ensure_redo(st, rtx::trace_redo_bytes(S, ts))) != RTX_OK) return rc;
-    const rtx::StreamWorkspace *ws = nullptr;
-    if ((rc = ensure_stream_ws(st, S, ts, &ws)) != RTX_OK) return rc;
-    if (count)
-        RTX_HIP(hipMemsetAsync(st.d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
-    RTX_HIP(hipEventRecord(st.ev0, st.stream));
-    RTX_HIP(rtx::launch_trace_shade(S, ts, st.d_out, st.d_redo, ws, count ? st.d_counters : nullptr, nullptr,
-                                    kernel_variant(), st.stream, st.ring[st.launches % RTX_TIMING_RING]));
-    if (ts.local_rows) ++st.launches;
+    if ((rc = st.d_out.reserve(bytes ? bytes : 16)) != RTX_OK) return rc;
+    unsigned long long *counters = count ? st.d_counters.as<unsigned long long>() : nullptr;
+    rc = render_launch(st, device_scene(scene, st), ts, st.d_out.as<uint8_t>(), counters, nullptr, st.stream, [&]() -> int {
+        if (count) RTX_HIP(hipMemsetAsync(counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
+        RTX_HIP(hipEventRecord(st.ev0, st.stream));
+        return RTX_OK;
+    });
+    if (rc != RTX_OK) return rc;
     RTX_HIP(hipEventRecord(st.ev1, st.stream));
     return RTX_OK;
 }
 
-// ---- ray queries -------------------------------------------------------------------------------------------------------
+// ---- ray batches: the queries (rtx_query.hip) and shading (rtx_shade.hip) ----------------------------------------------
 
 // The box the regrouping keys quantise origins in: the tree proper's root (beside the global triangles — the ground is
 // as large as the scene and would leave the mesh a handful of cells), else the stream's root.
@@ -370,124 +449,24 @@ rtxq::KeyBox query_key_box(const rtx::PreparedScene &p)
     return box;
 }
 
-// the regrouping pass's buffers for n rays; caller holds st.mu and has the device current
-int ensure_query_sort(DeviceState &st, uint32_t n)
+// sizes the regrouping pass's buffers for n entries and gives their argument block; caller holds the slot's lock and has
+// the device current
+int reserve_query_sort(DeviceState &st, uint32_t n, rtxq::SortBuffers *sort)
 {
     const size_t words = static_cast<size_t>(n) * sizeof(uint32_t);
     size_t temp = 0;
     RTX_HIP(rtxq::sort_temp_bytes(n, &temp));
-    int rc;
-    if ((rc = grow_buffer(&st.q_sort.keys, &st.q_keys_cap, words)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st.q_sort.keys_sorted, &st.q_keys_sorted_cap, words)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st.q_sort.index, &st.q_index_cap, words)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st.q_sort.index_sorted, &st.q_index_sorted_cap, words)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(reinterpret_cast<char **>(&st.q_sort.temp), &st.q_temp_cap, temp ? temp : 16)) != RTX_OK) return rc;
-    st.q_sort.temp_bytes = st.q_temp_cap;
+    const int rc = reserve_all({{st.q_sort.keys, words}, {st.q_sort.keys_sorted, words}, {st.q_sort.index, words},
+                                {st.q_sort.index_sorted, words}, {st.q_sort.temp, temp ? temp : 16}});
+    if (rc != RTX_OK) return rc;
+    *sort = rtxq::SortBuffers{st.q_sort.keys.as<uint32_t>(), st.q_sort.keys_sorted.as<uint32_t>(), st.q_sort.index.as<uint32_t>(),
+                              st.q_sort.index_sorted.as<uint32_t>(), st.q_sort.temp.as<void>(), st.q_sort.temp.capacity()};
     return RTX_OK;
 }
 
 static_assert(sizeof(RtxRayHit) == 32, "closest_kernel writes a hit as two 16-byte words");
-constexpr uint32_t kQueryFlags = RTX_RAYS_KEEP_ORDER | RTX_RAYS_FORCE_REGROUP;
-
-bool query_regroups(uint32_t n_rays, uint32_t flags)
-{
-    if (flags & RTX_RAYS_KEEP_ORDER) return false;
-    return n_rays >= rtxq::kRegroupMinRays || (flags & RTX_RAYS_FORCE_REGROUP) != 0u;
-}
-
-// key + sort + trace of one batch on `stream`; caller holds st.mu, has the device current and the scene uploaded
-int query_launch(RtxScene *scene, DeviceState &st, bool occlusion, uint32_t n_rays, const float *d_first,
-                 const float *d_second, uint32_t flags, void *d_out, unsigned long long *d_counters, hipStream_t stream)
-{
-    const bool regroup = query_regroups(n_rays, flags);
-    int rc;
-    if (regroup && (rc = ensure_query_sort(st, n_rays)) != RTX_OK) return rc;
-    const rtx::DeviceScene S = device_scene(scene, st);
-    RTX_HIP(rtxq::launch_query(S, occlusion, n_rays, d_first, d_second, query_key_box(scene->prep),
-                               scene->prep.cull_delta * 0x1p19f, regroup ? &st.q_sort : nullptr, d_out, d_counters, stream));
-    return RTX_OK;
-}
-
-// the host entry points: copy in, launch, copy out
-int query_host(RtxScene *scene, int device, bool occlusion, uint32_t n_rays, const float *first, const float *second,
-               uint32_t flags, void *out, RtxStats *stats)
-{
-    if (!scene || !first || !second || !out || (flags & ~kQueryFlags) || n_rays > rtxq::kMaxRays) return RTX_ERR_BAD_ARG;
-    const double t0 = wall_ms();
-    if (n_rays == 0u) {
-        if (stats) { std::memset(stats, 0, sizeof *stats); stats->total_ms = wall_ms() - t0; }
-        return RTX_OK;
-    }
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
-    if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
-    const size_t in_bytes = static_cast<size_t>(n_rays) * 3u * sizeof(float);
-    const size_t out_bytes = static_cast<size_t>(n_rays) * (occlusion ? 1u : sizeof(RtxRayHit));
-    if ((rc = grow_buffer(&st->q_first, &st->q_first_cap, in_bytes)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st->q_second, &st->q_second_cap, in_bytes)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st->q_out, &st->q_out_cap, out_bytes)) != RTX_OK) return rc;
-    if (st->q_sorted) RTX_HIP(hipStreamWaitEvent(st->stream, st->q_sorted, 0));   // a device-resident call may still be sorting
-    RTX_HIP(hipMemcpyAsync(st->q_first, first, in_bytes, hipMemcpyHostToDevice, st->stream));
-    RTX_HIP(hipMemcpyAsync(st->q_second, second, in_bytes, hipMemcpyHostToDevice, st->stream));
-    if (stats) RTX_HIP(hipMemsetAsync(st->d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st->stream));
-    RTX_HIP(hipEventRecord(st->ev0, st->stream));
-    if ((rc = query_launch(scene, *st, occlusion, n_rays, st->q_first, st->q_second, flags, st->q_out,
-                           stats ? st->d_counters : nullptr, st->stream)) != RTX_OK) {
-        (void)hipStreamSynchronize(st->stream);      // the copies above read the caller's arrays
-        return rc;
-    }
-    RTX_HIP(hipEventRecord(st->ev1, st->stream));
-    RTX_HIP(hipMemcpyAsync(out, st->q_out, out_bytes, hipMemcpyDeviceToHost, st->stream));
-    unsigned long long c[rtx::kNumCounters] = {0};
-    if (stats) RTX_HIP(hipMemcpyAsync(c, st->d_counters, sizeof c, hipMemcpyDeviceToHost, st->stream));
-    RTX_HIP(hipStreamSynchronize(st->stream));
-    if (stats) {
-        float ms = 0.0f;
-        RTX_HIP(hipEventElapsedTime(&ms, st->ev0, st->ev1));
-        std::memset(stats, 0, sizeof *stats);
-        stats->primary_rays = stats->rays = n_rays;
-        stats->primary_hits = c[0];
-        stats->box_tests = c[1];
-        stats->tri_tests = c[2];
-        stats->wave_node_visits = c[3];
-        stats->wave_tri_visits = c[4];
-        stats->redo_tiles = c[5];
-        stats->kernel_ms = ms;
-        stats->total_ms = wall_ms() - t0;
-    }
-    return RTX_OK;
-}
-
-int query_device(RtxScene *scene, int device, bool occlusion, uint32_t n_rays, const void *d_first, const void *d_second,
-                 uint32_t flags, void *d_out, void *stream)
-{
-    if (!scene || !d_first || !d_second || !d_out || (flags & ~kQueryFlags) || n_rays > rtxq::kMaxRays) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_first) | reinterpret_cast<uintptr_t>(d_second)) & 3u) return RTX_ERR_BAD_ARG;
-    if (!occlusion && (reinterpret_cast<uintptr_t>(d_out) & 15u)) return RTX_ERR_BAD_ARG;
-    if (n_rays == 0u) return RTX_OK;
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
-    if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
-    if ((rc = query_launch(scene, *st, occlusion, n_rays, static_cast<const float *>(d_first), static_cast<const float *>(d_second),
-                           flags, d_out, nullptr, static_cast<hipStream_t>(stream))) != RTX_OK) return rc;
-    if (query_regroups(n_rays, flags)) {     // the library's sort buffers are busy until this point of the caller's stream
-        if (!st->q_sorted) RTX_HIP(hipEventCreateWithFlags(&st->q_sorted, hipEventDisableTiming));
-        RTX_HIP(hipEventRecord(st->q_sorted, static_cast<hipStream_t>(stream)));
-    }
-    return RTX_OK;
-}
-
-// ---- shading caller-supplied rays (rtx_shade.hip) ----------------------------------------------------------------------
-
 static_assert(sizeof(RtxPixelShade) == 16, "shade_kernel writes a pixel as one 16-byte word");
+constexpr uint32_t kQueryFlags = RTX_RAYS_KEEP_ORDER | RTX_RAYS_FORCE_REGROUP;
 
 // n_pixels * nb_ray, or 0 when it is beyond what one batch may hold
 uint32_t shade_ray_count(const RtxScene *scene, uint32_t n_pixels)
@@ -496,93 +475,148 @@ uint32_t shade_ray_count(const RtxScene *scene, uint32_t n_pixels)
     return n <= rtxq::kMaxRays ? static_cast<uint32_t>(n) : 0u;
 }
 
-// key + sort + shade of one batch on `stream`; caller holds st.mu, has the device current and the scene uploaded.  The
-// regrouping policy, its buffers, the key box and the origin bound are the ray queries' (query_launch); the unit is a pixel.
-int shade_launch(RtxScene *scene, DeviceState &st, uint32_t n_pixels, const float *d_origins, const float *d_directions,
-                 uint32_t flags, void *d_shade, void *d_hits, unsigned long long *d_counters, hipStream_t stream)
+// what a family's launcher is handed: the scene, the regrouping pass's box, bound and buffers (NULL: the caller's order),
+// the two input arrays, the one or two outputs, the counters (or NULL), all on the device, and the stream
+struct BatchArgs {
+    rtx::DeviceScene S;
+    uint32_t n;
+    const float *first, *second;
+    rtxq::KeyBox box;
+    float origin_bound;
+    const rtxq::SortBuffers *sort;
+    void *out[2];
+    unsigned long long *counters;
+    hipStream_t stream;
+};
+
+template <bool Occlusion>
+hipError_t launch_queried(const BatchArgs &a)
 {
-    const bool regroup = query_regroups(n_pixels, flags);
+    return rtxq::launch_query(a.S, Occlusion, a.n, a.first, a.second, a.box, a.origin_bound, a.sort, a.out[0], a.counters, a.stream);
+}
+
+hipError_t launch_shaded(const BatchArgs &a)
+{
+    return rtxs::launch_shade(a.S, a.n, a.first, a.second, a.box, a.origin_bound, a.sort, a.out[0], a.out[1], a.counters, a.stream);
+}
+
+// What differs between rtx_trace_rays, rtx_occluded_rays and rtx_shade_rays (and their _device twins), checked by them.
+struct Batch {
+    uint32_t n;                    // entries the launcher works on and the regrouping pass sorts: rays, or pixels of nb_ray rays
+    uint32_t n_rays;               // rays in each of the two input arrays
+    uint32_t flags;
+    size_t out_bytes[2];           // the output segments, one behind the other in the library's device buffer (the first is
+                                   // a multiple of 16 where there is a second: the hit records behind stay aligned); 0: none
+    uint32_t shadow_rays_per_hit;  // RtxStats
+    hipError_t (*launch)(const BatchArgs &);
+};
+
+bool batch_regroups(const Batch &b)
+{
+    if (b.flags & RTX_RAYS_KEEP_ORDER) return false;
+    return b.n >= rtxq::kRegroupMinRays || (b.flags & RTX_RAYS_FORCE_REGROUP) != 0u;
+}
+
+// key + sort + kernel of one batch on `stream`; caller holds the slot's lock, has the device current and the scene uploaded
+int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *d_first, const float *d_second,
+                 void *const d_out[2], unsigned long long *d_counters, hipStream_t stream)
+{
+    rtxq::SortBuffers sort{};
+    const bool regroup = batch_regroups(b);
     int rc;
-    if (regroup && (rc = ensure_query_sort(st, n_pixels)) != RTX_OK) return rc;
-    const rtx::DeviceScene S = device_scene(scene, st);
-    RTX_HIP(rtxs::launch_shade(S, n_pixels, d_origins, d_directions, query_key_box(scene->prep),
-                               scene->prep.cull_delta * 0x1p19f, regroup ? &st.q_sort : nullptr, d_shade, d_hits, d_counters,
-                               stream));
+    if (regroup && (rc = reserve_query_sort(st, b.n, &sort)) != RTX_OK) return rc;
+    RTX_HIP(b.launch(BatchArgs{device_scene(scene, st), b.n, d_first, d_second, query_key_box(scene->prep),
+                               scene->prep.cull_delta * 0x1p19f, regroup ? &sort : nullptr, {d_out[0], d_out[1]}, d_counters,
+                               stream}));
     return RTX_OK;
 }
 
-// the host entry point: copy in, launch, copy out (staging and ordering as query_host)
-int shade_host(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions, uint32_t flags,
-               RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
+// the host entry points: copy in, launch, copy out
+int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, const float *second, void *out0, void *out1,
+               RtxStats *stats)
 {
-    if (!scene || !origins || !directions || !out_shade || (flags & ~kQueryFlags)) return RTX_ERR_BAD_ARG;
-    const uint32_t n_rays = shade_ray_count(scene, n_pixels);
-    if (n_pixels != 0u && n_rays == 0u) return RTX_ERR_BAD_ARG;
+    void *const out[2] = {out0, out1};
     const double t0 = wall_ms();
-    if (n_pixels == 0u) {
+    if (b.n == 0u) {
         if (stats) { std::memset(stats, 0, sizeof *stats); stats->total_ms = wall_ms() - t0; }
         return RTX_OK;
     }
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const size_t in_bytes = static_cast<size_t>(b.n_rays) * 3u * sizeof(float);
+    int rc = reserve_all({{st.q_first, in_bytes}, {st.q_second, in_bytes}, {st.q_out, b.out_bytes[0] + b.out_bytes[1]}});
     if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
-    const size_t in_bytes = static_cast<size_t>(n_rays) * 3u * sizeof(float);
-    const size_t shade_bytes = static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade);     // a multiple of 16: the hit
-    const size_t hit_bytes = out_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u;   // records behind stay aligned
-    if ((rc = grow_buffer(&st->q_first, &st->q_first_cap, in_bytes)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st->q_second, &st->q_second_cap, in_bytes)) != RTX_OK) return rc;
-    if ((rc = grow_buffer(&st->q_out, &st->q_out_cap, shade_bytes + hit_bytes)) != RTX_OK) return rc;
-    uint8_t *d_shade = st->q_out, *d_hits = out_hits ? st->q_out + shade_bytes : nullptr;
-    if (st->q_sorted) RTX_HIP(hipStreamWaitEvent(st->stream, st->q_sorted, 0));   // a device-resident call may still be sorting
-    RTX_HIP(hipMemcpyAsync(st->q_first, origins, in_bytes, hipMemcpyHostToDevice, st->stream));
-    RTX_HIP(hipMemcpyAsync(st->q_second, directions, in_bytes, hipMemcpyHostToDevice, st->stream));
-    if (stats) RTX_HIP(hipMemsetAsync(st->d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st->stream));
-    RTX_HIP(hipEventRecord(st->ev0, st->stream));
-    if ((rc = shade_launch(scene, *st, n_pixels, st->q_first, st->q_second, flags, d_shade, d_hits,
-                           stats ? st->d_counters : nullptr, st->stream)) != RTX_OK) {
-        (void)hipStreamSynchronize(st->stream);      // the copies above read the caller's arrays
+    void *const d_out[2] = {st.q_out.as<uint8_t>(), b.out_bytes[1] ? st.q_out.as<uint8_t>() + b.out_bytes[0] : nullptr};
+    unsigned long long *d_counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
+    if (st.q_sorted) RTX_HIP(hipStreamWaitEvent(st.stream, st.q_sorted, 0));   // a device-resident call may still be sorting
+    RTX_HIP(hipMemcpyAsync(st.q_first.as<void>(), first, in_bytes, hipMemcpyHostToDevice, st.stream));
+    RTX_HIP(hipMemcpyAsync(st.q_second.as<void>(), second, in_bytes, hipMemcpyHostToDevice, st.stream));
+    if (stats) RTX_HIP(hipMemsetAsync(d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
+    RTX_HIP(hipEventRecord(st.ev0, st.stream));
+    if ((rc = batch_launch(scene, st, b, st.q_first.as<float>(), st.q_second.as<float>(), d_out, d_counters, st.stream)) != RTX_OK) {
+        (void)hipStreamSynchronize(st.stream);      // the copies above read the caller's arrays
         return rc;
     }
-    RTX_HIP(hipEventRecord(st->ev1, st->stream));
-    RTX_HIP(hipMemcpyAsync(out_shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st->stream));
-    if (out_hits) RTX_HIP(hipMemcpyAsync(out_hits, d_hits, hit_bytes, hipMemcpyDeviceToHost, st->stream));
+    RTX_HIP(hipEventRecord(st.ev1, st.stream));
+    for (int k = 0; k < 2; ++k)
+        if (b.out_bytes[k]) RTX_HIP(hipMemcpyAsync(out[k], d_out[k], b.out_bytes[k], hipMemcpyDeviceToHost, st.stream));
     unsigned long long c[rtx::kNumCounters] = {0};
-    if (stats) RTX_HIP(hipMemcpyAsync(c, st->d_counters, sizeof c, hipMemcpyDeviceToHost, st->stream));
-    RTX_HIP(hipStreamSynchronize(st->stream));
+    if (stats) RTX_HIP(hipMemcpyAsync(c, d_counters, sizeof c, hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
     if (stats) {
         float ms = 0.0f;
-        RTX_HIP(hipEventElapsedTime(&ms, st->ev0, st->ev1));
-        fill_stats(stats, scene, n_pixels, c, ms, wall_ms() - t0);
+        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
+        fill_stats(stats, b.n_rays, b.shadow_rays_per_hit, c, ms, wall_ms() - t0);
     }
     return RTX_OK;
 }
 
-int shade_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
-                 uint32_t flags, void *d_shade, void *d_hits, void *stream)
+// the device-resident entry points: the caller's arrays, the caller's stream, nothing waited for
+int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_first, const void *d_second, void *d_out0,
+                 void *d_out1, void *stream)
 {
-    if (!scene || !d_origins || !d_directions || !d_shade || (flags & ~kQueryFlags)) return RTX_ERR_BAD_ARG;
-    if (n_pixels != 0u && shade_ray_count(scene, n_pixels) == 0u) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_directions)) & 3u) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
-    if (n_pixels == 0u) return RTX_OK;
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
+    void *const d_out[2] = {d_out0, d_out1};
+    if ((reinterpret_cast<uintptr_t>(d_first) | reinterpret_cast<uintptr_t>(d_second)) & 3u) return RTX_ERR_BAD_ARG;
+    if (b.n == 0u) return RTX_OK;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const int rc = batch_launch(scene, st, b, static_cast<const float *>(d_first), static_cast<const float *>(d_second), d_out,
+                                nullptr, static_cast<hipStream_t>(stream));
     if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
-    if ((rc = shade_launch(scene, *st, n_pixels, static_cast<const float *>(d_origins), static_cast<const float *>(d_directions),
-                           flags, d_shade, d_hits, nullptr, static_cast<hipStream_t>(stream))) != RTX_OK) return rc;
-    if (query_regroups(n_pixels, flags)) {     // the library's sort buffers are busy until this point of the caller's stream
-        if (!st->q_sorted) RTX_HIP(hipEventCreateWithFlags(&st->q_sorted, hipEventDisableTiming));
-        RTX_HIP(hipEventRecord(st->q_sorted, static_cast<hipStream_t>(stream)));
+    if (batch_regroups(b)) {     // the library's sort buffers are busy until this point of the caller's stream
+        if (!st.q_sorted) RTX_HIP(hipEventCreateWithFlags(st.q_sorted.put(), hipEventDisableTiming));
+        RTX_HIP(hipEventRecord(st.q_sorted, static_cast<hipStream_t>(stream)));
     }
     return RTX_OK;
+}
+
+// the argument checks a family's host and device-resident entry points share
+bool query_args_ok(const RtxScene *scene, const void *first, const void *second, const void *out, uint32_t flags, uint32_t n_rays)
+{
+    return scene && first && second && out && !(flags & ~kQueryFlags) && n_rays <= rtxq::kMaxRays;
+}
+
+bool shade_args_ok(const RtxScene *scene, const void *first, const void *second, const void *out, uint32_t flags, uint32_t n_pixels)
+{
+    if (!scene || !first || !second || !out || (flags & ~kQueryFlags)) return false;
+    return n_pixels == 0u || shade_ray_count(scene, n_pixels) != 0u;
+}
+
+Batch query_batch(bool occlusion, uint32_t n_rays, uint32_t flags)
+{
+    return Batch{n_rays, n_rays, flags, {static_cast<size_t>(n_rays) * (occlusion ? 1u : sizeof(RtxRayHit)), 0u}, 0u,
+                 occlusion ? launch_queried<true> : launch_queried<false>};
+}
+
+// caller has checked n_pixels (shade_args_ok)
+Batch shade_batch(const RtxScene *scene, uint32_t n_pixels, uint32_t flags, bool want_hits)
+{
+    const uint32_t n_rays = shade_ray_count(scene, n_pixels);
+    return Batch{n_pixels, n_rays, flags,
+                 {static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade), want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u},
+                 scene->prep.nb_light_sample, launch_shaded};
 }
 
 }  // namespace
@@ -629,26 +663,7 @@ int rtx_scene_create(const RtxSceneDesc *desc, RtxScene **out)
 
 void rtx_scene_destroy(RtxScene *scene)
 {
-    if (!scene) return;
-    for (auto &kv : scene->dev) {
-        DeviceState &st = *kv.second;
-        DeviceGuard g(kv.first);
-        if (g.status() != hipSuccess) continue;
-        if (st.stream) (void)hipStreamSynchronize(st.stream);
-        void *bufs[] = {st.nodes, st.primary_nodes, st.ref_nodes, st.tris, st.shade, st.samples, st.lights, st.thr, st.planes, st.light_boxes, st.d_out, st.d_counters, st.d_redo,
-                        st.ws.hits, st.ws.pix_slot, st.ws.tiles, st.ws.chunks, st.ws.results, st.ws.acc, st.ws.ctr, st.ws.buckets, st.ws.cut,
-                        st.q_first, st.q_second, st.q_out, st.q_sort.keys, st.q_sort.keys_sorted, st.q_sort.index, st.q_sort.index_sorted,
-                        st.q_sort.temp};
-        for (void *b : bufs) if (b) (void)hipFree(b);
-        if (st.h_stage) (void)hipHostFree(st.h_stage);
-        if (st.ev0) (void)hipEventDestroy(st.ev0);
-        if (st.ev1) (void)hipEventDestroy(st.ev1);
-        if (st.q_sorted) (void)hipEventDestroy(st.q_sorted);
-        for (auto &slot : st.ring)
-            for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e);
-        if (st.stream) (void)hipStreamDestroy(st.stream);
-    }
-    delete scene;
+    delete scene;      // every device's state goes through ReleaseOnDevice, in ascending device id
 }
 
 int rtx_scene_info(const RtxScene *scene, RtxSceneInfo *info)
@@ -673,13 +688,7 @@ int rtx_scene_info(const RtxScene *scene, RtxSceneInfo *info)
 int rtx_scene_upload(RtxScene *scene, int device)
 {
     if (!scene) return RTX_ERR_BAD_ARG;
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
-    if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    return ensure_uploaded(scene, *st);
+    return Entry(scene, device, Entry::kUploaded).rc;
 }
 
 int rtx_render_rows(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint8_t *out_rgb, RtxStats *stats)
@@ -687,30 +696,28 @@ int rtx_render_rows(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, 
     if (!scene || !out_rgb) return RTX_ERR_BAD_ARG;
     const uint32_t H = scene->prep.height, W = scene->prep.width;
     if (row0 > H || nrows > H - row0) return RTX_ERR_BAD_ARG;
+    const uint32_t nb_ray = scene->prep.nb_ray, nb_light = scene->prep.nb_light_sample;
     const double t0 = wall_ms();
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
-    if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
+    Entry e(scene, device, Entry::kCurrent);
+    if (e.rc != RTX_OK) return e.rc;
+    unsigned long long c[rtx::kNumCounters] = {0};
     if (nrows == 0) {
-        unsigned long long zero[rtx::kNumCounters] = {0};
-        if (stats) fill_stats(stats, scene, 0, zero, 0.0, wall_ms() - t0);
+        if (stats) fill_stats(stats, 0, nb_light, c, 0.0, wall_ms() - t0);
         return RTX_OK;
     }
     const rtx::TileSpec ts{row0, nrows, nrows, nrows};
-    if ((rc = launch_on(scene, *st, ts, stats != nullptr)) != RTX_OK) return rc;
+    const int rc = launch_on(scene, *e.slot, ts, stats != nullptr);
+    if (rc != RTX_OK) return rc;
+    DeviceState &st = e.state();
     const size_t bytes = static_cast<size_t>(nrows) * W * 3u;
-    RTX_HIP(hipMemcpyAsync(out_rgb, st->d_out, bytes, hipMemcpyDeviceToHost, st->stream));
-    unsigned long long c[rtx::kNumCounters] = {0};
+    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
     if (stats)
-        RTX_HIP(hipMemcpyAsync(c, st->d_counters, sizeof c, hipMemcpyDeviceToHost, st->stream));
-    RTX_HIP(hipStreamSynchronize(st->stream));
+        RTX_HIP(hipMemcpyAsync(c, st.d_counters.as<void>(), sizeof c, hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
     if (stats) {
         float ms = 0.0f;
-        RTX_HIP(hipEventElapsedTime(&ms, st->ev0, st->ev1));
-        fill_stats(stats, scene, static_cast<uint64_t>(nrows) * W, c, ms, wall_ms() - t0);
+        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
+        fill_stats(stats, static_cast<uint64_t>(nrows) * W * nb_ray, nb_light, c, ms, wall_ms() - t0);
     }
     return RTX_OK;
 }
@@ -726,26 +733,24 @@ int rtx_render_frame(RtxScene *scene, const int *devices, int n_devices, uint32_
     const double t0 = wall_ms();
     // Share j = row tiles j, j + n, ... goes to devices[j].  A device may be named more than once: its shares are
     // then rendered one after another on its stream (this is also how the path is rehearsed on a one-GPU box).
-    struct Share { DeviceState *st; rtx::TileSpec spec; size_t stage_offset; };
+    struct Share { DeviceSlot *slot; rtx::TileSpec spec; size_t stage_offset; };
     std::vector<Share> shares(static_cast<size_t>(n_devices));
-    std::map<int, DeviceState *> unique;                   // ascending device id: the order the locks are taken in, so
+    std::map<int, DeviceSlot *> unique;                    // ascending device id: the order the locks are taken in, so
     for (int j = 0; j < n_devices; ++j) {                  // that concurrent calls naming {0,1} and {1,0} cannot deadlock
-        DeviceState *st = nullptr;
-        const int rc = get_state(scene, devices[j], &st);
+        const int rc = get_slot(scene, devices[j], &shares[j].slot);
         if (rc != RTX_OK) return rc;
-        shares[j].st = st;
-        unique[devices[j]] = st;
+        unique[devices[j]] = shares[j].slot;
     }
     std::vector<std::unique_lock<std::mutex>> locks;
     for (auto &kv : unique) locks.emplace_back(kv.second->mu);
     // per device: the largest share (device buffer) and the sum of its shares (pinned staging), sized BEFORE anything is
     // in flight — growing a buffer later would free memory a copy is still reading
-    std::map<DeviceState *, std::pair<size_t, size_t>> need;
+    std::map<DeviceSlot *, std::pair<size_t, size_t>> need;
     for (int j = 0; j < n_devices; ++j) {
         const uint32_t rows = tiles_rows(H, static_cast<uint32_t>(j), static_cast<uint32_t>(n_devices), tile_rows);
         shares[j].spec = rtx::TileSpec{static_cast<uint32_t>(j) * tile_rows, tile_rows,
                                        static_cast<uint32_t>(n_devices) * tile_rows, rows};
-        auto &n = need[shares[j].st];
+        auto &n = need[shares[j].slot];
         shares[j].stage_offset = n.second;
         n.first = std::max(n.first, rows * row_bytes);
         n.second += rows * row_bytes;
@@ -755,16 +760,18 @@ int rtx_render_frame(RtxScene *scene, const int *devices, int n_devices, uint32_
     auto fail = [&](int rc) {
         for (int d : launched) {
             DeviceGuard g(d);
-            if (g.status() == hipSuccess) (void)hipStreamSynchronize(unique[d]->stream);
+            if (g.status() == hipSuccess) (void)hipStreamSynchronize(unique[d]->st->stream);
         }
         return rc;
     };
     for (auto &kv : unique) {
         DeviceGuard g(kv.first);
-        if (g.status() != hipSuccess) { g_last_hip_error = static_cast<int>(g.status()); return RTX_ERR_HIP; }
+        RTX_HIP(g.status());
         const auto &n = need[kv.second];
-        const int rc = ensure_out(*kv.second, n.first ? n.first : 16, n.second ? n.second : 16);
+        int rc = ensure_state(*kv.second, kv.first);
         if (rc != RTX_OK) return rc;
+        if ((rc = kv.second->st->d_out.reserve(n.first ? n.first : 16)) != RTX_OK) return rc;
+        if ((rc = kv.second->st->h_stage.reserve(n.second ? n.second : 16)) != RTX_OK) return rc;
     }
     // launch everywhere first (asynchronous), then gather
     unsigned long long total[rtx::kNumCounters] = {0};
@@ -774,51 +781,50 @@ int rtx_render_frame(RtxScene *scene, const int *devices, int n_devices, uint32_
         Share &sh = shares[j];
         if (!sh.spec.local_rows) continue;
         DeviceGuard g(devices[j]);
-        if (g.status() != hipSuccess) { g_last_hip_error = static_cast<int>(g.status()); return fail(RTX_ERR_HIP); }
-        const int rc = launch_on(scene, *sh.st, sh.spec, stats != nullptr);
+        if (g.status() != hipSuccess) return fail(hip_rc(g.status()));
+        const int rc = launch_on(scene, *sh.slot, sh.spec, stats != nullptr);
         if (rc != RTX_OK) return fail(rc);
         launched.push_back(devices[j]);
-        hipError_t e = hipMemcpyAsync(sh.st->h_stage + sh.stage_offset, sh.st->d_out, sh.spec.local_rows * row_bytes,
-                                      hipMemcpyDeviceToHost, sh.st->stream);
+        DeviceState &st = *sh.slot->st;
+        hipError_t e = hipMemcpyAsync(st.h_stage.as<uint8_t>() + sh.stage_offset, st.d_out.as<void>(), sh.spec.local_rows * row_bytes,
+                                      hipMemcpyDeviceToHost, st.stream);
         if (e == hipSuccess && stats)   // a device's next share reuses its counter block: read this share's now (stream order)
-            e = hipMemcpyAsync(&counters[static_cast<size_t>(j) * rtx::kNumCounters], sh.st->d_counters,
-                               rtx::kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, sh.st->stream);
-        if (e != hipSuccess) { g_last_hip_error = static_cast<int>(e); return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP); }
+            e = hipMemcpyAsync(&counters[static_cast<size_t>(j) * rtx::kNumCounters], st.d_counters.as<void>(),
+                               rtx::kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st.stream);
+        if (e != hipSuccess) return fail(hip_rc(e));
         if (stats && unique.size() != static_cast<size_t>(n_devices)) {
             // shares of one device run back to back and share its two timing events: take each share's time now
-            if ((e = hipStreamSynchronize(sh.st->stream)) != hipSuccess || (e = hipEventElapsedTime(&share_ms[j], sh.st->ev0, sh.st->ev1)) != hipSuccess) {
-                g_last_hip_error = static_cast<int>(e);
-                return fail(RTX_ERR_HIP);
-            }
+            if ((e = hipStreamSynchronize(st.stream)) != hipSuccess || (e = hipEventElapsedTime(&share_ms[j], st.ev0, st.ev1)) != hipSuccess)
+                return fail(hip_rc(e));
         }
     }
     double kernel_ms = 0.0;
     for (auto &kv : unique) {
         DeviceGuard g(kv.first);
-        if (g.status() != hipSuccess) { g_last_hip_error = static_cast<int>(g.status()); return fail(RTX_ERR_HIP); }
-        const hipError_t e = hipStreamSynchronize(kv.second->stream);
-        if (e != hipSuccess) { g_last_hip_error = static_cast<int>(e); return fail(RTX_ERR_HIP); }
+        if (g.status() != hipSuccess) return fail(hip_rc(g.status()));
+        const hipError_t e = hipStreamSynchronize(kv.second->st->stream);
+        if (e != hipSuccess) return fail(hip_rc(e));
     }
     for (int j = 0; j < n_devices; ++j) {
         const Share &sh = shares[j];
         if (!sh.spec.local_rows) continue;
         // the packed tiles of this share go to their rows of the frame (disjoint rows per share)
-        rtxh_scatter_tiles(out_rgb, H, W, sh.st->h_stage + sh.stage_offset, static_cast<uint32_t>(j), static_cast<uint32_t>(n_devices), tile_rows);
+        rtxh_scatter_tiles(out_rgb, H, W, sh.slot->st->h_stage.as<uint8_t>() + sh.stage_offset, static_cast<uint32_t>(j), static_cast<uint32_t>(n_devices), tile_rows);
         if (stats) {
             if (unique.size() == static_cast<size_t>(n_devices)) {
                 DeviceGuard g(devices[j]);
                 float ms = 0.0f;
-                if (g.status() == hipSuccess && hipEventElapsedTime(&ms, sh.st->ev0, sh.st->ev1) == hipSuccess) share_ms[j] = ms;
+                if (g.status() == hipSuccess && hipEventElapsedTime(&ms, sh.slot->st->ev0, sh.slot->st->ev1) == hipSuccess) share_ms[j] = ms;
             }
             for (int k = 0; k < rtx::kNumCounters; ++k) total[k] += counters[static_cast<size_t>(j) * rtx::kNumCounters + k];
         }
     }
     if (stats) {
         // the frame's device time: the slowest device, a device's shares added up
-        std::map<DeviceState *, double> per_device;
-        for (int j = 0; j < n_devices; ++j) per_device[shares[j].st] += share_ms[j];
+        std::map<DeviceSlot *, double> per_device;
+        for (int j = 0; j < n_devices; ++j) per_device[shares[j].slot] += share_ms[j];
         for (auto &kv : per_device) kernel_ms = std::max(kernel_ms, kv.second);
-        fill_stats(stats, scene, static_cast<uint64_t>(H) * W, total, kernel_ms, wall_ms() - t0);
+        fill_stats(stats, static_cast<uint64_t>(H) * W * scene->prep.nb_ray, scene->prep.nb_light_sample, total, kernel_ms, wall_ms() - t0);
     }
     return RTX_OK;
 }
@@ -844,60 +850,56 @@ int rtx_render_tiles_device(RtxScene *scene, int device, uint32_t first_tile, ui
     if (static_cast<size_t>(rows) * scene->prep.width * 3u > d_out_bytes) return RTX_ERR_BAD_ARG;
     if (static_cast<uint64_t>(first_tile) * tile_rows > 0xFFFFFFFFull ||
         static_cast<uint64_t>(tile_stride) * tile_rows > 0xFFFFFFFFull) return RTX_ERR_BAD_ARG;
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
-    if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
     const rtx::TileSpec ts{first_tile * tile_rows, tile_rows, tile_stride * tile_rows, rows};
-    const rtx::DeviceScene S = device_scene(scene, *st);
-    // the redo queue is library-owned per device: launches on one device must be ordered on one stream
-    if ((rc = ensure_redo(*st, rtx::trace_redo_bytes(S, ts))) != RTX_OK) return rc;
-    const rtx::StreamWorkspace *ws = nullptr;
-    if ((rc = ensure_stream_ws(*st, S, ts, &ws)) != RTX_OK) return rc;
-    RTX_HIP(rtx::launch_trace_shade(S, ts, static_cast<uint8_t *>(d_out_rgb), st->d_redo, ws,
-                                    reinterpret_cast<unsigned long long *>(d_counters), nullptr, kernel_variant(),
-                                    static_cast<hipStream_t>(stream), st->ring[st->launches % RTX_TIMING_RING]));
-    if (ts.local_rows) ++st->launches;
-    return RTX_OK;
+    return render_launch(e.state(), device_scene(scene, e.state()), ts, static_cast<uint8_t *>(d_out_rgb),
+                         reinterpret_cast<unsigned long long *>(d_counters), nullptr, static_cast<hipStream_t>(stream),
+                         [] { return static_cast<int>(RTX_OK); });
 }
 
 int rtx_trace_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
                    uint32_t flags, RtxRayHit *out_hits, RtxStats *stats)
 {
-    return query_host(scene, device, false, n_rays, origins, directions, flags, out_hits, stats);
+    if (!query_args_ok(scene, origins, directions, out_hits, flags, n_rays)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, query_batch(false, n_rays, flags), origins, directions, out_hits, nullptr, stats);
 }
 
 int rtx_occluded_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
                       uint32_t flags, uint8_t *out_occluded, RtxStats *stats)
 {
-    return query_host(scene, device, true, n_rays, origins, targets, flags, out_occluded, stats);
+    if (!query_args_ok(scene, origins, targets, out_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, query_batch(true, n_rays, flags), origins, targets, out_occluded, nullptr, stats);
 }
 
 int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
                           uint32_t flags, void *d_hits, void *stream)
 {
-    return query_device(scene, device, false, n_rays, d_origins, d_directions, flags, d_hits, stream);
+    if (!query_args_ok(scene, d_origins, d_directions, d_hits, flags, n_rays) || (reinterpret_cast<uintptr_t>(d_hits) & 15u))
+        return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, query_batch(false, n_rays, flags), d_origins, d_directions, d_hits, nullptr, stream);
 }
 
 int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
                              uint32_t flags, void *d_occluded, void *stream)
 {
-    return query_device(scene, device, true, n_rays, d_origins, d_targets, flags, d_occluded, stream);
+    if (!query_args_ok(scene, d_origins, d_targets, d_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, query_batch(true, n_rays, flags), d_origins, d_targets, d_occluded, nullptr, stream);
 }
 
 int rtx_shade_rays(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
                    uint32_t flags, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
-    return shade_host(scene, device, n_pixels, origins, directions, flags, out_shade, out_hits, stats);
+    if (!shade_args_ok(scene, origins, directions, out_shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, shade_batch(scene, n_pixels, flags, out_hits != nullptr), origins, directions, out_shade, out_hits, stats);
 }
 
 int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
                           uint32_t flags, void *d_shade, void *d_hits, void *stream)
 {
-    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, d_shade, d_hits, stream);
+    if (!shade_args_ok(scene, d_origins, d_directions, d_shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, shade_batch(scene, n_pixels, flags, d_hits != nullptr), d_origins, d_directions, d_shade, d_hits, stream);
 }
 
 int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint64_t *out,
@@ -911,32 +913,27 @@ int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t 
     (void)device; (void)out; (void)out_tiles;
     return RTX_ERR_UNSUPPORTED;
 #else
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
-    if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    if ((rc = ensure_uploaded(scene, *st)) != RTX_OK) return rc;
-    const rtx::DeviceScene S = device_scene(scene, *st);
+    Entry en(scene, device, Entry::kUploaded);
+    if (en.rc != RTX_OK) return en.rc;
+    DeviceState &st = en.state();
+    const rtx::DeviceScene S = device_scene(scene, st);
     *tiles_x = rtx::trace_tiles_x(S, kernel_variant());
     *tiles_y = (nrows + 7u) / 8u;
     const size_t n = static_cast<size_t>(*tiles_x) * *tiles_y;
     if (!out) return RTX_OK;   // size query
     if (out_tiles < n) return RTX_ERR_BAD_ARG;
-    if ((rc = ensure_out(*st, static_cast<size_t>(nrows) * scene->prep.width * 3u, 0)) != RTX_OK) return rc;
+    int rc = st.d_out.reserve(static_cast<size_t>(nrows) * scene->prep.width * 3u);
+    if (rc != RTX_OK) return rc;
     unsigned long long *d_prof = nullptr;
     const size_t prof_bytes = n * rtx::kWaveProfWords * sizeof(unsigned long long);
     RTX_HIP(hipMalloc(reinterpret_cast<void **>(&d_prof), prof_bytes));
-    hipError_t e = hipMemsetAsync(d_prof, 0, prof_bytes, st->stream);
     const rtx::TileSpec ts{row0, nrows, nrows, nrows};
-    if (ensure_redo(*st, rtx::trace_redo_bytes(S, ts)) != RTX_OK) { (void)hipFree(d_prof); return RTX_ERR_OOM; }
-    if (e == hipSuccess)
-        e = rtx::launch_trace_shade(S, ts, st->d_out, st->d_redo, nullptr, nullptr, d_prof, kernel_variant(), st->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_prof, prof_bytes, hipMemcpyDeviceToHost, st->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(st->stream);
+    rc = render_launch(st, S, ts, st.d_out.as<uint8_t>(), nullptr, d_prof, st.stream,
+                       [&] { return hip_rc(hipMemsetAsync(d_prof, 0, prof_bytes, st.stream)); });
+    if (rc == RTX_OK) rc = hip_rc(hipMemcpyAsync(out, d_prof, prof_bytes, hipMemcpyDeviceToHost, st.stream));
+    if (rc == RTX_OK) rc = hip_rc(hipStreamSynchronize(st.stream));
     (void)hipFree(d_prof);
-    RTX_HIP(e);
+    if (rc != RTX_OK) return rc;
     for (size_t t = 0; t < n; ++t)   // the kernel keeps the earliest start as max(~t)
         out[rtx::kWaveProfWords * t + 2] = ~out[rtx::kWaveProfWords * t + 2];
     return RTX_OK;
@@ -946,32 +943,28 @@ int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t 
 int rtx_debug_tile_descs(RtxScene *scene, int device, uint32_t *out, size_t max_tiles)
 {
     if (!scene) return RTX_ERR_BAD_ARG;
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
+    Entry e(scene, device, Entry::kLocked);
+    if (e.rc != RTX_OK) return e.rc;
+    const DeviceState &st = e.state();
+    if (!out) return static_cast<int>(st.last_tiles);      // (answered without making the device current)
+    const int rc = e.make_current();
     if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    if (!out) return static_cast<int>(st->last_tiles);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    const size_t n = st->last_tiles < max_tiles ? st->last_tiles : max_tiles;
+    const size_t n = st.last_tiles < max_tiles ? st.last_tiles : max_tiles;
     RTX_HIP(hipDeviceSynchronize());
-    if (n) RTX_HIP(hipMemcpy(out, st->ws.tiles, n * sizeof(rtx::TileDesc), hipMemcpyDeviceToHost));
+    if (n) RTX_HIP(hipMemcpy(out, st.ws.tiles.as<void>(), n * sizeof(rtx::TileDesc), hipMemcpyDeviceToHost));
     return static_cast<int>(n);
 }
 
 int rtx_launch_timings(RtxScene *scene, int device, int max_launches, float *schedule_ms, float *shade_ms)
 {
     if (!scene || max_launches < 0 || !schedule_ms || !shade_ms) return RTX_ERR_BAD_ARG;
-    DeviceState *st;
-    int rc = get_state(scene, device, &st);
-    if (rc != RTX_OK) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    DeviceGuard g(device);
-    RTX_HIP(g.status());
-    unsigned long long n = st->launches < RTX_TIMING_RING ? st->launches : RTX_TIMING_RING;
+    Entry e(scene, device, Entry::kCurrent);
+    if (e.rc != RTX_OK) return e.rc;
+    const DeviceState &st = e.state();
+    unsigned long long n = st.launches < RTX_TIMING_RING ? st.launches : RTX_TIMING_RING;
     if (n > static_cast<unsigned long long>(max_launches)) n = static_cast<unsigned long long>(max_launches);
     for (unsigned long long i = 0; i < n; ++i) {
-        hipEvent_t *ev = st->ring[(st->launches - n + i) % RTX_TIMING_RING];
+        const Event *ev = st.ring[(st.launches - n + i) % RTX_TIMING_RING];
         RTX_HIP(hipEventSynchronize(ev[2]));
         RTX_HIP(hipEventElapsedTime(&schedule_ms[i], ev[0], ev[1]));
         RTX_HIP(hipEventElapsedTime(&shade_ms[i], ev[1], ev[2]));

@@ -252,6 +252,37 @@ def test_statistics_equal_those_of_the_first_call_on_a_fresh_scene(rtx, refs, bu
         assert got[key] == fresh[key], key
 
 
+def test_host_batches_grow_then_shrink_across_the_families(rtx, refs, bunny_sets):
+    """The three host entry points share one pair of input buffers and one output buffer, which only grow: a batch of 70
+    one-byte answers sizes the output, a shade batch then keeps two segments in it (pixels, and hit records behind them),
+    257 regrouped rays follow, the whole occlusion set with statistics, and three pixels at the end.  Every answer is its
+    slice of the oracle's (the sets are answered ray by ray; the first 70 pairs hold 17 occluded and 53 lit, the first
+    257 rays 138 hits, two of the first three pixels' rays hit); a scene destroyed and created again answers the same."""
+    d = refs("B")["desc"]
+    o, dirs, exp = bunny_sets["trace"]
+    oo, targets, occluded = bunny_sets["occlusion"]
+    sh = bunny_sets["shade"]
+    n_px = len(sh["shade"])
+    assert d["nb_ray"] == 1 and np.array_equal(sh["origins"], o[:n_px]) and np.array_equal(sh["directions"], dirs[:n_px])
+
+    def shade_with_hits(s, what):
+        got, hits = s.shade_rays(sh["origins"], sh["directions"], want_hits=True)
+        check_shade(got, bunny_sets, what)
+        qs.check_hits(hits, exp[:n_px], s.normals(), what)
+
+    with sq.make_scene(rtx, d) as s:
+        assert s.occluded_rays(oo[:70], targets[:70]).tobytes() == occluded[:70].tobytes()
+        shade_with_hits(s, "shade with hits behind 70 occlusion bytes")
+        qs.check_hits(s.trace_rays(o[:257], dirs[:257], force_regroup=True), exp[:257], s.normals(), "257 rays, regrouped")
+        got, st = s.occluded_rays(oo, targets, stats=True)
+        assert got.tobytes() == occluded.tobytes()
+        assert st["primary_rays"] == st["rays"] == len(oo) and st["shadow_rays"] == 0, st
+        assert st["primary_hits"] == int(occluded.sum()), (st["primary_hits"], int(occluded.sum()))
+        assert s.shade_rays(sh["origins"][:3], sh["directions"][:3]).tobytes() == sh["shade"][:3].tobytes()
+    with sq.make_scene(rtx, d) as s:
+        shade_with_hits(s, "shade with hits on the scene created again")
+
+
 # ------------------------------------------------------------------------------------------- 4. back-to-back device renders
 def packed(ref, first, stride):
     return ref["frame"][sq.share_rows(ref["desc"]["H"], first, stride, sq.ASYNC_TILE_ROWS)]
