@@ -277,6 +277,43 @@ int rtx_shade_rays(RtxScene *scene, int device, uint32_t n_pixels, const float *
 int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
                           uint32_t flags, void *d_shade, void *d_hits /* may be NULL */, void *stream);
 
+/* ---- any pinhole view of the uploaded scene ----------------------------------- */
+/* rtx_render_rows renders the camera rtx_scene_create was given.  These entry points render a rectangle of ANY view —
+ * another eye, another frame, a crop, a thumbnail — of the scene as it is uploaded: no new scene, no tree build, no ray
+ * arrays.  Pixel (px, py) gets exactly render_pixel(px, py) (main.rs:180-240) of a reference Scene that has the view's
+ * width, height and camera; primitives, light, nb_ray, nb_light_sample and the sample table are the uploaded scene's.
+ * The rays are create_rays' (main.rs:151-178) bit for bit.  Kernels of its own, beside the render pipeline, the ray
+ * queries and ray shading: one wavefront per 8x8 tile of the rectangle, no regrouping pass. */
+typedef struct RtxView {          /* 76 bytes, alignment 4 */
+    uint32_t width, height;       /* the frame create_rays sees: w, h of main.rs:156-157 and the table index
+                                     (px*width + py + i) % n_samples (u32 arithmetic) */
+    float eye[3], u[3], v[3], w[3];
+    float distance;               /* Camera after Camera::new (camera.rs:17-35); rtxh_camera_new computes u, v, w */
+    uint32_t x0, y0, nx, ny;      /* the pixels to render: columns [x0,x0+nx) x rows [y0,y0+ny) */
+} RtxView;
+
+/* the scene's own camera and whole frame: what rtx_scene_create was given */
+int rtx_scene_view(const RtxScene *scene, RtxView *out);
+/* out_rgb:   NULL or ny*nx*3 bytes, rows packed: pixel (x,y) at ((y-y0)*nx + (x-x0))*3 — the bytes rtx_render_rows of a
+ *            scene created with that camera holds for the pixel;
+ * out_shade: NULL or ny*nx records, same order; out_hits: NULL or ny*nx*nb_ray records, a pixel's rays consecutive — both
+ *            byte-identical to what rtx_shade_rays / rtx_trace_rays return for the view's rays.
+ * RTX_ERR_BAD_ARG: NULL scene or view, all three outputs NULL, width == 0 or height == 0, width*height >= 2^31, a
+ * rectangle outside the frame, nx*ny*nb_ray > 2^28.  nx == 0 or ny == 0: RTX_OK, nothing written, stats zeroed, no device
+ * needed.  No usable device: RTX_ERR_NO_DEVICE (there is no CPU fallback).  Non-finite camera values are outside the
+ * parity contract (the call still terminates with RTX_OK).  The eye may lie anywhere: beyond the scene's and its own
+ * camera's largest coordinate the primary walks use the exact box test (slower, same results).
+ * stats may be NULL; when non-NULL the counted kernel form runs (same results) and the fields mean what rtx_shade_rays
+ * gives them, with primary_rays = nx*ny*nb_ray.
+ * A view call leaves every later render, query or shade call on the scene unchanged. */
+int rtx_render_view(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxPixelShade *out_shade,
+                    RtxRayHit *out_hits, RtxStats *stats);
+/* Device-resident variant, asynchronous on `stream` (a hipStream_t; NULL = the default stream): device pointers the caller
+ * owns, each NULL or sized as above (d_shade and d_hits 16-byte aligned: else RTX_ERR_BAD_ARG).  It uses no library
+ * buffer: no ordering rule ties it to the query or shade calls.  The scene is uploaded (synchronously) first if needed. */
+int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, void *d_shade, void *d_hits,
+                           void *stream);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

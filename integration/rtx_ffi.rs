@@ -101,6 +101,23 @@ pub struct RtxPixelShade {
     pub rgb8: [u8; 3],
     pub hits: u8,
 }
+/// A pinhole view of an uploaded scene for `rtx_render_view`: the frame `create_rays` sees, the `Camera` after
+/// `Camera::new` (`rtxh_camera_new` computes `u`, `v`, `w`) and the rectangle of pixels to render.
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxView {
+    pub width: u32,
+    pub height: u32,
+    pub eye: [f32; 3],
+    pub u: [f32; 3],
+    pub v: [f32; 3],
+    pub w: [f32; 3],
+    pub distance: f32,
+    pub x0: u32,
+    pub y0: u32,
+    pub nx: u32,
+    pub ny: u32,
+}
 pub const RTX_NO_HIT: u32 = 0xFFFF_FFFF;
 pub const RTX_RAYS_KEEP_ORDER: u32 = 1;
 pub const RTX_RAYS_FORCE_REGROUP: u32 = 2;
@@ -140,12 +157,18 @@ extern "C" {
     pub fn rtx_shade_rays_device(scene: *mut RtxScene, device: c_int, n_pixels: u32, d_origins: *const c_void,
                                  d_directions: *const c_void, flags: u32, d_shade: *mut c_void, d_hits: *mut c_void,
                                  stream: *mut c_void) -> c_int;
+    pub fn rtx_scene_view(scene: *const RtxScene, out: *mut RtxView) -> c_int;
+    pub fn rtx_render_view(scene: *mut RtxScene, device: c_int, view: *const RtxView, out_rgb: *mut u8,
+                           out_shade: *mut RtxPixelShade, out_hits: *mut RtxRayHit, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, d_rgb: *mut c_void,
+                                  d_shade: *mut c_void, d_hits: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn rtx_launch_timings(scene: *mut RtxScene, device: c_int, max_launches: c_int, schedule_ms: *mut f32,
                               shade_ms: *mut f32) -> c_int;
     pub fn rtx_strerror(err: c_int) -> *const c_char;
     pub fn rtx_last_hip_error() -> c_int;
     pub fn rtxh_scatter_tiles(frame: *mut u8, height: u32, width: u32, packed: *const u8, first_tile: u32,
                               tile_stride: u32, tile_rows: u32) -> c_int;
+    pub fn rtxh_camera_new(eye: *const f32, look_at: *const f32, up: *const f32, u: *mut f32, v: *mut f32, w: *mut f32);
     pub fn rtxh_ref_leaf_rank(n_tris: u32, v0v1v2: *const f32, out_rank: *mut u32) -> c_int;
 }
 

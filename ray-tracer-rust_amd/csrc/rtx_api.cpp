@@ -21,6 +21,7 @@
 #include "rtx_device.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
+#include "rtx_view.h"
 #include "scene_prep.h"
 
 namespace {
@@ -138,7 +139,7 @@ public:
     PinnedBuffer h_stage;
     struct { DeviceBuffer hits, pix_slot, tiles, chunks, results, acc, ctr, buckets, cut; } ws;   // streamed pipeline:
                                                                                     // intermediate products in HBM
-    // ray queries and ray shading (rtx_query.hip, rtx_shade.hip): device copies of the host entry points' arrays, the
+    // ray queries, ray shading and views (rtx_query.hip, rtx_shade.hip, rtx_view.hip): device copies of the host entry points' arrays, the
     // regrouping pass's (key, ray number) buffers and the sort's temporary storage; none shared with the render workspace
     DeviceBuffer q_first, q_second, q_out;
     struct { DeviceBuffer keys, keys_sorted, index, index_sorted, temp; } q_sort;
@@ -431,7 +432,7 @@ int launch_on(RtxScene *scene, DeviceSlot &slot, const rtx::TileSpec &ts, bool c
     return RTX_OK;
 }
 
-// ---- ray batches: the queries (rtx_query.hip) and shading (rtx_shade.hip) ----------------------------------------------
+// ---- ray batches: the queries (rtx_query.hip), shading (rtx_shade.hip) and views (rtx_view.hip) -------------------------
 
 // The box the regrouping keys quantise origins in: the tree proper's root (beside the global triangles — the ground is
 // as large as the scene and would leave the mesh a handful of cells), else the stream's root.
@@ -466,6 +467,7 @@ int reserve_query_sort(DeviceState &st, uint32_t n, rtxq::SortBuffers *sort)
 
 static_assert(sizeof(RtxRayHit) == 32, "closest_kernel writes a hit as two 16-byte words");
 static_assert(sizeof(RtxPixelShade) == 16, "shade_kernel writes a pixel as one 16-byte word");
+static_assert(sizeof(RtxView) == sizeof(rtxv::ViewBlock) && alignof(RtxView) == 4, "view_kernel is handed an RtxView");
 constexpr uint32_t kQueryFlags = RTX_RAYS_KEEP_ORDER | RTX_RAYS_FORCE_REGROUP;
 
 // n_pixels * nb_ray, or 0 when it is beyond what one batch may hold
@@ -476,15 +478,18 @@ uint32_t shade_ray_count(const RtxScene *scene, uint32_t n_pixels)
 }
 
 // what a family's launcher is handed: the scene, the regrouping pass's box, bound and buffers (NULL: the caller's order),
-// the two input arrays, the one or two outputs, the counters (or NULL), all on the device, and the stream
+// the two input arrays (a view has none: its kernel makes the rays), the view (or NULL), the outputs, the counters (or
+// NULL), all on the device, and the stream
+constexpr int kBatchOuts = 3;
 struct BatchArgs {
     rtx::DeviceScene S;
     uint32_t n;
     const float *first, *second;
+    const RtxView *view;
     rtxq::KeyBox box;
     float origin_bound;
     const rtxq::SortBuffers *sort;
-    void *out[2];
+    void *out[kBatchOuts];
     unsigned long long *counters;
     hipStream_t stream;
 };
@@ -500,15 +505,27 @@ hipError_t launch_shaded(const BatchArgs &a)
     return rtxs::launch_shade(a.S, a.n, a.first, a.second, a.box, a.origin_bound, a.sort, a.out[0], a.out[1], a.counters, a.stream);
 }
 
-// What differs between rtx_trace_rays, rtx_occluded_rays and rtx_shade_rays (and their _device twins), checked by them.
+// a view's outputs in Batch::out_bytes' order: the 16-byte records first, so that they stay aligned in the library's buffer
+enum { kViewShade, kViewHits, kViewRgb };
+
+hipError_t launch_viewed(const BatchArgs &a)
+{
+    rtxv::ViewBlock v;
+    std::memcpy(&v, a.view, sizeof v);
+    return rtxv::launch_view(a.S, v, a.origin_bound, a.out[kViewRgb], a.out[kViewShade], a.out[kViewHits], a.counters, a.stream);
+}
+
+// What differs between rtx_trace_rays, rtx_occluded_rays, rtx_shade_rays and rtx_render_view (and their _device twins),
+// checked by them.
 struct Batch {
     uint32_t n;                    // entries the launcher works on and the regrouping pass sorts: rays, or pixels of nb_ray rays
-    uint32_t n_rays;               // rays in each of the two input arrays
+    uint32_t n_rays;               // rays in each of the two input arrays (a view: rays its kernel makes)
     uint32_t flags;
-    size_t out_bytes[2];           // the output segments, one behind the other in the library's device buffer (the first is
-                                   // a multiple of 16 where there is a second: the hit records behind stay aligned); 0: none
+    size_t out_bytes[kBatchOuts];  // the output segments, one behind the other in the library's device buffer (a segment
+                                   // of 16-byte records follows multiples of 16 only: it stays aligned); 0: none
     uint32_t shadow_rays_per_hit;  // RtxStats
     hipError_t (*launch)(const BatchArgs &);
+    const RtxView *view;           // rtx_render_view: the caller's, read while the call runs; else NULL
 };
 
 bool batch_regroups(const Batch &b)
@@ -519,23 +536,22 @@ bool batch_regroups(const Batch &b)
 
 // key + sort + kernel of one batch on `stream`; caller holds the slot's lock, has the device current and the scene uploaded
 int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *d_first, const float *d_second,
-                 void *const d_out[2], unsigned long long *d_counters, hipStream_t stream)
+                 void *const d_out[kBatchOuts], unsigned long long *d_counters, hipStream_t stream)
 {
     rtxq::SortBuffers sort{};
     const bool regroup = batch_regroups(b);
     int rc;
     if (regroup && (rc = reserve_query_sort(st, b.n, &sort)) != RTX_OK) return rc;
-    RTX_HIP(b.launch(BatchArgs{device_scene(scene, st), b.n, d_first, d_second, query_key_box(scene->prep),
-                               scene->prep.cull_delta * 0x1p19f, regroup ? &sort : nullptr, {d_out[0], d_out[1]}, d_counters,
-                               stream}));
+    RTX_HIP(b.launch(BatchArgs{device_scene(scene, st), b.n, d_first, d_second, b.view, query_key_box(scene->prep),
+                               scene->prep.cull_delta * 0x1p19f, regroup ? &sort : nullptr, {d_out[0], d_out[1], d_out[2]},
+                               d_counters, stream}));
     return RTX_OK;
 }
 
-// the host entry points: copy in, launch, copy out
-int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, const float *second, void *out0, void *out1,
-               RtxStats *stats)
+// the host entry points: copy in (first, second: the two input arrays, or NULL twice), launch, copy out
+int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, const float *second,
+               void *const (&out)[kBatchOuts], RtxStats *stats)
 {
-    void *const out[2] = {out0, out1};
     const double t0 = wall_ms();
     if (b.n == 0u) {
         if (stats) { std::memset(stats, 0, sizeof *stats); stats->total_ms = wall_ms() - t0; }
@@ -544,14 +560,19 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    const size_t in_bytes = static_cast<size_t>(b.n_rays) * 3u * sizeof(float);
-    int rc = reserve_all({{st.q_first, in_bytes}, {st.q_second, in_bytes}, {st.q_out, b.out_bytes[0] + b.out_bytes[1]}});
+    const size_t in_bytes = first ? static_cast<size_t>(b.n_rays) * 3u * sizeof(float) : 0u;
+    size_t offset[kBatchOuts + 1] = {0};
+    for (int k = 0; k < kBatchOuts; ++k) offset[k + 1] = offset[k] + b.out_bytes[k];
+    int rc = reserve_all({{st.q_first, in_bytes}, {st.q_second, in_bytes}, {st.q_out, offset[kBatchOuts]}});
     if (rc != RTX_OK) return rc;
-    void *const d_out[2] = {st.q_out.as<uint8_t>(), b.out_bytes[1] ? st.q_out.as<uint8_t>() + b.out_bytes[0] : nullptr};
+    void *d_out[kBatchOuts];
+    for (int k = 0; k < kBatchOuts; ++k) d_out[k] = b.out_bytes[k] ? st.q_out.as<uint8_t>() + offset[k] : nullptr;
     unsigned long long *d_counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
     if (st.q_sorted) RTX_HIP(hipStreamWaitEvent(st.stream, st.q_sorted, 0));   // a device-resident call may still be sorting
-    RTX_HIP(hipMemcpyAsync(st.q_first.as<void>(), first, in_bytes, hipMemcpyHostToDevice, st.stream));
-    RTX_HIP(hipMemcpyAsync(st.q_second.as<void>(), second, in_bytes, hipMemcpyHostToDevice, st.stream));
+    if (in_bytes) {
+        RTX_HIP(hipMemcpyAsync(st.q_first.as<void>(), first, in_bytes, hipMemcpyHostToDevice, st.stream));
+        RTX_HIP(hipMemcpyAsync(st.q_second.as<void>(), second, in_bytes, hipMemcpyHostToDevice, st.stream));
+    }
     if (stats) RTX_HIP(hipMemsetAsync(d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
     RTX_HIP(hipEventRecord(st.ev0, st.stream));
     if ((rc = batch_launch(scene, st, b, st.q_first.as<float>(), st.q_second.as<float>(), d_out, d_counters, st.stream)) != RTX_OK) {
@@ -559,7 +580,7 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
         return rc;
     }
     RTX_HIP(hipEventRecord(st.ev1, st.stream));
-    for (int k = 0; k < 2; ++k)
+    for (int k = 0; k < kBatchOuts; ++k)
         if (b.out_bytes[k]) RTX_HIP(hipMemcpyAsync(out[k], d_out[k], b.out_bytes[k], hipMemcpyDeviceToHost, st.stream));
     unsigned long long c[rtx::kNumCounters] = {0};
     if (stats) RTX_HIP(hipMemcpyAsync(c, d_counters, sizeof c, hipMemcpyDeviceToHost, st.stream));
@@ -573,10 +594,9 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
 }
 
 // the device-resident entry points: the caller's arrays, the caller's stream, nothing waited for
-int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_first, const void *d_second, void *d_out0,
-                 void *d_out1, void *stream)
+int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_first, const void *d_second,
+                 void *const (&d_out)[kBatchOuts], void *stream)
 {
-    void *const d_out[2] = {d_out0, d_out1};
     if ((reinterpret_cast<uintptr_t>(d_first) | reinterpret_cast<uintptr_t>(d_second)) & 3u) return RTX_ERR_BAD_ARG;
     if (b.n == 0u) return RTX_OK;
     Entry e(scene, device, Entry::kUploaded);
@@ -606,8 +626,8 @@ bool shade_args_ok(const RtxScene *scene, const void *first, const void *second,
 
 Batch query_batch(bool occlusion, uint32_t n_rays, uint32_t flags)
 {
-    return Batch{n_rays, n_rays, flags, {static_cast<size_t>(n_rays) * (occlusion ? 1u : sizeof(RtxRayHit)), 0u}, 0u,
-                 occlusion ? launch_queried<true> : launch_queried<false>};
+    return Batch{n_rays, n_rays, flags, {static_cast<size_t>(n_rays) * (occlusion ? 1u : sizeof(RtxRayHit)), 0u, 0u}, 0u,
+                 occlusion ? launch_queried<true> : launch_queried<false>, nullptr};
 }
 
 // caller has checked n_pixels (shade_args_ok)
@@ -615,8 +635,28 @@ Batch shade_batch(const RtxScene *scene, uint32_t n_pixels, uint32_t flags, bool
 {
     const uint32_t n_rays = shade_ray_count(scene, n_pixels);
     return Batch{n_pixels, n_rays, flags,
-                 {static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade), want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u},
-                 scene->prep.nb_light_sample, launch_shaded};
+                 {static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade), want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u, 0u},
+                 scene->prep.nb_light_sample, launch_shaded, nullptr};
+}
+
+// the argument checks rtx_render_view and its _device twin share (`rgb`, `shade`, `hits`: the three outputs)
+bool view_args_ok(const RtxScene *scene, const RtxView *v, const void *rgb, const void *shade, const void *hits)
+{
+    if (!scene || !v || (!rgb && !shade && !hits)) return false;
+    if (v->width == 0u || v->height == 0u || static_cast<uint64_t>(v->width) * v->height >= (1ull << 31)) return false;
+    if (static_cast<uint64_t>(v->x0) + v->nx > v->width || static_cast<uint64_t>(v->y0) + v->ny > v->height) return false;
+    return static_cast<uint64_t>(v->nx) * v->ny * scene->prep.nb_ray <= rtxv::kMaxRays;     // (nx * ny < 2^31)
+}
+
+// caller has checked the view (view_args_ok); the rays are made tile by tile: no regrouping pass
+Batch view_batch(const RtxScene *scene, const RtxView *v, bool want_rgb, bool want_shade, bool want_hits)
+{
+    const uint32_t n_pixels = v->nx * v->ny, n_rays = n_pixels * scene->prep.nb_ray;
+    Batch b{n_pixels, n_rays, RTX_RAYS_KEEP_ORDER, {0u, 0u, 0u}, scene->prep.nb_light_sample, launch_viewed, v};
+    b.out_bytes[kViewShade] = want_shade ? static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade) : 0u;
+    b.out_bytes[kViewHits] = want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u;
+    b.out_bytes[kViewRgb] = want_rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
+    return b;
 }
 
 }  // namespace
@@ -862,14 +902,14 @@ int rtx_trace_rays(RtxScene *scene, int device, uint32_t n_rays, const float *or
                    uint32_t flags, RtxRayHit *out_hits, RtxStats *stats)
 {
     if (!query_args_ok(scene, origins, directions, out_hits, flags, n_rays)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, query_batch(false, n_rays, flags), origins, directions, out_hits, nullptr, stats);
+    return batch_host(scene, device, query_batch(false, n_rays, flags), origins, directions, {out_hits, nullptr, nullptr}, stats);
 }
 
 int rtx_occluded_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
                       uint32_t flags, uint8_t *out_occluded, RtxStats *stats)
 {
     if (!query_args_ok(scene, origins, targets, out_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, query_batch(true, n_rays, flags), origins, targets, out_occluded, nullptr, stats);
+    return batch_host(scene, device, query_batch(true, n_rays, flags), origins, targets, {out_occluded, nullptr, nullptr}, stats);
 }
 
 int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
@@ -877,21 +917,22 @@ int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const vo
 {
     if (!query_args_ok(scene, d_origins, d_directions, d_hits, flags, n_rays) || (reinterpret_cast<uintptr_t>(d_hits) & 15u))
         return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, query_batch(false, n_rays, flags), d_origins, d_directions, d_hits, nullptr, stream);
+    return batch_device(scene, device, query_batch(false, n_rays, flags), d_origins, d_directions, {d_hits, nullptr, nullptr}, stream);
 }
 
 int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
                              uint32_t flags, void *d_occluded, void *stream)
 {
     if (!query_args_ok(scene, d_origins, d_targets, d_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, query_batch(true, n_rays, flags), d_origins, d_targets, d_occluded, nullptr, stream);
+    return batch_device(scene, device, query_batch(true, n_rays, flags), d_origins, d_targets, {d_occluded, nullptr, nullptr}, stream);
 }
 
 int rtx_shade_rays(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
                    uint32_t flags, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
     if (!shade_args_ok(scene, origins, directions, out_shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, shade_batch(scene, n_pixels, flags, out_hits != nullptr), origins, directions, out_shade, out_hits, stats);
+    return batch_host(scene, device, shade_batch(scene, n_pixels, flags, out_hits != nullptr), origins, directions,
+                      {out_shade, out_hits, nullptr}, stats);
 }
 
 int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
@@ -899,7 +940,44 @@ int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const 
 {
     if (!shade_args_ok(scene, d_origins, d_directions, d_shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, shade_batch(scene, n_pixels, flags, d_hits != nullptr), d_origins, d_directions, d_shade, d_hits, stream);
+    return batch_device(scene, device, shade_batch(scene, n_pixels, flags, d_hits != nullptr), d_origins, d_directions,
+                        {d_shade, d_hits, nullptr}, stream);
+}
+
+int rtx_scene_view(const RtxScene *scene, RtxView *out)
+{
+    if (!scene || !out) return RTX_ERR_BAD_ARG;
+    const rtx::PreparedScene &p = scene->prep;
+    std::memset(out, 0, sizeof *out);
+    out->width = out->nx = p.width;
+    out->height = out->ny = p.height;
+    std::memcpy(out->eye, p.eye, 12);
+    std::memcpy(out->u, p.cam_u, 12);
+    std::memcpy(out->v, p.cam_v, 12);
+    std::memcpy(out->w, p.cam_w, 12);
+    out->distance = p.distance;
+    return RTX_OK;
+}
+
+int rtx_render_view(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxPixelShade *out_shade,
+                    RtxRayHit *out_hits, RtxStats *stats)
+{
+    if (!view_args_ok(scene, view, out_rgb, out_shade, out_hits)) return RTX_ERR_BAD_ARG;
+    void *out[kBatchOuts];
+    out[kViewShade] = out_shade; out[kViewHits] = out_hits; out[kViewRgb] = out_rgb;
+    return batch_host(scene, device, view_batch(scene, view, out_rgb != nullptr, out_shade != nullptr, out_hits != nullptr),
+                      nullptr, nullptr, out, stats);
+}
+
+int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, void *d_shade, void *d_hits,
+                           void *stream)
+{
+    if (!view_args_ok(scene, view, d_rgb, d_shade, d_hits)) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
+    void *d_out[kBatchOuts];
+    d_out[kViewShade] = d_shade; d_out[kViewHits] = d_hits; d_out[kViewRgb] = d_rgb;
+    return batch_device(scene, device, view_batch(scene, view, d_rgb != nullptr, d_shade != nullptr, d_hits != nullptr),
+                        nullptr, nullptr, d_out, stream);
 }
 
 int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint64_t *out,

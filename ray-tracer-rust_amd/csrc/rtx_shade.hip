@@ -9,11 +9,8 @@
 // sort rtx_query.hip uses, in the same buffers).  A result is written to the pixel's ORIGINAL number, so the order changes
 // how long a batch takes and nothing else.
 //
-// The walks are rtx_traverse.hpp's, chosen as the ray-query kernels choose them (rtx_query.hip): closest_hit for the
-// primary ray, any_hit with limit = distance to the light point for a shadow ray; a 64-lane walk holding a "hard"
-// direction goes through closest_hit_reference; a walk holding an origin beyond origin_bound uses the exact slab test.
-// That last vote is taken twice: on the caller's origins for the primary walk and on the HIT POINTS for the shadow walks
-// (a far origin's p_hit can round to just outside the bound although the scene lies inside it).
+// The per-ray body — the walks, both votes, the shadow loop, the ordered sum — is rtx_shade_pixel.hpp's shade_ray, shared
+// with rtx_view.hip.
 //
 // The kernels live in namespace rtxs: librtx.so's rtx:: kernels stay the render pipeline's six, its rtxq:: kernels the
 // ray queries' nine.
@@ -25,7 +22,7 @@
 #undef getenv
 
 #include "rtx_shade.h"
-#include "rtx_traverse.hpp"
+#include "rtx_shade_pixel.hpp"
 
 namespace rtxs {
 
@@ -34,32 +31,6 @@ using namespace rtx;
 namespace {
 
 constexpr uint32_t kWavesPerGroup = 4u;      // independent wavefronts: no barrier, no LDS
-constexpr uint32_t kNoHit = 0xFFFFFFFFu;     // RTX_NO_HIT
-
-// which stream a walk with a hard ray takes (reference_tiles_kernel's choice)
-__device__ __forceinline__ const NodeRec RTX_CONSTANT *reference_stream(const DeviceScene &S, uint32_t &n_stream, bool &have_ref)
-{
-    have_ref = S.n_ref_nodes != 0u;
-    n_stream = have_ref ? S.n_ref_nodes : S.n_nodes;
-    return (const NodeRec RTX_CONSTANT *)(have_ref ? S.ref_nodes : S.nodes);
-}
-
-// the multiply-based culling is proven for origins within origin_bound (rtx_query.hip: origins_in_range); one vote per walk
-__device__ __forceinline__ bool origins_in_range(bool active, float ox, float oy, float oz, float origin_bound)
-{
-    const bool inside = fabsf(ox) <= origin_bound && fabsf(oy) <= origin_bound && fabsf(oz) <= origin_bound;
-    return ballot(active && !inside) == 0ull;
-}
-
-// byte of a linear channel: number of thresholds (b >= 1) that are <= x  (color.rs:28-33); the render kernels' search
-__device__ __forceinline__ uint32_t quantise(const float *__restrict__ thr, float x)
-{
-    uint32_t b = 0;
-#pragma unroll
-    for (uint32_t step = 128; step; step >>= 1)
-        if (x >= thr[b + step]) b += step;
-    return b;
-}
 
 // spreads the low nine bits of x to every third bit
 __device__ __forceinline__ uint32_t spread3(uint32_t x)
@@ -122,13 +93,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) shade_kernel(DeviceScene 
     const bool active = base + lane < n_pixels;
     uint32_t pixel = base + lane;
     if (active && order) pixel = order[pixel];
-    const TriRec RTX_CONSTANT *tris = (const TriRec RTX_CONSTANT *)S.tris;
-    const NodeRec RTX_CONSTANT *nodes = (const NodeRec RTX_CONSTANT *)S.nodes;
-    const float RTX_CONSTANT *lights = (const float RTX_CONSTANT *)S.light_points;   // wave-uniform reads: scalar operands
-    WaveCounters wc;
-    unsigned long long primary_hits = 0, reference_walks = 0;
-    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;                                  // avg_col, main.rs:182
-    uint32_t n_hit = 0;
+    ShadeTally tally;
+    PixelSum sum;
     const float denom = (float)(S.nb_ray * S.nb_light);                              // main.rs:211
     for (uint32_t k = 0; k < S.nb_ray; ++k) {
         // the pixel's ray k, Ray::new(origin, direction) (ray.rs:15); lanes without a pixel carry a harmless regular one
@@ -139,92 +105,11 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) shade_kernel(DeviceScene 
             ox = a[0]; oy = a[1]; oz = a[2];
             vx = b[0]; vy = b[1]; vz = b[2];
         }
-        float hx = 0.0f, hy = 0.0f, hz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-        bool hit;
-        {
-            float len, dx, dy, dz;
-            (void)length_and_direction(vx, vy, vz, len, dx, dy, dz);
-            LaneRay r = make_ray(active, ox, oy, oz, dx, dy, dz);
-            const bool walked = origins_in_range(active, ox, oy, oz, origin_bound)
-                                    ? closest_hit<COUNT, true, SPHERES>(nodes, tris, S.shade, S.n_nodes, r, wc, S.n_global)
-                                    : closest_hit<COUNT, false, SPHERES>(nodes, tris, S.shade, S.n_nodes, r, wc, S.n_global);
-            if (!walked) {
-                uint32_t n_stream;
-                bool have_ref;
-                const NodeRec RTX_CONSTANT *stream = reference_stream(S, n_stream, have_ref);
-                closest_hit_reference<COUNT, SPHERES>(stream, tris, S.shade, n_stream, have_ref, active, ox, oy, oz, dx, dy, dz,
-                                                      r.best_t, r.best_idx, wc);
-                reference_walks += 1;
-            }
-            hit = active && r.best_idx != kNone;
-            uint4 w0 = make_uint4(kNoHit, 0u, 0u, 0u), w1 = make_uint4(0u, 0u, 0u, 0u);
-            if (hit) {
-                const float t = r.best_t;
-                hx = ox + t * dx; hy = oy + t * dy; hz = oz + t * dz;                // p_hit, bvh.rs:69
-                const ShadeRec sh = S.shade[r.best_idx];
-                hit_normal<SPHERES>(sh, hx, hy, hz, nx, ny, nz);                     // bvh.rs:72
-                cr = sh.rgb[0]; cg = sh.rgb[1]; cb = sh.rgb[2];
-                w0 = make_uint4(r.best_idx, __float_as_uint(t), __float_as_uint(hx), __float_as_uint(hy));
-                w1 = make_uint4(__float_as_uint(hz), __float_as_uint(nx), __float_as_uint(ny), __float_as_uint(nz));
-            }
-            if (out_hits && active) {
-                out_hits[2u * ray] = w0;
-                out_hits[2u * ray + 1u] = w1;
-            }
-        }
-        const unsigned long long hit_mask = ballot(hit);
-        if (hit_mask == 0ull) continue;                                              // main.rs:188: every lane's `None` arm
-        if (COUNT) primary_hits += __popcll(hit_mask);
-        if (hit && n_hit < 255u) ++n_hit;
-        const bool hits_in_range = origins_in_range(hit, hx, hy, hz, origin_bound);
-        for (uint32_t i = 0; i < S.nb_light; ++i) {                                  // main.rs:193
-            const float RTX_CONSTANT *lp = lights + 3u * (k * S.nb_light + i);       // main.rs:194-196 (hoisted to the host)
-            const float sx = lp[0] - hx, sy = lp[1] - hy, sz = lp[2] - hz;           // p - p_hit, main.rs:201
-            float dist, dx, dy, dz;
-            (void)length_and_direction(sx, sy, sz, dist, dx, dy, dz);                // main.rs:202, ray.rs:15
-            LaneRay r = make_ray(hit, hx, hy, hz, dx, dy, dz);
-            r.limit = dist;
-            bool occluded;
-            const bool walked = hits_in_range
-                                    ? any_hit<COUNT, true, SPHERES>(nodes, tris, S.shade, S.n_nodes, r, wc, S.n_global)
-                                    : any_hit<COUNT, false, SPHERES>(nodes, tris, S.shade, S.n_nodes, r, wc, S.n_global);
-            if (walked) {
-                occluded = r.best_idx != kNone;
-            } else {
-                uint32_t n_stream, idx;
-                bool have_ref;
-                float t;
-                const NodeRec RTX_CONSTANT *stream = reference_stream(S, n_stream, have_ref);
-                closest_hit_reference<COUNT, SPHERES>(stream, tris, S.shade, n_stream, have_ref, hit, hx, hy, hz, dx, dy, dz, t, idx, wc);
-                occluded = false;
-                if (idx != kNone) {
-                    const float qx = hx - (hx + t * dx), qy = hy - (hy + t * dy), qz = hz - (hz + t * dz);   // main.rs:220
-                    occluded = !(sqrtf(qx * qx + qy * qy + qz * qz) > dist);                                 // main.rs:221
-                }
-                reference_walks += 1;
-            }
-            const float lnd = fabsf(nx * dx + ny * dy + nz * dz);                    // main.rs:207
-            // an occluded sample adds (black * 1.0) / denom = +0.0 (main.rs:226): left out, as shade_tiles_kernel leaves it out
-            if (hit && !occluded) {
-                acc_r = acc_r + ((cr * lnd) / denom);                                // main.rs:211-215
-                acc_g = acc_g + ((cg * lnd) / denom);
-                acc_b = acc_b + ((cb * lnd) / denom);
-            }
-        }
+        shade_ray<COUNT, SPHERES>(S, active, k, ox, oy, oz, vx, vy, vz, origins_in_range(active, ox, oy, oz, origin_bound),
+                                  origin_bound, denom, out_hits, ray, sum, tally);
     }
-    if (active) {
-        const uint32_t bytes = quantise(S.gamma_thr, acc_r) | (quantise(S.gamma_thr, acc_g) << 8) |
-                               (quantise(S.gamma_thr, acc_b) << 16) | (n_hit << 24);
-        out_shade[pixel] = make_uint4(__float_as_uint(acc_r), __float_as_uint(acc_g), __float_as_uint(acc_b), bytes);
-    }
-    if (COUNT && lane == 0 && counters) {
-        if (primary_hits) atomicAdd(&counters[0], primary_hits);
-        atomicAdd(&counters[1], wc.box_tests);
-        atomicAdd(&counters[2], wc.tri_tests);
-        atomicAdd(&counters[3], wc.node_visits);
-        atomicAdd(&counters[4], wc.tri_visits);
-        if (reference_walks) atomicAdd(&counters[5], reference_walks);
-    }
+    if (active) out_shade[pixel] = pixel_word(sum, pixel_bytes(S, sum));
+    if (COUNT && lane == 0 && counters) flush_tally(counters, tally);
 }
 
 namespace {

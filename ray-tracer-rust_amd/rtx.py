@@ -108,6 +108,17 @@ PIXEL_SHADE_DTYPE = np.dtype([("linear", np.float32, 3), ("rgb8", np.uint8, 3), 
 assert PIXEL_SHADE_DTYPE.itemsize == C.sizeof(PixelShade) == 16
 
 
+class RtxView(C.Structure):
+    """RtxView: a pinhole view of an uploaded scene (frame, camera after Camera::new) and the rectangle of it to render."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32),
+                ("eye", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("w", C.c_float * 3),
+                ("distance", C.c_float),
+                ("x0", C.c_uint32), ("y0", C.c_uint32), ("nx", C.c_uint32), ("ny", C.c_uint32)]
+
+
+assert C.sizeof(RtxView) == 76 and C.alignment(RtxView) == 4
+
+
 # every symbol include/rtx.h declares (tests check the export list against the header)
 _SIGS = {
     "rtx_abi_version": (C.c_int, []),
@@ -130,6 +141,10 @@ _SIGS = {
                                  C.POINTER(RayHit), C.POINTER(Stats)]),
     "rtx_shade_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "rtx_scene_view": (C.c_int, [C.c_void_p, C.POINTER(RtxView)]),
+    "rtx_render_view": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.c_void_p, C.POINTER(PixelShade), C.POINTER(RayHit),
+                                  C.POINTER(Stats)]),
+    "rtx_render_view_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -550,6 +565,46 @@ class Scene:
                                           self._ray_flags(keep_order, force_regroup), C.c_void_p(d_shade_ptr),
                                           C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
                                           C.c_void_p(stream) if stream else None), "rtx_shade_rays_device")
+
+    # -- any pinhole view of the uploaded scene (GPU only)
+    @staticmethod
+    def view(width, height, eye, look_at, up=DEFAULT_UP, distance=DEFAULT_DISTANCE, rect=None):
+        """An RtxView: a width x height frame seen through Camera::new(eye, look_at, up) at `distance` (camera_new);
+        rect = (x0, y0, nx, ny) picks the pixels to render, default the whole frame."""
+        u, v, w = camera_new(eye, look_at, up)
+        x0, y0, nx, ny = (0, 0, width, height) if rect is None else rect
+        out = RtxView(width=int(width), height=int(height), distance=float(distance), x0=int(x0), y0=int(y0), nx=int(nx), ny=int(ny))
+        out.eye[:], out.u[:], out.v[:], out.w[:] = _f3(eye).tolist(), u.tolist(), v.tolist(), w.tolist()
+        return out
+
+    def own_view(self):
+        """The scene's own camera and whole frame as an RtxView (rtx_scene_view)."""
+        out = RtxView()
+        _check(_lib.rtx_scene_view(self._h, C.byref(out)), "rtx_scene_view")
+        return out
+
+    def render_view(self, view, device=0, stats=False, want_shade=False, want_hits=False):
+        """render_pixel for every pixel of the view's rectangle -> uint8 [ny, nx, 3]; want_shade adds the pixels' records
+        (PIXEL_SHADE_DTYPE [ny, nx]: what shade_rays returns for the view's rays), want_hits the rays' closest hits
+        (RAY_HIT_DTYPE [ny, nx, nb_ray]: trace_rays'), stats the statistics, last."""
+        out = np.zeros((view.ny, view.nx, 3), np.uint8)
+        shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
+        hits = np.zeros((view.ny, view.nx, self.nb_ray), RAY_HIT_DTYPE) if want_hits else None
+        st = Stats()
+        _check(_lib.rtx_render_view(self._h, device, C.byref(view), out.ctypes.data,
+                                    shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
+                                    hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None,
+                                    C.byref(st) if stats else None), "rtx_render_view")
+        res = (out,) + ((shade,) if want_shade else ()) + ((hits,) if want_hits else ()) + ((st.asdict(),) if stats else ())
+        return res if len(res) > 1 else out
+
+    def render_view_device(self, device, view, d_rgb_ptr=None, d_shade_ptr=None, d_hits_ptr=None, stream=None):
+        """Asynchronous view launch into device buffers the caller owns, each optional: ny*nx*3 bytes, ny*nx x 16 bytes,
+        ny*nx*nb_ray x 32 bytes."""
+        _check(_lib.rtx_render_view_device(self._h, device, C.byref(view), C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
+                                           C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
+                                           C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
+                                           C.c_void_p(stream) if stream else None), "rtx_render_view_device")
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
