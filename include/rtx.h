@@ -347,6 +347,12 @@ int rtx_last_hip_error(void);
 /* ---- prepared-scene read-back (host logic tests, no device needed) --------- */
 /* out: n_light_points x 3 floats — Light::get_sample(T[(r*nb_ray+i) % n]) (src/main.rs:194-196) */
 int rtx_scene_light_points(const RtxScene *scene, float *out);
+/* out: n_light_points words — the order in which the shading pass WALKS the light samples of primary ray r: the samples
+   are cut into batches of min(nb_light_sample, 128) consecutive ones, and word r*nb_light_sample + k is the sample index
+   (0 <= index < nb_light_sample) at walk position k.  Every batch is a permutation of its own indices that starts with
+   its first sample: a short tour of the light (nearest neighbour, then 2-opt).  The order of a pixel's additions is the
+   reference's, by ascending sample index, whatever this order is. */
+int rtx_scene_light_order(const RtxScene *scene, uint32_t *out);
 /* out: 256 floats; byte value of a linear channel x = number of thresholds b>=1 with thr[b] <= x */
 int rtx_scene_gamma_thresholds(const RtxScene *scene, float *out256);
 /* out: (n_tris + n_spheres) x 3 in Vec order: unit normal of a triangle (Triangle::new, triangle.rs:29),

@@ -133,7 +133,7 @@ public:
     Event ring[RTX_TIMING_RING][3];      // launch start / end of the scheduling pass / launch end (rtx_launch_timings)
     Event q_sorted;                      // recorded behind a device-resident call that used q_sort on the CALLER's stream: a host
                                          // call, which uses the same buffers on the library's stream, waits for it first
-    DeviceBuffer nodes, primary_nodes, ref_nodes, tris, shade, samples, lights, thr, planes, light_boxes;
+    DeviceBuffer nodes, primary_nodes, ref_nodes, tris, shade, samples, lights, light_tour, thr, planes, light_boxes;
     DeviceBuffer d_out, d_counters;
     DeviceBuffer d_redo;                 // queue of tiles for reference_tiles_kernel
     PinnedBuffer h_stage;
@@ -249,6 +249,18 @@ int upload_all(RtxScene *scene, DeviceState &st)
     if ((rc = upload_vec(st.shade, p.shade)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.samples, p.samples)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.lights, p.light_points)) != RTX_OK) return rc;
+#if RTX_LIGHT_TOUR == 0
+    // A/B builds only: the records of the walk in index order (position k = sample k of its batch)
+    std::vector<float> tour(p.light_tour.size());
+    for (size_t k = 0; k < tour.size() / 4; ++k) {
+        const uint32_t in_batch = static_cast<uint32_t>((k % (p.nb_light_sample ? p.nb_light_sample : 1u)) % rtx::kMaxLightBatch);
+        std::memcpy(&tour[4 * k], &p.light_points[3 * k], 12);
+        std::memcpy(&tour[4 * k + 3], &in_batch, 4);
+    }
+    if ((rc = upload_vec(st.light_tour, tour)) != RTX_OK) return rc;
+#else
+    if ((rc = upload_vec(st.light_tour, p.light_tour)) != RTX_OK) return rc;
+#endif
     if (!p.global_planes.empty() && (rc = upload_vec(st.planes, p.global_planes)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.light_boxes, p.light_boxes)) != RTX_OK) return rc;
     if ((rc = st.thr.reserve(sizeof(p.gamma_thr))) != RTX_OK) return rc;
@@ -303,7 +315,7 @@ rtx::DeviceScene device_scene(const RtxScene *scene, const DeviceState &st)
     rtx::DeviceScene S;
     S.nodes = st.nodes.as<const rtx::NodeRec>();
     S.primary_nodes = st.primary_nodes.capacity() ? st.primary_nodes.as<const rtx::NodeRec>() : S.nodes;
-    S.wide = nullptr;
+    S.light_tour = st.light_tour.as<const float>();
     S.n_wide = 0u;
     S.ref_nodes = st.ref_nodes.as<const rtx::NodeRec>();
     S.n_ref_nodes = static_cast<uint32_t>(p.ref_nodes.size());
@@ -1054,6 +1066,13 @@ int rtx_scene_light_points(const RtxScene *scene, float *out)
 {
     if (!scene || !out) return RTX_ERR_BAD_ARG;
     std::memcpy(out, scene->prep.light_points.data(), scene->prep.light_points.size() * sizeof(float));
+    return RTX_OK;
+}
+
+int rtx_scene_light_order(const RtxScene *scene, uint32_t *out)
+{
+    if (!scene || !out) return RTX_ERR_BAD_ARG;
+    std::memcpy(out, scene->prep.light_order.data(), scene->prep.light_order.size() * sizeof(uint32_t));
     return RTX_OK;
 }
 

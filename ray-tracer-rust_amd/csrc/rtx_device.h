@@ -16,9 +16,11 @@ struct DeviceScene {
     //  test then needs no widening of its own, rtx_traverse.hpp: box_mask)
     const NodeRec  *nodes;         // (n_nodes + 1) x 32 B, pre-order with skip links; last = zeroed sentinel
     const NodeRec  *primary_nodes; // the same tree, the same size, nearest-to-the-eye child first: the primary rays' stream (= nodes when there is none)
-    const void     *wide;          // unused (NULL), as is n_wide below: the four-child tree's slots.  They stay because the
-                                   // kernels' register allocation depends on the argument layout (without them the SGPR
-                                   // spill counts of probe_kernel and shade_tiles_kernel move by up to 12 either way)
+    const float    *light_tour;    // nb_ray x nb_light x 4: the light points in the order shade_tiles_kernel walks them
+                                   // (PreparedScene::light_tour: x, y, z, the sample's index within its batch as bits).
+                                   // In the slot the four-child tree's pointer had, whose count n_wide below stays unused:
+                                   // the kernels' register allocation depends on the argument layout (without the two the
+                                   // SGPR spill counts of probe_kernel and shade_tiles_kernel move by up to 12 either way)
     const NodeRec  *ref_nodes;     // (n_ref_nodes + 1) x 32 B: the reference's own tree, or NULL
     const TriRec   *tris;          // n_tris x 64 B, leaf order
     const ShadeRec *shade;         // n_tris x 32 B, caller order
@@ -123,11 +125,19 @@ constexpr uint32_t kStreamCtrWords = 4u;   // counters of the streamed (ablation
 // 5 tiles re-rendered by reference_tiles_kernel, 6 / 7 the part of 3 / 4 spent in probe_kernel (primary rays)
 constexpr int kNumCounters = 8;
 
-// Light samples per LDS batch (results of one batch: 64 pixels x batch floats).
-#ifndef RTX_LIGHT_BATCH
-#define RTX_LIGHT_BATCH 128
+// Light samples per LDS batch (results of one batch: 64 pixels x batch floats): RTX_LIGHT_BATCH, scene_prep.h — the
+// host orders each batch's walk.
+// In which order shade_tiles_kernel walks a batch's light samples, and which wavefront walks which (results land in the
+// sample's own column whatever the order, and the ordered accumulation reads the columns by ascending index):
+//   0  index order — the order of the sample table, two consecutive points a third of the light's side apart;
+//   1  along PreparedScene::light_tour, chunks dealt and drawn as before: the eight wavefronts of a workgroup walk
+//      neighbouring light points at the same time;
+//   2  along the tour, every wavefront of a walking tile of the cut form with a contiguous run of it, taken in order:
+//      a wavefront's consecutive walks are one tour step apart (the ring's premise, rtx_traverse.hpp: walk_cut_stream).
+#ifndef RTX_LIGHT_TOUR
+#define RTX_LIGHT_TOUR 1
 #endif
-constexpr uint32_t kMaxLightBatch = RTX_LIGHT_BATCH;
+static_assert(RTX_LIGHT_TOUR >= 0 && RTX_LIGHT_TOUR <= 2, "RTX_LIGHT_TOUR: 0, 1 or 2");
 
 // Kernel variants, kept selectable (RTX_VARIANT) so that profiles can show what each choice is worth:
 // bit 0 = conservative multiply-based box test for inner nodes (else the exact division-based one);

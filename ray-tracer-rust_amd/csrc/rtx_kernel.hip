@@ -118,11 +118,14 @@ __device__ __forceinline__ void primary_ray(const DeviceScene &S, bool in_frame,
     (void)length_and_direction(rx, ry, rz, rn, dx, dy, dz);                          // ray.rs:15: sqrt, three divisions (bit for bit)
 }
 
-// One shadow ray of phase 2: ray number -> (compacted hit pixel, light sample), origin = the pixel's hit
-// point, direction = towards the light point (main.rs:194-202).
+// One shadow ray of phase 2: ray number -> (compacted hit pixel, walk position of the batch), origin = the pixel's hit
+// point, direction = towards the light point at that position (main.rs:194-202).  l_light holds the batch's records of
+// DeviceScene::light_tour, four words per position: the point, and the index within the batch of the sample it is — the
+// column of l_res its result belongs to, which arrives with the point's own read.
+constexpr uint32_t kLightStride = 4u;
 struct ShadowRay {
     LaneRay ray;
-    uint32_t hp, si;
+    uint32_t hp, si;     // si: the SAMPLE (the result's column), not the position
     bool valid;          // the lane carries a ray (ray.active is consumed by the any-hit walk)
     bool not_hard;       // wave-uniform: no lane's direction is "hard" (length_and_direction took its short way)
 };
@@ -133,11 +136,12 @@ __device__ __forceinline__ ShadowRay shadow_ray_at(const float *__restrict__ l_h
 {
     ShadowRay s;
     s.hp = sample_major ? rem : quo;     // compacted hit pixel
-    s.si = sample_major ? quo : rem;     // light sample within the batch
+    const uint32_t pos = sample_major ? quo : rem;     // walk position within the batch
     const float *h = l_hit + __umul24(kHitStride, s.hp);
-    const float *lp = l_light + __umul24(3u, s.si);
+    const float4 lp = *reinterpret_cast<const float4 *>(l_light + __umul24(kLightStride, pos));
+    s.si = __float_as_uint(lp.w);
     const float hx = h[0], hy = h[1], hz = h[2];
-    const float vx = lp[0] - hx, vy = lp[1] - hy, vz = lp[2] - hz;                   // p - orig
+    const float vx = lp.x - hx, vy = lp.y - hy, vz = lp.z - hz;                      // p - orig
     float dist_light, sx, sy, sz;
     s.not_hard = length_and_direction(vx, vy, vz, dist_light, sx, sy, sz);            // main.rs:202; Ray::new, main.rs:201 -> ray.rs:15
     s.ray = make_ray_bare(valid, hx, hy, hz, sx, sy, sz);     // the caller adds the culling constants when the ray walks
@@ -229,12 +233,15 @@ __device__ __forceinline__ void flush_counters(unsigned long long *__restrict__ 
 
 }  // namespace
 
-// LDS image of a workgroup (floats): light points of the current batch [3*batch], hit records
+// LDS image of a workgroup (floats): light records of the current batch [4*batch], hit records
 // [64][8] = {p_hit.xyz, normal.xyz, -, -}, sample results [64][res_stride], {hit count, redo flag}.
+// control words of a workgroup: [0] chunks drawn, [1] redo flag, [2] grey tile, [3] job, [4 + w] RTX_LIGHT_TOUR=2: the next
+// chunk of wavefront w's run of the tour (at most 16 wavefronts)
+constexpr uint32_t kCtlWords = 20u;
 __host__ __device__ inline uint32_t lds_res_stride(uint32_t batch) { return batch | 1u; }   // odd: conflict-free column reads
 __host__ __device__ inline uint32_t lds_floats(uint32_t batch)
 {
-    return 3u * batch + 64u * kHitStride + 64u * lds_res_stride(batch) + 64u * 4u + 4u + kCutWords * kMaxCut + 256u;
+    return kLightStride * batch + 64u * kHitStride + 64u * lds_res_stride(batch) + 64u * 4u + kCtlWords + kCutWords * kMaxCut + 256u;
 }
 
 
@@ -955,12 +962,12 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
 {
     extern __shared__ __align__(16) float lds[];
     float *const l_light = lds;
-    float *const l_hit = l_light + 3u * batch;
+    float *const l_hit = l_light + kLightStride * batch;
     float *const l_res = l_hit + 64u * kHitStride;
     const uint32_t res_stride = lds_res_stride(batch);
     float *const l_pix = l_res + 64u * res_stride;                                    // per pixel: running sums r,g,b + hit slot
     uint32_t *const l_ctl = reinterpret_cast<uint32_t *>(l_pix + 64u * 4u);           // [1] redo flag, [3] tile
-    uint32_t *const l_cut = l_ctl + 4u;                                                // the tile's cut: CutEntry records
+    uint32_t *const l_cut = l_ctl + kCtlWords;                                                // the tile's cut: CutEntry records
     float *const l_thr = reinterpret_cast<float *>(l_cut + kCutWords * kMaxCut);        // the 256 gamma thresholds (eight dependent
     for (uint32_t k = threadIdx.x; k < 256u; k += 64u * NW) l_thr[k] = S.gamma_thr[k];   // reads per channel per pixel: LDS, not L1)
 #if RTX_ABLATION
@@ -1008,7 +1015,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
     // holds them all they are staged once, not once per job (a global round trip of 2.4 us in front of every job's rays)
     const bool lights_once = S.nb_light <= batch;
     if (lights_once)
-        for (uint32_t k = threadIdx.x; k < 3u * S.nb_light; k += 64u * NW) l_light[k] = S.light_points[3u * (r * S.nb_light) + k];
+        for (uint32_t k = threadIdx.x; k < kLightStride * S.nb_light; k += 64u * NW) l_light[k] = S.light_tour[kLightStride * (r * S.nb_light) + k];
     for (;;) {
         if (threadIdx.x == 0) {
             if (!have_ahead) {   // the first job, and after jobs without a last phase
@@ -1132,10 +1139,20 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                 for (uint32_t b0 = 0; b0 < S.nb_light; b0 += batch) {                 // main.rs:193, in batches that fit LDS
                     const uint32_t bc = (S.nb_light - b0 < batch) ? S.nb_light - b0 : batch;
                     if (!lights_once) {
-                        for (uint32_t k = threadIdx.x; k < 3u * bc; k += 64u * NW)
-                            l_light[k] = S.light_points[3u * (r * S.nb_light + b0) + k]; // main.rs:194-196 (hoisted to the host)
+                        for (uint32_t k = threadIdx.x; k < kLightStride * bc; k += 64u * NW)
+                            l_light[k] = S.light_tour[kLightStride * (r * S.nb_light + b0) + k]; // main.rs:194-196 (hoisted to the host)
                     }
                     if ((WHOLE || RTX_CUT_DRAW_MIN != 0) && threadIdx.x == 0) l_ctl[0] = 0u;   // chunks drawn so far (behind the first NW)
+                    // RTX_LIGHT_TOUR=2, a tile of the cut form that walks: wavefront w owns chunks [w n / NW, (w + 1) n / NW) of
+                    // the batch's n — a contiguous run of the tour (sample-major) — and takes them in order, so that its
+                    // walk begins where the walk towards the NEIGHBOURING light point ended (first_entry); a wavefront whose
+                    // run is used up takes chunks from the front of the next run that has some.  (The counted form keeps to
+                    // its own run: which records a chunk walks depends on the wavefront's previous chunk, and RtxStats of a
+                    // frame must not depend on timing.)
+                    const bool tour_runs = RTX_LIGHT_TOUR == 2 && !WHOLE && n_cut != 0u;
+                    const uint32_t n_chunks = (n_hit * bc + 63u) >> 6;
+                    static_assert(NW + 4 <= (int)kCtlWords, "one run counter per wavefront");
+                    if (RTX_LIGHT_TOUR == 2 && !WHOLE && threadIdx.x < (uint32_t)NW) l_ctl[4u + threadIdx.x] = (threadIdx.x * n_chunks) / (uint32_t)NW;
                     __syncthreads();   // (also publishes the grey flag)
                     // A tile with an empty cut is through its rays in 10 us: the next job's position in the list is requested
                     // now, by the work-item that claims the jobs, and turned into a job id when the ordered sums start —
@@ -1190,9 +1207,9 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                         float dd_ = uniform(denom_d.d), dy_ = uniform(denom_d.y);   // (formed by vector instructions: same in every lane)
                         asm volatile("" : "+s"(pn0), "+s"(pn1), "+s"(pn2), "+s"(pkd), "+s"(dd_), "+s"(dy_));
                         for (; c_first < total; c_first += 64u * NW) {
-                            const uint32_t sample = c_first >> 6;
-                            const float *lp = l_light + 3u * sample;
-                            const float vx = lp[0] - my_hit[0], vy = lp[1] - my_hit[1], vz = lp[2] - my_hit[2];   // p - orig
+                            const float4 lp = *reinterpret_cast<const float4 *>(l_light + kLightStride * (c_first >> 6));   // chunk = walk position
+                            const uint32_t sample = __float_as_uint(lp.w);
+                            const float vx = lp.x - my_hit[0], vy = lp.y - my_hit[1], vz = lp.z - my_hit[2];   // p - orig
                             float dist_light, sx, sy, sz;
                             if (!length_and_direction(vx, vy, vz, dist_light, sx, sy, sz)) break;    // main.rs:201-202
                             // (the certificate's "magnitude" half: these origins lie on the ground, "moving away" certifies
@@ -1219,7 +1236,19 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                     //  drew it, and box_tests / tri_tests / the visit counts of one frame differed from launch to launch by
                     //  0.1 %, the bytes never.  Dealt chunks make RtxStats reproducible; the counted form is not timed.)
                     const bool kDrawChunks = WHOLE || (!COUNT && RTX_CUT_DRAW_MIN != 0 && n_cut >= RTX_CUT_DRAW_MIN);
-                    for (uint32_t c0 = c_first; c0 < total; ) {
+                    uint32_t run = wave;              // the run this wavefront takes its chunks from
+                    auto next_of_runs = [&]() -> uint32_t {   // first ray of the chunk, or `total` when nothing is left for this wavefront
+                        for (uint32_t tried = 0; tried < (uint32_t)NW; ++tried) {
+                            uint32_t c = 0u;
+                            if (lane == 0) c = atomicAdd(&l_ctl[4u + run], 1u);
+                            c = __builtin_amdgcn_readfirstlane(c);
+                            if (c < ((run + 1u) * n_chunks) / (uint32_t)NW) return c * 64u;
+                            if (COUNT) break;
+                            run = run + 1u == (uint32_t)NW ? 0u : run + 1u;
+                        }
+                        return total;
+                    };
+                    for (uint32_t c0 = tour_runs ? next_of_runs() : c_first; c0 < total; ) {
                         const bool valid = c0 + lane < total;
                         const uint32_t quo = (uint32_t)(((float)(c0 + lane) + 0.5f) * inv_div);
                         const uint32_t rem = (c0 + lane) - __umul24(quo, div);
@@ -1258,7 +1287,9 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                         if (!ok && lane == 0) l_ctl[1] = 1u;
                         if (grey_tile) shadow_result_grey<!WHOLE>(l_hit, l_res, res_stride, sr, denom_d);   // (whole-stream form: no registers to spare, +0.7 %)
                         else shadow_result(l_hit, l_res, res_stride, sr);
-                        if (kDrawChunks) {
+                        if (tour_runs) {
+                            c0 = next_of_runs();
+                        } else if (kDrawChunks) {
                             uint32_t drawn = 0u;
                             if (lane == 0) drawn = atomicAdd(&l_ctl[0], 1u);
                             c0 = (NW + __builtin_amdgcn_readfirstlane(drawn)) * 64u;
@@ -1561,7 +1592,7 @@ hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t 
 #define RTX_SW_STR(x) RTX_SW_STR2(x)
 #define RTX_SW(x) " " #x "=" RTX_SW_STR(x)
 extern "C" __attribute__((used, visibility("hidden"))) const char rtx_build_switches_text[] = "rtx-build-switches:"
-    RTX_SW(RTX_CLAIM_RUN_LOG) RTX_SW(RTX_CUT_DRAW_MIN) RTX_SW(RTX_CUT_UNION_MIN) RTX_SW(RTX_LIGHT_BATCH) RTX_SW(RTX_MAX_CUT)
+    RTX_SW(RTX_CLAIM_RUN_LOG) RTX_SW(RTX_CUT_DRAW_MIN) RTX_SW(RTX_CUT_UNION_MIN) RTX_SW(RTX_LIGHT_BATCH) RTX_SW(RTX_LIGHT_TOUR) RTX_SW(RTX_MAX_CUT)
     RTX_SW(RTX_PACKED_WAVES_PER_SIMD) RTX_SW(RTX_PROBE_VISIT_SCALE) RTX_SW(RTX_PROBE_WAVES_PER_SIMD)
     RTX_SW(RTX_SHADE_CUT_WAVES_PER_SIMD) RTX_SW(RTX_SHADE_NW) RTX_SW(RTX_SHADE_WAVES_PER_SIMD)
     RTX_SW(RTX_SPLIT_SCALE_MIN) RTX_SW(RTX_SPLIT_SHARE_PERCENT) RTX_SW(RTX_TILE_PARTS_MAX) RTX_SW(RTX_WAVES_PER_SIMD)

@@ -483,6 +483,58 @@ private:
 
 }  // namespace
 
+void light_tour_order(const float *points, uint32_t n, uint32_t *order)
+{
+    if (n == 0u) return;
+    std::vector<double> dist(static_cast<size_t>(n) * n);
+    for (uint32_t a = 0; a < n; ++a)
+        for (uint32_t b = 0; b < n; ++b) {
+            double q = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                const double e = static_cast<double>(points[3 * a + k]) - static_cast<double>(points[3 * b + k]);
+                q += e * e;
+            }
+            dist[static_cast<size_t>(a) * n + b] = std::sqrt(q);
+        }
+    auto D = [&](uint32_t a, uint32_t b) { return dist[static_cast<size_t>(a) * n + b]; };
+    // nearest neighbour from point 0; `d < best` only: a NaN or infinite distance never wins, and a step that nothing
+    // wins goes to the lowest index left
+    std::vector<char> used(n, 0);
+    order[0] = 0u;
+    used[0] = 1;
+    for (uint32_t k = 1; k < n; ++k) {
+        const uint32_t at = order[k - 1u];
+        uint32_t next = n;
+        double best = std::numeric_limits<double>::infinity();
+        for (uint32_t j = 0; j < n; ++j) {
+            if (used[j]) continue;
+            if (next == n) next = j;
+            const double d = D(at, j);
+            if (d < best) { best = d; next = j; }
+        }
+        order[k] = next;
+        used[next] = 1;
+    }
+    // 2-opt on the open path: reversing positions [i, j] replaces the edges (i-1, i) and (j, j+1) by (i-1, j) and
+    // (i, j+1) (the last one only when j is not the path's end); position 0 never moves
+    for (uint32_t pass = 0; pass < 32u; ++pass) {
+        bool improved = false;
+        for (uint32_t i = 1; i + 1u < n; ++i)
+            for (uint32_t j = i + 1u; j < n; ++j) {
+                double before = D(order[i - 1u], order[i]), after = D(order[i - 1u], order[j]);
+                if (j + 1u < n) {
+                    before += D(order[j], order[j + 1u]);
+                    after += D(order[i], order[j + 1u]);
+                }
+                if (after < before) {
+                    std::reverse(order + i, order + j + 1u);
+                    improved = true;
+                }
+            }
+        if (!improved) break;
+    }
+}
+
 int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
 {
     const uint64_t n_prims64 = static_cast<uint64_t>(d.n_tris) + d.n_spheres;
@@ -522,6 +574,22 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
                 const size_t k = (static_cast<size_t>(r) * d.nb_ray + i) % d.n_samples;
                 light_sample(d.light_v0, d.light_v1, d.light_v2, d.samples[2 * k], d.samples[2 * k + 1],
                              &s.light_points[3 * (static_cast<size_t>(r) * d.nb_light_sample + i)]);
+            }
+
+        // the order of walking them (scene_prep.h: light_tour): per primary ray, per batch of the shading pass
+        s.light_tour.resize(4 * static_cast<size_t>(d.nb_ray) * d.nb_light_sample);
+        s.light_order.resize(static_cast<size_t>(d.nb_ray) * d.nb_light_sample);
+        for (uint32_t r = 0; r < d.nb_ray; ++r)
+            for (uint32_t b0 = 0; b0 < d.nb_light_sample; b0 += kMaxLightBatch) {
+                const uint32_t bc = std::min(d.nb_light_sample - b0, kMaxLightBatch);
+                const size_t first = static_cast<size_t>(r) * d.nb_light_sample + b0;
+                uint32_t order[kMaxLightBatch];
+                light_tour_order(&s.light_points[3 * first], bc, order);
+                for (uint32_t k = 0; k < bc; ++k) {
+                    std::memcpy(&s.light_tour[4 * (first + k)], &s.light_points[3 * (first + order[k])], 12);
+                    std::memcpy(&s.light_tour[4 * (first + k) + 3], &order[k], 4);
+                    s.light_order[first + k] = b0 + order[k];
+                }
             }
 
         // bounding box of the light points of primary ray r: one end of a tile's shaft (rtx_kernel.hip: shaft_cut)

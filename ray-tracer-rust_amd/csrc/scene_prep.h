@@ -95,6 +95,13 @@ struct PreparedScene {
     std::vector<ShadeRec> shade;       // in caller order
     std::vector<float>    samples;     // n_samples x 2
     std::vector<float>    light_points;// nb_ray x nb_light_sample x 3
+    // The same points in the order the shading pass WALKS them: per primary ray and per batch of kMaxLightBatch
+    // consecutive samples a short tour that starts at the batch's first sample (light_tour_order).  One 16-byte record
+    // per walk position, at the position's place in its batch: x, y, z and — as bits, not a value — the sample's index
+    // WITHIN the batch, the column its result belongs to.  light_order: the same order as sample indices
+    // (r, batch after batch: the index within nb_light_sample at each walk position).
+    std::vector<float>    light_tour;  // nb_ray x nb_light_sample x 4
+    std::vector<uint32_t> light_order; // nb_ray x nb_light_sample
     float gamma_thr[256];
     uint32_t n_leaves = 0, max_leaf_tris = 0, depth = 0;
     // Outward shift of the culling planes on the device, 2^-19 x the largest coordinate magnitude of the scene and the
@@ -113,6 +120,17 @@ struct PreparedScene {
 constexpr uint32_t kMaxGlobalPrims = 8u;
 // the walk addresses primitive records by 32-bit byte offsets, 64 B each
 constexpr uint64_t kMaxPrimitives = 1ull << 26;
+
+// Light samples per LDS batch of the shading pass (results of one batch: 64 pixels x batch floats).
+#ifndef RTX_LIGHT_BATCH
+#define RTX_LIGHT_BATCH 128
+#endif
+constexpr uint32_t kMaxLightBatch = RTX_LIGHT_BATCH;
+
+// Order of walking n points (xyz, f32): order[0] = 0, then nearest neighbour (Euclidean, in double, ties to the lower
+// index), then 2-opt reversals that keep position 0, a bounded number of passes.  Always a permutation of 0 .. n-1: a
+// distance that is NaN or infinite never wins a comparison.  Deterministic.
+void light_tour_order(const float *points, uint32_t n, uint32_t *order);
 
 // Returns RTX_OK or a negative RtxError.
 int prepare_scene(const RtxSceneDesc &desc, PreparedScene &out);

@@ -151,6 +151,7 @@ _SIGS = {
     "rtx_strerror": (C.c_char_p, [C.c_int]),
     "rtx_last_hip_error": (C.c_int, []),
     "rtx_scene_light_points": (C.c_int, [C.c_void_p, f32p]),
+    "rtx_scene_light_order": (C.c_int, [C.c_void_p, u32p]),
     "rtx_scene_gamma_thresholds": (C.c_int, [C.c_void_p, f32p]),
     "rtx_scene_normals": (C.c_int, [C.c_void_p, f32p]),
     "rtx_scene_nodes": (C.c_int, [C.c_void_p, u32p, u32p]),
@@ -383,6 +384,13 @@ class Scene:
         n = self.info()["n_light_points"]
         out = np.zeros((n, 3), np.float32)
         _check(_lib.rtx_scene_light_points(self._h, _fp(out)), "rtx_scene_light_points")
+        return out
+
+    def light_order(self):
+        """-> (nb_ray, nb_light_sample) sample indices in the order the shading pass walks them, batch after batch"""
+        out = np.zeros(self.info()["n_light_points"], np.uint32)
+        if len(out):
+            _check(_lib.rtx_scene_light_order(self._h, out.ctypes.data_as(u32p)), "rtx_scene_light_order")
         return out
 
     def gamma_thresholds(self):
