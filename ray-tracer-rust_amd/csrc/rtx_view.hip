@@ -23,12 +23,6 @@ namespace rtxv {
 
 using namespace rtx;
 
-namespace {
-
-constexpr uint32_t kWavesPerGroup = 4u;      // independent wavefronts: no barrier, no LDS
-
-}  // namespace
-
 // out_rgb (may be NULL): three bytes per pixel; out_shade (may be NULL): one 16-byte word per pixel {avg_col.rgb as f32,
 // bytes r, g, b, hits}; out_hits (may be NULL): closest_kernel's two 16-byte words per ray.  Lanes outside the rectangle
 // carry a harmless regular ray and never vote.
@@ -40,15 +34,15 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) view_kernel(DeviceScene S
                                                                    unsigned long long *__restrict__ counters,
                                                                    float origin_bound, uint32_t eye_in_range)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerGroup + (threadIdx.x >> 6));
+    uint32_t lane;
+    const uint32_t tile = wave_of_launch(lane);
     if (tile >= n_tiles) return;                 // the whole wavefront
     const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const uint32_t lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);
     const bool active = lx < V.nx && ly < V.ny;
     const uint32_t px = V.x0 + lx, py = V.y0 + ly;                                   // the pixel in the view's frame
     const size_t slot = (size_t)ly * V.nx + lx;                                      // ... and in the outputs: < 2^28
-    ShadeTally tally;
+    WalkTally tally;
     PixelSum sum;
     const float denom = (float)(S.nb_ray * S.nb_light);                              // main.rs:211
     for (uint32_t k = 0; k < S.nb_ray; ++k) {
@@ -78,22 +72,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) view_kernel(DeviceScene S
         }
         if (out_shade) out_shade[slot] = pixel_word(sum, bytes);
     }
-    if (COUNT && lane == 0 && counters) flush_tally(counters, tally);
+    if (COUNT) flush_tally(counters, lane, tally);
 }
-
-namespace {
-
-template <bool COUNT, bool SPHERES>
-void launch_form(const DeviceScene &S, const ViewBlock &V, uint32_t tiles_x, uint32_t n_tiles, void *d_rgb, void *d_shade,
-                 void *d_hits, unsigned long long *counters, float origin_bound, bool eye_in_range, hipStream_t stream)
-{
-    const dim3 grid((n_tiles + kWavesPerGroup - 1u) / kWavesPerGroup), block(64u * kWavesPerGroup);
-    hipLaunchKernelGGL((view_kernel<COUNT, SPHERES>), grid, block, 0, stream, S, V, tiles_x, n_tiles, static_cast<uint8_t *>(d_rgb),
-                       static_cast<uint4 *>(d_shade), static_cast<uint4 *>(d_hits), counters, origin_bound,
-                       eye_in_range ? 1u : 0u);
-}
-
-}  // namespace
 
 hipError_t launch_view(const DeviceScene &S, const ViewBlock &V, float origin_bound, void *d_rgb, void *d_shade, void *d_hits,
                        unsigned long long *counters, hipStream_t stream)
@@ -104,17 +84,13 @@ hipError_t launch_view(const DeviceScene &S, const ViewBlock &V, float origin_bo
     const uint64_t tiles_x = (static_cast<uint64_t>(V.nx) + 7u) / 8u, tiles_y = (static_cast<uint64_t>(V.ny) + 7u) / 8u;
     const uint64_t n_tiles = tiles_x * tiles_y;      // <= (nx/8 + 1)(ny/8 + 1) <= 2^22 + 2^25 + 2
     if (n_tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    // origins_in_range (rtx_shade_pixel.hpp) for the one origin every lane has
+    // origins_in_range (rtx_ray_walk.hpp) for the one origin every lane has
     const bool eye_in_range = fabsf(V.eye[0]) <= origin_bound && fabsf(V.eye[1]) <= origin_bound && fabsf(V.eye[2]) <= origin_bound;
-    const bool spheres = S.n_spheres != 0u;
-    const uint32_t tx = static_cast<uint32_t>(tiles_x), nt = static_cast<uint32_t>(n_tiles);
-    if (counters) {
-        if (spheres) launch_form<true, true>(S, V, tx, nt, d_rgb, d_shade, d_hits, counters, origin_bound, eye_in_range, stream);
-        else launch_form<true, false>(S, V, tx, nt, d_rgb, d_shade, d_hits, counters, origin_bound, eye_in_range, stream);
-    } else {
-        if (spheres) launch_form<false, true>(S, V, tx, nt, d_rgb, d_shade, d_hits, counters, origin_bound, eye_in_range, stream);
-        else launch_form<false, false>(S, V, tx, nt, d_rgb, d_shade, d_hits, counters, origin_bound, eye_in_range, stream);
-    }
+    launch_form(counters != nullptr, S.n_spheres != 0u, static_cast<uint32_t>(n_tiles), [&](auto count, auto spheres, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((view_kernel<count.value, spheres.value>), grid, block, 0, stream, S, V, static_cast<uint32_t>(tiles_x),
+                           static_cast<uint32_t>(n_tiles), static_cast<uint8_t *>(d_rgb), static_cast<uint4 *>(d_shade),
+                           static_cast<uint4 *>(d_hits), counters, origin_bound, eye_in_range ? 1u : 0u);
+    });
     return hipGetLastError();
 }
 

@@ -117,6 +117,34 @@ def test_batch_sizes_with_two_rays_per_pixel(soup, n):
     shade_every_way(soup["scenes"][2], s, soup["nb_light"], "soup nb_ray=2 [:%d]" % n)
 
 
+def test_an_entry_is_keyed_by_its_ray_0(soup, orc, samples_seeded):
+    """128 pixels of two rays on the soup: ray 0 of every odd pixel is hard (-0.0 in y) and leaves the plane z = 0, in
+    front of the soup, along +z — away from it, a miss; every other ray is a regular ray of set A.  The key's bit 31
+    gathers hard entries and an entry's key comes from its ray 0 (rtxq::key_kernel, stride nb_ray), so the 64 odd pixels
+    share one wavefront after the regrouping pass: one reference walk, against two in the caller's order, where each of
+    the two wavefronts holds 32 of them.  A key read from flat ray i instead of ray i * nb_ray would call the pixels
+    2, 6, 10 ... hard — all regular — and leave the odd pixels in both wavefronts: two reference walks."""
+    a = soup["sets"]["a"]
+    so, sd, _, _ = qs.set_a(orc, samples_seeded)["trace"]
+    o, d = so[:256].copy(), sd[:256].copy()
+    odd_ray0 = np.arange(2, 256, 4)
+    o[odd_ray0, 2] = 0.0
+    d[odd_ray0] = (0.0, -0.0, 1.0)
+    assert a["hi"][2] < 0.0 and np.abs(o[odd_ray0]).max() <= a["bound"]         # outside the soup, inside the origin bound
+    s = ss.shade_set(orc, soup["sets"]["osc2"], o, d, 2, soup["nb_light"], a["kw"]["light_tri"], samples_seeded,
+                     soup["sets"]["tables"])
+    assert len(s["shade"]) == 128 and (s["hit"]["prim"][odd_ray0] == NO_HIT).all()
+    assert (s["hit"]["prim"][1::2] != NO_HIT).sum() >= 64                        # the other rays do meet the soup
+    scene = soup["scenes"][2]
+    walks = {}
+    for name, mode in (("keep_order", dict(keep_order=True)), ("force_regroup", dict(force_regroup=True))):
+        got, st = scene.shade_rays(o, d, stats=True, **mode)
+        print(name, "redo_tiles", st["redo_tiles"])
+        walks[name] = st["redo_tiles"]
+        assert got.tobytes() == s["shade"].tobytes(), name
+    assert walks == dict(keep_order=2, force_regroup=1), walks
+
+
 def test_a_batch_above_the_regrouping_threshold_with_default_flags(bunny):
     """the random set repeated and shuffled to 18,000 pixels (> 16,384): with flags = 0 the batch takes the regrouping pass"""
     base = bunny["sets"]["random"]

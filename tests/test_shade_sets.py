@@ -223,13 +223,28 @@ def test_no_device_means_error_not_fallback(rtx, scene):
 
 
 def test_shade_kernels_live_in_their_own_namespace():
-    """librtx.so carries rtxs::shade_kernel in every COUNT x SPHERES form and rtxs::key_kernel, and still imports no getenv
-    (a second translation unit brings the radix sort in)"""
+    """librtx.so carries rtxs::shade_kernel in exactly the four COUNT x SPHERES forms — the regrouping pass is the ray
+    queries' (rtxq::key_kernel and the one radix sort) — and imports no getenv"""
     lib = os.path.join(ROOT, "ray-tracer-rust_amd", "librtx.so")
     blob = open(lib, "rb").read()
     shade = set(m.decode() for m in re.findall(rb"_ZN4rtxs\d+([a-z0-9_]+_kernel(?:ILb[01]ELb[01]E)?)", blob)
                 if not m.startswith(b"__device_stub__"))
     forms = ["ILb%dELb%dE" % (c, s) for c in (0, 1) for s in (0, 1)]
-    assert shade == {"key_kernel"} | {"shade_kernel" + f for f in forms}, shade
+    assert shade == {"shade_kernel" + f for f in forms}, shade
     undefined = subprocess.run(["nm", "-D", "--undefined-only", lib], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in undefined
+
+
+def test_the_radix_sort_is_in_the_library_once():
+    """every rocprim kernel's descriptor name occurs in librtx.so as often as rtxq::key_kernel's own does: the code object
+    that holds the key kernel holds the sort, and no other does"""
+    blob = open(os.path.join(ROOT, "ray-tracer-rust_amd", "librtx.so"), "rb").read()
+    key = re.findall(rb"_ZN4rtxq10key_kernel\w*\.kd\0", blob)
+    assert len(set(key)) == 1 and len(key) >= 1, key
+    counts = {}
+    for name in re.findall(rb"_ZN7rocprim\w*\.kd\0", blob):
+        counts[name] = counts.get(name, 0) + 1
+    assert len(counts) >= 10, len(counts)                                # the sort is there at all
+    more = {n[:60]: c for n, c in counts.items() if c != len(key)}
+    assert not more, "%d of %d rocprim kernels occur another number of times than key_kernel's %d: %s" % (
+        len(more), len(counts), len(key), sorted(more.items())[:3])
