@@ -773,7 +773,8 @@ __global__ void __launch_bounds__(64 * kProbeWaves, RTX_PROBE_WAVES_PER_SIMD) pr
 }
 
 // Counting sort of the scheduled tiles by cost class, costliest first.  Workspace words (W.buckets):
-//   [0] number of jobs in the order   [kOrderHist + k] tiles of class k (count_classes_kernel)
+//   [0] number of jobs in the order   [kOrderRaisedEnd] how many of them, from the front, run raised (RTX_JOB_PRIORITY)
+//   [kOrderHist + k] tiles of class k (count_classes_kernel)
 //   [kOrderCursor + k] tiles of class k already placed   [kOrderList + i] the i-th job
 // One workgroup per 1024 tiles: a class's position range starts where the costlier classes end (prefix over the
 // histogram); inside it each workgroup reserves a block with one atomic per class it holds, and its tiles take
@@ -800,24 +801,42 @@ constexpr uint32_t kOrderHist = kCostBuckets, kOrderCursor = 2u * kCostBuckets, 
 #define RTX_CLAIM_RUN_LOG 10      // runs of 16 / 64 / 256 / 1024 / 4096 jobs: the 1M-triangle soup -1.7 / -2.3 / -3.5 / -4.3 / -3.7 %
 #endif
 constexpr uint32_t kOrderClaim = 8u, kClaimRunLog = RTX_CLAIM_RUN_LOG;
+// Which jobs' ray loops issue ahead of the others' on their SIMD (shade_tiles_kernel: s_setprio).  A persistent launch's
+// wavefronts are all of one age, so at one priority a wavefront of the pass's longest job and one of a 28 us job tie for
+// the issue port; the pass is as long as its costliest jobs, and what the cheap ones give up they get back a little later.
+//   0  none: every ray loop at priority 0 (the kernel of before round 5, instruction for instruction)
+//   1  by cost class: the jobs of the classes that cost at least kRaisedShare of order_tiles_kernel's limit (a
+//      workgroup's fair share of the launch) run their ray loops at kJobLevelRaised.  The order is costliest first, so
+//      these are the jobs in front of one position of it ([kOrderRaisedEnd]); the claimer compares its position.
+// (kRaisedShare 1/4: big_bunny 1080p -2.1 % on each of two boxes, the 1M-triangle soup -1.7 %, 4096x4096 equal, one share
+//  of an 8-way frame -1.5 % and equal; 1/2 and 1: inside the parent's range; 1/8: 1080p -3.2 %, 4096x4096 +0.16 % with
+//  its range above the parent's; "every workgroup's first job" instead: -1.0 %; profiles/r06/b_ab_*.log, c_ab_*.log)
+#ifndef RTX_JOB_PRIORITY
+#define RTX_JOB_PRIORITY 1
+#endif
+constexpr bool kJobLevels = RTX_JOB_PRIORITY != 0;
+[[maybe_unused]] constexpr float kRaisedShare = 0.25f;
+[[maybe_unused]] constexpr uint32_t kOrderRaisedEnd = 1u;      // (words 1 .. 7 of W.buckets are spare, and zeroed with the histogram)
+[[maybe_unused]] constexpr uint32_t kJobLevelRaised = 2u;
 __device__ __forceinline__ uint32_t claimed_index(uint32_t group, uint32_t k)
 {
     return ((((k >> kClaimRunLog) << 3) + group) << kClaimRunLog) + (k & ((1u << kClaimRunLog) - 1u));
 }
 // the work-item that claims the jobs: the next job of its XCD's group, or of the groups after it; kNone when all are used up
-__device__ __forceinline__ uint32_t claim_job(uint32_t *__restrict__ buckets, uint32_t n_jobs, uint32_t group0, uint32_t &groups_done)
+// (pos: where the caller wants the job's position in the order)
+__device__ __forceinline__ uint32_t claim_job(uint32_t *__restrict__ buckets, uint32_t n_jobs, uint32_t group0, uint32_t &groups_done,
+                                              uint32_t *pos = nullptr)
 {
     while (groups_done < 8u) {
         const uint32_t g = (group0 + groups_done) & 7u;
         const uint32_t idx = claimed_index(g, atomicAdd(&buckets[kOrderClaim + g], 1u));
+        if (pos) *pos = idx;
         if (idx < n_jobs) return buckets[kOrderList + idx];
         ++groups_done;
     }
     return kNone;
 }
-#ifndef RTX_SPLIT_SCALE_MIN
-#define RTX_SPLIT_SCALE_MIN 0.25f
-#endif
+constexpr float kSplitScaleMin = 0.25f;
 // (8 until the walks got the ring and the cut stream: a part is then mostly its fixed work, and four are enough — one
 //  share of an 8-way 1080p frame 0.246 -> 0.231 ms, of a 4-way / 2-way one and the whole frame equal; 16: +12 %, 2: +25 %;
 //  profiles/r03/xb_ab_parts_per_tile.log)
@@ -869,6 +888,9 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
 {
     __shared__ uint32_t count[kCostBuckets], start[kCostBuckets], parts_log[kCostBuckets], jobs[kCostBuckets];
     __shared__ float weight[kCostBuckets];
+#if RTX_JOB_PRIORITY
+    __shared__ float raised_cost;             // classes that cost at least this much run their ray loops at a raised priority
+#endif
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (tid < kCostBuckets) {
         count[tid] = 0u;
@@ -897,7 +919,7 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
         // for their fixed cost, which they do not when every workgroup has many jobs to even things out
         // (tools/share_timing.py: a quarter of the share costs a full C3 frame 3 %, and gains an eighth of it 10 %).
         const float per_wg = (float)scheduled / (float)shade_grid;
-        const float scale = per_wg >= 16.0f ? 1.0f : (per_wg <= 16.0f * RTX_SPLIT_SCALE_MIN ? RTX_SPLIT_SCALE_MIN : per_wg * (1.0f / 16.0f));
+        const float scale = per_wg >= 16.0f ? 1.0f : (per_wg <= 16.0f * kSplitScaleMin ? kSplitScaleMin : per_wg * (1.0f / 16.0f));
         const float limit = split_share * scale * total / (float)shade_grid;
         // ... and a part is a workgroup's fixed work plus a few chunks per wavefront: round 2 found eight parts worth it
         // only where a workgroup has fewer than three jobs, four otherwise (profiles/r02/j_ab_parts_per_tile.log); since
@@ -907,6 +929,9 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
         while ((1u << lg) < most_parts && class_cost(tid) > limit * (float)(1u << lg)) ++lg;
         parts_log[tid] = lg;
         jobs[tid] = W.buckets[kOrderHist + tid] << lg;
+#if RTX_JOB_PRIORITY
+        if (tid == 0) raised_cost = limit * kRaisedShare;
+#endif
     }
     __syncthreads();
     if (tid < kCostBuckets) {
@@ -915,6 +940,13 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
         const uint32_t mine = count[tid];
         start[tid] = before + ((mine ? atomicAdd(&W.buckets[kOrderCursor + tid], mine) : 0u) << parts_log[tid]);
         if (blockIdx.x == 0 && tid == 0) W.buckets[0] = before + jobs[0];
+#if RTX_JOB_PRIORITY
+        // the order is costliest first: the raised classes' jobs are its first [kOrderRaisedEnd]
+        // (written by the cheapest raised class; when no class costs that much the word stays zero)
+        const bool raised = tid != 0u && class_cost(tid) >= raised_cost;
+        const bool cheaper_raised = tid > 1u && class_cost(tid - 1u) >= raised_cost;
+        if (blockIdx.x == 0 && raised && !cheaper_raised) W.buckets[kOrderRaisedEnd] = before + jobs[tid];
+#endif
     }
     __syncthreads();
     if (key != kNone) {
@@ -952,8 +984,22 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
 #ifndef RTX_SHADE_CUT_WAVES_PER_SIMD
 #define RTX_SHADE_CUT_WAVES_PER_SIMD 8
 #endif
-// s_setprio of a job's serial stretches (its loads into LDS, the ordered sums, the store); its ray loops run at 0
+// s_setprio levels of a job: its serial stretches (its loads into LDS, the ordered sums, the store) run at kShadePriority,
+// its ray loops at the job's own level — 0, or kJobLevelRaised for the launch's costly jobs (RTX_JOB_PRIORITY), whose
+// ray loops then issue ahead of the other jobs' serial stretches as well (the serial stretches at 3 instead, above the
+// raised loops: +0.4 % on the "first job" rule, not taken; profiles/r06/b_ab_*.log)
 constexpr int kShadePriority = 1;
+[[maybe_unused]] constexpr uint32_t kCtlJobLevel = 12u;        // l_ctl word: the job's level (RTX_JOB_PRIORITY), published with the job id
+// s_setprio takes an immediate: a uniform branch over the levels
+__device__ __forceinline__ void set_wave_priority(uint32_t level)
+{
+    switch (level) {
+    case 0u: __builtin_amdgcn_s_setprio(0); break;
+    case 1u: __builtin_amdgcn_s_setprio(1); break;
+    case 2u: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
 template <bool COUNT, bool FAST, int NW, bool SPHERES, bool WHOLE>
 __global__ void __launch_bounds__(64 * NW, COUNT ? 1 : (WHOLE ? RTX_SHADE_WAVES_PER_SIMD : RTX_SHADE_CUT_WAVES_PER_SIMD))
 shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x, uint32_t n_tiles, uint32_t r,
@@ -1005,6 +1051,11 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
     // at a time: +17 % on a 1080p frame.)
     const uint32_t n_jobs = W.buckets[0];
     uint32_t job_ahead = kNone, q_ahead = 0u;
+#if RTX_JOB_PRIORITY
+    static_assert(NW + 4 <= (int)kCtlJobLevel && kCtlJobLevel < kCtlWords, "the level's word lies behind the run counters");
+    const uint32_t raised_end = W.buckets[kOrderRaisedEnd];   // the jobs in front of this position run their ray loops raised
+#endif
+    [[maybe_unused]] uint32_t pos_ahead = 0u;     // job_ahead's position in the order
     bool have_ahead = false;
     // (the whole-stream form only — scenes whose records do not fit an XCD's L2; measured on one box, interleaved, runs of 16:
     //  the 1M-triangle soup -1.7 %, and with the cut form big_bunny 4096x4096 -0.4 %, 1080p +2 %, the ground-only frame +10 %)
@@ -1020,13 +1071,17 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
         if (threadIdx.x == 0) {
             if (!have_ahead) {   // the first job, and after jobs without a last phase
                 if (xcd_queues) {
-                    job_ahead = claim_job(W.buckets, n_jobs, group0, groups_done);
+                    job_ahead = claim_job(W.buckets, n_jobs, group0, groups_done, kJobLevels ? &pos_ahead : nullptr);
                 } else {
                     const uint32_t q = atomicAdd(&queue[kQueueNextTile], 1u);        // q-th job, costliest class first
                     job_ahead = q < n_jobs ? W.buckets[kOrderList + q] : kNone;
+                    if (kJobLevels) pos_ahead = q;
                 }
             }
             l_ctl[3] = job_ahead;
+#if RTX_JOB_PRIORITY
+            l_ctl[kCtlJobLevel] = pos_ahead < raised_end ? kJobLevelRaised : 0u;
+#endif
             have_ahead = false;
             l_ctl[1] = 0u;
 #if RTX_EXPERIMENT_TIMELINE
@@ -1174,6 +1229,10 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                     const uint32_t total = n_hit * bc;
                     const uint32_t div = sample_major ? n_hit : bc;
                     const bool grey_tile = __builtin_amdgcn_readfirstlane(l_ctl[2]) != 0u;
+#if RTX_JOB_PRIORITY
+                    // (read here, once per batch, not held in a scalar register across the job)
+                    const uint32_t job_level = __builtin_amdgcn_readfirstlane(l_ctl[kCtlJobLevel]);
+#endif
                     // (carrying the chunk's quotient and remainder in scalar registers, advanced by additions, removes
                     //  the division per ray and was measured 3 % SLOWER on C2/C4, same box, interleaved runs)
                     // Ray number / div in six full-rate instructions: trunc((ray + 0.5) * fl(1/div)) is the exact quotient
@@ -1181,7 +1240,11 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                     // it from the next integer (checked exhaustively for the domain, ray < 8320, div <= 128).  The
                     // general 32-bit division costs three quarter-rate multiplies and a dozen more instructions.
                     const float inv_div = 1.0f / (float)div;
+#if RTX_JOB_PRIORITY
+                    set_wave_priority(job_level);
+#else
                     __builtin_amdgcn_s_setprio(0);
+#endif
                     // The chunks of a full grey tile of the open ground — no subtree in its cut, the ground the only global
                     // triangle — in a loop of their own: ray, the ground's certificate, the sample's contribution; nothing
                     // of the walk is in it (no copies into the general loop's registers, none of its spilled scalars).  A
@@ -1308,6 +1371,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                             if (!xcd_queues) {
                                 if (!claim_early) q_ahead = atomicAdd(&queue[kQueueNextTile], 1u);
                                 job_ahead = q_ahead < n_jobs ? W.buckets[kOrderList + q_ahead] : kNone;
+                                if (kJobLevels) pos_ahead = q_ahead;
                             } else if (groups_done >= 8u) {
                                 job_ahead = kNone;
                             } else {
@@ -1318,9 +1382,10 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                                 const uint32_t idx = claimed_index(g_ahead, q_ahead);
                                 if (idx < n_jobs) {
                                     job_ahead = W.buckets[kOrderList + idx];
+                                    if (kJobLevels) pos_ahead = idx;
                                 } else {       // the group's share is used up: on to the next group's (the end of a launch only)
                                     ++groups_done;
-                                    job_ahead = claim_job(W.buckets, n_jobs, group0, groups_done);
+                                    job_ahead = claim_job(W.buckets, n_jobs, group0, groups_done, kJobLevels ? &pos_ahead : nullptr);
                                 }
                             }
                             have_ahead = true;
@@ -1595,6 +1660,6 @@ extern "C" __attribute__((used, visibility("hidden"))) const char rtx_build_swit
     RTX_SW(RTX_CLAIM_RUN_LOG) RTX_SW(RTX_CUT_DRAW_MIN) RTX_SW(RTX_CUT_UNION_MIN) RTX_SW(RTX_LIGHT_BATCH) RTX_SW(RTX_LIGHT_TOUR) RTX_SW(RTX_MAX_CUT)
     RTX_SW(RTX_PACKED_WAVES_PER_SIMD) RTX_SW(RTX_PROBE_VISIT_SCALE) RTX_SW(RTX_PROBE_WAVES_PER_SIMD)
     RTX_SW(RTX_SHADE_CUT_WAVES_PER_SIMD) RTX_SW(RTX_SHADE_NW) RTX_SW(RTX_SHADE_WAVES_PER_SIMD)
-    RTX_SW(RTX_SPLIT_SCALE_MIN) RTX_SW(RTX_SPLIT_SHARE_PERCENT) RTX_SW(RTX_TILE_PARTS_MAX) RTX_SW(RTX_WAVES_PER_SIMD)
+    RTX_SW(RTX_SPLIT_SHARE_PERCENT) RTX_SW(RTX_TILE_PARTS_MAX) RTX_SW(RTX_WAVES_PER_SIMD) RTX_SW(RTX_JOB_PRIORITY)
     RTX_SW(RTX_EXPERIMENT_TIMELINE) RTX_SW(RTX_EXPERIMENT_PHASES) RTX_SW(RTX_EXPERIMENT_PROBE_PHASES) RTX_SW(RTX_ABLATION);
 #undef RTX_SW

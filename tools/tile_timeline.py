@@ -57,7 +57,7 @@ for k in sorted(set(cls[work].tolist())):
     print("    class %2d: %6d tiles  %8.1f / %7.1f / %7.1f us   pixel-major %5d (mean %7.1f us)" % (
         k, int(m.sum()), us[m].mean(), us[m].min(), us[m].max(), int((m & ((flags & 1) == 0)).sum()),
         us[m & ((flags & 1) == 0)].mean() if (m & ((flags & 1) == 0)).any() else 0.0))
-top = np.argsort(-us)[:8]
+top = np.argsort(-us)[:10]
 tx = (W + 7) // 8
 def tile_xy(t):   # the library numbers tiles by 8 x 8 blocks (rtx_kernel.hip: tile_xy)
     blocks_x, b, j = (tx + 7) // 8, t >> 6, t & 63
