@@ -314,6 +314,46 @@ int rtx_render_view(RtxScene *scene, int device, const RtxView *view, uint8_t *o
 int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, void *d_shade, void *d_hits,
                            void *stream);
 
+/* ---- any view through the render pipeline --------------------------------------- */
+/* Rows [y0, y0+ny) of the view's frame through the RENDER PIPELINE (scheduling pass + shading pass: per-tile cuts, compacted
+ * hit records, the cost-ordered schedule — what rtx_render_rows runs), full width: x0 == 0 and nx == width, else
+ * RTX_ERR_BAD_ARG.  out_rgb: ny*width*3 bytes, rows packed — the bytes rtx_render_view gives for the same view, i.e.
+ * rtx_render_rows(y0, ny) of a scene created with that camera.  A turntable is one scene and N of these calls.
+ *
+ * The pipeline's kernels read the camera and the frame from their argument block, which is built per launch; what a new
+ * eye needs made is the stream its primary rays walk (of every node's children the one nearer the EYE first: an ordering
+ * for speed, no result depends on it).  The library keeps ONE such stream per device in a buffer of its own and makes it on
+ * the device (two small kernels, rtx_aim.hip) on the call's stream, ahead of the scheduling pass.  Cache rule: the buffer
+ * remembers the 12 bytes of the eye it was aimed at and the stream it was aimed on; a call with the same eye bytes on the
+ * same stream runs no aim kernel, any other call runs them again.  A scene without a primary stream of its own
+ * (RTX_ACCEL_BRUTE, or nothing beside the global triangles) aims nothing: its primary rays walk rtx_scene_nodes' stream.
+ *
+ * Errors: RTX_ERR_BAD_ARG for rtx_render_view's argument checks (NULL scene / view / output, width == 0 or height == 0,
+ * width*height >= 2^31, rows outside the frame) and for a rectangle that is not the full width; the device variant also for
+ * d_bytes < ny*width*3.  ny == 0: RTX_OK, nothing written, stats zeroed, no device needed.
+ * Range rule: RTX_ERR_UNSUPPORTED unless max |eye[k]| <= cull_delta * 2^19 — the largest coordinate magnitude of the scene's
+ * primitives and the eye rtx_scene_create was given (a NaN fails the comparison); checked before a device is looked for.
+ * The pipeline's walks use the multiply-based box test only, whose culling planes were moved outwards for origins within
+ * that magnitude: the pipeline has no exact-slab form to fall back on, and the tile shaft test's margin was sized without
+ * such an eye.  rtx_render_view serves those eyes (its primary walks switch to the exact box test), as it serves rectangles
+ * narrower than the frame and shade / hit records.  No usable device: RTX_ERR_NO_DEVICE (there is no CPU fallback).
+ * stats mean what they mean for rtx_render_rows, with primary_rays = ny*width*nb_ray and redo_tiles in tiles; kernel_ms
+ * includes the aim kernels when they run.  The launches count in rtx_launch_timings (the aim kernels lie outside both of its
+ * passes) and rtx_debug_tile_descs like any render launch, and the rule of rtx_render_tiles_device holds unchanged:
+ * pipeline launches on one device — these included — must be ordered on one stream.
+ * A view call leaves every later render, query, shade or view call on the scene unchanged: the prepared scene and its
+ * uploaded streams are not written. */
+int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats);
+/* Device-resident variant, asynchronous on `stream` (a hipStream_t; NULL = the default stream), as rtx_render_tiles_device
+ * is: d_rgb is a device pointer the caller owns, d_bytes >= ny*width*3; d_counters: NULL or rtx_render_tiles_device's 8
+ * uint64 the kernels ADD to.  The scene is uploaded (synchronously) first if needed. */
+int rtx_render_view_rows_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, size_t d_bytes,
+                                void *stream, uint64_t *d_counters);
+/* Diagnostic: runs the aim kernels for `eye` on `device` (whatever the buffer holds), blocks, and copies the device's aimed
+ * stream back: n_nodes*8 dwords in NodeRec word order, as rtx_scene_nodes.  A scene without a primary stream of its own:
+ * its uploaded stream, nothing run. */
+int rtx_debug_aimed_nodes(RtxScene *scene, int device, const float eye[3], uint32_t *out_dwords);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with
@@ -364,6 +404,13 @@ int rtx_scene_nodes(const RtxScene *scene, uint32_t *out_dwords /* n_nodes*8 */,
    the one nearer the eye first (the shadow rays' stream puts the one farther from the light first); *out_own = 1 when the
    scene has such a stream of its own, 0 when the primary rays walk rtx_scene_nodes' stream (which is then what is copied) */
 int rtx_scene_primary_nodes(const RtxScene *scene, uint32_t *out_dwords /* n_nodes*8 */, uint32_t *out_own);
+/* host only, no device: the stream the primary rays of a view with this eye walk (rtx_render_view_rows): n_nodes*8 dwords,
+   NodeRec word order as rtx_scene_nodes.  It is rtx_scene_nodes' stream with every plane moved outwards by cull_delta, in
+   f32, as the device holds it, and below the tree proper's root the child nearer the eye first: of a node's children a
+   (the next record) and b (named by info), with c_k = (0.5*lo_k + 0.5*hi_k) - eye_k and d2 = c_0^2 + c_1^2 + c_2^2 in
+   double, a stays first unless d2(b) < d2(a).  The host statement of what the aim kernels make (rtx_debug_aimed_nodes);
+   a scene without a primary stream of its own: the moved stream in its own order. */
+int rtx_scene_aimed_nodes(const RtxScene *scene, const float eye[3], uint32_t *out_dwords);
 /* the reference-tree stream (n_ref_nodes*8 dwords; leaf info = 0x80000000 | position in out_tri_order) */
 int rtx_scene_ref_nodes(const RtxScene *scene, uint32_t *out_dwords);
 

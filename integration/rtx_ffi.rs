@@ -162,6 +162,12 @@ extern "C" {
                            out_shade: *mut RtxPixelShade, out_hits: *mut RtxRayHit, stats: *mut RtxStats) -> c_int;
     pub fn rtx_render_view_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, d_rgb: *mut c_void,
                                   d_shade: *mut c_void, d_hits: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Rows `[y0, y0 + ny)` of the view through the render pipeline, full width (`x0 == 0`, `nx == width`): `rtx_render_view`'s
+    /// bytes at `rtx_render_rows`' speed.  `RTX_ERR_UNSUPPORTED` (-5) for an eye beyond the scene's largest coordinate.
+    pub fn rtx_render_view_rows(scene: *mut RtxScene, device: c_int, view: *const RtxView, out_rgb: *mut u8,
+                                stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_rows_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, d_rgb: *mut c_void,
+                                       d_bytes: usize, stream: *mut c_void, d_counters: *mut u64) -> c_int;
     pub fn rtx_launch_timings(scene: *mut RtxScene, device: c_int, max_launches: c_int, schedule_ms: *mut f32,
                               shade_ms: *mut f32) -> c_int;
     pub fn rtx_strerror(err: c_int) -> *const c_char;

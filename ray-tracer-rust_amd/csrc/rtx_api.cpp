@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../include/rtx.h"
+#include "rtx_aim.h"
 #include "rtx_device.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
@@ -143,6 +145,15 @@ public:
     // regrouping pass's (key, ray number) buffers and the sort's temporary storage; none shared with the render workspace
     DeviceBuffer q_first, q_second, q_out;
     struct { DeviceBuffer keys, keys_sorted, index, index_sorted, temp; } q_sort;
+    // rtx_render_view_rows (rtx_aim.hip): the primary rays' stream of the most recent view's eye — (n_nodes + 1) records,
+    // the last one the zeroed sentinel — the aim kernels' scratch, and what the stream was aimed at and on: a call with the
+    // same eye on the same stream walks it as it stands
+    struct {
+        DeviceBuffer nodes, links;
+        float eye[3] = {0.0f, 0.0f, 0.0f};
+        hipStream_t on = nullptr;
+        bool valid = false;
+    } aimed;
 private:
     ~DeviceState() = default;
     friend struct ReleaseOnDevice;
@@ -671,6 +682,108 @@ Batch view_batch(const RtxScene *scene, const RtxView *v, bool want_rgb, bool wa
     return b;
 }
 
+// ---- any view through the render pipeline (rtx_render_view_rows; the aim kernels: rtx_aim.hip) ------------------------------
+
+// first record of the tree proper: behind the root and the leaf of the global triangles when there are any
+uint32_t aim_root(const rtx::PreparedScene &p)
+{
+    return (p.n_global != 0u && p.nodes.size() > 2u) ? 2u : 0u;
+}
+
+// The multiply-based culling of the pipeline's walks is proven for origins whose coordinates stay within the magnitude
+// behind cull_delta (scene_prep.cpp); the bound is the one batch_launch hands the ray-batch kernels.  A NaN fails it.
+bool eye_in_pipeline_range(const RtxScene *scene, const float eye[3])
+{
+    const float bound = scene->prep.cull_delta * 0x1p19f;
+    for (int k = 0; k < 3; ++k)
+        if (!(std::fabs(eye[k]) <= bound)) return false;
+    return true;
+}
+
+// the argument checks rtx_render_view_rows and its _device twin share: rtx_render_view's, and full width
+bool view_rows_args_ok(const RtxScene *scene, const RtxView *v, const void *out)
+{
+    if (!scene || !v || !out) return false;
+    if (v->width == 0u || v->height == 0u || static_cast<uint64_t>(v->width) * v->height >= (1ull << 31)) return false;
+    if (v->x0 != 0u || v->nx != v->width) return false;
+    return static_cast<uint64_t>(v->y0) + v->ny <= v->height;
+}
+
+// The stream the view's primary rays walk, on `stream`: the scene's shadow stream when it has no primary stream of its own
+// (nothing is aimed then), else the device's aimed buffer, the aim kernels run first unless it stands for this eye on this
+// stream.  Caller holds the slot's lock and has the device current and the scene uploaded; reserve_aimed() comes first.
+int reserve_aimed(RtxScene *scene, DeviceState &st)
+{
+    if (scene->prep.primary_nodes.empty()) return RTX_OK;
+    const size_t n = scene->prep.nodes.size();
+    const size_t had = st.aimed.nodes.capacity();
+    const int rc = reserve_all({{st.aimed.nodes, (n + 1u) * sizeof(rtx::NodeDev)}, {st.aimed.links, n * sizeof(rtxa::AimLink)}});
+    if (rc != RTX_OK || st.aimed.nodes.capacity() != had) st.aimed.valid = false;
+    return rc;
+}
+
+const rtx::NodeRec *aimed_stream(const RtxScene *scene, const DeviceState &st)
+{
+    return (scene->prep.primary_nodes.empty() ? st.nodes : st.aimed.nodes).as<const rtx::NodeRec>();
+}
+
+int aim_at(RtxScene *scene, DeviceState &st, const float eye[3], hipStream_t stream)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    if (p.primary_nodes.empty()) return RTX_OK;
+    if (st.aimed.valid && st.aimed.on == stream && std::memcmp(st.aimed.eye, eye, 12) == 0) return RTX_OK;
+    st.aimed.valid = false;
+    const uint32_t n = static_cast<uint32_t>(p.nodes.size());
+    RTX_HIP(hipMemsetAsync(st.aimed.nodes.as<rtx::NodeDev>() + n, 0, sizeof(rtx::NodeDev), stream));      // the sentinel
+    RTX_HIP(rtxa::launch_aim(st.nodes.as<const rtx::NodeDev>(), n, aim_root(p), eye, st.aimed.links.as<rtxa::AimLink>(),
+                             st.aimed.nodes.as<rtx::NodeDev>(), stream));
+    std::memcpy(st.aimed.eye, eye, 12);
+    st.aimed.on = stream;
+    st.aimed.valid = true;
+    return RTX_OK;
+}
+
+// rtx_render_rows / rtx_render_tiles_device for a view: device_scene() with the view's frame and camera and the aimed
+// stream, rows [y0, y0 + ny) as one share.  `before`: as render_launch's; the aim kernels follow it on the stream.
+template <class Before>
+int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t *d_out, unsigned long long *d_counters,
+                     hipStream_t stream, Before before)
+{
+    int rc = reserve_aimed(scene, st);
+    if (rc != RTX_OK) return rc;
+    rtx::DeviceScene S = device_scene(scene, st);
+    S.width = v.width;
+    S.height = v.height;
+    std::memcpy(S.eye, v.eye, 12);
+    std::memcpy(S.cu, v.u, 12);
+    std::memcpy(S.cv, v.v, 12);
+    std::memcpy(S.cw, v.w, 12);
+    S.distance = v.distance;
+    S.primary_nodes = aimed_stream(scene, st);
+    const rtx::TileSpec ts{v.y0, v.ny, v.ny, v.ny};
+    return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
+        const int brc = before();
+        return brc != RTX_OK ? brc : aim_at(scene, st, v.eye, stream);
+    });
+}
+
+// host statement of the aim kernels: stream_nearest_first over the shadow stream with its planes moved as
+// nodes_in_device_order moves them (f32); a scene without a primary stream of its own: that stream as it is
+std::vector<rtx::NodeRec> aimed_on_host(const rtx::PreparedScene &p, const float eye[3])
+{
+    std::vector<rtx::NodeRec> moved(p.nodes);
+    const float inflate = p.cull_delta;
+    for (rtx::NodeRec &n : moved)
+        for (int k = 0; k < 3; ++k) {
+            n.bmin[k] = n.bmin[k] - inflate;
+            n.bmax[k] = n.bmax[k] + inflate;
+        }
+    if (p.primary_nodes.empty()) return moved;
+    std::vector<rtx::NodeRec> out;
+    rtx::stream_nearest_first(moved, aim_root(p), eye, out);
+    return out;
+}
+
 }  // namespace
 
 extern "C" {
@@ -990,6 +1103,95 @@ int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, voi
     d_out[kViewShade] = d_shade; d_out[kViewHits] = d_hits; d_out[kViewRgb] = d_rgb;
     return batch_device(scene, device, view_batch(scene, view, d_rgb != nullptr, d_shade != nullptr, d_hits != nullptr),
                         nullptr, nullptr, d_out, stream);
+}
+
+int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats)
+{
+    if (!view_rows_args_ok(scene, view, out_rgb)) return RTX_ERR_BAD_ARG;
+    const uint32_t nb_ray = scene->prep.nb_ray, nb_light = scene->prep.nb_light_sample;
+    const double t0 = wall_ms();
+    unsigned long long c[rtx::kNumCounters] = {0};
+    if (view->ny == 0u) {
+        if (stats) fill_stats(stats, 0, nb_light, c, 0.0, wall_ms() - t0);
+        return RTX_OK;
+    }
+    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const RtxView v = *view;                 // (the caller's may change while the call runs)
+    const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
+    int rc = st.d_out.reserve(bytes);
+    if (rc != RTX_OK) return rc;
+    unsigned long long *counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
+    rc = view_rows_launch(scene, st, v, st.d_out.as<uint8_t>(), counters, st.stream, [&]() -> int {
+        if (stats) RTX_HIP(hipMemsetAsync(counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
+        RTX_HIP(hipEventRecord(st.ev0, st.stream));
+        return RTX_OK;
+    });
+    if (rc != RTX_OK) return rc;
+    RTX_HIP(hipEventRecord(st.ev1, st.stream));
+    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
+    if (stats) RTX_HIP(hipMemcpyAsync(c, st.d_counters.as<void>(), sizeof c, hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    if (stats) {
+        float ms = 0.0f;
+        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
+        fill_stats(stats, static_cast<uint64_t>(v.ny) * v.width * nb_ray, nb_light, c, ms, wall_ms() - t0);
+    }
+    return RTX_OK;
+}
+
+int rtx_render_view_rows_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, size_t d_bytes, void *stream,
+                                uint64_t *d_counters)
+{
+    if (!view_rows_args_ok(scene, view, d_rgb)) return RTX_ERR_BAD_ARG;
+    if (d_bytes < static_cast<size_t>(view->ny) * view->width * 3u) return RTX_ERR_BAD_ARG;
+    if (view->ny == 0u) return RTX_OK;
+    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    return view_rows_launch(scene, e.state(), *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
+                            static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); });
+}
+
+int rtx_scene_aimed_nodes(const RtxScene *scene, const float eye[3], uint32_t *out_dwords)
+{
+    if (!scene || !eye || !out_dwords) return RTX_ERR_BAD_ARG;
+    try {
+        const std::vector<rtx::NodeRec> v = aimed_on_host(scene->prep, eye);
+        std::memcpy(out_dwords, v.data(), v.size() * sizeof(rtx::NodeRec));
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_debug_aimed_nodes(RtxScene *scene, int device, const float eye[3], uint32_t *out_dwords)
+{
+    if (!scene || !eye || !out_dwords) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    int rc = reserve_aimed(scene, st);
+    if (rc != RTX_OK) return rc;
+    st.aimed.valid = false;                  // the kernels run whatever the buffer holds
+    if ((rc = aim_at(scene, st, eye, st.stream)) != RTX_OK) return rc;
+    const size_t n = scene->prep.nodes.size();
+    std::vector<rtx::NodeDev> dev;
+    try {
+        dev.resize(n);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    if (n) RTX_HIP(hipMemcpyAsync(dev.data(), aimed_stream(scene, st), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    for (size_t i = 0; i < n; ++i) {         // NodeDev word order -> NodeRec's
+        const rtx::NodeDev &d = dev[i];
+        const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
+        std::memcpy(out_dwords + 8u * i, &r, sizeof r);
+    }
+    return RTX_OK;
 }
 
 int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint64_t *out,

@@ -145,6 +145,11 @@ _SIGS = {
     "rtx_render_view": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.c_void_p, C.POINTER(PixelShade), C.POINTER(RayHit),
                                   C.POINTER(Stats)]),
     "rtx_render_view_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_render_view_rows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.c_void_p, C.POINTER(Stats)]),
+    "rtx_render_view_rows_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p]),
+    "rtx_scene_aimed_nodes": (C.c_int, [C.c_void_p, f32p, u32p]),
+    "rtx_debug_aimed_nodes": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -613,6 +618,37 @@ class Scene:
                                            C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
                                            C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
                                            C.c_void_p(stream) if stream else None), "rtx_render_view_device")
+
+    # -- any view through the render pipeline (GPU only)
+    def render_view_rows(self, view, device=0, stats=False):
+        """Rows [y0, y0 + ny) of the view's frame through the render pipeline, full width (x0 = 0, nx = width)
+        -> uint8 [ny, width, 3]: render_view's bytes at the pipeline's speed.  An eye beyond the scene's largest
+        coordinate raises RtxError(ERR_UNSUPPORTED): render_view serves it."""
+        out = np.zeros((view.ny, view.width, 3), np.uint8)
+        st = Stats()
+        _check(_lib.rtx_render_view_rows(self._h, device, C.byref(view), out.ctypes.data, C.byref(st) if stats else None),
+               "rtx_render_view_rows")
+        return (out, st.asdict()) if stats else out
+
+    def render_view_rows_device(self, device, view, d_rgb_ptr, d_bytes, stream=None, d_counters_ptr=None):
+        """Asynchronous pipeline launch of the view's rows into a device buffer the caller owns (ny*width*3 bytes)."""
+        _check(_lib.rtx_render_view_rows_device(self._h, device, C.byref(view), C.c_void_p(d_rgb_ptr), d_bytes,
+                                                C.c_void_p(stream) if stream else None,
+                                                C.c_void_p(d_counters_ptr) if d_counters_ptr else None),
+               "rtx_render_view_rows_device")
+
+    def aimed_nodes(self, eye):
+        """Host only: records [n_nodes, 8] of the stream the primary rays of a view with this eye walk (planes moved by
+        cull_delta, the child nearer the eye first), NodeRec word order as nodes()."""
+        nd = np.zeros((self.info()["n_nodes"], 8), np.uint32)
+        _check(_lib.rtx_scene_aimed_nodes(self._h, _fp(_f3(eye)), nd.ctypes.data_as(u32p)), "rtx_scene_aimed_nodes")
+        return nd
+
+    def debug_aimed_nodes(self, eye, device=0):
+        """Diagnostics: the same stream as the aim kernels make it on `device`, copied back, same word order."""
+        nd = np.zeros((self.info()["n_nodes"], 8), np.uint32)
+        _check(_lib.rtx_debug_aimed_nodes(self._h, device, _fp(_f3(eye)), nd.ctypes.data_as(u32p)), "rtx_debug_aimed_nodes")
+        return nd
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
