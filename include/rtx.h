@@ -354,6 +354,55 @@ int rtx_render_view_rows_device(RtxScene *scene, int device, const RtxView *view
  * its uploaded stream, nothing run. */
 int rtx_debug_aimed_nodes(RtxScene *scene, int device, const float eye[3], uint32_t *out_dwords);
 
+/* ---- another light for views and shaded rays ------------------------------------- */
+/* rtx_scene_create turns the light into nb_ray * nb_light_sample light points once.  These entry points shade with ANY
+ * area light of the reference's kind and any sample count, on the scene as it is uploaded: no new scene, no tree build, no
+ * upload.  A pixel is render_pixel's (main.rs:180-240) of a reference Scene that differs in two ways: scene.light.primitives[0]
+ * is the given triangle, and NB_LIGHT_SAMPLE is the given count — the shadow loop's bound (main.rs:193) and the denominator
+ * nb_ray * nb_light_sample (main.rs:211).  Light point [r][i] is get_sample(T[(r*nb_ray + i) % n_samples]) (main.rs:194-196,
+ * triangle.rs:113-127; the third weight is v * sqrt(u), as the reference has it).
+ *
+ * The library makes the points on the device (one small kernel, rtx_light.hip) on the call's stream, ahead of the view or
+ * shade kernel, in ONE buffer of its own per device, which grows only (growing waits for the device).  There is no cache:
+ * every lit call runs the kernel.  The ordering rule is the regrouping buffers': device-resident lit launches on one device
+ * must be ordered on one stream; the host entry points use the same buffer on the library's stream and wait (on the device,
+ * by an event) for the most recent device-resident lit launch first, so they may be mixed with those freely.
+ * rtx_shade_rays_lit* also uses the regrouping buffers and inherits their rule unchanged (rtx_shade_rays_device).
+ *
+ * There is no range rule on the light: a vertex may lie anywhere, beyond the scene's largest coordinate included.  A shadow
+ * ray's ORIGIN is the hit point, which is what the walks' choice of box test is voted on; the light point is the ray's
+ * target, unrestricted as rtx_occluded_rays' targets are.
+ * The render pipeline (rtx_render_rows, rtx_render_view_rows) has no lit form: it also reads the light's tour, boxes and
+ * shaft margin, which rtx_scene_create alone makes.
+ * A lit call leaves every later call on the scene unchanged: the prepared scene and its uploaded light are not written. */
+typedef struct RtxLight {          /* 40 bytes, alignment 4 */
+    float v0[3], v1[3], v2[3];     /* Light.primitives[0] (light.rs:11-13): the triangle get_sample samples */
+    uint32_t nb_light_sample;      /* NB_LIGHT_SAMPLE for this call (main.rs:39); 0 = the scene's */
+} RtxLight;
+
+/* the light and the sample count rtx_scene_create was given */
+int rtx_scene_light(const RtxScene *scene, RtxLight *out);
+/* Each lit call is its unlit twin — rtx_render_view, rtx_render_view_device, rtx_shade_rays, rtx_shade_rays_device — in
+ * every respect: argument checks, outputs, flags, regrouping, alignment rules.  Beyond those:
+ *   RTX_ERR_BAD_ARG      light == NULL, or nb_ray * count > 2^20 (count: the light's, or the scene's for 0);
+ *   nx == 0, ny == 0 or n_pixels == 0: RTX_OK as in the twin, nothing written, stats zeroed, no device needed;
+ *   RTX_ERR_UNSUPPORTED  a vertex coordinate that is not finite — decided on the host, before a device is looked for.
+ * The light is read before the call returns.  stats: as the twin's, with shadow_rays = count * primary_hits; kernel_ms
+ * includes the light kernel. */
+int rtx_render_view_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
+                        RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats);
+int rtx_render_view_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
+                               void *d_shade, void *d_hits, void *stream);
+int rtx_shade_rays_lit(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
+                       uint32_t flags, const RtxLight *light, RtxPixelShade *out_shade, RtxRayHit *out_hits /* may be NULL */,
+                       RtxStats *stats);
+int rtx_shade_rays_lit_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
+                              uint32_t flags, const RtxLight *light, void *d_shade, void *d_hits /* may be NULL */,
+                              void *stream);
+/* Diagnostic: runs the light kernel for `light` on `device`, blocks, and copies the device's points back: nb_ray * count
+ * x 3 floats, as rtx_scene_light_points_for.  Errors as the lit calls'. */
+int rtx_debug_light_points(RtxScene *scene, int device, const RtxLight *light, float *out);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with
@@ -387,6 +436,12 @@ int rtx_last_hip_error(void);
 /* ---- prepared-scene read-back (host logic tests, no device needed) --------- */
 /* out: n_light_points x 3 floats — Light::get_sample(T[(r*nb_ray+i) % n]) (src/main.rs:194-196) */
 int rtx_scene_light_points(const RtxScene *scene, float *out);
+/* host only, no device: the points of ANY light on this scene — nb_ray * n points x 3 floats, n the light's count or, for
+   0, the scene's; point [r][i] = get_sample(T[(r*nb_ray + i) % n_samples]), the index in 64 bits.  The host statement of
+   what the light kernel makes (rtx_debug_light_points); for rtx_scene_light's value it is rtx_scene_light_points bit for
+   bit.  out may be NULL.  Returns the number of points, or a negative RtxError: RTX_ERR_BAD_ARG for a NULL scene or light
+   and for nb_ray * n > 2^20.  Vertices are not checked: a coordinate that is not finite gives points that are not. */
+int rtx_scene_light_points_for(const RtxScene *scene, const RtxLight *light, float *out);
 /* out: n_light_points words — the order in which the shading pass WALKS the light samples of primary ray r: the samples
    are cut into batches of min(nb_light_sample, 128) consecutive ones, and word r*nb_light_sample + k is the sample index
    (0 <= index < nb_light_sample) at walk position k.  Every batch is a permutation of its own indices that starts with

@@ -118,6 +118,16 @@ pub struct RtxView {
     pub nx: u32,
     pub ny: u32,
 }
+/// The area light of one lit call (`rtx_render_view_lit`, `rtx_shade_rays_lit`): the vertices of `Light.primitives[0]`,
+/// the triangle `get_sample` samples, and `NB_LIGHT_SAMPLE` for the call (0 = the scene's).  40 bytes, alignment 4.
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxLight {
+    pub v0: [f32; 3],
+    pub v1: [f32; 3],
+    pub v2: [f32; 3],
+    pub nb_light_sample: u32,
+}
 pub const RTX_NO_HIT: u32 = 0xFFFF_FFFF;
 pub const RTX_RAYS_KEEP_ORDER: u32 = 1;
 pub const RTX_RAYS_FORCE_REGROUP: u32 = 2;
@@ -168,6 +178,27 @@ extern "C" {
                                 stats: *mut RtxStats) -> c_int;
     pub fn rtx_render_view_rows_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, d_rgb: *mut c_void,
                                        d_bytes: usize, stream: *mut c_void, d_counters: *mut u64) -> c_int;
+    /// The light and sample count `rtx_scene_create` was given.
+    pub fn rtx_scene_light(scene: *const RtxScene, out: *mut RtxLight) -> c_int;
+    /// `rtx_render_view` / `rtx_shade_rays` (and their device-resident forms) under another light: no new scene.  A NULL
+    /// light or more than 2^20 light points: `RTX_ERR_BAD_ARG`; a vertex that is not finite: `RTX_ERR_UNSUPPORTED` (-5).
+    /// Device-resident lit launches on one device must be ordered on one stream (one library-owned light buffer).
+    pub fn rtx_render_view_lit(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                               out_rgb: *mut u8, out_shade: *mut RtxPixelShade, out_hits: *mut RtxRayHit,
+                               stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_lit_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                      d_rgb: *mut c_void, d_shade: *mut c_void, d_hits: *mut c_void,
+                                      stream: *mut c_void) -> c_int;
+    pub fn rtx_shade_rays_lit(scene: *mut RtxScene, device: c_int, n_pixels: u32, origins: *const f32,
+                              directions: *const f32, flags: u32, light: *const RtxLight, out_shade: *mut RtxPixelShade,
+                              out_hits: *mut RtxRayHit, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_shade_rays_lit_device(scene: *mut RtxScene, device: c_int, n_pixels: u32, d_origins: *const c_void,
+                                     d_directions: *const c_void, flags: u32, light: *const RtxLight, d_shade: *mut c_void,
+                                     d_hits: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Host only: the points of `light` on this scene (`out` may be NULL); returns their number or a negative error.
+    pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
+    /// Diagnostic: the same points as the light kernel makes them on `device`.
+    pub fn rtx_debug_light_points(scene: *mut RtxScene, device: c_int, light: *const RtxLight, out: *mut f32) -> c_int;
     pub fn rtx_launch_timings(scene: *mut RtxScene, device: c_int, max_launches: c_int, schedule_ms: *mut f32,
                               shade_ms: *mut f32) -> c_int;
     pub fn rtx_strerror(err: c_int) -> *const c_char;

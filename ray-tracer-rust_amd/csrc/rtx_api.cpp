@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "../../include/rtx.h"
 #include "rtx_aim.h"
 #include "rtx_device.h"
+#include "rtx_light.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
 #include "rtx_view.h"
@@ -154,6 +156,13 @@ public:
         hipStream_t on = nullptr;
         bool valid = false;
     } aimed;
+    // rtx_*_lit (rtx_light.hip): the points of the most recent lit call's light, made on that call's stream ahead of its
+    // view or shade kernel; `used` is recorded behind a device-resident lit launch on the CALLER's stream: a host call, which
+    // uses the same buffer on the library's stream, waits for it first
+    struct {
+        DeviceBuffer points;
+        Event used;
+    } lit;
 private:
     ~DeviceState() = default;
     friend struct ReleaseOnDevice;
@@ -538,8 +547,14 @@ hipError_t launch_viewed(const BatchArgs &a)
     return rtxv::launch_view(a.S, v, a.origin_bound, a.out[kViewRgb], a.out[kViewShade], a.out[kViewHits], a.counters, a.stream);
 }
 
-// What differs between rtx_trace_rays, rtx_occluded_rays, rtx_shade_rays and rtx_render_view (and their _device twins),
-// checked by them.
+// What a lit call takes from its RtxLight: the triangle and the sample count, the scene's for 0 (lit_of)
+struct Lit {
+    rtxl::LightTriangle tri;
+    uint32_t count;
+};
+
+// What differs between rtx_trace_rays, rtx_occluded_rays, rtx_shade_rays and rtx_render_view (and their _device and _lit
+// twins), checked by them.
 struct Batch {
     uint32_t n;                    // entries the launcher works on and the regrouping pass sorts: rays, or pixels of nb_ray rays
     uint32_t n_rays;               // rays in each of the two input arrays (a view: rays its kernel makes)
@@ -549,12 +564,40 @@ struct Batch {
     uint32_t shadow_rays_per_hit;  // RtxStats
     hipError_t (*launch)(const BatchArgs &);
     const RtxView *view;           // rtx_render_view: the caller's, read while the call runs; else NULL
+    const Lit *lit;                // the lit twins: the call's light (shadow_rays_per_hit is its count); else NULL
 };
 
 bool batch_regroups(const Batch &b)
 {
     if (b.flags & RTX_RAYS_KEEP_ORDER) return false;
     return b.n >= rtxq::kRegroupMinRays || (b.flags & RTX_RAYS_FORCE_REGROUP) != 0u;
+}
+
+// The light kernel of a lit call on `stream`, and its points and count in the call's copy of the scene's argument block: the
+// view and shade kernels read nothing else of the light (rtx_shade_pixel.hpp).  The buffer is library-owned per device and
+// grows only; growing it waits for the device first, since an earlier launch may still read it.  Caller holds the slot's lock
+// and has the device current and the scene uploaded.
+int light_launch(const RtxScene *scene, DeviceState &st, const Lit &lit, rtx::DeviceScene *S, hipStream_t stream)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const size_t bytes = static_cast<size_t>(p.nb_ray) * lit.count * 3u * sizeof(float);
+    if (st.lit.points.capacity() < (bytes ? bytes : 16u)) {
+        RTX_HIP(hipDeviceSynchronize());
+        const int rc = st.lit.points.reserve(bytes ? bytes : 16u);
+        if (rc != RTX_OK) return rc;
+    }
+    RTX_HIP(rtxl::launch_light_points(st.samples.as<const float2>(), p.n_samples, lit.tri, p.nb_ray, lit.count,
+                                      st.lit.points.as<float>(), stream));
+    S->light_points = st.lit.points.as<const float>();
+    S->nb_light = lit.count;
+    return RTX_OK;
+}
+
+bool light_is_finite(const Lit &lit)
+{
+    for (float x : lit.tri.v)
+        if (!std::isfinite(x)) return false;
+    return true;
 }
 
 // key + sort + kernel of one batch on `stream`; caller holds the slot's lock, has the device current and the scene uploaded
@@ -565,7 +608,9 @@ int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *
     const bool regroup = batch_regroups(b);
     int rc;
     if (regroup && (rc = reserve_query_sort(st, b.n, &sort)) != RTX_OK) return rc;
-    RTX_HIP(b.launch(BatchArgs{device_scene(scene, st), b.n, d_first, d_second, b.view, query_key_box(scene->prep),
+    rtx::DeviceScene S = device_scene(scene, st);
+    if (b.lit && (rc = light_launch(scene, st, *b.lit, &S, stream)) != RTX_OK) return rc;
+    RTX_HIP(b.launch(BatchArgs{S, b.n, d_first, d_second, b.view, query_key_box(scene->prep),
                                scene->prep.cull_delta * 0x1p19f, regroup ? &sort : nullptr, {d_out[0], d_out[1], d_out[2]},
                                d_counters, stream}));
     return RTX_OK;
@@ -580,6 +625,7 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
         if (stats) { std::memset(stats, 0, sizeof *stats); stats->total_ms = wall_ms() - t0; }
         return RTX_OK;
     }
+    if (b.lit && !light_is_finite(*b.lit)) return RTX_ERR_UNSUPPORTED;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
@@ -592,6 +638,7 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
     for (int k = 0; k < kBatchOuts; ++k) d_out[k] = b.out_bytes[k] ? st.q_out.as<uint8_t>() + offset[k] : nullptr;
     unsigned long long *d_counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
     if (st.q_sorted) RTX_HIP(hipStreamWaitEvent(st.stream, st.q_sorted, 0));   // a device-resident call may still be sorting
+    if (b.lit && st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));   // ... or reading its light's points
     if (in_bytes) {
         RTX_HIP(hipMemcpyAsync(st.q_first.as<void>(), first, in_bytes, hipMemcpyHostToDevice, st.stream));
         RTX_HIP(hipMemcpyAsync(st.q_second.as<void>(), second, in_bytes, hipMemcpyHostToDevice, st.stream));
@@ -622,6 +669,7 @@ int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_firs
 {
     if ((reinterpret_cast<uintptr_t>(d_first) | reinterpret_cast<uintptr_t>(d_second)) & 3u) return RTX_ERR_BAD_ARG;
     if (b.n == 0u) return RTX_OK;
+    if (b.lit && !light_is_finite(*b.lit)) return RTX_ERR_UNSUPPORTED;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
@@ -631,6 +679,10 @@ int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_firs
     if (batch_regroups(b)) {     // the library's sort buffers are busy until this point of the caller's stream
         if (!st.q_sorted) RTX_HIP(hipEventCreateWithFlags(st.q_sorted.put(), hipEventDisableTiming));
         RTX_HIP(hipEventRecord(st.q_sorted, static_cast<hipStream_t>(stream)));
+    }
+    if (b.lit) {                 // ... and its light buffer
+        if (!st.lit.used) RTX_HIP(hipEventCreateWithFlags(st.lit.used.put(), hipEventDisableTiming));
+        RTX_HIP(hipEventRecord(st.lit.used, static_cast<hipStream_t>(stream)));
     }
     return RTX_OK;
 }
@@ -650,7 +702,7 @@ bool shade_args_ok(const RtxScene *scene, const void *first, const void *second,
 Batch query_batch(bool occlusion, uint32_t n_rays, uint32_t flags)
 {
     return Batch{n_rays, n_rays, flags, {static_cast<size_t>(n_rays) * (occlusion ? 1u : sizeof(RtxRayHit)), 0u, 0u}, 0u,
-                 occlusion ? launch_queried<true> : launch_queried<false>, nullptr};
+                 occlusion ? launch_queried<true> : launch_queried<false>, nullptr, nullptr};
 }
 
 // caller has checked n_pixels (shade_args_ok)
@@ -659,7 +711,7 @@ Batch shade_batch(const RtxScene *scene, uint32_t n_pixels, uint32_t flags, bool
     const uint32_t n_rays = shade_ray_count(scene, n_pixels);
     return Batch{n_pixels, n_rays, flags,
                  {static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade), want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u, 0u},
-                 scene->prep.nb_light_sample, launch_shaded, nullptr};
+                 scene->prep.nb_light_sample, launch_shaded, nullptr, nullptr};
 }
 
 // the argument checks rtx_render_view and its _device twin share (`rgb`, `shade`, `hits`: the three outputs)
@@ -675,10 +727,33 @@ bool view_args_ok(const RtxScene *scene, const RtxView *v, const void *rgb, cons
 Batch view_batch(const RtxScene *scene, const RtxView *v, bool want_rgb, bool want_shade, bool want_hits)
 {
     const uint32_t n_pixels = v->nx * v->ny, n_rays = n_pixels * scene->prep.nb_ray;
-    Batch b{n_pixels, n_rays, RTX_RAYS_KEEP_ORDER, {0u, 0u, 0u}, scene->prep.nb_light_sample, launch_viewed, v};
+    Batch b{n_pixels, n_rays, RTX_RAYS_KEEP_ORDER, {0u, 0u, 0u}, scene->prep.nb_light_sample, launch_viewed, v, nullptr};
     b.out_bytes[kViewShade] = want_shade ? static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade) : 0u;
     b.out_bytes[kViewHits] = want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u;
     b.out_bytes[kViewRgb] = want_rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
+    return b;
+}
+
+static_assert(sizeof(RtxLight) == 40 && alignof(RtxLight) == 4 && offsetof(RtxLight, nb_light_sample) == sizeof(rtxl::LightTriangle),
+              "the light kernel is handed the first 36 bytes of an RtxLight");
+
+// The argument checks the lit entry points add to their twins': a light, and at most kMaxCallLightPoints points.  *out: the
+// call's copy of the light (the caller's may change while the call runs), the count the scene's for 0.
+bool lit_of(const RtxScene *scene, const RtxLight *light, Lit *out)
+{
+    if (!scene || !light) return false;
+    std::memcpy(out->tri.v, light->v0, 12);
+    std::memcpy(out->tri.v + 3, light->v1, 12);
+    std::memcpy(out->tri.v + 6, light->v2, 12);
+    out->count = light->nb_light_sample ? light->nb_light_sample : scene->prep.nb_light_sample;
+    return static_cast<uint64_t>(scene->prep.nb_ray) * out->count <= rtx::kMaxCallLightPoints;
+}
+
+// a twin's batch under the call's light: the light kernel ahead of its kernel, the light's count per hit in the statistics
+Batch relit(Batch b, const Lit &lit)
+{
+    b.lit = &lit;
+    b.shadow_rays_per_hit = lit.count;
     return b;
 }
 
@@ -1103,6 +1178,86 @@ int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, voi
     d_out[kViewShade] = d_shade; d_out[kViewHits] = d_hits; d_out[kViewRgb] = d_rgb;
     return batch_device(scene, device, view_batch(scene, view, d_rgb != nullptr, d_shade != nullptr, d_hits != nullptr),
                         nullptr, nullptr, d_out, stream);
+}
+
+int rtx_scene_light(const RtxScene *scene, RtxLight *out)
+{
+    if (!scene || !out) return RTX_ERR_BAD_ARG;
+    const rtx::PreparedScene &p = scene->prep;
+    std::memcpy(out->v0, p.light_v, 12);
+    std::memcpy(out->v1, p.light_v + 3, 12);
+    std::memcpy(out->v2, p.light_v + 6, 12);
+    out->nb_light_sample = p.nb_light_sample;
+    return RTX_OK;
+}
+
+int rtx_render_view_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
+                        RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
+{
+    Lit lit;
+    if (!view_args_ok(scene, view, out_rgb, out_shade, out_hits) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    void *out[kBatchOuts];
+    out[kViewShade] = out_shade; out[kViewHits] = out_hits; out[kViewRgb] = out_rgb;
+    return batch_host(scene, device, relit(view_batch(scene, view, out_rgb != nullptr, out_shade != nullptr, out_hits != nullptr), lit),
+                      nullptr, nullptr, out, stats);
+}
+
+int rtx_render_view_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
+                               void *d_shade, void *d_hits, void *stream)
+{
+    Lit lit;
+    if (!view_args_ok(scene, view, d_rgb, d_shade, d_hits) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
+    void *d_out[kBatchOuts];
+    d_out[kViewShade] = d_shade; d_out[kViewHits] = d_hits; d_out[kViewRgb] = d_rgb;
+    return batch_device(scene, device, relit(view_batch(scene, view, d_rgb != nullptr, d_shade != nullptr, d_hits != nullptr), lit),
+                        nullptr, nullptr, d_out, stream);
+}
+
+int rtx_shade_rays_lit(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
+                       uint32_t flags, const RtxLight *light, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
+{
+    Lit lit;
+    if (!shade_args_ok(scene, origins, directions, out_shade, flags, n_pixels) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, relit(shade_batch(scene, n_pixels, flags, out_hits != nullptr), lit), origins, directions,
+                      {out_shade, out_hits, nullptr}, stats);
+}
+
+int rtx_shade_rays_lit_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
+                              uint32_t flags, const RtxLight *light, void *d_shade, void *d_hits, void *stream)
+{
+    Lit lit;
+    if (!shade_args_ok(scene, d_origins, d_directions, d_shade, flags, n_pixels) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, relit(shade_batch(scene, n_pixels, flags, d_hits != nullptr), lit), d_origins, d_directions,
+                        {d_shade, d_hits, nullptr}, stream);
+}
+
+int rtx_scene_light_points_for(const RtxScene *scene, const RtxLight *light, float *out)
+{
+    Lit lit;
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    const rtx::PreparedScene &p = scene->prep;
+    if (out) rtx::light_points_of(lit.tri.v, p.samples.data(), p.n_samples, p.nb_ray, lit.count, out);
+    return static_cast<int>(p.nb_ray * lit.count);      // <= 2^20
+}
+
+int rtx_debug_light_points(RtxScene *scene, int device, const RtxLight *light, float *out)
+{
+    Lit lit;
+    if (!out || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    if (!light_is_finite(lit)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    if (st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));
+    rtx::DeviceScene S = device_scene(scene, st);
+    const int rc = light_launch(scene, st, lit, &S, st.stream);
+    if (rc != RTX_OK) return rc;
+    const size_t bytes = static_cast<size_t>(S.nb_ray) * S.nb_light * 3u * sizeof(float);
+    if (bytes) RTX_HIP(hipMemcpyAsync(out, S.light_points, bytes, hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    return RTX_OK;
 }
 
 int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats)

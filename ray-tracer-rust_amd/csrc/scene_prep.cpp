@@ -77,17 +77,23 @@ void triangle_derive(const float v0[3], const float v1[3], const float v2[3],
     }
 }
 
-// Triangle::get_sample — triangle.rs:113-127.  The third weight is v*sqrt(u), as in the
-// reference (the weights do not sum to one); kept on purpose.
+// Triangle::get_sample — triangle.rs:113-127: scene_prep.h's light_sample_point, the statement the device compiles too
 void light_sample(const float v0[3], const float v1[3], const float v2[3], float u, float v, float out[3])
 {
-    const float su = std::sqrt(u);
-    const float sv = std::sqrt(v);
-    const float w0 = 1.0f - su;
-    const float w1 = su * (1.0f - sv);
-    const float w2 = v * su;
-    for (int k = 0; k < 3; ++k)
-        out[k] = w0 * v0[k] + w1 * v1[k] + w2 * v2[k];
+    light_sample_point(v0, v1, v2, u, v, out);
+}
+
+// light points: for ray r of a pixel and sample i the reference reads T[(r*NB_RAY + i) % len] (src/main.rs:194-196) —
+// the same points for every pixel
+void light_points_of(const float tri[9], const float *samples, uint32_t n_samples, uint32_t nb_ray, uint32_t nb_light,
+                     float *out)
+{
+    for (uint32_t r = 0; r < nb_ray; ++r)
+        for (uint32_t i = 0; i < nb_light; ++i) {
+            const size_t k = (static_cast<size_t>(r) * nb_ray + i) % n_samples;
+            light_sample_point(tri, tri + 3, tri + 6, samples[2 * k], samples[2 * k + 1],
+                               &out[3 * (static_cast<size_t>(r) * nb_light + i)]);
+        }
 }
 
 // Color::to_rgba on one channel — src/tracer/utils/color.rs:10-13,28-33.
@@ -566,15 +572,11 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
     try {
         s.samples.assign(d.samples, d.samples + 2 * static_cast<size_t>(d.n_samples));
 
-        // light points: for ray r of a pixel and sample i the reference reads
-        // T[(r*NB_RAY + i) % len] (src/main.rs:194-196) — the same points for every pixel
+        std::memcpy(s.light_v, d.light_v0, 12);
+        std::memcpy(s.light_v + 3, d.light_v1, 12);
+        std::memcpy(s.light_v + 6, d.light_v2, 12);
         s.light_points.resize(3 * static_cast<size_t>(d.nb_ray) * d.nb_light_sample);
-        for (uint32_t r = 0; r < d.nb_ray; ++r)
-            for (uint32_t i = 0; i < d.nb_light_sample; ++i) {
-                const size_t k = (static_cast<size_t>(r) * d.nb_ray + i) % d.n_samples;
-                light_sample(d.light_v0, d.light_v1, d.light_v2, d.samples[2 * k], d.samples[2 * k + 1],
-                             &s.light_points[3 * (static_cast<size_t>(r) * d.nb_light_sample + i)]);
-            }
+        light_points_of(s.light_v, d.samples, d.n_samples, d.nb_ray, d.nb_light_sample, s.light_points.data());
 
         // the order of walking them (scene_prep.h: light_tour): per primary ray, per batch of the shading pass
         s.light_tour.resize(4 * static_cast<size_t>(d.nb_ray) * d.nb_light_sample);

@@ -7,12 +7,38 @@
 // Record layouts are shared with the kernel (rtx_kernel.hip includes this file).
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/rtx.h"
 
+// one statement for the host's compiler and the device's, where both must give the same bits
+#if defined(__HIP__)
+#define RTX_HOST_DEVICE __host__ __device__
+#else
+#define RTX_HOST_DEVICE
+#endif
+
 namespace rtx {
+
+// Triangle::get_sample — triangle.rs:113-127.  The third weight is v*sqrt(u), as in the reference (the weights do not sum
+// to one); kept on purpose.  Compiled by the host (light_sample, scene_prep.cpp) and by the device (rtxl::
+// light_points_kernel, rtx_light.hip) from this one text: with -ffp-contract=off on both sides and the device's correctly
+// rounded square root every operation rounds once, in this order, and the two agree bit for bit.
+RTX_HOST_DEVICE inline void light_sample_point(const float v0[3], const float v1[3], const float v2[3], float u, float v,
+                                               float out[3])
+{
+    const float su = sqrtf(u);
+    const float sv = sqrtf(v);
+    const float w0 = 1.0f - su;
+    const float w1 = su * (1.0f - sv);
+    const float w2 = v * su;
+    for (int k = 0; k < 3; ++k)
+        out[k] = w0 * v0[k] + w1 * v1[k] + w2 * v2[k];
+}
+// a call's light may have at most this many points (nb_ray x its sample count): rtx_*_lit, rtx_scene_light_points_for
+constexpr uint64_t kMaxCallLightPoints = 1ull << 20;
 
 // One node of the threaded (pre-order, skip-linked) BVH stream: 8 dwords, fetched
 // by the kernel with one scalar 32-byte load.
@@ -94,6 +120,7 @@ struct PreparedScene {
     std::vector<TriRec>   tris;        // primitive records (triangles and spheres) in leaf order
     std::vector<ShadeRec> shade;       // in caller order
     std::vector<float>    samples;     // n_samples x 2
+    float light_v[9];                  // the light triangle as given: v0, v1, v2 (rtx_scene_light)
     std::vector<float>    light_points;// nb_ray x nb_light_sample x 3
     // The same points in the order the shading pass WALKS them: per primary ray and per batch of kMaxLightBatch
     // consecutive samples a short tour that starts at the batch's first sample (light_tour_order).  One 16-byte record
@@ -145,6 +172,10 @@ void camera_new(const float eye[3], const float look_at[3], const float up[3],
 void triangle_derive(const float v0[3], const float v1[3], const float v2[3],
                      float e1[3], float e2[3], float normal[3], float bmin[3], float bmax[3]);
 void light_sample(const float v0[3], const float v1[3], const float v2[3], float u, float v, float out[3]);
+// out[3 * (r * nb_light + i)] = light_sample(tri, T[(r * nb_ray + i) % n_samples]) for r < nb_ray, i < nb_light
+// (main.rs:194-196; samples: n_samples pairs, n_samples != 0): a scene's light points, and any other light's on it
+void light_points_of(const float tri[9], const float *samples, uint32_t n_samples, uint32_t nb_ray, uint32_t nb_light,
+                     float *out);
 // byte = (x.powf(1/2.2) * 255.0) as u8 with the host libm — color.rs:10-13,28-33
 uint8_t gamma_quantise(float linear);
 int  build_gamma_thresholds(float thr[256]);

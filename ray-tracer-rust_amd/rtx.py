@@ -119,6 +119,14 @@ class RtxView(C.Structure):
 assert C.sizeof(RtxView) == 76 and C.alignment(RtxView) == 4
 
 
+class RtxLight(C.Structure):
+    """RtxLight: the area light of one lit call — Light.primitives[0]'s vertices and NB_LIGHT_SAMPLE (0 = the scene's)."""
+    _fields_ = [("v0", C.c_float * 3), ("v1", C.c_float * 3), ("v2", C.c_float * 3), ("nb_light_sample", C.c_uint32)]
+
+
+assert C.sizeof(RtxLight) == 40 and C.alignment(RtxLight) == 4
+
+
 # every symbol include/rtx.h declares (tests check the export list against the header)
 _SIGS = {
     "rtx_abi_version": (C.c_int, []),
@@ -150,6 +158,17 @@ _SIGS = {
                                               C.c_void_p]),
     "rtx_scene_aimed_nodes": (C.c_int, [C.c_void_p, f32p, u32p]),
     "rtx_debug_aimed_nodes": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p]),
+    "rtx_scene_light": (C.c_int, [C.c_void_p, C.POINTER(RtxLight)]),
+    "rtx_scene_light_points_for": (C.c_int, [C.c_void_p, C.POINTER(RtxLight), f32p]),
+    "rtx_debug_light_points": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxLight), f32p]),
+    "rtx_render_view_lit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
+                                      C.POINTER(PixelShade), C.POINTER(RayHit), C.POINTER(Stats)]),
+    "rtx_render_view_lit_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "rtx_shade_rays_lit": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, C.POINTER(RtxLight),
+                                     C.POINTER(PixelShade), C.POINTER(RayHit), C.POINTER(Stats)]),
+    "rtx_shade_rays_lit_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.POINTER(RtxLight), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -551,11 +570,12 @@ class Scene:
 
     # -- shading rays the caller supplies (GPU only)
     def shade_rays(self, origins, directions, device=0, keep_order=False, stats=False, force_regroup=False,
-                   want_hits=False):
+                   want_hits=False, light=None):
         """render_pixel's body (main.rs:182-239) per pixel of nb_ray consecutive rays -> structured array
         (PIXEL_SHADE_DTYPE) of n / nb_ray records {linear, rgb8, hits}.  want_hits adds the rays' closest hits
         (RAY_HIT_DTYPE, n records, what trace_rays returns); stats adds the statistics, last.  Directions may have any
-        length; keep_order shades in the given order (no regrouping pass): the same bytes either way."""
+        length; keep_order shades in the given order (no regrouping pass): the same bytes either way.  light (an RtxLight:
+        make_light, light()) shades under that light and sample count instead of the scene's (rtx_shade_rays_lit)."""
         o, d = self._ray_arrays(origins, directions)
         if len(o) % self.nb_ray:
             raise ValueError("a pixel is nb_ray = %d consecutive rays" % self.nb_ray)
@@ -563,21 +583,27 @@ class Scene:
         out = np.zeros(n, PIXEL_SHADE_DTYPE)
         hits = np.zeros(len(o), RAY_HIT_DTYPE) if want_hits else None
         st = Stats()
-        _check(_lib.rtx_shade_rays(self._h, device, n, _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup),
-                                   out.ctypes.data_as(C.POINTER(PixelShade)),
-                                   hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None,
-                                   C.byref(st) if stats else None), "rtx_shade_rays")
+        tail = (out.ctypes.data_as(C.POINTER(PixelShade)), hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None,
+                C.byref(st) if stats else None)
+        head = (self._h, device, n, _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup))
+        if light is None:
+            _check(_lib.rtx_shade_rays(*head, *tail), "rtx_shade_rays")
+        else:
+            _check(_lib.rtx_shade_rays_lit(*head, C.byref(light), *tail), "rtx_shade_rays_lit")
         res = (out,) + ((hits,) if want_hits else ()) + ((st.asdict(),) if stats else ())
         return res if len(res) > 1 else out
 
     def shade_rays_device(self, device, n_pixels, d_origins_ptr, d_directions_ptr, d_shade_ptr, d_hits_ptr=None,
-                          stream=None, keep_order=False, force_regroup=False):
+                          stream=None, keep_order=False, force_regroup=False, light=None):
         """Asynchronous shading launch on device buffers the caller owns (n_pixels * nb_ray x 3 float32 twice,
         n_pixels x 16 bytes out, optionally n_pixels * nb_ray x 32 bytes of hit records)."""
-        _check(_lib.rtx_shade_rays_device(self._h, device, n_pixels, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
-                                          self._ray_flags(keep_order, force_regroup), C.c_void_p(d_shade_ptr),
-                                          C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
-                                          C.c_void_p(stream) if stream else None), "rtx_shade_rays_device")
+        head = (self._h, device, n_pixels, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
+                self._ray_flags(keep_order, force_regroup))
+        tail = (C.c_void_p(d_shade_ptr), C.c_void_p(d_hits_ptr) if d_hits_ptr else None, C.c_void_p(stream) if stream else None)
+        if light is None:
+            _check(_lib.rtx_shade_rays_device(*head, *tail), "rtx_shade_rays_device")
+        else:
+            _check(_lib.rtx_shade_rays_lit_device(*head, C.byref(light), *tail), "rtx_shade_rays_lit_device")
 
     # -- any pinhole view of the uploaded scene (GPU only)
     @staticmethod
@@ -596,28 +622,68 @@ class Scene:
         _check(_lib.rtx_scene_view(self._h, C.byref(out)), "rtx_scene_view")
         return out
 
-    def render_view(self, view, device=0, stats=False, want_shade=False, want_hits=False):
+    def render_view(self, view, device=0, stats=False, want_shade=False, want_hits=False, light=None):
         """render_pixel for every pixel of the view's rectangle -> uint8 [ny, nx, 3]; want_shade adds the pixels' records
         (PIXEL_SHADE_DTYPE [ny, nx]: what shade_rays returns for the view's rays), want_hits the rays' closest hits
-        (RAY_HIT_DTYPE [ny, nx, nb_ray]: trace_rays'), stats the statistics, last."""
+        (RAY_HIT_DTYPE [ny, nx, nb_ray]: trace_rays'), stats the statistics, last.  light (an RtxLight: make_light, light())
+        renders under that light and sample count instead of the scene's (rtx_render_view_lit)."""
         out = np.zeros((view.ny, view.nx, 3), np.uint8)
         shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
         hits = np.zeros((view.ny, view.nx, self.nb_ray), RAY_HIT_DTYPE) if want_hits else None
         st = Stats()
-        _check(_lib.rtx_render_view(self._h, device, C.byref(view), out.ctypes.data,
-                                    shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
-                                    hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None,
-                                    C.byref(st) if stats else None), "rtx_render_view")
+        tail = (out.ctypes.data, shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
+                hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None, C.byref(st) if stats else None)
+        if light is None:
+            _check(_lib.rtx_render_view(self._h, device, C.byref(view), *tail), "rtx_render_view")
+        else:
+            _check(_lib.rtx_render_view_lit(self._h, device, C.byref(view), C.byref(light), *tail), "rtx_render_view_lit")
         res = (out,) + ((shade,) if want_shade else ()) + ((hits,) if want_hits else ()) + ((st.asdict(),) if stats else ())
         return res if len(res) > 1 else out
 
-    def render_view_device(self, device, view, d_rgb_ptr=None, d_shade_ptr=None, d_hits_ptr=None, stream=None):
+    def render_view_device(self, device, view, d_rgb_ptr=None, d_shade_ptr=None, d_hits_ptr=None, stream=None, light=None):
         """Asynchronous view launch into device buffers the caller owns, each optional: ny*nx*3 bytes, ny*nx x 16 bytes,
         ny*nx*nb_ray x 32 bytes."""
-        _check(_lib.rtx_render_view_device(self._h, device, C.byref(view), C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
-                                           C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
-                                           C.c_void_p(d_hits_ptr) if d_hits_ptr else None,
-                                           C.c_void_p(stream) if stream else None), "rtx_render_view_device")
+        tail = (C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None, C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
+                C.c_void_p(d_hits_ptr) if d_hits_ptr else None, C.c_void_p(stream) if stream else None)
+        if light is None:
+            _check(_lib.rtx_render_view_device(self._h, device, C.byref(view), *tail), "rtx_render_view_device")
+        else:
+            _check(_lib.rtx_render_view_lit_device(self._h, device, C.byref(view), C.byref(light), *tail),
+                   "rtx_render_view_lit_device")
+
+    # -- another light for views and shaded rays: the light= keyword of render_view* and shade_rays*
+    @staticmethod
+    def make_light(light_tri, nb_light_sample=0):
+        """An RtxLight: the nine floats of Light.primitives[0] (v0, v1, v2) and the sample count, 0 = the scene's."""
+        lt = np.asarray(light_tri, dtype=np.float32).reshape(9)
+        out = RtxLight(nb_light_sample=int(nb_light_sample))
+        out.v0[:], out.v1[:], out.v2[:] = lt[0:3].tolist(), lt[3:6].tolist(), lt[6:9].tolist()
+        return out
+
+    def light(self):
+        """The light and sample count the scene was created with, as an RtxLight (rtx_scene_light)."""
+        out = RtxLight()
+        _check(_lib.rtx_scene_light(self._h, C.byref(out)), "rtx_scene_light")
+        return out
+
+    def light_points_for(self, light):
+        """Host only: float32 [nb_ray * n, 3], the points of `light` on this scene (n: its count, or the scene's for 0)."""
+        n = _lib.rtx_scene_light_points_for(self._h, C.byref(light), None)
+        if n < 0:
+            raise RtxError(n, "rtx_scene_light_points_for")
+        out = np.zeros((n, 3), np.float32)
+        if n and _lib.rtx_scene_light_points_for(self._h, C.byref(light), _fp(out)) != n:
+            raise RtxError(ERR_INTERNAL, "rtx_scene_light_points_for")
+        return out
+
+    def debug_light_points(self, light, device=0):
+        """Diagnostics: the same points as the light kernel makes them on `device`, copied back."""
+        n = _lib.rtx_scene_light_points_for(self._h, C.byref(light), None)
+        if n < 0:
+            raise RtxError(n, "rtx_scene_light_points_for")
+        out = np.zeros((max(n, 1), 3), np.float32)
+        _check(_lib.rtx_debug_light_points(self._h, device, C.byref(light), _fp(out)), "rtx_debug_light_points")
+        return out[:n]
 
     # -- any view through the render pipeline (GPU only)
     def render_view_rows(self, view, device=0, stats=False):
