@@ -172,7 +172,12 @@ int rtx_render_frame(RtxScene *scene, const int *devices, int n_devices, uint32_
  * `stream` (a hipStream_t; NULL = the default stream); inputs must already be uploaded or are
  * uploaded synchronously first.  d_counters: NULL, or a device buffer of 8 uint64 that the kernel
  * ADDS its counters to (primary_hits, box_tests, tri_tests, wave_node_visits, wave_tri_visits, redo_tiles).
- * Launches on one device must be ordered on one stream (the library keeps a per-device work queue). */
+ * Launches on one device must be ordered on one stream (the library keeps a per-device work queue).
+ * Each call must be ENQUEUED by the library: do not capture a render launch into a graph and replay it, and do not
+ * re-enqueue recorded dispatches.  A launch's kernels take, as arguments, which of two sets of counting words this
+ * launch works on — the launch before it zeroed them — and the library advances that choice per call; a replay would run
+ * on words nobody zeroed.  (This holds for every entry point that goes through the render pipeline: rtx_render_rows,
+ * rtx_render_frame, rtx_render_tiles_device, rtx_render_view_rows and rtx_render_view_rows_device.) */
 int rtx_render_tiles_device(RtxScene *scene, int device, uint32_t first_tile, uint32_t tile_stride,
                             uint32_t tile_rows, void *d_out_rgb, size_t d_out_bytes,
                             void *stream, uint64_t *d_counters);
@@ -340,7 +345,7 @@ int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, voi
  * stats mean what they mean for rtx_render_rows, with primary_rays = ny*width*nb_ray and redo_tiles in tiles; kernel_ms
  * includes the aim kernels when they run.  The launches count in rtx_launch_timings (the aim kernels lie outside both of its
  * passes) and rtx_debug_tile_descs like any render launch, and the rule of rtx_render_tiles_device holds unchanged:
- * pipeline launches on one device — these included — must be ordered on one stream.
+ * pipeline launches on one device — these included — must be ordered on one stream, and none may be captured and replayed.
  * A view call leaves every later render, query, shade or view call on the scene unchanged: the prepared scene and its
  * uploaded streams are not written. */
 int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats);

@@ -140,6 +140,12 @@ public:
     DeviceBuffer nodes, primary_nodes, ref_nodes, tris, shade, samples, lights, light_tour, thr, planes, light_boxes;
     DeviceBuffer d_out, d_counters;
     DeviceBuffer d_redo;                 // queue of tiles for reference_tiles_kernel
+    // The two-pass pipeline zeroes its counting words (d_redo's headers, ws.buckets) for the NEXT launch inside each
+    // launch (rtx_kernel.hip: order_tiles_kernel): render_launch zeroes them (zero_launch_words) when they are not known to
+    // be in that state — new or grown, used by another pipeline, a launch that failed — and counts what they have
+    // served since, whose parities select the words a launch works on.
+    bool launch_words_ready = false;
+    uint32_t words_launches = 0, words_passes = 0;
     PinnedBuffer h_stage;
     struct { DeviceBuffer hits, pix_slot, tiles, chunks, results, acc, ctr, buckets, cut; } ws;   // streamed pipeline:
                                                                                     // intermediate products in HBM
@@ -432,6 +438,7 @@ int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpe
                   unsigned long long *d_counters, unsigned long long *d_wave_prof, hipStream_t stream, Before before)
 {
     int rc;
+    const size_t redo_cap = st.d_redo.capacity(), buckets_cap = st.ws.buckets.capacity();
     if ((rc = st.d_redo.reserve(rtx::trace_redo_bytes(S, ts))) != RTX_OK) return rc;
     rtx::StreamWorkspace ws{};
     bool use_ws = false;
@@ -439,8 +446,19 @@ int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpe
     if ((rc = before()) != RTX_OK) return rc;
     const Event *slot = st.ring[st.launches % RTX_TIMING_RING];
     hipEvent_t phases[3] = {slot[0], slot[1], slot[2]};
+    const bool two_pass = use_ws && (kernel_variant() & rtx::kVariantProbe) != 0u && ts.local_rows != 0u;
+    if (two_pass && (!st.launch_words_ready || st.d_redo.capacity() != redo_cap || st.ws.buckets.capacity() != buckets_cap)) {
+        RTX_HIP(rtx::zero_launch_words(st.d_redo.as<uint32_t>(), ws, stream));
+        st.words_launches = st.words_passes = 0;
+    }
+    if (ts.local_rows) st.launch_words_ready = false;     // until this launch is known to have gone out whole
     RTX_HIP(rtx::launch_trace_shade(S, ts, d_out, st.d_redo.as<uint32_t>(), use_ws ? &ws : nullptr, d_counters, d_wave_prof,
-                                    kernel_variant(), stream, d_wave_prof ? nullptr : phases));
+                                    kernel_variant(), stream, d_wave_prof ? nullptr : phases, st.words_launches, st.words_passes));
+    if (two_pass) {
+        st.launch_words_ready = true;
+        ++st.words_launches;
+        st.words_passes += S.nb_ray;
+    }
     if (!d_wave_prof && ts.local_rows) ++st.launches;
     return RTX_OK;
 }

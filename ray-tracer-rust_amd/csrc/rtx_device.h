@@ -159,15 +159,25 @@ constexpr size_t kWaveProfWords = 8;
 uint32_t trace_tiles_x(const DeviceScene &S, uint32_t variant);
 // d_redo: the device work queue of a launch: [kQueueRedoCount] = number of tiles queued for the literal
 // reference traversal, [kQueueNextTile] = next tile the persistent workgroups pull, tile ids from
-// [kQueueHeader]; trace_redo_bytes() is its size for a launch.  Reset and consumed inside the launch.
-constexpr uint32_t kQueueRedoCount = 0u, kQueueNextTile = 1u, kQueueHeader = 4u;
+// [kQueueHeader]; trace_redo_bytes() is its size for a launch.
+// The two-pass pipeline keeps TWO such queues in the buffer, the second kQueueSlotStride words behind the first (its
+// header in the first one's spare words), and launch n works on queue n & 1: no launch zeroes its own count — a launch
+// zeroes the count of the NEXT one's queue, which nobody has read since the launch before (the invariant is written down
+// at order_tiles_kernel).  The single-kernel forms use the first queue and zero its header themselves.
+constexpr uint32_t kQueueRedoCount = 0u, kQueueNextTile = 1u, kQueueHeader = 4u, kQueueSlotStride = 2u;
 size_t trace_redo_bytes(const DeviceScene &S, const TileSpec &ts);
 // ws: workspace of the streamed / probe pipelines (may be NULL: the fused kernel is used then)
 // phase_events: NULL or three events recorded on `stream`: launch start, end of the scheduling pass (probe + order;
 // = start for the single-kernel variants), launch end (rtx_launch_timings)
+// launch_no, pass_no (two-pass pipeline): how many launches, and how many primary-ray passes (nb_ray per launch), this
+// d_redo and this workspace have served since their counting words were last zeroed (zero_launch_words) — by the caller, when
+// either buffer is allocated or grown and after any other pipeline used them.  Their parities select the queue and the
+// histogram a launch works on.
 hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
                               const StreamWorkspace *ws, unsigned long long *d_counters,
                               unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
-                              hipEvent_t *phase_events = nullptr);
+                              hipEvent_t *phase_events = nullptr, uint32_t launch_no = 0u, uint32_t pass_no = 0u);
+// zeroes those counting words (both queues' headers, the workspace's order words in front of its job list) on `stream`
+hipError_t zero_launch_words(uint32_t *d_redo, const StreamWorkspace &ws, hipStream_t stream);
 
 }  // namespace rtx

@@ -4,10 +4,11 @@
 // (src/main.rs:151-240, src/tracer/**); citations are path:line in that repository.
 // The traversal itself is in rtx_traverse.hpp.
 //
-// A launch (launch_probe, further down) is two passes over the 8x8-pixel tiles of its rows:
+// A launch (launch_probe, further down) is two passes over the 8x8-pixel tiles of its rows, four dispatches:
 //   scheduling pass   probe_kernel (one wavefront per tile, one work-item per pixel: primary ray, closest hit,
-//                     compacted hit records to HBM, one probing shadow walk = the tile's cost estimate),
-//                     count_classes_kernel + order_tiles_kernel (counting sort of the tiles by cost class);
+//                     compacted hit records to HBM, one probing shadow walk = the tile's cost estimate, counted in
+//                     a sharded histogram), order_tiles_kernel (counting sort of the tiles by cost class; it also
+//                     zeroes the words the next pass and the next launch count in);
 //   shading pass      shade_tiles_kernel — persistent workgroups of 8 wavefronts pull jobs (tiles or parts of
 //                     tiles) costliest first.  Per job: one work-item per SHADOW RAY — the (hit pixel, light sample)
 //                     pairs are dealt to the wavefronts in chunks of 64 consecutive rays, a thin shaft towards the
@@ -20,7 +21,8 @@
 //                     re-rendered here, one work-item per pixel, with the literal reference traversal.  It reads
 //                     the queue length on the device, so an empty queue costs one kernel boundary.
 //
-// librtx.so holds these five kernels and nothing else.  The earlier forms of the pipeline (a fused single kernel,
+// librtx.so holds these four kernels and two small ones off the frame's path: reset_kernel (the counting words of a new
+// or grown workspace, once) and count_classes_kernel (the whole-stream form's histogram).  The earlier forms of the pipeline (a fused single kernel,
 // a streamed three-kernel pipeline, two rays per lane) live in rtx_ablation_kernels.hpp and are compiled only into
 // librtx_ablation.so (-DRTX_ABLATION=1), where RTX_VARIANT selects them for A/B runs and the variant-equality test.
 //
@@ -564,6 +566,20 @@ __device__ __forceinline__ uint32_t shaft_cut_binary(const NodeDev *__restrict__
     return n_out;
 }
 
+// Where probe_kernel counts its tile's cost class (W.buckets; the layout and who zeroes it: order_tiles_kernel).
+constexpr uint32_t kHistShardsLog = 8u, kHistShards = 1u << kHistShardsLog;
+constexpr uint32_t kOrderHist = kCostBuckets;                                  // first word of counting set 0
+constexpr uint32_t kOrderCursor = kHistShards * kCostBuckets;                  // within a counting set
+constexpr uint32_t kOrderSetWords = kOrderCursor + kCostBuckets;
+// The workspace as the kernels that count see it: W.buckets moved to counting set `set` (0 or 1), so that
+// buckets[kOrderHist + ...] is that set's first word.  The launcher hands this to probe_kernel and count_classes_kernel,
+// and order_tiles_kernel finds its own and the next pass's set through the same function.
+__host__ __device__ inline StreamWorkspace counting_set(StreamWorkspace W, uint32_t set)
+{
+    W.buckets += set * kOrderSetWords;
+    return W;
+}
+
 // WHOLE: the scene does not cut per tile (S.n_nodes > S.cut_max_nodes: shade_tiles_kernel's whole-stream form follows) — an
 // instantiation of its own, so that each carries one probing walk only (the kernel is short of scalar registers)
 template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE>
@@ -752,6 +768,10 @@ __global__ void __launch_bounds__(64 * kProbeWaves, RTX_PROBE_WAVES_PER_SIMD) pr
     if (lane == 0) {
         const bool count_it = !(flags & 2u);
         const uint32_t key = (sky || (flags & 2u)) ? kNone : cost_class(cost);
+        // the histogram order_tiles_kernel sorts by: one add, nothing returned, in the shard of the tile number's low bits.
+        // (Not in the whole-stream form, which is short of scalar registers — the add took its spills from 21 to 39 —
+        //  and whose launches last tens of milliseconds: count_classes_kernel counts for it, as before.)
+        if (!WHOLE && key != kNone) atomicAdd(&W.buckets[kOrderHist + (tile_id & (kHistShards - 1u)) * kCostBuckets + key], 1u);
 #if RTX_EXPERIMENT_PROBE_PHASES
         const unsigned long long pp_t2 = wall_clock64();
         const uint32_t walk_ticks = (uint32_t)(pp_t1 - pp_t0) > 0xFFFFu ? 0xFFFFu : (uint32_t)(pp_t1 - pp_t0);
@@ -774,8 +794,28 @@ __global__ void __launch_bounds__(64 * kProbeWaves, RTX_PROBE_WAVES_PER_SIMD) pr
 
 // Counting sort of the scheduled tiles by cost class, costliest first.  Workspace words (W.buckets):
 //   [0] number of jobs in the order   [kOrderRaisedEnd] how many of them, from the front, run raised (RTX_JOB_PRIORITY)
-//   [kOrderHist + k] tiles of class k (count_classes_kernel)
-//   [kOrderCursor + k] tiles of class k already placed   [kOrderList + i] the i-th job
+//   [kOrderClaim + g] claims of XCD group g (further down)
+//   two counting sets, kOrderSetWords each, from [kOrderHist]; a pass works on set (pass number & 1):
+//     [s * kCostBuckets + k] tiles of class k, shard s of kHistShards — probe_kernel adds 1 for its tile, in the shard
+//                            of the tile number's low bits (whole-stream form: count_classes_kernel, into shard 0);   [kOrderCursor + k] tiles of class k already placed
+//   [kOrderList + i] the i-th job
+// Who zeroes what (no kernel of a launch only zeroes; launch n works on queue n & 1 of d_redo, rtx_device.h):
+//   the counting set of pass p      by order_tiles_kernel of pass p - 1, all workgroups: its last reader is the
+//                                   order_tiles_kernel of pass p - 2, its first writer the probe_kernel of pass p
+//   [0], [kOrderRaisedEnd], the claims, queue[kQueueNextTile]
+//                                   written by workgroup 0 of order_tiles_kernel of the SAME pass: only the shading
+//                                   pass behind it reads them (next tile: the first job nobody is dealt, below)
+//   queue[kQueueRedoCount] of launch n + 1
+//                                   by workgroup 0 of order_tiles_kernel of launch n, every pass: its last reader is the
+//                                   reference_tiles_kernel of launch n - 1; launch n appends to the other queue, over
+//                                   all its passes, and its reference_tiles_kernel reads that
+// The first pass and the first two launches find their words zero because the caller runs zero_launch_words (reset_kernel,
+// once) when it allocates or grows a buffer, and after another pipeline used them (launch_trace_shade).  A kernel boundary
+// is the only synchronisation anywhere.
+// The shards: probe_kernel's wavefronts finish a few hundred tiles per microsecond, four fifths of them in ONE class on
+// a 4096 x 4096 frame (262,144 tiles in 0.3 ms = 700 adds per us to that class).  Tiles in flight together have
+// neighbouring numbers, hence different shards: with 256 shards a word takes under 3 adds per us, where one word per
+// class would be a hot address (a returning atomic per tile on such words once cost 0.38 ms).
 // One workgroup per 1024 tiles: a class's position range starts where the costlier classes end (prefix over the
 // histogram); inside it each workgroup reserves a block with one atomic per class it holds, and its tiles take
 // consecutive slots.  Equal classes within a wavefront are counted by one lane — neighbouring tiles mostly share a
@@ -789,14 +829,15 @@ __global__ void __launch_bounds__(64 * kProbeWaves, RTX_PROBE_WAVES_PER_SIMD) pr
 // outlasts everything else (tools/share_timing.py: 0.48 ms of shading for an eighth of a 1.2 ms frame).  Every class
 // whose tiles cost more than kSplitShare of a workgroup's fair share of the launch's estimated cost is cut into the
 // power of two of parts that brings it below, at most kMaxTileParts.
-constexpr uint32_t kOrderHist = kCostBuckets, kOrderCursor = 2u * kCostBuckets, kOrderList = 3u * kCostBuckets;
+// (kOrderHist, kHistShards, kOrderCursor, kOrderSetWords: in front of probe_kernel, which counts)
+constexpr uint32_t kOrderList = kOrderHist + 2u * kOrderSetWords;
 // Who takes which job.  The persistent workgroups b, b + 8, b + 16, ... share an XCD and with it an L2 (workgroups are
 // dealt round-robin over the eight XCDs: MI355X_MICROARCH.md, workgroup dispatch); the order is dealt to these eight
 // groups in runs of kClaimRun consecutive jobs — neighbouring tiles of one cost class, or the parts of one tile — so that
 // what one L2 holds (node and primitive records of one region of the scene, a tile's hit records and cut) is what its
 // own compute units ask for next.  Group g's k-th claim is job ((k / run) * 8 + g) * run + k % run of the order: every
 // group still goes through the order costliest first, and a group whose share is used up draws from the next group's
-// ([kOrderClaim + g]: claims of group g, zeroed with the histogram).  Speed only: any workgroup may run any job.
+// ([kOrderClaim + g]: claims of group g, zeroed by order_tiles_kernel).  Speed only: any workgroup may run any job.
 #ifndef RTX_CLAIM_RUN_LOG
 #define RTX_CLAIM_RUN_LOG 10      // runs of 16 / 64 / 256 / 1024 / 4096 jobs: the 1M-triangle soup -1.7 / -2.3 / -3.5 / -4.3 / -3.7 %
 #endif
@@ -815,8 +856,15 @@ constexpr uint32_t kOrderClaim = 8u, kClaimRunLog = RTX_CLAIM_RUN_LOG;
 #define RTX_JOB_PRIORITY 1
 #endif
 constexpr bool kJobLevels = RTX_JOB_PRIORITY != 0;
-[[maybe_unused]] constexpr float kRaisedShare = 0.25f;
-[[maybe_unused]] constexpr uint32_t kOrderRaisedEnd = 1u;      // (words 1 .. 7 of W.buckets are spare, and zeroed with the histogram)
+// Round 6, the share by launch size: a launch with fewer than kRaisedSmallJobs jobs per workgroup (a 1080p frame has
+// about 16, one share of an 8-way frame 2, a 4096 x 4096 frame 128) raises from an EIGHTH of the limit — the workgroups
+// of a small launch idle at its end, which is what raising wins back, and a large one has no idle share and only pays
+// for the disturbance (1/8 everywhere had put C4 above the parent's range): C3 0.762 ... 0.770 against 0.771 ... 0.786
+// with a quarter everywhere, one share of 8 0.1926 ... 0.1931 against 0.1934 ... 0.1942, C4 equal, the small bunny's
+// 1080p frame about +0.3 % (0.2686 ... 0.2695 against 0.2679 ... 0.2681 in the shipped build's rounds; against the
+// parent it is -4.7 %)  (profiles/r07/b_ab_piece4.log, d_ab_shipped.log)
+[[maybe_unused]] constexpr float kRaisedShare = 0.25f, kRaisedShareSmall = 0.125f, kRaisedSmallJobs = 64.0f;
+[[maybe_unused]] constexpr uint32_t kOrderRaisedEnd = 1u;      // (words 2 .. 7 of W.buckets are spare)
 [[maybe_unused]] constexpr uint32_t kJobLevelRaised = 2u;
 __device__ __forceinline__ uint32_t claimed_index(uint32_t group, uint32_t k)
 {
@@ -857,7 +905,9 @@ __device__ __forceinline__ float class_cost(uint32_t k)
     return lz ? (float)(2u + half) * (float)(1u << (lz - 1u)) : 1.0f;
 }
 
-// the words a launch's kernels count in, zeroed: queue[first, end) and buckets[0, n)
+// The counting words of a workspace and a queue, zeroed: queue[first, end) and buckets[0, n).  Not part of a launch: the
+// launches keep these words zero for each other (the table in front of kOrderList); zero_launch_words runs this once
+// when a buffer is new or grown or was used by something else.
 __global__ void __launch_bounds__(256) reset_kernel(uint32_t *__restrict__ queue, uint32_t first, uint32_t end,
                                                     uint32_t *__restrict__ buckets, uint32_t n)
 {
@@ -865,6 +915,8 @@ __global__ void __launch_bounds__(256) reset_kernel(uint32_t *__restrict__ queue
     for (uint32_t i = threadIdx.x; i < n; i += 256u) buckets[i] = 0u;
 }
 
+// The whole-stream form's histogram (its probe_kernel does not count): one workgroup per 1024 tiles, equal classes
+// within a wavefront counted by one lane, one global add per class and workgroup, into shard 0 of the pass's set.
 __global__ void __launch_bounds__(1024) count_classes_kernel(uint32_t n_tiles, StreamWorkspace W)
 {
     __shared__ uint32_t count[kCostBuckets];
@@ -884,19 +936,37 @@ __global__ void __launch_bounds__(1024) count_classes_kernel(uint32_t n_tiles, S
     if (tid < kCostBuckets && count[tid] != 0u) atomicAdd(&W.buckets[kOrderHist + tid], count[tid]);
 }
 
-__global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, StreamWorkspace W, uint32_t shade_grid, float split_share)
+// hist_set: the pass's counting set; queue: the launch's queue; next_redo_count: the count word of the next launch's;
+// first_claim: the first job of the order that no workgroup is dealt (shade_tiles_kernel)
+__global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, StreamWorkspace W, uint32_t shade_grid, float split_share,
+                                                           uint32_t hist_set, uint32_t first_claim, uint32_t *__restrict__ queue,
+                                                           uint32_t *__restrict__ next_redo_count)
 {
-    __shared__ uint32_t count[kCostBuckets], start[kCostBuckets], parts_log[kCostBuckets], jobs[kCostBuckets];
-    __shared__ float weight[kCostBuckets];
+    __shared__ uint32_t count[kCostBuckets], start[kCostBuckets], parts_log[kCostBuckets], jobs[kCostBuckets], hist[kCostBuckets];
 #if RTX_JOB_PRIORITY
     __shared__ float raised_cost;             // classes that cost at least this much run their ray loops at a raised priority
 #endif
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint32_t *const set = counting_set(W, hist_set).buckets + kOrderHist;
+    uint32_t *const next_set = counting_set(W, hist_set ^ 1u).buckets + kOrderHist;
     if (tid < kCostBuckets) {
         count[tid] = 0u;
-        weight[tid] = (float)W.buckets[kOrderHist + tid] * class_cost(tid);
+        hist[tid] = 0u;
     }
+    // the histogram: every workgroup adds up the shards for itself, sixteen work-items per class
+    static_assert(kHistShards % 16u == 0u && kCostBuckets == 64u, "1024 work-items: 16 shards x 64 classes at a time");
+    uint32_t in_shards = 0u;
+    for (uint32_t s = tid >> 6; s < kHistShards; s += 16u) in_shards += set[s * kCostBuckets + lane];
     __syncthreads();
+    if (in_shards != 0u) atomicAdd(&hist[lane], in_shards);
+    // what the next pass and the next launch count in, and what this pass's shade_tiles_kernel claims from
+    // (the table in front of kOrderList)
+    for (uint32_t w = blockIdx.x * 1024u + tid; w < kOrderSetWords; w += gridDim.x * 1024u) next_set[w] = 0u;
+    if (blockIdx.x == 0) {
+        if (tid < 8u) W.buckets[kOrderClaim + tid] = 0u;
+        if (tid == 8u) queue[kQueueNextTile] = first_claim;
+        if (tid == 9u) *next_redo_count = 0u;
+    }
     const uint32_t i = blockIdx.x * 1024u + tid;
     const uint32_t key = i < n_tiles ? W.tiles[i].first : kNone;
     uint32_t slot = 0u;                       // this tile's position among the workgroup's tiles of its class
@@ -910,11 +980,12 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
         if (key == k0) slot = off + (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
         todo &= ~same;
     }
+    __syncthreads();
     if (tid < kCostBuckets) {
         // parts per tile of this class: the same numbers in every workgroup (histogram and arguments only)
         float total = 0.0f;
         uint32_t scheduled = 0u;
-        for (uint32_t k = 0; k < kCostBuckets; ++k) { total += weight[k]; scheduled += W.buckets[kOrderHist + k]; }
+        for (uint32_t k = 0; k < kCostBuckets; ++k) { total += (float)hist[k] * class_cost(k); scheduled += hist[k]; }
         // With few tiles per workgroup the makespan is quantised by whole jobs (2 or 3 of them): finer parts then pay
         // for their fixed cost, which they do not when every workgroup has many jobs to even things out
         // (tools/share_timing.py: a quarter of the share costs a full C3 frame 3 %, and gains an eighth of it 10 %).
@@ -928,9 +999,9 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
         uint32_t lg = 0u;
         while ((1u << lg) < most_parts && class_cost(tid) > limit * (float)(1u << lg)) ++lg;
         parts_log[tid] = lg;
-        jobs[tid] = W.buckets[kOrderHist + tid] << lg;
+        jobs[tid] = hist[tid] << lg;
 #if RTX_JOB_PRIORITY
-        if (tid == 0) raised_cost = limit * kRaisedShare;
+        if (tid == 0) raised_cost = limit * (per_wg < kRaisedSmallJobs ? kRaisedShareSmall : kRaisedShare);
 #endif
     }
     __syncthreads();
@@ -938,14 +1009,16 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(uint32_t n_tiles, Str
         uint32_t before = 0u;                 // jobs of costlier classes
         for (uint32_t k = tid + 1u; k < kCostBuckets; ++k) before += jobs[k];
         const uint32_t mine = count[tid];
-        start[tid] = before + ((mine ? atomicAdd(&W.buckets[kOrderCursor + tid], mine) : 0u) << parts_log[tid]);
+        start[tid] = before + ((mine ? atomicAdd(&set[kOrderCursor + tid], mine) : 0u) << parts_log[tid]);
         if (blockIdx.x == 0 && tid == 0) W.buckets[0] = before + jobs[0];
 #if RTX_JOB_PRIORITY
         // the order is costliest first: the raised classes' jobs are its first [kOrderRaisedEnd]
-        // (written by the cheapest raised class; when no class costs that much the word stays zero)
+        // (written by the cheapest raised class; class_cost rises with the class, so when the costliest class does not
+        //  cost that much none does, and that class writes zero: the word is written by every pass)
         const bool raised = tid != 0u && class_cost(tid) >= raised_cost;
         const bool cheaper_raised = tid > 1u && class_cost(tid - 1u) >= raised_cost;
         if (blockIdx.x == 0 && raised && !cheaper_raised) W.buckets[kOrderRaisedEnd] = before + jobs[tid];
+        if (blockIdx.x == 0 && tid == kCostBuckets - 1u && !raised) W.buckets[kOrderRaisedEnd] = 0u;
 #endif
     }
     __syncthreads();
@@ -1062,6 +1135,16 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
     constexpr bool xcd_queues = WHOLE;
     const uint32_t group0 = blockIdx.x & 7u;
     uint32_t groups_done = 0u, g_ahead = 0u;      // (state of the work-item that claims the jobs)
+    // A workgroup's FIRST job is dealt, not claimed: workgroup b takes job b of the order, and the claims start behind
+    // the grid (order_tiles_kernel sets the cursor there).  The grid's workgroups start within a microsecond of each
+    // other, and a thousand claims on one word take about ten (88 adds per us): the order's first jobs, the costliest,
+    // started that late.  Measured: the shading pass 9 ... 10 us shorter on a 1080p frame of either bunny and on the
+    // 4096 x 4096 frame (profiles/r07/a_ab_pieces.log).
+    if (!xcd_queues) {
+        job_ahead = blockIdx.x < n_jobs ? W.buckets[kOrderList + blockIdx.x] : kNone;
+        if (kJobLevels) pos_ahead = blockIdx.x;
+        have_ahead = true;
+    }
     // the light points are the same for every job of a launch (main.rs:194-196: sample i of primary ray r): when one batch
     // holds them all they are staged once, not once per job (a global round trip of 2.4 us in front of every job's rays)
     const bool lights_once = S.nb_light <= batch;
@@ -1480,7 +1563,10 @@ namespace {
 // (the ablation build reads RTX_SPLIT_SHARE once instead: tools/share_timing.py sweeps it)
 // (50 until the estimates learned to tell the tiles apart — the probing walk of cut tiles, mixed tiles twice; with them
 //  a whole fair share: big_bunny 1080p 0.855 -> 0.825 ms over five interleaved rounds, one share of 4 / 8 -1.3 / -0.4 %,
-//  of 2 +0.8 %; profiles/r03/xh_ab_split_share.log)
+//  of 2 +0.8 %; profiles/r03/xh_ab_split_share.log.  Round 6 gave half a share its six rounds: alone, big_bunny 1080p
+//  0.7585 ... 0.7655 against 0.7714 ... 0.7864, everything else +0.1 ... 0.3 %; TOGETHER with the raised share by launch
+//  size, which is worth as much there and costs less elsewhere, the small bunny's frame +4 % (0.2802 ... 0.2818 against
+//  0.2688 ... 0.2694): a whole share stays; profiles/r07/b_ab_piece4.log, c_ab_piece4_combined.log)
 #ifndef RTX_SPLIT_SHARE_PERCENT
 #define RTX_SPLIT_SHARE_PERCENT 100
 #endif
@@ -1501,7 +1587,8 @@ float split_share()
 
 template <bool COUNT, bool FAST, bool SPHERES>
 hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
-                        const StreamWorkspace &W, unsigned long long *d_counters, hipStream_t stream, hipEvent_t *ev)
+                        const StreamWorkspace &W, unsigned long long *d_counters, hipStream_t stream, hipEvent_t *ev,
+                        uint32_t launch_no, uint32_t pass_no)
 {
 #ifndef RTX_SHADE_NW
 #define RTX_SHADE_NW 8
@@ -1537,28 +1624,30 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
     if (n_tiles > kJobTileMask) return hipErrorInvalidValue;
     const uint64_t most_jobs = (uint64_t)n_tiles * kMaxTileParts;
     const uint32_t grid = most_jobs < static_cast<uint64_t>(cached_blocks) ? (uint32_t)most_jobs : static_cast<uint32_t>(cached_blocks);
+    uint32_t *const queue = d_redo + (launch_no & 1u) * kQueueSlotStride;            // rtx_device.h: two queues, taken in turn
+    uint32_t *const next_redo_count = d_redo + ((launch_no + 1u) & 1u) * kQueueSlotStride + kQueueRedoCount;
     for (uint32_t r = 0; r < S.nb_ray; ++r) {                                        // main.rs:186
-        // one small kernel instead of two fills (a launch's dispatches are what an eighth of a 1080p frame is made of):
-        // the queue's header before the first primary ray, its tile cursor before the others; the order's histogram,
-        // cursors and claims every time
-        hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(256), 0, stream, d_redo, r == 0u ? 0u : kQueueNextTile,
-                           r == 0u ? kQueueHeader : kQueueNextTile + 1u, W.buckets, 3u * kCostBuckets);
+        // four dispatches a pass, five in the whole-stream form: no kernel only zeroes, and only the whole-stream form has
+        // one that only counts (the table in front of kOrderList)
+        const uint32_t hist_set = (pass_no + r) & 1u;
+        const StreamWorkspace Wp = counting_set(W, hist_set);      // what the kernels that count are handed
         hipLaunchKernelGGL(whole ? (probe_kernel<COUNT, FAST, SPHERES, true>) : (probe_kernel<COUNT, FAST, SPHERES, false>),
                            dim3(512u * ((n_tiles + 511u) / 512u)), dim3(64 * kProbeWaves), 0, stream,   // whole runs of 64 tile numbers, 8 XCDs
-                           S, ts, tiles_x, n_tiles, r, W, d_out, d_redo, d_counters);
-        hipLaunchKernelGGL(count_classes_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, W);
-        hipLaunchKernelGGL(order_tiles_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, W, grid, split_share());
+                           S, ts, tiles_x, n_tiles, r, Wp, d_out, queue, d_counters);
+        if (whole) hipLaunchKernelGGL(count_classes_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, Wp);
+        hipLaunchKernelGGL(order_tiles_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, W, grid, split_share(),
+                           hist_set, whole ? 0u : grid, queue, next_redo_count);
         if (ev && r == 0u && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;   // end of the scheduling pass
         if (whole)
             hipLaunchKernelGGL((shade_tiles_kernel<COUNT, FAST, NW, SPHERES, true>), dim3(grid), dim3(64 * NW), lds_bytes, stream, S, ts,
-                               batch, tiles_x, n_tiles, r, W, d_out, d_redo, d_counters);
+                               batch, tiles_x, n_tiles, r, W, d_out, queue, d_counters);
         else
             hipLaunchKernelGGL((shade_tiles_kernel<COUNT, FAST, NW, SPHERES, false>), dim3(grid), dim3(64 * NW), lds_bytes, stream, S, ts,
-                               batch, tiles_x, n_tiles, r, W, d_out, d_redo, d_counters);
+                               batch, tiles_x, n_tiles, r, W, d_out, queue, d_counters);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL((reference_tiles_kernel<COUNT, SPHERES>), dim3(n_tiles < 1024u ? n_tiles : 1024u), dim3(64), 0, stream,
-                       S, ts, tiles_x, d_out, d_redo, d_counters, true);
+                       S, ts, tiles_x, d_out, queue, d_counters, true);
     return hipGetLastError();
 }
 
@@ -1570,9 +1659,15 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
 
 uint32_t trace_tiles_x(const DeviceScene &S, uint32_t variant) { return (S.width + 7u) / 8u; }
 
+hipError_t zero_launch_words(uint32_t *d_redo, const StreamWorkspace &W, hipStream_t stream)
+{
+    hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(256), 0, stream, d_redo, 0u, kQueueSlotStride + kQueueHeader, W.buckets, kOrderList);
+    return hipGetLastError();
+}
+
 size_t trace_redo_bytes(const DeviceScene &S, const TileSpec &ts)
 {
-    return sizeof(uint32_t) * (kQueueHeader + static_cast<size_t>(numbered_tiles((S.width + 7u) / 8u, (ts.local_rows + 7u) / 8u)));
+    return sizeof(uint32_t) * (kQueueSlotStride + kQueueHeader + static_cast<size_t>(numbered_tiles((S.width + 7u) / 8u, (ts.local_rows + 7u) / 8u)));
 }
 
 StreamWorkspaceBytes stream_workspace_bytes(const DeviceScene &S, const TileSpec &ts, uint32_t variant)
@@ -1590,46 +1685,47 @@ StreamWorkspaceBytes stream_workspace_bytes(const DeviceScene &S, const TileSpec
     b.results = streamed ? pixels * (S.nb_light ? S.nb_light : 1u) * sizeof(float) : 0u;
     b.acc = S.nb_ray > 1u ? pixels * 3u * sizeof(float) : 0u;
     b.ctr = kStreamCtrWords * sizeof(uint32_t);   // streamed (ablation) pipeline only; 16 B
-    b.buckets = probe ? (3u * kCostBuckets + tiles * kMaxTileParts) * sizeof(uint32_t) : 0u;
+    b.buckets = probe ? (kOrderList + tiles * kMaxTileParts) * sizeof(uint32_t) : 0u;
     b.cut = probe ? cut_stream_offset(tiles) + tiles * kCutStreamRecords * sizeof(NodeDev) : 0u;     // CutEntry arrays, then the cut streams
     return b;
 }
 
 static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
                                   const StreamWorkspace *ws, unsigned long long *d_counters,
-                                  unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream, hipEvent_t *ev)
+                                  unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream, hipEvent_t *ev,
+                                  uint32_t launch_no, uint32_t pass_no)
 {
 #if RTX_ABLATION
     if (!((variant & kVariantProbe) && ws && !d_wave_prof))
         return launch_dispatch_ablation(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream);
     if (!(variant & 1u)) {   // the two-pass pipeline with the exact (division-based) box test on inner nodes
         if (S.n_spheres)
-            return d_counters ? launch_probe<true, false, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev)
-                              : launch_probe<false, false, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev);
-        return d_counters ? launch_probe<true, false, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev)
-                          : launch_probe<false, false, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev);
+            return d_counters ? launch_probe<true, false, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no)
+                              : launch_probe<false, false, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no);
+        return d_counters ? launch_probe<true, false, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no)
+                          : launch_probe<false, false, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no);
     }
 #else
     if (variant != kDefaultVariant || !ws || d_wave_prof) return hipErrorInvalidValue;   // one pipeline in this build
 #endif
     if (S.n_spheres)
-        return d_counters ? launch_probe<true, true, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev)
-                          : launch_probe<false, true, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev);
-    return d_counters ? launch_probe<true, true, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev)
-                      : launch_probe<false, true, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev);
+        return d_counters ? launch_probe<true, true, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no)
+                          : launch_probe<false, true, true>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no);
+    return d_counters ? launch_probe<true, true, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no)
+                      : launch_probe<false, true, false>(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no);
 }
 
 hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
                               const StreamWorkspace *ws, unsigned long long *d_counters,
                               unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
-                              hipEvent_t *phase_events)
+                              hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no)
 {
     if (ts.local_rows == 0) return hipSuccess;
     hipError_t e;
     if (phase_events && (e = hipEventRecord(phase_events[0], stream)) != hipSuccess) return e;
     const bool probe = (variant & kVariantProbe) && ws && !d_wave_prof;
     if (phase_events && !probe && (e = hipEventRecord(phase_events[1], stream)) != hipSuccess) return e;
-    e = launch_dispatch(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream, probe ? phase_events : nullptr);
+    e = launch_dispatch(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream, probe ? phase_events : nullptr, launch_no, pass_no);
     if (e != hipSuccess) return e;
     if (phase_events && (e = hipEventRecord(phase_events[2], stream)) != hipSuccess) return e;
     return hipSuccess;

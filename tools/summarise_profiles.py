@@ -5,7 +5,9 @@ profiles/pmc_summary.json and profiles/traffic.json, and copy the evidence into 
     python tools/summarise_profiles.py gpurun_out/prof_j c3 profiles/r01 j
 
 Counters are averaged over the dispatches of the uncounted kernels (template argument COUNT = false) of the
-profiled run; one launch = reset_kernel + probe_kernel + count_classes_kernel + order_tiles_kernel + shade_tiles_kernel + reference_tiles_kernel.
+profiled run; one launch = probe_kernel + order_tiles_kernel + shade_tiles_kernel + reference_tiles_kernel (the whole-stream
+form: count_classes_kernel between the first two; reset_kernel runs once per allocation; profiles from before round 6
+have both in every launch).
 FETCH_SIZE / WRITE_SIZE are in KiB; FETCH_SIZE under-reports wide coalesced reads by 2x on gfx950
 (MI355X_MICROARCH.md), so the x2 figure is used as the upper bound, WRITE_SIZE as it is.
 """
