@@ -377,8 +377,8 @@ int rtx_debug_aimed_nodes(RtxScene *scene, int device, const float eye[3], uint3
  * There is no range rule on the light: a vertex may lie anywhere, beyond the scene's largest coordinate included.  A shadow
  * ray's ORIGIN is the hit point, which is what the walks' choice of box test is voted on; the light point is the ray's
  * target, unrestricted as rtx_occluded_rays' targets are.
- * The render pipeline (rtx_render_rows, rtx_render_view_rows) has no lit form: it also reads the light's tour, boxes and
- * shaft margin, which rtx_scene_create alone makes.
+ * The render pipeline reads more of the light than its points — the tour, the boxes and the shaft margin that
+ * rtx_scene_create makes: its lit form is rtx_render_view_rows_lit, below, which makes them per call.
  * A lit call leaves every later call on the scene unchanged: the prepared scene and its uploaded light are not written. */
 typedef struct RtxLight {          /* 40 bytes, alignment 4 */
     float v0[3], v1[3], v2[3];     /* Light.primitives[0] (light.rs:11-13): the triangle get_sample samples */
@@ -407,6 +407,44 @@ int rtx_shade_rays_lit_device(RtxScene *scene, int device, uint32_t n_pixels, co
 /* Diagnostic: runs the light kernel for `light` on `device`, blocks, and copies the device's points back: nb_ray * count
  * x 3 floats, as rtx_scene_light_points_for.  Errors as the lit calls'. */
 int rtx_debug_light_points(RtxScene *scene, int device, const RtxLight *light, float *out);
+
+/* ---- another light through the render pipeline ------------------------------------ */
+/* rtx_render_view_rows under ANY light: the bytes are rtx_render_rows(y0, ny) of a reference Scene created with the view's
+ * camera and frame, the given triangle as light.primitives[0] and the given count as NB_LIGHT_SAMPLE — the bytes
+ * rtx_render_view_lit gives for the same view and light, at the pipeline's speed.
+ *
+ * The pipeline's kernels are the ones rtx_render_view_rows launches, unchanged; they read the light as five fields of their
+ * argument block, which a lit call swaps: the points (rtx_light.hip's kernel), the order each batch of 128 samples is
+ * walked in and the points' box per primary ray (two kernels, rtx_tour.hip), the sample count, and the tile shaft test's
+ * margin, which the host computes (O(nb_ray * count), microseconds) as rtx_scene_create does: 2^-16 x the largest coordinate
+ * magnitude of the scene, the eye rtx_scene_create was given and this light's points, + 2^-100.  The light kernels run on
+ * the call's stream behind the aim kernels, ahead of the scheduling pass, in buffers of the library's own per device
+ * beside the points', under the same rules: they grow only (growing waits for the device), there is no cache (every lit
+ * call runs the kernels), device-resident lit launches on one device must be ordered on one stream, and the host entry
+ * points wait (on the device, by an event) for the most recent of them.  The tour is a statement of its own
+ * (rtx_scene_light_walk_for): rtx_scene_create's scan with f32 distances, so that the device makes it word for word; it
+ * decides the order shadow rays are walked in, never a byte.
+ *
+ * Each call is its unlit twin — rtx_render_view_rows, rtx_render_view_rows_device — in every other respect: full width only,
+ * the eye's range rule (RTX_ERR_UNSUPPORTED before a device is looked for), ny == 0 gives RTX_OK with stats zeroed and no
+ * device needed, d_bytes is checked, stats as rtx_render_rows' with shadow_rays = count * primary_hits, kernel_ms includes the
+ * aim and light kernels, the launch counts in rtx_launch_timings (the light kernels lie outside both passes, as the aim
+ * kernels do) and rtx_debug_tile_descs, no capture and replay, pipeline launches on one device ordered on one stream.
+ * The lit calls' own rules: RTX_ERR_BAD_ARG for light == NULL or nb_ray * count > 2^20 (count: the light's, or the scene's
+ * for 0); RTX_ERR_UNSUPPORTED for a vertex coordinate that is not finite, decided on the host; the light is read before the
+ * call returns.  One more rule, rtx_scene_create's own: RTX_ERR_UNSUPPORTED when the margin above is not finite — a pipeline
+ * call accepts exactly the lights rtx_scene_create would accept.  There is no other range rule on the light: it is never a
+ * ray's origin, and the margin grows with its coordinates as it does for a created scene.  When the scene's own count is 0
+ * and the light's is 0 no light kernel runs: the bytes are the unlit call's.
+ * A lit call leaves every later call on the scene unchanged. */
+int rtx_render_view_rows_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
+                             RtxStats *stats);
+int rtx_render_view_rows_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
+                                    size_t d_bytes, void *stream, uint64_t *d_counters);
+/* Diagnostic: runs the light kernels for `light` on `device`, blocks, and copies back the tour records — nb_ray * count x 4
+ * words: x, y, z and, as bits, the sample's index within its batch, in walk order — and the boxes, nb_ray x 6 floats (lo
+ * xyz, hi xyz).  Errors as the lit calls' (the margin is not looked at); both outputs are required. */
+int rtx_debug_light_walk(RtxScene *scene, int device, const RtxLight *light, float *out_tour, float *out_boxes);
 
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
@@ -453,6 +491,19 @@ int rtx_scene_light_points_for(const RtxScene *scene, const RtxLight *light, flo
    its first sample: a short tour of the light (nearest neighbour, then 2-opt).  The order of a pixel's additions is the
    reference's, by ascending sample index, whatever this order is. */
 int rtx_scene_light_order(const RtxScene *scene, uint32_t *out);
+/* host only, no device: what the walk kernels make for `light` on this scene (rtx_render_view_rows_lit), n its count or, for
+   0, the scene's.  out_order: nb_ray * n words in rtx_scene_light_order's form.  Every batch is a permutation of its own
+   indices that starts with its first sample, whatever the points hold, made by this scan in f32: D(a, b) =
+   sqrtf((e0*e0 + e1*e1) + e2*e2), e_k = a_k - b_k; nearest neighbour from the batch's first point with `d < best` only (a
+   NaN or infinite distance never wins; a step that nothing wins goes to the lowest index left); then first-improvement 2-opt
+   on the open path, i ascending, then j ascending, reversing positions [i, j] when after < before, where before = D(i-1, i)
+   [+ D(j, j+1)] and after = D(i-1, j) [+ D(i, j+1)] are f32 sums (the second term when j is not the path's end), at most 32
+   passes, position 0 never moving.  It is not rtx_scene_light_order's scan, which measures in double.  out_boxes: nb_ray x
+   6 floats, lo xyz and hi xyz of the ray's points by fmin / fmax from -+infinity (a NaN is ignored).  out_shaft_delta: the
+   margin of the shaft test under this light, bit for bit rtx_scene_create's for rtx_scene_light's value.  Each output may
+   be NULL.  Returns the number of points, or a negative RtxError: RTX_ERR_BAD_ARG as rtx_scene_light_points_for. */
+int rtx_scene_light_walk_for(const RtxScene *scene, const RtxLight *light, uint32_t *out_order, float *out_boxes,
+                             float *out_shaft_delta);
 /* out: 256 floats; byte value of a linear channel x = number of thresholds b>=1 with thr[b] <= x */
 int rtx_scene_gamma_thresholds(const RtxScene *scene, float *out256);
 /* out: (n_tris + n_spheres) x 3 in Vec order: unit normal of a triangle (Triangle::new, triangle.rs:29),

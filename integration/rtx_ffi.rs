@@ -199,6 +199,20 @@ extern "C" {
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.
     pub fn rtx_debug_light_points(scene: *mut RtxScene, device: c_int, light: *const RtxLight, out: *mut f32) -> c_int;
+    /// `rtx_render_view_rows` / `_device` under another light: `rtx_render_view_lit`'s bytes at the pipeline's speed.  The
+    /// twins' rules (full width, the eye's range) and the lit calls' (NULL light, 2^20 points, finite vertices); also
+    /// `RTX_ERR_UNSUPPORTED` for a light `rtx_scene_create` would refuse (its shaft margin is not finite).
+    pub fn rtx_render_view_rows_lit(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                    out_rgb: *mut u8, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_rows_lit_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                           d_rgb: *mut c_void, d_bytes: usize, stream: *mut c_void,
+                                           d_counters: *mut u64) -> c_int;
+    /// Host only: the walk order, boxes and shaft margin of `light` on this scene (each may be NULL); returns the point count.
+    pub fn rtx_scene_light_walk_for(scene: *const RtxScene, light: *const RtxLight, out_order: *mut u32, out_boxes: *mut f32,
+                                    out_shaft_delta: *mut f32) -> c_int;
+    /// Diagnostic: the tour records and boxes as the light kernels make them on `device`.
+    pub fn rtx_debug_light_walk(scene: *mut RtxScene, device: c_int, light: *const RtxLight, out_tour: *mut f32,
+                                out_boxes: *mut f32) -> c_int;
     pub fn rtx_launch_timings(scene: *mut RtxScene, device: c_int, max_launches: c_int, schedule_ms: *mut f32,
                               shade_ms: *mut f32) -> c_int;
     pub fn rtx_strerror(err: c_int) -> *const c_char;

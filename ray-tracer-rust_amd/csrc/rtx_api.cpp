@@ -25,6 +25,7 @@
 #include "rtx_light.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
+#include "rtx_tour.h"
 #include "rtx_view.h"
 #include "scene_prep.h"
 
@@ -165,8 +166,9 @@ public:
     // rtx_*_lit (rtx_light.hip): the points of the most recent lit call's light, made on that call's stream ahead of its
     // view or shade kernel; `used` is recorded behind a device-resident lit launch on the CALLER's stream: a host call, which
     // uses the same buffer on the library's stream, waits for it first
+    // rtx_render_view_rows_lit (rtx_tour.hip) adds the tour and the boxes of that light, under the same rules
     struct {
-        DeviceBuffer points;
+        DeviceBuffer points, tour, boxes;
         Event used;
     } lit;
 private:
@@ -618,6 +620,80 @@ bool light_is_finite(const Lit &lit)
     return true;
 }
 
+// What the render pipeline reads of a call's light beside its points, as the host states it: per primary ray and batch the
+// tour as sample indices (rtx_scene_light_order's form), the boxes, and the shaft margin, PreparedScene::shaft_delta's fold
+// over this light's boxes.  Each output may be NULL.  O(nb_ray * count) for the margin alone; the tour costs what
+// light_tour_order_f32 costs.  May throw std::bad_alloc.
+void light_walk_on_host(const rtx::PreparedScene &p, const Lit &lit, uint32_t *order, float *boxes, float *shaft_delta)
+{
+    const size_t n = static_cast<size_t>(p.nb_ray) * lit.count;
+    std::vector<float> points(3u * n), box(6u * static_cast<size_t>(p.nb_ray));
+    rtx::light_points_of(lit.tri.v, p.samples.data(), p.n_samples, p.nb_ray, lit.count, points.data());
+    rtx::light_boxes_of(points.data(), p.nb_ray, lit.count, box.data());
+    if (boxes) std::memcpy(boxes, box.data(), box.size() * sizeof(float));
+    if (shaft_delta) *shaft_delta = rtx::shaft_delta_of(p.scene_magnitude, box.data(), box.size());
+    if (!order) return;
+    for (uint32_t r = 0; r < p.nb_ray; ++r)
+        for (uint32_t b0 = 0; b0 < lit.count; b0 += rtx::kMaxLightBatch) {
+            const uint32_t bc = std::min(lit.count - b0, rtx::kMaxLightBatch);
+            const size_t first = static_cast<size_t>(r) * lit.count + b0;
+            rtx::light_tour_order_f32(&points[3u * first], bc, order + first);
+            for (uint32_t k = 0; k < bc; ++k) order[first + k] += b0;
+        }
+}
+
+// The checks a lit pipeline call adds on the host, before a device is looked for, and the margin of its shaft test: the
+// vertices finite, and the margin finite — prepare_scene's own rule, so that a pipeline call accepts exactly the lights
+// rtx_scene_create would accept.  A count of 0 (the scene's own is 0 and so is the light's): nothing is swapped.
+int lit_rows_margin(const RtxScene *scene, const Lit &lit, float *shaft_delta)
+{
+    if (!light_is_finite(lit)) return RTX_ERR_UNSUPPORTED;
+    *shaft_delta = scene->prep.shaft_delta;
+    if (lit.count == 0u) return RTX_OK;
+    try {
+        light_walk_on_host(scene->prep, lit, nullptr, nullptr, shaft_delta);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return std::isfinite(*shaft_delta) ? RTX_OK : RTX_ERR_UNSUPPORTED;
+}
+
+// the three buffers of a lit pipeline call, sized before anything of the call is on a stream (light_launch's rule)
+int reserve_light_walk(const RtxScene *scene, DeviceState &st, const Lit &lit)
+{
+    const size_t n = static_cast<size_t>(scene->prep.nb_ray) * lit.count;
+    const size_t points = std::max<size_t>(n * 3u * sizeof(float), 16u), tour = std::max<size_t>(n * 4u * sizeof(float), 16u);
+    const size_t boxes = std::max<size_t>(static_cast<size_t>(scene->prep.nb_ray) * 6u * sizeof(float), 16u);
+    if (st.lit.points.capacity() >= points && st.lit.tour.capacity() >= tour && st.lit.boxes.capacity() >= boxes) return RTX_OK;
+    RTX_HIP(hipDeviceSynchronize());
+    return reserve_all({{st.lit.points, points}, {st.lit.tour, tour}, {st.lit.boxes, boxes}});
+}
+
+// The light kernels of a lit pipeline call on `stream`: the points, their tour, their boxes.  Caller holds the slot's lock,
+// has the device current and the scene uploaded, and has called reserve_light_walk.
+int light_walk_launch(const RtxScene *scene, DeviceState &st, const Lit &lit, hipStream_t stream)
+{
+    if (lit.count == 0u) return RTX_OK;
+    const rtx::PreparedScene &p = scene->prep;
+    RTX_HIP(rtxl::launch_light_points(st.samples.as<const float2>(), p.n_samples, lit.tri, p.nb_ray, lit.count,
+                                      st.lit.points.as<float>(), stream));
+    RTX_HIP(rtxt::launch_tour(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.tour.as<float>(), stream));
+    RTX_HIP(rtxt::launch_light_boxes(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.boxes.as<float>(), stream));
+    return RTX_OK;
+}
+
+// ... and the five fields of the call's copy of the scene's argument block that the pipeline's kernels read of the light
+// (rtx_kernel.hip reads nothing else of it); the workspace and the LDS of the launch are sized by S.nb_light
+void light_walk_swap(const DeviceState &st, const Lit &lit, float shaft_delta, rtx::DeviceScene *S)
+{
+    if (lit.count == 0u) return;
+    S->light_points = st.lit.points.as<const float>();
+    S->light_tour = st.lit.tour.as<const float>();
+    S->light_boxes = st.lit.boxes.as<const float>();
+    S->shaft_delta = shaft_delta;
+    S->nb_light = lit.count;
+}
+
 // key + sort + kernel of one batch on `stream`; caller holds the slot's lock, has the device current and the scene uploaded
 int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *d_first, const float *d_second,
                  void *const d_out[kBatchOuts], unsigned long long *d_counters, hipStream_t stream)
@@ -837,14 +913,18 @@ int aim_at(RtxScene *scene, DeviceState &st, const float eye[3], hipStream_t str
 }
 
 // rtx_render_rows / rtx_render_tiles_device for a view: device_scene() with the view's frame and camera and the aimed
-// stream, rows [y0, y0 + ny) as one share.  `before`: as render_launch's; the aim kernels follow it on the stream.
+// stream, rows [y0, y0 + ny) as one share.  `before`: as render_launch's; the aim kernels follow it on the stream.  lit:
+// NULL, or the call's light with its margin (lit_rows_margin): the light kernels follow the aim kernels, and the pipeline's
+// kernels are handed that light's five fields.
 template <class Before>
 int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t *d_out, unsigned long long *d_counters,
-                     hipStream_t stream, Before before)
+                     hipStream_t stream, Before before, const Lit *lit = nullptr, float shaft_delta = 0.0f)
 {
     int rc = reserve_aimed(scene, st);
     if (rc != RTX_OK) return rc;
+    if (lit && (rc = reserve_light_walk(scene, st, *lit)) != RTX_OK) return rc;
     rtx::DeviceScene S = device_scene(scene, st);
+    if (lit) light_walk_swap(st, *lit, shaft_delta, &S);
     S.width = v.width;
     S.height = v.height;
     std::memcpy(S.eye, v.eye, 12);
@@ -855,8 +935,10 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t
     S.primary_nodes = aimed_stream(scene, st);
     const rtx::TileSpec ts{v.y0, v.ny, v.ny, v.ny};
     return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
-        const int brc = before();
-        return brc != RTX_OK ? brc : aim_at(scene, st, v.eye, stream);
+        int brc = before();
+        if (brc == RTX_OK) brc = aim_at(scene, st, v.eye, stream);
+        if (brc == RTX_OK && lit) brc = light_walk_launch(scene, st, *lit, stream);
+        return brc;
     });
 }
 
@@ -1326,6 +1408,106 @@ int rtx_render_view_rows_device(RtxScene *scene, int device, const RtxView *view
     if (e.rc != RTX_OK) return e.rc;
     return view_rows_launch(scene, e.state(), *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); });
+}
+
+int rtx_render_view_rows_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
+                             RtxStats *stats)
+{
+    Lit lit;
+    if (!view_rows_args_ok(scene, view, out_rgb) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    const uint32_t nb_ray = scene->prep.nb_ray;
+    const double t0 = wall_ms();
+    unsigned long long c[rtx::kNumCounters] = {0};
+    if (view->ny == 0u) {
+        if (stats) fill_stats(stats, 0, lit.count, c, 0.0, wall_ms() - t0);
+        return RTX_OK;
+    }
+    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
+    float shaft_delta = 0.0f;
+    int rc = lit_rows_margin(scene, lit, &shaft_delta);
+    if (rc != RTX_OK) return rc;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const RtxView v = *view;                 // (the caller's may change while the call runs)
+    const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
+    if ((rc = st.d_out.reserve(bytes)) != RTX_OK) return rc;
+    unsigned long long *counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
+    if (st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));   // a device-resident call may still read its light
+    rc = view_rows_launch(scene, st, v, st.d_out.as<uint8_t>(), counters, st.stream, [&]() -> int {
+        if (stats) RTX_HIP(hipMemsetAsync(counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
+        RTX_HIP(hipEventRecord(st.ev0, st.stream));
+        return RTX_OK;
+    }, &lit, shaft_delta);
+    if (rc != RTX_OK) return rc;
+    RTX_HIP(hipEventRecord(st.ev1, st.stream));
+    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
+    if (stats) RTX_HIP(hipMemcpyAsync(c, st.d_counters.as<void>(), sizeof c, hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    if (stats) {
+        float ms = 0.0f;
+        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
+        fill_stats(stats, static_cast<uint64_t>(v.ny) * v.width * nb_ray, lit.count, c, ms, wall_ms() - t0);
+    }
+    return RTX_OK;
+}
+
+int rtx_render_view_rows_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
+                                    size_t d_bytes, void *stream, uint64_t *d_counters)
+{
+    Lit lit;
+    if (!view_rows_args_ok(scene, view, d_rgb) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    if (d_bytes < static_cast<size_t>(view->ny) * view->width * 3u) return RTX_ERR_BAD_ARG;
+    if (view->ny == 0u) return RTX_OK;
+    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
+    float shaft_delta = 0.0f;
+    int rc = lit_rows_margin(scene, lit, &shaft_delta);
+    if (rc != RTX_OK) return rc;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    rc = view_rows_launch(scene, st, *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
+                          static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, &lit, shaft_delta);
+    if (rc != RTX_OK) return rc;
+    // the library's light buffers are busy until this point of the caller's stream
+    if (!st.lit.used) RTX_HIP(hipEventCreateWithFlags(st.lit.used.put(), hipEventDisableTiming));
+    RTX_HIP(hipEventRecord(st.lit.used, static_cast<hipStream_t>(stream)));
+    return RTX_OK;
+}
+
+int rtx_scene_light_walk_for(const RtxScene *scene, const RtxLight *light, uint32_t *out_order, float *out_boxes,
+                             float *out_shaft_delta)
+{
+    Lit lit;
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    try {
+        light_walk_on_host(scene->prep, lit, out_order, out_boxes, out_shaft_delta);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return static_cast<int>(scene->prep.nb_ray * lit.count);      // <= 2^20
+}
+
+int rtx_debug_light_walk(RtxScene *scene, int device, const RtxLight *light, float *out_tour, float *out_boxes)
+{
+    Lit lit;
+    if (!out_tour || !out_boxes || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    if (!light_is_finite(lit)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    int rc = reserve_light_walk(scene, st, lit);
+    if (rc != RTX_OK) return rc;
+    if (st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));
+    if ((rc = light_walk_launch(scene, st, lit, st.stream)) != RTX_OK) return rc;
+    const size_t n = static_cast<size_t>(scene->prep.nb_ray) * lit.count;
+    if (n) {
+        RTX_HIP(hipMemcpyAsync(out_tour, st.lit.tour.as<void>(), n * 4u * sizeof(float), hipMemcpyDeviceToHost, st.stream));
+        RTX_HIP(hipMemcpyAsync(out_boxes, st.lit.boxes.as<void>(), static_cast<size_t>(scene->prep.nb_ray) * 6u * sizeof(float),
+                               hipMemcpyDeviceToHost, st.stream));
+    }
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    return RTX_OK;
 }
 
 int rtx_scene_aimed_nodes(const RtxScene *scene, const float eye[3], uint32_t *out_dwords)

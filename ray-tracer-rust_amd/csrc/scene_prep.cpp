@@ -541,6 +541,64 @@ void light_tour_order(const float *points, uint32_t n, uint32_t *order)
     }
 }
 
+void light_tour_order_f32(const float *points, uint32_t n, uint32_t *order)
+{
+    if (n == 0u) return;
+    auto D = [&](uint32_t a, uint32_t b) { return tour_distance(points + 3 * a, points + 3 * b); };
+    std::vector<char> used(n, 0);
+    order[0] = 0u;
+    used[0] = 1;
+    for (uint32_t k = 1; k < n; ++k) {
+        const uint32_t at = order[k - 1u];
+        uint32_t next = n;
+        float best = std::numeric_limits<float>::infinity();
+        for (uint32_t j = 0; j < n; ++j) {
+            if (used[j]) continue;
+            if (next == n) next = j;
+            const float d = D(at, j);
+            if (d < best) { best = d; next = j; }
+        }
+        order[k] = next;
+        used[next] = 1;
+    }
+    for (uint32_t pass = 0; pass < 32u; ++pass) {
+        bool improved = false;
+        for (uint32_t i = 1; i + 1u < n; ++i)
+            for (uint32_t j = i + 1u; j < n; ++j) {
+                float before = D(order[i - 1u], order[i]), after = D(order[i - 1u], order[j]);
+                if (j + 1u < n) {
+                    before = before + D(order[j], order[j + 1u]);
+                    after = after + D(order[i], order[j + 1u]);
+                }
+                if (after < before) {
+                    std::reverse(order + i, order + j + 1u);
+                    improved = true;
+                }
+            }
+        if (!improved) break;
+    }
+}
+
+void light_boxes_of(const float *points, uint32_t nb_ray, uint32_t nb_light, float *out)
+{
+    for (uint32_t r = 0; r < nb_ray; ++r) {
+        float *b = out + 6 * static_cast<size_t>(r);
+        for (int k = 0; k < 3; ++k) { b[k] = std::numeric_limits<float>::infinity(); b[3 + k] = -b[k]; }
+        for (uint32_t i = 0; i < nb_light; ++i) {
+            const float *p = points + 3 * (static_cast<size_t>(r) * nb_light + i);
+            for (int k = 0; k < 3; ++k) { b[k] = std::fmin(b[k], p[k]); b[3 + k] = std::fmax(b[3 + k], p[k]); }
+        }
+    }
+}
+
+float shaft_delta_of(float scene_magnitude, const float *light_boxes, size_t n)
+{
+    float magnitude = scene_magnitude;
+    for (size_t k = 0; k < n; ++k)
+        if (std::isfinite(light_boxes[k])) magnitude = std::fmax(magnitude, std::fabs(light_boxes[k]));
+    return magnitude * 0x1p-16f + 0x1p-100f;
+}
+
 int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
 {
     const uint64_t n_prims64 = static_cast<uint64_t>(d.n_tris) + d.n_spheres;
@@ -596,14 +654,7 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
 
         // bounding box of the light points of primary ray r: one end of a tile's shaft (rtx_kernel.hip: shaft_cut)
         s.light_boxes.assign(6 * static_cast<size_t>(d.nb_ray), 0.0f);
-        for (uint32_t r = 0; r < d.nb_ray; ++r) {
-            float *b = &s.light_boxes[6 * static_cast<size_t>(r)];
-            for (int k = 0; k < 3; ++k) { b[k] = std::numeric_limits<float>::infinity(); b[3 + k] = -b[k]; }
-            for (uint32_t i = 0; i < d.nb_light_sample; ++i) {
-                const float *p = &s.light_points[3 * (static_cast<size_t>(r) * d.nb_light_sample + i)];
-                for (int k = 0; k < 3; ++k) { b[k] = std::fmin(b[k], p[k]); b[3 + k] = std::fmax(b[3 + k], p[k]); }
-            }
-        }
+        light_boxes_of(s.light_points.data(), d.nb_ray, d.nb_light_sample, s.light_boxes.data());
 
         const int grc = build_gamma_thresholds(s.gamma_thr);
         if (grc != RTX_OK) return grc;
@@ -665,9 +716,8 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
             s.cull_delta = magnitude * 0x1p-19f + 0x1p-100f;
             if (!std::isfinite(s.cull_delta)) return RTX_ERR_UNSUPPORTED;
             // PreparedScene::shaft_delta: the same with the light points counted in (a shaft ends on them)
-            for (float b : s.light_boxes)
-                if (std::isfinite(b)) magnitude = std::fmax(magnitude, std::fabs(b));
-            s.shaft_delta = magnitude * 0x1p-16f + 0x1p-100f;
+            s.scene_magnitude = magnitude;
+            s.shaft_delta = shaft_delta_of(magnitude, s.light_boxes.data(), s.light_boxes.size());
             if (!std::isfinite(s.shaft_delta)) return RTX_ERR_UNSUPPORTED;
         }
 

@@ -37,6 +37,16 @@ RTX_HOST_DEVICE inline void light_sample_point(const float v0[3], const float v1
     for (int k = 0; k < 3; ++k)
         out[k] = w0 * v0[k] + w1 * v1[k] + w2 * v2[k];
 }
+// Distance of two light points for the tour of a call's light (light_tour_order_f32 on the host, rtxt::tour_kernel on the
+// device): f32, the squares added in this order, one correctly rounded square root.  One text for both compilers, as
+// light_sample_point is; D(a, b) and D(b, a) are the same bits (the differences are each other's negations).
+RTX_HOST_DEVICE inline float tour_distance(const float a[3], const float b[3])
+{
+    const float e0 = a[0] - b[0];
+    const float e1 = a[1] - b[1];
+    const float e2 = a[2] - b[2];
+    return sqrtf((e0 * e0 + e1 * e1) + e2 * e2);
+}
 // a call's light may have at most this many points (nb_ray x its sample count): rtx_*_lit, rtx_scene_light_points_for
 constexpr uint64_t kMaxCallLightPoints = 1ull << 20;
 
@@ -139,6 +149,9 @@ struct PreparedScene {
     // 2^-16 x the largest coordinate magnitude of scene, eye and light points (rtx_kernel.hip: shaft_cut)
     std::vector<float>    light_boxes;
     float shaft_delta = 0.0f;
+    // what shaft_delta is folded from beside the light boxes: the largest coordinate magnitude of the scene and the eye
+    // (shaft_delta_of; a call's light folds its own boxes onto it)
+    float scene_magnitude = 0.0f;
     uint32_t n_global = 0;   // > 0: records [0, n_global) are the "global" triangles, stream = root, their leaf, the tree proper
     // one per global triangle, in TriRec clothing: v0 = v0, e1 = fl(e1 x e2), e2 = (|e1| x |e2| with plus signs, rounded
     // up), bmin[0] = the denominator's error allowance — what rtx_traverse.hpp: plane_rules_out needs
@@ -158,6 +171,17 @@ constexpr uint32_t kMaxLightBatch = RTX_LIGHT_BATCH;
 // index), then 2-opt reversals that keep position 0, a bounded number of passes.  Always a permutation of 0 .. n-1: a
 // distance that is NaN or infinite never wins a comparison.  Deterministic.
 void light_tour_order(const float *points, uint32_t n, uint32_t *order);
+
+// The tour of a light given per call (rtx_render_view_rows_lit): light_tour_order's scan in f32 — distances by
+// tour_distance, `before` and `after` each an f32 sum of two of them — so that the device can make it word for word
+// (rtxt::tour_kernel).  A statement of its own: a created scene's tour stays light_tour_order's.  Always a permutation of
+// 0 .. n-1 that starts with 0, whatever the points hold.
+void light_tour_order_f32(const float *points, uint32_t n, uint32_t *order);
+// per primary ray r < nb_ray the bounding box (lo xyz, hi xyz) of its nb_light points, fmin / fmax from -+infinity (a NaN
+// is ignored): PreparedScene::light_boxes.  out: nb_ray x 6.
+void light_boxes_of(const float *points, uint32_t nb_ray, uint32_t nb_light, float *out);
+// PreparedScene::shaft_delta from PreparedScene::scene_magnitude and n light-box bounds (the finite ones count)
+float shaft_delta_of(float scene_magnitude, const float *light_boxes, size_t n);
 
 // Returns RTX_OK or a negative RtxError.
 int prepare_scene(const RtxSceneDesc &desc, PreparedScene &out);

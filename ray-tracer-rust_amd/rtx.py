@@ -161,6 +161,12 @@ _SIGS = {
     "rtx_scene_light": (C.c_int, [C.c_void_p, C.POINTER(RtxLight)]),
     "rtx_scene_light_points_for": (C.c_int, [C.c_void_p, C.POINTER(RtxLight), f32p]),
     "rtx_debug_light_points": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxLight), f32p]),
+    "rtx_render_view_rows_lit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
+                                           C.POINTER(Stats)]),
+    "rtx_render_view_rows_lit_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
+                                                  C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rtx_scene_light_walk_for": (C.c_int, [C.c_void_p, C.POINTER(RtxLight), u32p, f32p, f32p]),
+    "rtx_debug_light_walk": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxLight), f32p, f32p]),
     "rtx_render_view_lit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
                                       C.POINTER(PixelShade), C.POINTER(RayHit), C.POINTER(Stats)]),
     "rtx_render_view_lit_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p, C.c_void_p,
@@ -685,23 +691,55 @@ class Scene:
         _check(_lib.rtx_debug_light_points(self._h, device, C.byref(light), _fp(out)), "rtx_debug_light_points")
         return out[:n]
 
-    # -- any view through the render pipeline (GPU only)
-    def render_view_rows(self, view, device=0, stats=False):
+    def light_walk_for(self, light):
+        """Host only: what the walk kernels make for `light` on this scene -> (order uint32 [nb_ray * n] in light_order()'s
+        form, boxes float32 [nb_ray, 6], shaft_delta float32)."""
+        n = _lib.rtx_scene_light_walk_for(self._h, C.byref(light), None, None, None)
+        if n < 0:
+            raise RtxError(n, "rtx_scene_light_walk_for")
+        order = np.zeros(max(n, 1), np.uint32)
+        boxes = np.zeros((self.nb_ray, 6), np.float32)
+        delta = C.c_float(0.0)
+        if _lib.rtx_scene_light_walk_for(self._h, C.byref(light), order.ctypes.data_as(u32p), _fp(boxes), C.byref(delta)) != n:
+            raise RtxError(ERR_INTERNAL, "rtx_scene_light_walk_for")
+        return order[:n], boxes, np.float32(delta.value)
+
+    def debug_light_walk(self, light, device=0):
+        """Diagnostics: the tour records (uint32 [nb_ray * n, 4]: x, y, z bits and the index within the batch) and the boxes
+        (float32 [nb_ray, 6]) as the light kernels make them on `device`, copied back."""
+        n = _lib.rtx_scene_light_points_for(self._h, C.byref(light), None)
+        if n < 0:
+            raise RtxError(n, "rtx_scene_light_points_for")
+        tour = np.zeros((max(n, 1), 4), np.uint32)
+        boxes = np.zeros((self.nb_ray, 6), np.float32)
+        _check(_lib.rtx_debug_light_walk(self._h, device, C.byref(light), tour.ctypes.data_as(f32p), _fp(boxes)),
+               "rtx_debug_light_walk")
+        return tour[:n], boxes
+
+    # -- any view through the render pipeline (GPU only); light=: under another light (rtx_render_view_rows_lit)
+    def render_view_rows(self, view, device=0, stats=False, light=None):
         """Rows [y0, y0 + ny) of the view's frame through the render pipeline, full width (x0 = 0, nx = width)
         -> uint8 [ny, width, 3]: render_view's bytes at the pipeline's speed.  An eye beyond the scene's largest
         coordinate raises RtxError(ERR_UNSUPPORTED): render_view serves it."""
         out = np.zeros((view.ny, view.width, 3), np.uint8)
         st = Stats()
-        _check(_lib.rtx_render_view_rows(self._h, device, C.byref(view), out.ctypes.data, C.byref(st) if stats else None),
-               "rtx_render_view_rows")
+        if light is None:
+            _check(_lib.rtx_render_view_rows(self._h, device, C.byref(view), out.ctypes.data, C.byref(st) if stats else None),
+                   "rtx_render_view_rows")
+        else:
+            _check(_lib.rtx_render_view_rows_lit(self._h, device, C.byref(view), C.byref(light), out.ctypes.data,
+                                                 C.byref(st) if stats else None), "rtx_render_view_rows_lit")
         return (out, st.asdict()) if stats else out
 
-    def render_view_rows_device(self, device, view, d_rgb_ptr, d_bytes, stream=None, d_counters_ptr=None):
+    def render_view_rows_device(self, device, view, d_rgb_ptr, d_bytes, stream=None, d_counters_ptr=None, light=None):
         """Asynchronous pipeline launch of the view's rows into a device buffer the caller owns (ny*width*3 bytes)."""
-        _check(_lib.rtx_render_view_rows_device(self._h, device, C.byref(view), C.c_void_p(d_rgb_ptr), d_bytes,
-                                                C.c_void_p(stream) if stream else None,
-                                                C.c_void_p(d_counters_ptr) if d_counters_ptr else None),
-               "rtx_render_view_rows_device")
+        tail = (C.c_void_p(d_rgb_ptr), d_bytes, C.c_void_p(stream) if stream else None,
+                C.c_void_p(d_counters_ptr) if d_counters_ptr else None)
+        if light is None:
+            _check(_lib.rtx_render_view_rows_device(self._h, device, C.byref(view), *tail), "rtx_render_view_rows_device")
+        else:
+            _check(_lib.rtx_render_view_rows_lit_device(self._h, device, C.byref(view), C.byref(light), *tail),
+                   "rtx_render_view_rows_lit_device")
 
     def aimed_nodes(self, eye):
         """Host only: records [n_nodes, 8] of the stream the primary rays of a view with this eye walk (planes moved by
