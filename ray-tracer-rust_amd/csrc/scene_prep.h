@@ -122,8 +122,9 @@ struct PreparedScene {
     uint32_t n_samples = 0;
     std::vector<NodeRec>  nodes;
     // The same tree as a second stream for the PRIMARY rays (probe_kernel), of every node's two children the one whose box
-    // centre lies nearer the EYE first: a closest-hit walk prunes by the closest hit so far, and finds a close one early
-    // this way; `nodes` puts the child farther from the LIGHT first, which is what the shadow walks want.  Same records,
+    // centre lies nearer the EYE first (made while the closest-hit walks pruned by the closest hit so far; they no longer do,
+    // rtx_traverse.hpp: advance_to_leaf, and visit the same records in either order); `nodes` puts the child farther from
+    // the LIGHT first, which is what the shadow walks want.  Same records,
     // same leaves (a leaf names its run of the primitive array), other order and links.  Empty: `nodes` serves both.
     std::vector<NodeRec>  primary_nodes;
     std::vector<NodeRec>  ref_nodes;   // the reference's own tree as a stream (empty when not built)

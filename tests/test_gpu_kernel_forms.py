@@ -117,7 +117,7 @@ def _render_and_compare(rtx, orc, samples, scene):
 @pytest.mark.parametrize("eye_oct,light_oct,with_spheres", gf.OCTANT_CASES,
                          ids=["eye%d-light%d%s" % (e, l, "-spheres" if s else "") for e, l, s in gf.OCTANT_CASES])
 def test_box_loop_of_each_octant(rtx, orc, samples_seeded, eye_oct, light_oct, with_spheres):
-    """advance_to_leaf's loop `eye_oct` under the primary rays (closest hit, PRUNE) and loop `light_oct` under the shadow
+    """advance_to_leaf's loop `eye_oct` under the primary rays (closest hit) and loop `light_oct` under the shadow
     rays (any hit), in the sense of walk_octant: bit a of the octant set = direction component a negative.  Shown from
     the inputs: every primary direction of the frame has the eye octant's signs, and the light triangle's box lies
     strictly beyond the box of all primitives on every axis, on the light octant's side."""
