@@ -41,11 +41,13 @@ int hip_rc(hipError_t e)
     return e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP;
 }
 
-#define RTX_HIP(call)                          \
+// leave the function with the code of a step that failed: RTX_TRY for a step that gives the ABI's code, RTX_HIP for a HIP call
+#define RTX_TRY(step)                          \
     do {                                       \
-        const int rc_ = hip_rc(call);          \
+        const int rc_ = (step);                \
         if (rc_ != RTX_OK) return rc_;         \
     } while (0)
+#define RTX_HIP(call) RTX_TRY(hip_rc(call))
 
 // makes a device current; restores the caller's current device on scope exit
 class DeviceGuard {
@@ -85,6 +87,22 @@ private:
 };
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+// "The library's buffer is busy up to this point of the caller's stream": a device-resident call that used a library-owned
+// buffer records the buffer's event behind its kernels (the event is made on first use), and a call that uses the buffer
+// on the library's stream waits for it first.  A buffer no device-resident call has used has no event: nothing to wait for.
+int mark_busy(Event &e, hipStream_t callers)
+{
+    if (!e) RTX_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+    RTX_HIP(hipEventRecord(e, callers));
+    return RTX_OK;
+}
+
+int wait_for(const Event &e, hipStream_t stream)
+{
+    if (e) RTX_HIP(hipStreamWaitEvent(stream, e, 0));
+    return RTX_OK;
+}
 
 hipError_t alloc_device(void **p, size_t bytes) { return hipMalloc(p, bytes); }
 hipError_t alloc_pinned(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
@@ -136,8 +154,7 @@ public:
     Stream stream;
     Event ev0, ev1;
     Event ring[RTX_TIMING_RING][3];      // launch start / end of the scheduling pass / launch end (rtx_launch_timings)
-    Event q_sorted;                      // recorded behind a device-resident call that used q_sort on the CALLER's stream: a host
-                                         // call, which uses the same buffers on the library's stream, waits for it first
+    Event q_sorted;                      // guards q_sort (mark_busy / wait_for)
     DeviceBuffer nodes, primary_nodes, ref_nodes, tris, shade, samples, lights, light_tour, thr, planes, light_boxes;
     DeviceBuffer d_out, d_counters;
     DeviceBuffer d_redo;                 // queue of tiles for reference_tiles_kernel
@@ -164,9 +181,8 @@ public:
         bool valid = false;
     } aimed;
     // rtx_*_lit (rtx_light.hip): the points of the most recent lit call's light, made on that call's stream ahead of its
-    // view or shade kernel; `used` is recorded behind a device-resident lit launch on the CALLER's stream: a host call, which
-    // uses the same buffer on the library's stream, waits for it first
-    // rtx_render_view_rows_lit (rtx_tour.hip) adds the tour and the boxes of that light, under the same rules
+    // view or shade kernel; rtx_render_view_rows_lit (rtx_tour.hip) adds the tour and the boxes of that light.  One owner
+    // (reserve_light, light_launch), one guard: `used` (mark_busy / wait_for)
     struct {
         DeviceBuffer points, tour, boxes;
         Event used;
@@ -430,6 +446,41 @@ void fill_stats(RtxStats *s, uint64_t primary_rays, uint32_t shadow_rays_per_hit
     s->total_ms = total_ms;
 }
 
+// The bracket of a host call that times and counts on the library's stream (stats == NULL: neither).  In the call's order:
+// the wall clock starts with the object; empty() answers a call without work; begin() goes on the stream once the call's
+// buffers stand and whatever it copies in is enqueued, end() behind its kernels; the call enqueues its copies back, and
+// gather() waits for all of it and fills the statistics.  Caller holds the slot's lock and has the device current.
+struct Timed {
+    explicit Timed(RtxStats *s) : stats(s) {}
+    RtxStats *const stats;
+    const double t0 = wall_ms();
+    unsigned long long *counters(const DeviceState &st) const { return stats ? st.d_counters.as<unsigned long long>() : nullptr; }
+    int empty() const
+    {
+        const unsigned long long none[rtx::kNumCounters] = {0};
+        if (stats) fill_stats(stats, 0, 0, none, 0.0, wall_ms() - t0);
+        return RTX_OK;
+    }
+    int begin(const DeviceState &st) const
+    {
+        if (stats) RTX_HIP(hipMemsetAsync(counters(st), 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
+        RTX_HIP(hipEventRecord(st.ev0, st.stream));
+        return RTX_OK;
+    }
+    int end(const DeviceState &st) const { return hip_rc(hipEventRecord(st.ev1, st.stream)); }
+    int gather(const DeviceState &st, uint64_t primary_rays, uint32_t shadow_rays_per_hit) const
+    {
+        unsigned long long c[rtx::kNumCounters] = {0};
+        if (stats) RTX_HIP(hipMemcpyAsync(c, counters(st), sizeof c, hipMemcpyDeviceToHost, st.stream));
+        RTX_HIP(hipStreamSynchronize(st.stream));
+        if (!stats) return RTX_OK;
+        float ms = 0.0f;
+        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
+        fill_stats(stats, primary_rays, shadow_rays_per_hit, c, ms, wall_ms() - t0);
+        return RTX_OK;
+    }
+};
+
 // The one render launch, on `stream`: the redo queue and the streamed pipeline's workspace sized, `before()` (what the
 // caller puts on the stream once the buffers stand), the kernels, the launch's slot of the timing ring.  The per-tile
 // profile (d_wave_prof, ablation build) is the fused kernel's: no workspace, no slot.  Caller holds the slot's lock and
@@ -465,26 +516,30 @@ int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpe
     return RTX_OK;
 }
 
-// launch one device's share into its d_out; caller holds slot.mu, with a state in the slot, and has the device current
-int launch_on(RtxScene *scene, DeviceSlot &slot, const rtx::TileSpec &ts, bool count)
+// launch one device's share into its d_out, between timed's begin() and end(); caller holds slot.mu, with a state in the
+// slot, and has the device current
+int launch_on(RtxScene *scene, DeviceSlot &slot, const rtx::TileSpec &ts, const Timed &timed)
 {
-    int rc = ensure_uploaded(scene, slot);
-    if (rc != RTX_OK) return rc;
+    RTX_TRY(ensure_uploaded(scene, slot));
     DeviceState &st = *slot.st;
     const size_t bytes = static_cast<size_t>(ts.local_rows) * scene->prep.width * 3u;
-    if ((rc = st.d_out.reserve(bytes ? bytes : 16)) != RTX_OK) return rc;
-    unsigned long long *counters = count ? st.d_counters.as<unsigned long long>() : nullptr;
-    rc = render_launch(st, device_scene(scene, st), ts, st.d_out.as<uint8_t>(), counters, nullptr, st.stream, [&]() -> int {
-        if (count) RTX_HIP(hipMemsetAsync(counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
-        RTX_HIP(hipEventRecord(st.ev0, st.stream));
-        return RTX_OK;
-    });
-    if (rc != RTX_OK) return rc;
-    RTX_HIP(hipEventRecord(st.ev1, st.stream));
-    return RTX_OK;
+    RTX_TRY(st.d_out.reserve(bytes ? bytes : 16));
+    RTX_TRY(render_launch(st, device_scene(scene, st), ts, st.d_out.as<uint8_t>(), timed.counters(st), nullptr, st.stream,
+                          [&] { return timed.begin(st); }));
+    return timed.end(st);
 }
 
 // ---- ray batches: the queries (rtx_query.hip), shading (rtx_shade.hip) and views (rtx_view.hip) -------------------------
+
+// first record of the tree proper: behind the root and the leaf of the global triangles when there are any
+uint32_t tree_root(const rtx::PreparedScene &p)
+{
+    return (p.n_global != 0u && p.nodes.size() > 2u) ? 2u : 0u;
+}
+
+// The multiply-based culling of the walks is proven for origins whose coordinates stay within the magnitude behind
+// cull_delta (scene_prep.cpp): the bound the ray-batch kernels are handed, and the one a pipeline view's eye is held to.
+float origin_bound(const RtxScene *scene) { return scene->prep.cull_delta * 0x1p19f; }
 
 // The box the regrouping keys quantise origins in: the tree proper's root (beside the global triangles — the ground is
 // as large as the scene and would leave the mesh a handful of cells), else the stream's root.
@@ -492,7 +547,7 @@ rtxq::KeyBox query_key_box(const rtx::PreparedScene &p)
 {
     rtxq::KeyBox box{};
     if (p.nodes.empty()) return box;
-    const rtx::NodeRec &root = p.nodes[(p.n_global != 0u && p.nodes.size() > 2u) ? 2u : 0u];
+    const rtx::NodeRec &root = p.nodes[tree_root(p)];
     for (int a = 0; a < 3; ++a) {
         const float extent = root.bmax[a] - root.bmin[a];
         const float scale = static_cast<float>(1u << rtxq::kMortonBitsPerAxis) / extent;
@@ -593,24 +648,46 @@ bool batch_regroups(const Batch &b)
     return b.n >= rtxq::kRegroupMinRays || (b.flags & RTX_RAYS_FORCE_REGROUP) != 0u;
 }
 
-// The light kernel of a lit call on `stream`, and its points and count in the call's copy of the scene's argument block: the
-// view and shade kernels read nothing else of the light (rtx_shade_pixel.hpp).  The buffer is library-owned per device and
-// grows only; growing it waits for the device first, since an earlier launch may still read it.  Caller holds the slot's lock
-// and has the device current and the scene uploaded.
-int light_launch(const RtxScene *scene, DeviceState &st, const Lit &lit, rtx::DeviceScene *S, hipStream_t stream)
+// A call's light on the device.  The view and shade kernels read its points and count (rtx_shade_pixel.hpp); the render
+// pipeline's kernels also walk its tour and boxes and test shafts with its margin (rtx_kernel.hip) — `walk`, here and below.
+// The buffers are library-owned per device and grow only.  reserve_light sizes them before the call's kernels that read them
+// are on a stream; growing one waits for the device first, since an earlier launch may still read it.  Caller holds the
+// slot's lock and has the device current and the scene uploaded.
+int reserve_light(const RtxScene *scene, DeviceState &st, const Lit &lit, bool walk)
+{
+    const size_t rays = scene->prep.nb_ray, n = rays * lit.count;
+    const size_t points = std::max<size_t>(n * 3u * sizeof(float), 16u);
+    const size_t tour = walk ? std::max<size_t>(n * 4u * sizeof(float), 16u) : 0u;
+    const size_t boxes = walk ? std::max<size_t>(rays * 6u * sizeof(float), 16u) : 0u;
+    if (st.lit.points.capacity() >= points && st.lit.tour.capacity() >= tour && st.lit.boxes.capacity() >= boxes) return RTX_OK;
+    RTX_HIP(hipDeviceSynchronize());
+    return reserve_all({{st.lit.points, points}, {st.lit.tour, tour}, {st.lit.boxes, boxes}});
+}
+
+// the light kernels on `stream`, after reserve_light: the points; walk: their tour and their boxes too
+int light_launch(const RtxScene *scene, DeviceState &st, const Lit &lit, bool walk, hipStream_t stream)
 {
     const rtx::PreparedScene &p = scene->prep;
-    const size_t bytes = static_cast<size_t>(p.nb_ray) * lit.count * 3u * sizeof(float);
-    if (st.lit.points.capacity() < (bytes ? bytes : 16u)) {
-        RTX_HIP(hipDeviceSynchronize());
-        const int rc = st.lit.points.reserve(bytes ? bytes : 16u);
-        if (rc != RTX_OK) return rc;
-    }
+    if (lit.count == 0u) return RTX_OK;      // (the scene's own count is 0 then: no kernel reads a point)
     RTX_HIP(rtxl::launch_light_points(st.samples.as<const float2>(), p.n_samples, lit.tri, p.nb_ray, lit.count,
                                       st.lit.points.as<float>(), stream));
+    if (!walk) return RTX_OK;
+    RTX_HIP(rtxt::launch_tour(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.tour.as<float>(), stream));
+    RTX_HIP(rtxt::launch_light_boxes(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.boxes.as<float>(), stream));
+    return RTX_OK;
+}
+
+// ... and the fields of the call's copy of the scene's argument block that the kernels read of the light; the pipeline's
+// workspace and the LDS of its launch are sized by S.nb_light.  shaft_delta: lit_rows_margin's (walk only)
+void light_swap(const DeviceState &st, const Lit &lit, bool walk, float shaft_delta, rtx::DeviceScene *S)
+{
+    if (lit.count == 0u) return;
     S->light_points = st.lit.points.as<const float>();
     S->nb_light = lit.count;
-    return RTX_OK;
+    if (!walk) return;
+    S->light_tour = st.lit.tour.as<const float>();
+    S->light_boxes = st.lit.boxes.as<const float>();
+    S->shaft_delta = shaft_delta;
 }
 
 bool light_is_finite(const Lit &lit)
@@ -658,55 +735,22 @@ int lit_rows_margin(const RtxScene *scene, const Lit &lit, float *shaft_delta)
     return std::isfinite(*shaft_delta) ? RTX_OK : RTX_ERR_UNSUPPORTED;
 }
 
-// the three buffers of a lit pipeline call, sized before anything of the call is on a stream (light_launch's rule)
-int reserve_light_walk(const RtxScene *scene, DeviceState &st, const Lit &lit)
-{
-    const size_t n = static_cast<size_t>(scene->prep.nb_ray) * lit.count;
-    const size_t points = std::max<size_t>(n * 3u * sizeof(float), 16u), tour = std::max<size_t>(n * 4u * sizeof(float), 16u);
-    const size_t boxes = std::max<size_t>(static_cast<size_t>(scene->prep.nb_ray) * 6u * sizeof(float), 16u);
-    if (st.lit.points.capacity() >= points && st.lit.tour.capacity() >= tour && st.lit.boxes.capacity() >= boxes) return RTX_OK;
-    RTX_HIP(hipDeviceSynchronize());
-    return reserve_all({{st.lit.points, points}, {st.lit.tour, tour}, {st.lit.boxes, boxes}});
-}
-
-// The light kernels of a lit pipeline call on `stream`: the points, their tour, their boxes.  Caller holds the slot's lock,
-// has the device current and the scene uploaded, and has called reserve_light_walk.
-int light_walk_launch(const RtxScene *scene, DeviceState &st, const Lit &lit, hipStream_t stream)
-{
-    if (lit.count == 0u) return RTX_OK;
-    const rtx::PreparedScene &p = scene->prep;
-    RTX_HIP(rtxl::launch_light_points(st.samples.as<const float2>(), p.n_samples, lit.tri, p.nb_ray, lit.count,
-                                      st.lit.points.as<float>(), stream));
-    RTX_HIP(rtxt::launch_tour(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.tour.as<float>(), stream));
-    RTX_HIP(rtxt::launch_light_boxes(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.boxes.as<float>(), stream));
-    return RTX_OK;
-}
-
-// ... and the five fields of the call's copy of the scene's argument block that the pipeline's kernels read of the light
-// (rtx_kernel.hip reads nothing else of it); the workspace and the LDS of the launch are sized by S.nb_light
-void light_walk_swap(const DeviceState &st, const Lit &lit, float shaft_delta, rtx::DeviceScene *S)
-{
-    if (lit.count == 0u) return;
-    S->light_points = st.lit.points.as<const float>();
-    S->light_tour = st.lit.tour.as<const float>();
-    S->light_boxes = st.lit.boxes.as<const float>();
-    S->shaft_delta = shaft_delta;
-    S->nb_light = lit.count;
-}
-
-// key + sort + kernel of one batch on `stream`; caller holds the slot's lock, has the device current and the scene uploaded
+// key + sort + kernel of one batch on `stream`, the light kernel of a lit one ahead of them; caller holds the slot's lock,
+// has the device current and the scene uploaded
 int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *d_first, const float *d_second,
                  void *const d_out[kBatchOuts], unsigned long long *d_counters, hipStream_t stream)
 {
     rtxq::SortBuffers sort{};
     const bool regroup = batch_regroups(b);
-    int rc;
-    if (regroup && (rc = reserve_query_sort(st, b.n, &sort)) != RTX_OK) return rc;
+    if (regroup) RTX_TRY(reserve_query_sort(st, b.n, &sort));
     rtx::DeviceScene S = device_scene(scene, st);
-    if (b.lit && (rc = light_launch(scene, st, *b.lit, &S, stream)) != RTX_OK) return rc;
-    RTX_HIP(b.launch(BatchArgs{S, b.n, d_first, d_second, b.view, query_key_box(scene->prep),
-                               scene->prep.cull_delta * 0x1p19f, regroup ? &sort : nullptr, {d_out[0], d_out[1], d_out[2]},
-                               d_counters, stream}));
+    if (b.lit) {
+        RTX_TRY(reserve_light(scene, st, *b.lit, false));
+        RTX_TRY(light_launch(scene, st, *b.lit, false, stream));
+        light_swap(st, *b.lit, false, 0.0f, &S);
+    }
+    RTX_HIP(b.launch(BatchArgs{S, b.n, d_first, d_second, b.view, query_key_box(scene->prep), origin_bound(scene),
+                               regroup ? &sort : nullptr, {d_out[0], d_out[1], d_out[2]}, d_counters, stream}));
     return RTX_OK;
 }
 
@@ -714,11 +758,8 @@ int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *
 int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, const float *second,
                void *const (&out)[kBatchOuts], RtxStats *stats)
 {
-    const double t0 = wall_ms();
-    if (b.n == 0u) {
-        if (stats) { std::memset(stats, 0, sizeof *stats); stats->total_ms = wall_ms() - t0; }
-        return RTX_OK;
-    }
+    const Timed timed(stats);
+    if (b.n == 0u) return timed.empty();
     if (b.lit && !light_is_finite(*b.lit)) return RTX_ERR_UNSUPPORTED;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
@@ -726,35 +767,25 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
     const size_t in_bytes = first ? static_cast<size_t>(b.n_rays) * 3u * sizeof(float) : 0u;
     size_t offset[kBatchOuts + 1] = {0};
     for (int k = 0; k < kBatchOuts; ++k) offset[k + 1] = offset[k] + b.out_bytes[k];
-    int rc = reserve_all({{st.q_first, in_bytes}, {st.q_second, in_bytes}, {st.q_out, offset[kBatchOuts]}});
-    if (rc != RTX_OK) return rc;
+    RTX_TRY(reserve_all({{st.q_first, in_bytes}, {st.q_second, in_bytes}, {st.q_out, offset[kBatchOuts]}}));
     void *d_out[kBatchOuts];
     for (int k = 0; k < kBatchOuts; ++k) d_out[k] = b.out_bytes[k] ? st.q_out.as<uint8_t>() + offset[k] : nullptr;
-    unsigned long long *d_counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
-    if (st.q_sorted) RTX_HIP(hipStreamWaitEvent(st.stream, st.q_sorted, 0));   // a device-resident call may still be sorting
-    if (b.lit && st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));   // ... or reading its light's points
+    RTX_TRY(wait_for(st.q_sorted, st.stream));              // a device-resident call may still be sorting
+    if (b.lit) RTX_TRY(wait_for(st.lit.used, st.stream));   // ... or reading its light's points
     if (in_bytes) {
         RTX_HIP(hipMemcpyAsync(st.q_first.as<void>(), first, in_bytes, hipMemcpyHostToDevice, st.stream));
         RTX_HIP(hipMemcpyAsync(st.q_second.as<void>(), second, in_bytes, hipMemcpyHostToDevice, st.stream));
     }
-    if (stats) RTX_HIP(hipMemsetAsync(d_counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
-    RTX_HIP(hipEventRecord(st.ev0, st.stream));
-    if ((rc = batch_launch(scene, st, b, st.q_first.as<float>(), st.q_second.as<float>(), d_out, d_counters, st.stream)) != RTX_OK) {
+    RTX_TRY(timed.begin(st));
+    const int rc = batch_launch(scene, st, b, st.q_first.as<float>(), st.q_second.as<float>(), d_out, timed.counters(st), st.stream);
+    if (rc != RTX_OK) {
         (void)hipStreamSynchronize(st.stream);      // the copies above read the caller's arrays
         return rc;
     }
-    RTX_HIP(hipEventRecord(st.ev1, st.stream));
+    RTX_TRY(timed.end(st));
     for (int k = 0; k < kBatchOuts; ++k)
         if (b.out_bytes[k]) RTX_HIP(hipMemcpyAsync(out[k], d_out[k], b.out_bytes[k], hipMemcpyDeviceToHost, st.stream));
-    unsigned long long c[rtx::kNumCounters] = {0};
-    if (stats) RTX_HIP(hipMemcpyAsync(c, d_counters, sizeof c, hipMemcpyDeviceToHost, st.stream));
-    RTX_HIP(hipStreamSynchronize(st.stream));
-    if (stats) {
-        float ms = 0.0f;
-        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
-        fill_stats(stats, b.n_rays, b.shadow_rays_per_hit, c, ms, wall_ms() - t0);
-    }
-    return RTX_OK;
+    return timed.gather(st, b.n_rays, b.shadow_rays_per_hit);
 }
 
 // the device-resident entry points: the caller's arrays, the caller's stream, nothing waited for
@@ -767,17 +798,10 @@ int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_firs
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    const int rc = batch_launch(scene, st, b, static_cast<const float *>(d_first), static_cast<const float *>(d_second), d_out,
-                                nullptr, static_cast<hipStream_t>(stream));
-    if (rc != RTX_OK) return rc;
-    if (batch_regroups(b)) {     // the library's sort buffers are busy until this point of the caller's stream
-        if (!st.q_sorted) RTX_HIP(hipEventCreateWithFlags(st.q_sorted.put(), hipEventDisableTiming));
-        RTX_HIP(hipEventRecord(st.q_sorted, static_cast<hipStream_t>(stream)));
-    }
-    if (b.lit) {                 // ... and its light buffer
-        if (!st.lit.used) RTX_HIP(hipEventCreateWithFlags(st.lit.used.put(), hipEventDisableTiming));
-        RTX_HIP(hipEventRecord(st.lit.used, static_cast<hipStream_t>(stream)));
-    }
+    RTX_TRY(batch_launch(scene, st, b, static_cast<const float *>(d_first), static_cast<const float *>(d_second), d_out, nullptr,
+                         static_cast<hipStream_t>(stream)));
+    if (batch_regroups(b)) RTX_TRY(mark_busy(st.q_sorted, static_cast<hipStream_t>(stream)));
+    if (b.lit) RTX_TRY(mark_busy(st.lit.used, static_cast<hipStream_t>(stream)));
     return RTX_OK;
 }
 
@@ -799,33 +823,45 @@ Batch query_batch(bool occlusion, uint32_t n_rays, uint32_t flags)
                  occlusion ? launch_queried<true> : launch_queried<false>, nullptr, nullptr};
 }
 
-// caller has checked n_pixels (shade_args_ok)
-Batch shade_batch(const RtxScene *scene, uint32_t n_pixels, uint32_t flags, bool want_hits)
+// Caller has checked n_pixels (shade_args_ok).  lit, here and below: NULL for the scene's light, else the call's (lit_of):
+// the light kernel runs ahead of the batch's kernel, and the statistics count the light's samples per hit.
+Batch shade_batch(const RtxScene *scene, uint32_t n_pixels, uint32_t flags, const Lit *lit, bool want_hits)
 {
     const uint32_t n_rays = shade_ray_count(scene, n_pixels);
     return Batch{n_pixels, n_rays, flags,
                  {static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade), want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u, 0u},
-                 scene->prep.nb_light_sample, launch_shaded, nullptr, nullptr};
+                 lit ? lit->count : scene->prep.nb_light_sample, launch_shaded, nullptr, lit};
 }
 
-// the argument checks rtx_render_view and its _device twin share (`rgb`, `shade`, `hits`: the three outputs)
+// a frame has pixels, and fewer than 2^31 of them
+bool frame_ok(const RtxView *v)
+{
+    return v->width != 0u && v->height != 0u && static_cast<uint64_t>(v->width) * v->height < (1ull << 31);
+}
+
+// the argument checks rtx_render_view and its twins share (`rgb`, `shade`, `hits`: the three outputs)
 bool view_args_ok(const RtxScene *scene, const RtxView *v, const void *rgb, const void *shade, const void *hits)
 {
-    if (!scene || !v || (!rgb && !shade && !hits)) return false;
-    if (v->width == 0u || v->height == 0u || static_cast<uint64_t>(v->width) * v->height >= (1ull << 31)) return false;
+    if (!scene || !v || (!rgb && !shade && !hits) || !frame_ok(v)) return false;
     if (static_cast<uint64_t>(v->x0) + v->nx > v->width || static_cast<uint64_t>(v->y0) + v->ny > v->height) return false;
     return static_cast<uint64_t>(v->nx) * v->ny * scene->prep.nb_ray <= rtxv::kMaxRays;     // (nx * ny < 2^31)
 }
 
 // caller has checked the view (view_args_ok); the rays are made tile by tile: no regrouping pass
-Batch view_batch(const RtxScene *scene, const RtxView *v, bool want_rgb, bool want_shade, bool want_hits)
+Batch view_batch(const RtxScene *scene, const RtxView *v, const Lit *lit, const void *rgb, const void *shade, const void *hits)
 {
     const uint32_t n_pixels = v->nx * v->ny, n_rays = n_pixels * scene->prep.nb_ray;
-    Batch b{n_pixels, n_rays, RTX_RAYS_KEEP_ORDER, {0u, 0u, 0u}, scene->prep.nb_light_sample, launch_viewed, v, nullptr};
-    b.out_bytes[kViewShade] = want_shade ? static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade) : 0u;
-    b.out_bytes[kViewHits] = want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u;
-    b.out_bytes[kViewRgb] = want_rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
+    Batch b{n_pixels, n_rays, RTX_RAYS_KEEP_ORDER, {0u, 0u, 0u}, lit ? lit->count : scene->prep.nb_light_sample, launch_viewed, v, lit};
+    b.out_bytes[kViewShade] = shade ? static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade) : 0u;
+    b.out_bytes[kViewHits] = hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u;
+    b.out_bytes[kViewRgb] = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
     return b;
+}
+
+// a device-resident call writes 16-byte records (RtxPixelShade, RtxRayHit) through these; NULL: an output not asked for
+bool aligned16(const void *a, const void *b = nullptr)
+{
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0u;
 }
 
 static_assert(sizeof(RtxLight) == 40 && alignof(RtxLight) == 4 && offsetof(RtxLight, nb_light_sample) == sizeof(rtxl::LightTriangle),
@@ -843,37 +879,54 @@ bool lit_of(const RtxScene *scene, const RtxLight *light, Lit *out)
     return static_cast<uint64_t>(scene->prep.nb_ray) * out->count <= rtx::kMaxCallLightPoints;
 }
 
-// a twin's batch under the call's light: the light kernel ahead of its kernel, the light's count per hit in the statistics
-Batch relit(Batch b, const Lit &lit)
+// The bodies of rtx_render_view and rtx_shade_rays, each with its _lit twin's light as an argument.  A view's outputs in
+// Batch::out_bytes' order: {shade, hits, rgb}.
+static_assert(kViewShade == 0 && kViewHits == 1 && kViewRgb == 2, "view_host and view_device list a view's outputs in this order");
+int view_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, uint8_t *rgb, RtxPixelShade *shade, RtxRayHit *hits,
+              RtxStats *stats)
 {
-    b.lit = &lit;
-    b.shadow_rays_per_hit = lit.count;
-    return b;
+    if (!view_args_ok(scene, view, rgb, shade, hits)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, view_batch(scene, view, lit, rgb, shade, hits), nullptr, nullptr, {shade, hits, rgb}, stats);
+}
+
+int view_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, void *d_rgb, void *d_shade, void *d_hits, void *stream)
+{
+    if (!view_args_ok(scene, view, d_rgb, d_shade, d_hits) || !aligned16(d_shade, d_hits)) return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, view_batch(scene, view, lit, d_rgb, d_shade, d_hits), nullptr, nullptr, {d_shade, d_hits, d_rgb},
+                        stream);
+}
+
+int shade_host(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions, uint32_t flags,
+               const Lit *lit, RtxPixelShade *shade, RtxRayHit *hits, RtxStats *stats)
+{
+    if (!shade_args_ok(scene, origins, directions, shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, shade_batch(scene, n_pixels, flags, lit, hits != nullptr), origins, directions,
+                      {shade, hits, nullptr}, stats);
+}
+
+int shade_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions, uint32_t flags,
+                 const Lit *lit, void *d_shade, void *d_hits, void *stream)
+{
+    if (!shade_args_ok(scene, d_origins, d_directions, d_shade, flags, n_pixels) || !aligned16(d_shade, d_hits)) return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, shade_batch(scene, n_pixels, flags, lit, d_hits != nullptr), d_origins, d_directions,
+                        {d_shade, d_hits, nullptr}, stream);
 }
 
 // ---- any view through the render pipeline (rtx_render_view_rows; the aim kernels: rtx_aim.hip) ------------------------------
 
-// first record of the tree proper: behind the root and the leaf of the global triangles when there are any
-uint32_t aim_root(const rtx::PreparedScene &p)
-{
-    return (p.n_global != 0u && p.nodes.size() > 2u) ? 2u : 0u;
-}
-
-// The multiply-based culling of the pipeline's walks is proven for origins whose coordinates stay within the magnitude
-// behind cull_delta (scene_prep.cpp); the bound is the one batch_launch hands the ray-batch kernels.  A NaN fails it.
+// the pipeline's walks start at the eye: origin_bound holds for it.  A NaN fails it.
 bool eye_in_pipeline_range(const RtxScene *scene, const float eye[3])
 {
-    const float bound = scene->prep.cull_delta * 0x1p19f;
+    const float bound = origin_bound(scene);
     for (int k = 0; k < 3; ++k)
         if (!(std::fabs(eye[k]) <= bound)) return false;
     return true;
 }
 
-// the argument checks rtx_render_view_rows and its _device twin share: rtx_render_view's, and full width
+// the argument checks rtx_render_view_rows and its twins share: rtx_render_view's, and full width
 bool view_rows_args_ok(const RtxScene *scene, const RtxView *v, const void *out)
 {
-    if (!scene || !v || !out) return false;
-    if (v->width == 0u || v->height == 0u || static_cast<uint64_t>(v->width) * v->height >= (1ull << 31)) return false;
+    if (!scene || !v || !out || !frame_ok(v)) return false;
     if (v->x0 != 0u || v->nx != v->width) return false;
     return static_cast<uint64_t>(v->y0) + v->ny <= v->height;
 }
@@ -904,7 +957,7 @@ int aim_at(RtxScene *scene, DeviceState &st, const float eye[3], hipStream_t str
     st.aimed.valid = false;
     const uint32_t n = static_cast<uint32_t>(p.nodes.size());
     RTX_HIP(hipMemsetAsync(st.aimed.nodes.as<rtx::NodeDev>() + n, 0, sizeof(rtx::NodeDev), stream));      // the sentinel
-    RTX_HIP(rtxa::launch_aim(st.nodes.as<const rtx::NodeDev>(), n, aim_root(p), eye, st.aimed.links.as<rtxa::AimLink>(),
+    RTX_HIP(rtxa::launch_aim(st.nodes.as<const rtx::NodeDev>(), n, tree_root(p), eye, st.aimed.links.as<rtxa::AimLink>(),
                              st.aimed.nodes.as<rtx::NodeDev>(), stream));
     std::memcpy(st.aimed.eye, eye, 12);
     st.aimed.on = stream;
@@ -918,13 +971,12 @@ int aim_at(RtxScene *scene, DeviceState &st, const float eye[3], hipStream_t str
 // kernels are handed that light's five fields.
 template <class Before>
 int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t *d_out, unsigned long long *d_counters,
-                     hipStream_t stream, Before before, const Lit *lit = nullptr, float shaft_delta = 0.0f)
+                     hipStream_t stream, Before before, const Lit *lit, float shaft_delta)
 {
-    int rc = reserve_aimed(scene, st);
-    if (rc != RTX_OK) return rc;
-    if (lit && (rc = reserve_light_walk(scene, st, *lit)) != RTX_OK) return rc;
+    RTX_TRY(reserve_aimed(scene, st));
+    if (lit) RTX_TRY(reserve_light(scene, st, *lit, true));
     rtx::DeviceScene S = device_scene(scene, st);
-    if (lit) light_walk_swap(st, *lit, shaft_delta, &S);
+    if (lit) light_swap(st, *lit, true, shaft_delta, &S);
     S.width = v.width;
     S.height = v.height;
     std::memcpy(S.eye, v.eye, 12);
@@ -935,11 +987,57 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t
     S.primary_nodes = aimed_stream(scene, st);
     const rtx::TileSpec ts{v.y0, v.ny, v.ny, v.ny};
     return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
-        int brc = before();
-        if (brc == RTX_OK) brc = aim_at(scene, st, v.eye, stream);
-        if (brc == RTX_OK && lit) brc = light_walk_launch(scene, st, *lit, stream);
-        return brc;
+        RTX_TRY(before());
+        RTX_TRY(aim_at(scene, st, v.eye, stream));
+        return lit ? light_launch(scene, st, *lit, true, stream) : RTX_OK;
     });
+}
+
+// What a pipeline view with rows is checked for on the host, before a device is looked for: the eye in range, and with a
+// light of its own lit_rows_margin's rules; *shaft_delta: that light's margin.
+int view_rows_supported(const RtxScene *scene, const RtxView *view, const Lit *lit, float *shaft_delta)
+{
+    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
+    return lit ? lit_rows_margin(scene, *lit, shaft_delta) : RTX_OK;
+}
+
+// The bodies of rtx_render_view_rows and rtx_render_view_rows_device, each with its _lit twin's light as an argument (NULL:
+// the scene's, nothing swapped).  The host one renders into d_out on the library's stream and copies the rows back.
+int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, uint8_t *out_rgb, RtxStats *stats)
+{
+    if (!view_rows_args_ok(scene, view, out_rgb)) return RTX_ERR_BAD_ARG;
+    const Timed timed(stats);
+    if (view->ny == 0u) return timed.empty();
+    float shaft_delta = 0.0f;
+    RTX_TRY(view_rows_supported(scene, view, lit, &shaft_delta));
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const RtxView v = *view;                 // (the caller's may change while the call runs)
+    const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
+    RTX_TRY(st.d_out.reserve(bytes));
+    if (lit) RTX_TRY(wait_for(st.lit.used, st.stream));      // a device-resident call may still read its light
+    RTX_TRY(view_rows_launch(scene, st, v, st.d_out.as<uint8_t>(), timed.counters(st), st.stream, [&] { return timed.begin(st); }, lit,
+                             shaft_delta));
+    RTX_TRY(timed.end(st));
+    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
+    return timed.gather(st, static_cast<uint64_t>(v.ny) * v.width * scene->prep.nb_ray, lit ? lit->count : scene->prep.nb_light_sample);
+}
+
+// ... the device-resident one into the caller's buffer on the caller's stream, nothing waited for
+int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, void *d_rgb, size_t d_bytes, void *stream,
+                     uint64_t *d_counters)
+{
+    if (!view_rows_args_ok(scene, view, d_rgb)) return RTX_ERR_BAD_ARG;
+    if (d_bytes < static_cast<size_t>(view->ny) * view->width * 3u) return RTX_ERR_BAD_ARG;
+    if (view->ny == 0u) return RTX_OK;
+    float shaft_delta = 0.0f;
+    RTX_TRY(view_rows_supported(scene, view, lit, &shaft_delta));
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    RTX_TRY(view_rows_launch(scene, e.state(), *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
+                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta));
+    return lit ? mark_busy(e.state().lit.used, static_cast<hipStream_t>(stream)) : RTX_OK;
 }
 
 // host statement of the aim kernels: stream_nearest_first over the shadow stream with its planes moved as
@@ -955,7 +1053,7 @@ std::vector<rtx::NodeRec> aimed_on_host(const rtx::PreparedScene &p, const float
         }
     if (p.primary_nodes.empty()) return moved;
     std::vector<rtx::NodeRec> out;
-    rtx::stream_nearest_first(moved, aim_root(p), eye, out);
+    rtx::stream_nearest_first(moved, tree_root(p), eye, out);
     return out;
 }
 
@@ -1036,30 +1134,15 @@ int rtx_render_rows(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, 
     if (!scene || !out_rgb) return RTX_ERR_BAD_ARG;
     const uint32_t H = scene->prep.height, W = scene->prep.width;
     if (row0 > H || nrows > H - row0) return RTX_ERR_BAD_ARG;
-    const uint32_t nb_ray = scene->prep.nb_ray, nb_light = scene->prep.nb_light_sample;
-    const double t0 = wall_ms();
+    const Timed timed(stats);
     Entry e(scene, device, Entry::kCurrent);
     if (e.rc != RTX_OK) return e.rc;
-    unsigned long long c[rtx::kNumCounters] = {0};
-    if (nrows == 0) {
-        if (stats) fill_stats(stats, 0, nb_light, c, 0.0, wall_ms() - t0);
-        return RTX_OK;
-    }
-    const rtx::TileSpec ts{row0, nrows, nrows, nrows};
-    const int rc = launch_on(scene, *e.slot, ts, stats != nullptr);
-    if (rc != RTX_OK) return rc;
-    DeviceState &st = e.state();
-    const size_t bytes = static_cast<size_t>(nrows) * W * 3u;
-    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
-    if (stats)
-        RTX_HIP(hipMemcpyAsync(c, st.d_counters.as<void>(), sizeof c, hipMemcpyDeviceToHost, st.stream));
-    RTX_HIP(hipStreamSynchronize(st.stream));
-    if (stats) {
-        float ms = 0.0f;
-        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
-        fill_stats(stats, static_cast<uint64_t>(nrows) * W * nb_ray, nb_light, c, ms, wall_ms() - t0);
-    }
-    return RTX_OK;
+    if (nrows == 0) return timed.empty();
+    RTX_TRY(launch_on(scene, *e.slot, rtx::TileSpec{row0, nrows, nrows, nrows}, timed));
+    const DeviceState &st = e.state();
+    const uint64_t pixels = static_cast<uint64_t>(nrows) * W;
+    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), pixels * 3u, hipMemcpyDeviceToHost, st.stream));
+    return timed.gather(st, pixels * scene->prep.nb_ray, scene->prep.nb_light_sample);
 }
 
 int rtx_render_frame(RtxScene *scene, const int *devices, int n_devices, uint32_t tile_rows,
@@ -1122,7 +1205,7 @@ int rtx_render_frame(RtxScene *scene, const int *devices, int n_devices, uint32_
         if (!sh.spec.local_rows) continue;
         DeviceGuard g(devices[j]);
         if (g.status() != hipSuccess) return fail(hip_rc(g.status()));
-        const int rc = launch_on(scene, *sh.slot, sh.spec, stats != nullptr);
+        const int rc = launch_on(scene, *sh.slot, sh.spec, Timed(stats));      // (the frame gathers and times its shares itself)
         if (rc != RTX_OK) return fail(rc);
         launched.push_back(devices[j]);
         DeviceState &st = *sh.slot->st;
@@ -1215,8 +1298,7 @@ int rtx_occluded_rays(RtxScene *scene, int device, uint32_t n_rays, const float 
 int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
                           uint32_t flags, void *d_hits, void *stream)
 {
-    if (!query_args_ok(scene, d_origins, d_directions, d_hits, flags, n_rays) || (reinterpret_cast<uintptr_t>(d_hits) & 15u))
-        return RTX_ERR_BAD_ARG;
+    if (!query_args_ok(scene, d_origins, d_directions, d_hits, flags, n_rays) || !aligned16(d_hits)) return RTX_ERR_BAD_ARG;
     return batch_device(scene, device, query_batch(false, n_rays, flags), d_origins, d_directions, {d_hits, nullptr, nullptr}, stream);
 }
 
@@ -1230,18 +1312,13 @@ int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const
 int rtx_shade_rays(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
                    uint32_t flags, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
-    if (!shade_args_ok(scene, origins, directions, out_shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, shade_batch(scene, n_pixels, flags, out_hits != nullptr), origins, directions,
-                      {out_shade, out_hits, nullptr}, stats);
+    return shade_host(scene, device, n_pixels, origins, directions, flags, nullptr, out_shade, out_hits, stats);
 }
 
 int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
                           uint32_t flags, void *d_shade, void *d_hits, void *stream)
 {
-    if (!shade_args_ok(scene, d_origins, d_directions, d_shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, shade_batch(scene, n_pixels, flags, d_hits != nullptr), d_origins, d_directions,
-                        {d_shade, d_hits, nullptr}, stream);
+    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, nullptr, d_shade, d_hits, stream);
 }
 
 int rtx_scene_view(const RtxScene *scene, RtxView *out)
@@ -1262,22 +1339,13 @@ int rtx_scene_view(const RtxScene *scene, RtxView *out)
 int rtx_render_view(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxPixelShade *out_shade,
                     RtxRayHit *out_hits, RtxStats *stats)
 {
-    if (!view_args_ok(scene, view, out_rgb, out_shade, out_hits)) return RTX_ERR_BAD_ARG;
-    void *out[kBatchOuts];
-    out[kViewShade] = out_shade; out[kViewHits] = out_hits; out[kViewRgb] = out_rgb;
-    return batch_host(scene, device, view_batch(scene, view, out_rgb != nullptr, out_shade != nullptr, out_hits != nullptr),
-                      nullptr, nullptr, out, stats);
+    return view_host(scene, device, view, nullptr, out_rgb, out_shade, out_hits, stats);
 }
 
 int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, void *d_shade, void *d_hits,
                            void *stream)
 {
-    if (!view_args_ok(scene, view, d_rgb, d_shade, d_hits)) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
-    void *d_out[kBatchOuts];
-    d_out[kViewShade] = d_shade; d_out[kViewHits] = d_hits; d_out[kViewRgb] = d_rgb;
-    return batch_device(scene, device, view_batch(scene, view, d_rgb != nullptr, d_shade != nullptr, d_hits != nullptr),
-                        nullptr, nullptr, d_out, stream);
+    return view_device(scene, device, view, nullptr, d_rgb, d_shade, d_hits, stream);
 }
 
 int rtx_scene_light(const RtxScene *scene, RtxLight *out)
@@ -1295,42 +1363,32 @@ int rtx_render_view_lit(RtxScene *scene, int device, const RtxView *view, const 
                         RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
     Lit lit;
-    if (!view_args_ok(scene, view, out_rgb, out_shade, out_hits) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    void *out[kBatchOuts];
-    out[kViewShade] = out_shade; out[kViewHits] = out_hits; out[kViewRgb] = out_rgb;
-    return batch_host(scene, device, relit(view_batch(scene, view, out_rgb != nullptr, out_shade != nullptr, out_hits != nullptr), lit),
-                      nullptr, nullptr, out, stats);
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_host(scene, device, view, &lit, out_rgb, out_shade, out_hits, stats);
 }
 
 int rtx_render_view_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
                                void *d_shade, void *d_hits, void *stream)
 {
     Lit lit;
-    if (!view_args_ok(scene, view, d_rgb, d_shade, d_hits) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
-    void *d_out[kBatchOuts];
-    d_out[kViewShade] = d_shade; d_out[kViewHits] = d_hits; d_out[kViewRgb] = d_rgb;
-    return batch_device(scene, device, relit(view_batch(scene, view, d_rgb != nullptr, d_shade != nullptr, d_hits != nullptr), lit),
-                        nullptr, nullptr, d_out, stream);
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_device(scene, device, view, &lit, d_rgb, d_shade, d_hits, stream);
 }
 
 int rtx_shade_rays_lit(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
                        uint32_t flags, const RtxLight *light, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
     Lit lit;
-    if (!shade_args_ok(scene, origins, directions, out_shade, flags, n_pixels) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, relit(shade_batch(scene, n_pixels, flags, out_hits != nullptr), lit), origins, directions,
-                      {out_shade, out_hits, nullptr}, stats);
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return shade_host(scene, device, n_pixels, origins, directions, flags, &lit, out_shade, out_hits, stats);
 }
 
 int rtx_shade_rays_lit_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
                               uint32_t flags, const RtxLight *light, void *d_shade, void *d_hits, void *stream)
 {
     Lit lit;
-    if (!shade_args_ok(scene, d_origins, d_directions, d_shade, flags, n_pixels) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_shade) | reinterpret_cast<uintptr_t>(d_hits)) & 15u) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, relit(shade_batch(scene, n_pixels, flags, d_hits != nullptr), lit), d_origins, d_directions,
-                        {d_shade, d_hits, nullptr}, stream);
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, &lit, d_shade, d_hits, stream);
 }
 
 int rtx_scene_light_points_for(const RtxScene *scene, const RtxLight *light, float *out)
@@ -1350,129 +1408,40 @@ int rtx_debug_light_points(RtxScene *scene, int device, const RtxLight *light, f
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    if (st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));
-    rtx::DeviceScene S = device_scene(scene, st);
-    const int rc = light_launch(scene, st, lit, &S, st.stream);
-    if (rc != RTX_OK) return rc;
-    const size_t bytes = static_cast<size_t>(S.nb_ray) * S.nb_light * 3u * sizeof(float);
-    if (bytes) RTX_HIP(hipMemcpyAsync(out, S.light_points, bytes, hipMemcpyDeviceToHost, st.stream));
+    RTX_TRY(reserve_light(scene, st, lit, false));
+    RTX_TRY(wait_for(st.lit.used, st.stream));
+    RTX_TRY(light_launch(scene, st, lit, false, st.stream));
+    const size_t bytes = static_cast<size_t>(scene->prep.nb_ray) * lit.count * 3u * sizeof(float);
+    if (bytes) RTX_HIP(hipMemcpyAsync(out, st.lit.points.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
     RTX_HIP(hipStreamSynchronize(st.stream));
     return RTX_OK;
 }
 
 int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats)
 {
-    if (!view_rows_args_ok(scene, view, out_rgb)) return RTX_ERR_BAD_ARG;
-    const uint32_t nb_ray = scene->prep.nb_ray, nb_light = scene->prep.nb_light_sample;
-    const double t0 = wall_ms();
-    unsigned long long c[rtx::kNumCounters] = {0};
-    if (view->ny == 0u) {
-        if (stats) fill_stats(stats, 0, nb_light, c, 0.0, wall_ms() - t0);
-        return RTX_OK;
-    }
-    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    const RtxView v = *view;                 // (the caller's may change while the call runs)
-    const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
-    int rc = st.d_out.reserve(bytes);
-    if (rc != RTX_OK) return rc;
-    unsigned long long *counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
-    rc = view_rows_launch(scene, st, v, st.d_out.as<uint8_t>(), counters, st.stream, [&]() -> int {
-        if (stats) RTX_HIP(hipMemsetAsync(counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
-        RTX_HIP(hipEventRecord(st.ev0, st.stream));
-        return RTX_OK;
-    });
-    if (rc != RTX_OK) return rc;
-    RTX_HIP(hipEventRecord(st.ev1, st.stream));
-    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
-    if (stats) RTX_HIP(hipMemcpyAsync(c, st.d_counters.as<void>(), sizeof c, hipMemcpyDeviceToHost, st.stream));
-    RTX_HIP(hipStreamSynchronize(st.stream));
-    if (stats) {
-        float ms = 0.0f;
-        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
-        fill_stats(stats, static_cast<uint64_t>(v.ny) * v.width * nb_ray, nb_light, c, ms, wall_ms() - t0);
-    }
-    return RTX_OK;
+    return view_rows_host(scene, device, view, nullptr, out_rgb, stats);
 }
 
 int rtx_render_view_rows_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, size_t d_bytes, void *stream,
                                 uint64_t *d_counters)
 {
-    if (!view_rows_args_ok(scene, view, d_rgb)) return RTX_ERR_BAD_ARG;
-    if (d_bytes < static_cast<size_t>(view->ny) * view->width * 3u) return RTX_ERR_BAD_ARG;
-    if (view->ny == 0u) return RTX_OK;
-    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    return view_rows_launch(scene, e.state(), *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
-                            static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); });
+    return view_rows_device(scene, device, view, nullptr, d_rgb, d_bytes, stream, d_counters);
 }
 
 int rtx_render_view_rows_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
                              RtxStats *stats)
 {
     Lit lit;
-    if (!view_rows_args_ok(scene, view, out_rgb) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    const uint32_t nb_ray = scene->prep.nb_ray;
-    const double t0 = wall_ms();
-    unsigned long long c[rtx::kNumCounters] = {0};
-    if (view->ny == 0u) {
-        if (stats) fill_stats(stats, 0, lit.count, c, 0.0, wall_ms() - t0);
-        return RTX_OK;
-    }
-    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
-    float shaft_delta = 0.0f;
-    int rc = lit_rows_margin(scene, lit, &shaft_delta);
-    if (rc != RTX_OK) return rc;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    const RtxView v = *view;                 // (the caller's may change while the call runs)
-    const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
-    if ((rc = st.d_out.reserve(bytes)) != RTX_OK) return rc;
-    unsigned long long *counters = stats ? st.d_counters.as<unsigned long long>() : nullptr;
-    if (st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));   // a device-resident call may still read its light
-    rc = view_rows_launch(scene, st, v, st.d_out.as<uint8_t>(), counters, st.stream, [&]() -> int {
-        if (stats) RTX_HIP(hipMemsetAsync(counters, 0, rtx::kNumCounters * sizeof(unsigned long long), st.stream));
-        RTX_HIP(hipEventRecord(st.ev0, st.stream));
-        return RTX_OK;
-    }, &lit, shaft_delta);
-    if (rc != RTX_OK) return rc;
-    RTX_HIP(hipEventRecord(st.ev1, st.stream));
-    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
-    if (stats) RTX_HIP(hipMemcpyAsync(c, st.d_counters.as<void>(), sizeof c, hipMemcpyDeviceToHost, st.stream));
-    RTX_HIP(hipStreamSynchronize(st.stream));
-    if (stats) {
-        float ms = 0.0f;
-        RTX_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
-        fill_stats(stats, static_cast<uint64_t>(v.ny) * v.width * nb_ray, lit.count, c, ms, wall_ms() - t0);
-    }
-    return RTX_OK;
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_rows_host(scene, device, view, &lit, out_rgb, stats);
 }
 
 int rtx_render_view_rows_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
                                     size_t d_bytes, void *stream, uint64_t *d_counters)
 {
     Lit lit;
-    if (!view_rows_args_ok(scene, view, d_rgb) || !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    if (d_bytes < static_cast<size_t>(view->ny) * view->width * 3u) return RTX_ERR_BAD_ARG;
-    if (view->ny == 0u) return RTX_OK;
-    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
-    float shaft_delta = 0.0f;
-    int rc = lit_rows_margin(scene, lit, &shaft_delta);
-    if (rc != RTX_OK) return rc;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    rc = view_rows_launch(scene, st, *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
-                          static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, &lit, shaft_delta);
-    if (rc != RTX_OK) return rc;
-    // the library's light buffers are busy until this point of the caller's stream
-    if (!st.lit.used) RTX_HIP(hipEventCreateWithFlags(st.lit.used.put(), hipEventDisableTiming));
-    RTX_HIP(hipEventRecord(st.lit.used, static_cast<hipStream_t>(stream)));
-    return RTX_OK;
+    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_rows_device(scene, device, view, &lit, d_rgb, d_bytes, stream, d_counters);
 }
 
 int rtx_scene_light_walk_for(const RtxScene *scene, const RtxLight *light, uint32_t *out_order, float *out_boxes,
@@ -1496,10 +1465,9 @@ int rtx_debug_light_walk(RtxScene *scene, int device, const RtxLight *light, flo
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    int rc = reserve_light_walk(scene, st, lit);
-    if (rc != RTX_OK) return rc;
-    if (st.lit.used) RTX_HIP(hipStreamWaitEvent(st.stream, st.lit.used, 0));
-    if ((rc = light_walk_launch(scene, st, lit, st.stream)) != RTX_OK) return rc;
+    RTX_TRY(reserve_light(scene, st, lit, true));
+    RTX_TRY(wait_for(st.lit.used, st.stream));
+    RTX_TRY(light_launch(scene, st, lit, true, st.stream));
     const size_t n = static_cast<size_t>(scene->prep.nb_ray) * lit.count;
     if (n) {
         RTX_HIP(hipMemcpyAsync(out_tour, st.lit.tour.as<void>(), n * 4u * sizeof(float), hipMemcpyDeviceToHost, st.stream));
