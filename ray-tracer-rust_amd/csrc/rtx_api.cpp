@@ -159,7 +159,7 @@ public:
     DeviceBuffer d_out, d_counters;
     DeviceBuffer d_redo;                 // queue of tiles for reference_tiles_kernel
     // The two-pass pipeline zeroes its counting words (d_redo's headers, ws.buckets) for the NEXT launch inside each
-    // launch (rtx_kernel.hip: order_tiles_kernel): render_launch zeroes them (zero_launch_words) when they are not known to
+    // launch (rtx_pass_order.hpp: order_tiles_kernel): render_launch zeroes them (zero_launch_words) when they are not known to
     // be in that state — new or grown, used by another pipeline, a launch that failed — and counts what they have
     // served since, whose parities select the words a launch works on.
     bool launch_words_ready = false;
@@ -293,18 +293,7 @@ int upload_all(RtxScene *scene, DeviceState &st)
     if ((rc = upload_vec(st.shade, p.shade)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.samples, p.samples)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.lights, p.light_points)) != RTX_OK) return rc;
-#if RTX_LIGHT_TOUR == 0
-    // A/B builds only: the records of the walk in index order (position k = sample k of its batch)
-    std::vector<float> tour(p.light_tour.size());
-    for (size_t k = 0; k < tour.size() / 4; ++k) {
-        const uint32_t in_batch = static_cast<uint32_t>((k % (p.nb_light_sample ? p.nb_light_sample : 1u)) % rtx::kMaxLightBatch);
-        std::memcpy(&tour[4 * k], &p.light_points[3 * k], 12);
-        std::memcpy(&tour[4 * k + 3], &in_batch, 4);
-    }
-    if ((rc = upload_vec(st.light_tour, tour)) != RTX_OK) return rc;
-#else
     if ((rc = upload_vec(st.light_tour, p.light_tour)) != RTX_OK) return rc;
-#endif
     if (!p.global_planes.empty() && (rc = upload_vec(st.planes, p.global_planes)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.light_boxes, p.light_boxes)) != RTX_OK) return rc;
     if ((rc = st.thr.reserve(sizeof(p.gamma_thr))) != RTX_OK) return rc;

@@ -7,6 +7,11 @@
 
 #include "scene_prep.h"
 
+// 1: the ablation library (librtx_ablation.so), which holds the earlier kernel forms beside the product's pipeline
+#ifndef RTX_ABLATION
+#define RTX_ABLATION 0
+#endif
+
 namespace rtx {
 
 // Everything the kernel reads, resident in HBM for the life of the upload.
@@ -109,13 +114,13 @@ __host__ __device__ inline size_t cut_stream_offset(size_t tiles)      // bytes 
 }
 struct StreamWorkspaceBytes { size_t hits, pix_slot, tiles, chunks, results, acc, ctr, buckets, cut; };
 // Supported range of RTX_MAX_CUT.  Above: a job stages its tile's cut with ONE word per work-item of its 512
-// (rtx_kernel.hip: cut_word), so kCutWords * kMaxCut <= 512 — the build of round 2's cut-size sweep that printed no bench
+// (rtx_pass_shade.hpp: cut_word), so kCutWords * kMaxCut <= 512 — the build of round 2's cut-size sweep that printed no bench
 // line (profiles/r02/h_ab_cut_size_with_roots_in_lds.log, "build 5" = 64 entries of the ten-word CutEntry = 640 words) left
 // entries 51..63 of every cut unstaged and walked whatever LDS held; the same sweep before the roots moved into the
 // entries (two words each, 128) had run.  Also <= 64: one wavefront holds the cut's frontier.  Below: an empty array.
 static_assert(kMaxCut >= 1u && kMaxCut <= 51u && kCutWords * kMaxCut <= 512u, "RTX_MAX_CUT: 1 .. 51 (one staged word per work-item of 512)");
 constexpr uint32_t kTileCutShift = 8u;       // TileDesc::flags
-constexpr uint32_t kTileCompactHits = 8u;    // TileDesc::flags: the tile's hit records are in the compact form (rtx_kernel.hip: compact_hit_word)
+constexpr uint32_t kTileCompactHits = 8u;    // TileDesc::flags: the tile's hit records are in the compact form (rtx_pass_helpers.hpp: compact_hit_word)
 constexpr uint32_t kTileChunk0Kept = 4u;     // TileDesc::flags: probe_kernel's probing walk answers the shading pass's chunk 0
 StreamWorkspaceBytes stream_workspace_bytes(const DeviceScene &S, const TileSpec &ts, uint32_t variant);
 constexpr uint32_t kCostBuckets = 64u;
@@ -127,17 +132,11 @@ constexpr int kNumCounters = 8;
 
 // Light samples per LDS batch (results of one batch: 64 pixels x batch floats): RTX_LIGHT_BATCH, scene_prep.h — the
 // host orders each batch's walk.
-// In which order shade_tiles_kernel walks a batch's light samples, and which wavefront walks which (results land in the
-// sample's own column whatever the order, and the ordered accumulation reads the columns by ascending index):
-//   0  index order — the order of the sample table, two consecutive points a third of the light's side apart;
-//   1  along PreparedScene::light_tour, chunks dealt and drawn as before: the eight wavefronts of a workgroup walk
-//      neighbouring light points at the same time;
-//   2  along the tour, every wavefront of a walking tile of the cut form with a contiguous run of it, taken in order:
-//      a wavefront's consecutive walks are one tour step apart (the ring's premise, rtx_traverse.hpp: walk_cut_stream).
-#ifndef RTX_LIGHT_TOUR
-#define RTX_LIGHT_TOUR 1
-#endif
-static_assert(RTX_LIGHT_TOUR >= 0 && RTX_LIGHT_TOUR <= 2, "RTX_LIGHT_TOUR: 0, 1 or 2");
+// shade_tiles_kernel walks a batch's light samples along PreparedScene::light_tour, chunks dealt and drawn: the eight
+// wavefronts of a workgroup walk neighbouring light points at the same time (results land in the sample's own column
+// whatever the order, and the ordered accumulation reads the columns by ascending index).  The two other orders that
+// were measured — the sample table's index order, and a contiguous run of the tour per wavefront — left the sources with
+// their switch.
 
 // Kernel variants, kept selectable (RTX_VARIANT) so that profiles can show what each choice is worth:
 // bit 0 = conservative multiply-based box test for inner nodes (else the exact division-based one);

@@ -1,6 +1,6 @@
 // rtx_j1_ablation.hpp — the design BASELINE.json's north_star names, built so that it can be MEASURED against the one that
 // ships: "LDS-staged triangle blocks and wavefront-level min reductions for closest-hit", records served from LDS / the
-// vector memory path instead of scalar loads.  librtx_ablation.so only (-DRTX_ABLATION=1, included by rtx_kernel.hip inside
+// vector memory path instead of scalar loads.  librtx_ablation.so only (-DRTX_ABLATION=1, included by rtx_pass_schedule.hpp inside
 // namespace rtx); RTX_J1=<mode> in the environment selects a mode per process (rtx_api.cpp: DeviceScene::j1_mode):
 //   1  SHADING PASS: the walk's records arrive as VECTOR operands.  A job stages the stream window that holds its tile's cut
 //      (<= kJ1WindowNodes box records, 16 KB) in LDS; a step reads its record with two ds_read_b128 — every lane the same
@@ -9,7 +9,7 @@
 //   2  SCHEDULING PASS: a tile's 64 primary rays against ALL primitives, ray per lane, the primitives staged through LDS in
 //      blocks of 64 (lane l copies record b + l; every lane then reads record after record, broadcast).
 //   3  the same with a triangle per lane: lane l holds record b + l, the tile's rays are broadcast one after another
-//      (v_readlane), and the closest hit of a ray over the block is a wavefront min-reduction (DPP, rtx_kernel.hip: wave_min)
+//      (v_readlane), and the closest hit of a ray over the block is a wavefront min-reduction (DPP, rtx_pass_schedule.hpp: wave_min)
 //      of t, ties going to the greater reference rank by a second reduction (bvh.rs:123-130).
 // Modes 2 and 3 are brute force, as the north_star words it (no tree in the primary pass); triangle scenes only.  All three
 // produce the bytes of the shipped pipeline (tests/test_gpu_parity.py::test_north_star_variants...).  What they cost:

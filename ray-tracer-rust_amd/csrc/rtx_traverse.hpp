@@ -660,7 +660,7 @@ __device__ __forceinline__ NodeRec load_node_at(const NodeRec RTX_CONSTANT *base
 // carry 2^-100 for flushed products.  The kernel evaluates this next to the ray's set-up, for the FIRST global
 // triangle only, and tells the walk to leave that triangle out when every one of its lanes is certified.
 // The part of the certificate that depends on the ray's ORIGIN only (a full tile's lane keeps its origin for a whole
-// job: rtx_kernel.hip, the open-ground loop of shade_tiles_kernel): lhs = (|s_n| + k A_n)(1 + 2^-19), and s_n itself
+// job: rtx_pass_shade.hpp, the open-ground loop of shade_tiles_kernel): lhs = (|s_n| + k A_n)(1 + 2^-19), and s_n itself
 // where |s_n| > k A_n, else 0 (a zero makes "moving away" false).
 struct PlaneOrigin { float lhs, sn; };
 __device__ __forceinline__ PlaneOrigin plane_origin(const TriRec &g, float ox, float oy, float oz)
@@ -1016,7 +1016,7 @@ __device__ __forceinline__ bool any_hit(const NodeRec RTX_CONSTANT *__restrict__
     return closest_hit<COUNT, FAST, SPHERES, true, LEAN>(nodes, tris, shade, n_nodes, r, wc, n_global, first_global_ruled_out);
 }
 
-// The shadow walk of a chunk whose tile carries a CUT of the tree (rtx_kernel.hip: shaft_cut): the subtrees — record
+// The shadow walk of a chunk whose tile carries a CUT of the tree (rtx_pass_schedule.hpp: shaft_cut): the subtrees — record
 // ranges [begin, end) of the stream, at most kMaxCut of them — that the tile's shaft towards the light can touch.
 // Every box a ray of the tile passes lies in one of them (or holds one), so walking the ranges one after another
 // visits a superset of the candidates the whole-stream walk would find among the occluders, and an any-hit result does

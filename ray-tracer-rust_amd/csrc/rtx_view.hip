@@ -9,7 +9,7 @@
 // shadow rays towards one light point leave neighbouring hit points: the coherence the wave-uniform walk lives on, which
 // rtx_shade_rays gets for caller-made rays only from its regrouping pass.  No sort runs here, and no ray array is read:
 // a lane makes its rays in registers from the view block (kernel argument, wave-uniform; the eye is a scalar operand),
-// with create_rays' arithmetic as rtx_kernel.hip's primary_ray has it.
+// with create_rays' arithmetic as rtx_pass_helpers.hpp's primary_ray has it.
 //
 // Four independent wavefronts per workgroup: no barrier, no LDS.  The per-ray body is rtx_shade_pixel.hpp's shade_ray,
 // the one rtxs::shade_kernel calls: a view's records are byte for byte what rtx_shade_rays and rtx_trace_rays return for

@@ -652,7 +652,7 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
                 }
             }
 
-        // bounding box of the light points of primary ray r: one end of a tile's shaft (rtx_kernel.hip: shaft_cut)
+        // bounding box of the light points of primary ray r: one end of a tile's shaft (rtx_pass_schedule.hpp: shaft_cut)
         s.light_boxes.assign(6 * static_cast<size_t>(d.nb_ray), 0.0f);
         light_boxes_of(s.light_points.data(), d.nb_ray, d.nb_light_sample, s.light_boxes.data());
 

@@ -147,7 +147,7 @@ struct PreparedScene {
     // position units, rtx_traverse.hpp), so that the box test needs no per-test widening.
     float cull_delta = 0.0f;
     // per primary ray r: bounding box of its light points (lo xyz, hi xyz), and the margin of the tile shaft test,
-    // 2^-16 x the largest coordinate magnitude of scene, eye and light points (rtx_kernel.hip: shaft_cut)
+    // 2^-16 x the largest coordinate magnitude of scene, eye and light points (rtx_pass_schedule.hpp: shaft_cut)
     std::vector<float>    light_boxes;
     float shaft_delta = 0.0f;
     // what shaft_delta is folded from beside the light boxes: the largest coordinate magnitude of the scene and the eye

@@ -1,5 +1,5 @@
-"""shade_tiles_kernel gives a job's ray loops an issue priority that depends on the job (csrc/rtx_kernel.hip:
-RTX_JOB_PRIORITY) — which jobs run raised depends on who claims what and on the launch's order; the bytes and the
+"""shade_tiles_kernel gives a job's ray loops an issue priority that depends on the job (csrc/rtx_pass_order.hpp:
+kRaisedShare, and rtx_pass_shade.hpp: set_wave_priority) — which jobs run raised depends on who claims what and on the launch's order; the bytes and the
 counted statistics must not.  The shapes are the smallest that reach every level and every way a job gets its level:
 more jobs than workgroups (first and later jobs, costly and open-ground tiles), fewer jobs than workgroups (parts of
 tiles are the jobs), the whole-stream form with its per-XCD claims, the counted form, and a second primary ray whose

@@ -4,7 +4,7 @@ A launch of the two-pass pipeline is four dispatches — probe_kernel, order_til
 reference_tiles_kernel (the whole-stream form keeps count_classes_kernel as a fifth) — and none of them only zeroes: the
 queue's counts, the histogram of cost classes, the order's cursors and the claim words are zeroed for the NEXT pass or
 the NEXT launch by a kernel the launch runs anyway, selected by the parity of how many launches and passes the workspace
-has served, and zeroed by reset_kernel once when a buffer is allocated or grown (csrc/rtx_kernel.hip, the table at
+has served, and zeroed by reset_kernel once when a buffer is allocated or grown (csrc/rtx_pass_order.hpp, the table at
 order_tiles_kernel; csrc/rtx_api.cpp, render_launch).  A workgroup's first job
 is dealt by its number and only the later ones are claimed.  A word left stale shows as a wrong byte, a wrong
 primary_hits / redo_tiles, a tile rendered twice or not at all; so every launch here is compared, with zero tolerance,
@@ -12,7 +12,7 @@ with rtx_render_view of the same rows (its kernels use none of these words) and 
 the sequences are of odd and even length so that every kind of launch meets both parities.
 
 order_tiles_kernel also picks the share of the split limit from which a cost class runs raised by the launch's size: an
-eighth below kRaisedSmallJobs = 64 scheduled tiles per workgroup, a quarter from there (RTX_JOB_PRIORITY).  The last two
+eighth below kRaisedSmallJobs = 64 scheduled tiles per workgroup, a quarter from there (the jobs' levels).  The last two
 tests make launches on either side of that size on one workspace, so that the raised end of the order — the word every
 pass rewrites — moves between the whole order, a part of it and zero."""
 import importlib
@@ -235,7 +235,7 @@ def test_whole_stream_form(rtx, samples_seeded):
 
 # ------------------------------------------------------------------------------------------------------ both raised shares
 GRID = 1024                      # resident workgroups of shade_tiles_kernel on an MI355X: 256 CUs x 4
-RAISED_SMALL_JOBS = 64           # rtx_kernel.hip, kRaisedSmallJobs
+RAISED_SMALL_JOBS = 64           # rtx_pass_order.hpp, kRaisedSmallJobs
 TILE_UNSCHEDULED = 0xFFFFFFFF    # a descriptor's cost class when the tile has no job (no hit, or queued)
 
 

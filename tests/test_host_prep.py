@@ -72,7 +72,9 @@ def test_shipped_library_was_built_with_the_default_switches():
     assert shipped == default, "librtx.so was not built with the default switches:\n%s\n%s" % (shipped, default)
     named = set(re.findall(r" (RTX_[A-Z0-9_]+)=", shipped))
     defined = set()
-    for f in ("rtx_device.h", "rtx_traverse.hpp", "rtx_kernel.hip", "scene_prep.h", "rtx_ablation_kernels.hpp", "rtx_traverse_ablation.hpp"):
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".hpp", ".hip", ".cpp")))   # every one: a switch in a new header cannot hide
+    assert "rtx_kernel.hip" in sources and "rtx_traverse_ablation.hpp" in sources, sources
+    for f in sources:
         src = open(os.path.join(csrc, f)).read()
         defined |= set(re.findall(r"^#ifndef (RTX_[A-Z0-9_]+)[ \t]*(?://.*)?$", src, re.M))
         defined |= set(re.findall(r"^#\s*(?:if|elif)[^\n]*\b(RTX_EXPERIMENT_[A-Z0-9_]+)", src, re.M))

@@ -1,4 +1,4 @@
-// Development check (not part of the product): x / d for a divisor d that a whole launch shares (rtx_kernel.hip:
+// Development check (not part of the product): x / d for a divisor d that a whole launch shares (rtx_pass_helpers.hpp:
 // div_denom — the sample's contribution (colour * |n.l|) / (NB_RAY * NB_LIGHT_SAMPLE), main.rs:211-215), computed as
 //   y = 1/d (v_rcp_f32 + one Newton step), q0 = x*y; r0 = fma(-d,q0,x); q1 = fma(r0,y,q0); r1 = fma(-d,q1,x); q = fma(r1,y,q1)
 // — the compiler's IEEE division without its range scaling and fix-up — against x / d for EVERY binary32 x in

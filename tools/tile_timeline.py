@@ -59,7 +59,7 @@ for k in sorted(set(cls[work].tolist())):
         us[m & ((flags & 1) == 0)].mean() if (m & ((flags & 1) == 0)).any() else 0.0))
 top = np.argsort(-us)[:10]
 tx = (W + 7) // 8
-def tile_xy(t):   # the library numbers tiles by 8 x 8 blocks (rtx_kernel.hip: tile_xy)
+def tile_xy(t):   # the library numbers tiles by 8 x 8 blocks (rtx_pass_helpers.hpp: tile_xy)
     blocks_x, b, j = (tx + 7) // 8, t >> 6, t & 63
     return (b % blocks_x) * 8 + (j & 7), (b // blocks_x) * 8 + (j >> 3)
 print("costliest tiles:", [tile_xy(int(t)) + (int(n_cut[t]), int(n_hit[t]), round(float(us[t]), 1)) for t in top])
