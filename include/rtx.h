@@ -446,6 +446,86 @@ int rtx_render_view_rows_lit_device(RtxScene *scene, int device, const RtxView *
  * xyz, hi xyz).  Errors as the lit calls' (the margin is not looked at); both outputs are required. */
 int rtx_debug_light_walk(RtxScene *scene, int device, const RtxLight *light, float *out_tour, float *out_boxes);
 
+/* ---- posing an uploaded scene's triangles ----------------------------------------- */
+/* Geometry that moves without a new scene, a tree build or an upload.  A pose is n_tris x 9 floats in the layout of
+ * RtxSceneDesc.v0v1v2: one entry per triangle of the Vec<Primitive>, in Vec order with spheres skipped.  Spheres do not
+ * move, and the triangle count does not change.
+ *
+ * What a pose makes, on the device, on the call's stream, in buffers of the library's own (grow-only; growing waits for
+ * the device; ONE pose per scene per device: a new pose replaces the previous one; the uploaded scene is never written):
+ *   primitive record j (leaf order, caller index idx): v0, e1, e2 and the own box from the posed triangle by Triangle::new
+ *     and get_bounding_box (triangle.rs:22-56) — the one text rtx_scene_create runs on the host — idx unchanged; a sphere's
+ *     record is copied;
+ *   shading record idx: the normal from the posed triangle (a zero-area triangle: NaN, bits unspecified), rgb and kind
+ *     unchanged, the tie rank by the rule below; a sphere's record is copied, rank aside;
+ *   node record i: the tree keeps its shape (link and info unchanged).  Every record of the stream covers a contiguous run
+ *     [first_i, first_i + count_i) of the primitive array; its posed box is the fminf / fmaxf fold of those records' own
+ *     boxes, each plane then moved outwards by the SCENE's cull_delta in f32 (the sign of a zero is lost in the move: any
+ *     fold order gives the same words).  The two tables this needs — (first, count) per node, Vec position -> triangle
+ *     number — are made on the host once per scene and uploaded with the first pose.
+ * rtx_scene_posed_records is the host statement of these words; rtx_debug_pose reads the device's back.
+ *
+ * Range rule: every posed coordinate must be finite and of magnitude at most M, the largest coordinate magnitude of the
+ * created scene's primitives and eye (rtx_scene_pose_bound; 10,000 for main()'s scenes: the ground) — the bound
+ * cull_delta and the ray-batch calls' origin bound were sized for.  rtx_scene_pose decides it on the host, before a
+ * device is looked for: RTX_ERR_UNSUPPORTED.  For rtx_scene_pose_device it is a stated precondition: outside it the calls
+ * still terminate (the topology is fixed) and the values are unspecified.
+ *
+ * Parity: a posed call returns what the same call returns on a reference Scene holding the posed vertices, everything
+ * else the uploaded scene's.  For rays without a zero direction component results do not depend on the tree, so the
+ * refitted tree gives the reference's answer for the posed primitives.  Ties and 64-ray groups with a hard direction (a
+ * component -0.0, NaN or infinite) follow reference_tree:
+ *   RTX_REFTREE_NEVER (rtx_scene_pose_device always): ties by tie_rank (per Vec position, as RtxSceneDesc.tie_rank), or
+ *     by index when it is NULL; hard groups walk the refitted stream with the reference's box test — the result of SOME
+ *     tree over these primitives, RTX_REFTREE_NEVER's existing rule;
+ *   RTX_REFTREE_ALWAYS, or RTX_REFTREE_AUTO by rtx_scene_create's rule (rtx_scene_pose only): the reference's own tree
+ *     for the posed primitives is built on the host (O(n^2)) and uploaded beside the pose: it gives the ranks (unless
+ *     tie_rank is given) and the stream hard groups walk.
+ *
+ * rtx_scene_pose: RTX_ERR_BAD_ARG for a NULL scene or v0v1v2 or an unknown reference_tree; stats (may be NULL): kernel_ms
+ * is the pose kernels' time, the counters are zero.  Blocks until the pose stands.
+ * rtx_scene_pose_device: the caller's device arrays (4-byte aligned; d_tie_rank may be NULL) on the caller's stream,
+ * nothing waited for; they must stay valid until the kernels have run.
+ * Ordering is the lit buffers': device-resident poses and posed launches on one device must be ordered on one stream, and
+ * the host entry points wait (on the device, by an event) for the most recent of them. */
+int rtx_scene_pose_bound(const RtxScene *scene, float *out_magnitude);
+int rtx_scene_pose(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank /* may be NULL */,
+                   uint32_t reference_tree, RtxStats *stats);
+int rtx_scene_pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank /* may be NULL */,
+                          void *stream);
+/* Each posed call is its unposed twin — rtx_trace_rays, rtx_occluded_rays, rtx_shade_rays, rtx_render_view and their
+ * _device forms — in every respect (argument checks, outputs, flags, regrouping, alignment, stats), and launches the
+ * kernels its twin launches, with the geometry pointers of its argument block swapped for the pose's.  light: NULL for the
+ * scene's light, else the call is its _lit twin.  RTX_ERR_BAD_ARG when `device` holds no pose of this scene.  A posed call
+ * leaves every later unposed call unchanged.  The render pipeline (rtx_render_view_rows) has no posed form yet. */
+int rtx_trace_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
+                         uint32_t flags, RtxRayHit *out_hits, RtxStats *stats);
+int rtx_occluded_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
+                            uint32_t flags, uint8_t *out_occluded, RtxStats *stats);
+int rtx_trace_rays_posed_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
+                                uint32_t flags, void *d_hits, void *stream);
+int rtx_occluded_rays_posed_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
+                                   uint32_t flags, void *d_occluded, void *stream);
+int rtx_shade_rays_posed(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
+                         uint32_t flags, const RtxLight *light /* NULL = the scene's */, RtxPixelShade *out_shade,
+                         RtxRayHit *out_hits /* may be NULL */, RtxStats *stats);
+int rtx_shade_rays_posed_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
+                                uint32_t flags, const RtxLight *light /* NULL = the scene's */, void *d_shade,
+                                void *d_hits /* may be NULL */, void *stream);
+int rtx_render_view_posed(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                          uint8_t *out_rgb, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats);
+int rtx_render_view_posed_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                                 void *d_rgb, void *d_shade, void *d_hits, void *stream);
+/* Host only, no device: the words the pose kernels make.  out_tris: n_prims x 16 words (primitive records, leaf order:
+ * v0, e1, e2, own box min, own box max, idx); out_shade: n_prims x 8 (normal, rank, rgb, kind; Vec order); out_nodes:
+ * n_nodes x 8, NodeRec word order as rtx_scene_nodes, the planes moved by cull_delta.  tie_rank: per Vec position, NULL =
+ * the position (RTX_REFTREE_NEVER's rule).  Each output may be NULL.  The vertices are not checked against the range rule. */
+int rtx_scene_posed_records(const RtxScene *scene, const float *v0v1v2, const uint32_t *tie_rank, uint32_t *out_tris,
+                            uint32_t *out_shade, uint32_t *out_nodes);
+/* Diagnostic: blocks and copies the pose `device` holds back, in rtx_scene_posed_records' layout; each output may be NULL.
+ * RTX_ERR_BAD_ARG when the device holds no pose. */
+int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

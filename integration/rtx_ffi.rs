@@ -195,6 +195,42 @@ extern "C" {
     pub fn rtx_shade_rays_lit_device(scene: *mut RtxScene, device: c_int, n_pixels: u32, d_origins: *const c_void,
                                      d_directions: *const c_void, flags: u32, light: *const RtxLight, d_shade: *mut c_void,
                                      d_hits: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Posing: the uploaded scene's triangles moved to `v0v1v2` (`n_tris x 9` floats, Vec order, spheres skipped) on
+    /// `device`: one pose per scene and device, replaced by the next.  Every coordinate must be finite and at most
+    /// `rtx_scene_pose_bound`'s value in magnitude (`RTX_ERR_UNSUPPORTED`).  `tie_rank` may be NULL.
+    pub fn rtx_scene_pose_bound(scene: *const RtxScene, out_magnitude: *mut f32) -> c_int;
+    pub fn rtx_scene_pose(scene: *mut RtxScene, device: c_int, v0v1v2: *const f32, tie_rank: *const u32, reference_tree: u32,
+                          stats: *mut RtxStats) -> c_int;
+    pub fn rtx_scene_pose_device(scene: *mut RtxScene, device: c_int, d_v0v1v2: *const c_void, d_tie_rank: *const c_void,
+                                 stream: *mut c_void) -> c_int;
+    /// The posed calls: their unposed twins against the device's pose; `light` NULL = the scene's, else the `_lit` twin.
+    pub fn rtx_trace_rays_posed(scene: *mut RtxScene, device: c_int, n_rays: u32, origins: *const f32, directions: *const f32,
+                                flags: u32, out_hits: *mut RtxRayHit, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_occluded_rays_posed(scene: *mut RtxScene, device: c_int, n_rays: u32, origins: *const f32, targets: *const f32,
+                                   flags: u32, out_occluded: *mut u8, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_trace_rays_posed_device(scene: *mut RtxScene, device: c_int, n_rays: u32, d_origins: *const c_void,
+                                       d_directions: *const c_void, flags: u32, d_hits: *mut c_void,
+                                       stream: *mut c_void) -> c_int;
+    pub fn rtx_occluded_rays_posed_device(scene: *mut RtxScene, device: c_int, n_rays: u32, d_origins: *const c_void,
+                                          d_targets: *const c_void, flags: u32, d_occluded: *mut c_void,
+                                          stream: *mut c_void) -> c_int;
+    pub fn rtx_shade_rays_posed(scene: *mut RtxScene, device: c_int, n_pixels: u32, origins: *const f32, directions: *const f32,
+                                flags: u32, light: *const RtxLight, out_shade: *mut RtxPixelShade, out_hits: *mut RtxRayHit,
+                                stats: *mut RtxStats) -> c_int;
+    pub fn rtx_shade_rays_posed_device(scene: *mut RtxScene, device: c_int, n_pixels: u32, d_origins: *const c_void,
+                                       d_directions: *const c_void, flags: u32, light: *const RtxLight, d_shade: *mut c_void,
+                                       d_hits: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn rtx_render_view_posed(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                 out_rgb: *mut u8, out_shade: *mut RtxPixelShade, out_hits: *mut RtxRayHit,
+                                 stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_posed_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                        d_rgb: *mut c_void, d_shade: *mut c_void, d_hits: *mut c_void,
+                                        stream: *mut c_void) -> c_int;
+    /// Host only: the words the pose kernels make (each output may be NULL); `rtx_debug_pose` reads the device's back.
+    pub fn rtx_scene_posed_records(scene: *const RtxScene, v0v1v2: *const f32, tie_rank: *const u32, out_tris: *mut u32,
+                                   out_shade: *mut u32, out_nodes: *mut u32) -> c_int;
+    pub fn rtx_debug_pose(scene: *mut RtxScene, device: c_int, out_tris: *mut u32, out_shade: *mut u32,
+                          out_nodes: *mut u32) -> c_int;
     /// Host only: the points of `light` on this scene (`out` may be NULL); returns their number or a negative error.
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.

@@ -23,6 +23,7 @@
 #include "rtx_aim.h"
 #include "rtx_device.h"
 #include "rtx_light.h"
+#include "rtx_pose.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
 #include "rtx_tour.h"
@@ -187,6 +188,18 @@ public:
         DeviceBuffer points, tour, boxes;
         Event used;
     } lit;
+    // rtx_scene_pose (rtx_pose.hip): the host tables (rtx::PoseTables, uploaded with the first pose), the host variant's
+    // copies of the caller's arrays, and the one pose this device holds: posed primitive and shading records, the refitted
+    // stream, and — host variant with a reference tree — that tree's stream.  One guard: `used` (mark_busy / wait_for)
+    struct {
+        DeviceBuffer tri_of, ranges, order;
+        bool tables = false;
+        DeviceBuffer v, rank;
+        DeviceBuffer tris, shade, nodes, ref_nodes;
+        uint32_t n_ref_nodes = 0;
+        bool valid = false;
+        Event used;
+    } pose;
 private:
     ~DeviceState() = default;
     friend struct ReleaseOnDevice;
@@ -223,6 +236,8 @@ double wall_ms()
 struct RtxScene {
     rtx::PreparedScene prep;
     std::mutex mu;
+    rtx::PoseTables pose_tables;     // made by the first call that poses (pose_tables_of), under mu
+    bool pose_tables_made = false;
     std::map<int, DeviceSlot> dev;
 };
 
@@ -629,6 +644,7 @@ struct Batch {
     hipError_t (*launch)(const BatchArgs &);
     const RtxView *view;           // rtx_render_view: the caller's, read while the call runs; else NULL
     const Lit *lit;                // the lit twins: the call's light (shadow_rays_per_hit is its count); else NULL
+    bool posed;                    // the posed twins: the device's pose in place of the uploaded geometry (pose_swap)
 };
 
 bool batch_regroups(const Batch &b)
@@ -724,6 +740,95 @@ int lit_rows_margin(const RtxScene *scene, const Lit &lit, float *shaft_delta)
     return std::isfinite(*shaft_delta) ? RTX_OK : RTX_ERR_UNSUPPORTED;
 }
 
+// ---- posing (rtx_scene_pose; the kernels: rtx_pose.hip) --------------------------------------------------------------------
+
+// the scene's host tables, made once; may throw std::bad_alloc
+const rtx::PoseTables &pose_tables_of(RtxScene *scene)
+{
+    std::lock_guard<std::mutex> lk(scene->mu);
+    if (!scene->pose_tables_made) {
+        rtx::pose_tables(scene->prep, scene->pose_tables);
+        scene->pose_tables_made = true;
+    }
+    return scene->pose_tables;
+}
+
+uint32_t posed_triangles(const RtxScene *scene) { return scene->prep.n_tris - scene->prep.n_spheres; }
+
+// The pose's buffers, library-owned per device and grow-only, and the tables' upload with the first pose.  Growing a buffer
+// waits for the device first, since an earlier launch may still read it.  n_ref: records of the reference tree's stream that
+// goes beside the pose (host variant), or 0.  Caller holds the slot's lock and has the device current and the scene uploaded.
+int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_ref)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const size_t n_prims = p.tris.size(), n_nodes = p.nodes.size();
+    const size_t tris = (n_prims + 1u) * sizeof(rtx::TriRec), shade = std::max<size_t>(n_prims * sizeof(rtx::ShadeRec), 16u);
+    const size_t nodes = (n_nodes + 1u) * sizeof(rtx::NodeDev), ref = n_ref ? (n_ref + 1u) * sizeof(rtx::NodeDev) : 0u;
+    const size_t v = host_copies ? std::max<size_t>(static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float), 16u) : 0u;
+    const size_t rank = host_copies ? std::max<size_t>(n_prims * sizeof(uint32_t), 16u) : 0u;
+    auto &q = st.pose;
+    if (q.tris.capacity() < tris || q.shade.capacity() < shade || q.nodes.capacity() < nodes || q.ref_nodes.capacity() < ref ||
+        q.v.capacity() < v || q.rank.capacity() < rank) {
+        q.valid = false;
+        RTX_HIP(hipDeviceSynchronize());
+        RTX_TRY(reserve_all({{q.tris, tris}, {q.shade, shade}, {q.nodes, nodes}, {q.ref_nodes, ref}, {q.v, v}, {q.rank, rank}}));
+    }
+    if (q.tables) return RTX_OK;
+    try {
+        const rtx::PoseTables &t = pose_tables_of(scene);
+        RTX_TRY(upload_vec(q.tri_of, t.tri_of));
+        RTX_TRY(upload_vec(q.ranges, t.ranges));
+        RTX_TRY(upload_vec(q.order, t.order));
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    q.tables = true;
+    return RTX_OK;
+}
+
+// the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
+// copies of them; the records behind the last one (upload_all pads the scene's with the same) are zeroed on the same stream
+int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, hipStream_t stream)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const uint32_t n_prims = static_cast<uint32_t>(p.tris.size()), n_nodes = static_cast<uint32_t>(p.nodes.size());
+    auto &q = st.pose;
+    q.valid = false;
+    RTX_HIP(hipMemsetAsync(q.tris.as<rtx::TriRec>() + n_prims, 0, sizeof(rtx::TriRec), stream));
+    RTX_HIP(hipMemsetAsync(q.nodes.as<rtx::NodeDev>() + n_nodes, 0, sizeof(rtx::NodeDev), stream));
+    rtxp::PoseArgs a{};
+    a.tris = st.tris.as<const rtx::TriRec>();
+    a.shade = st.shade.as<const rtx::ShadeRec>();
+    a.nodes = st.nodes.as<const rtx::NodeDev>();
+    a.tri_of = q.tri_of.as<const uint32_t>();
+    a.ranges = q.ranges.as<const uint2>();
+    a.order = q.order.as<const uint32_t>();
+    a.n_prims = n_prims;
+    a.n_nodes = n_nodes;
+    a.n_long = scene->pose_tables.n_long;      // (made: reserve_pose)
+    a.cull_delta = p.cull_delta;
+    a.pose = d_pose;
+    a.rank = d_rank;
+    a.out_tris = q.tris.as<rtx::TriRec>();
+    a.out_shade = q.shade.as<rtx::ShadeRec>();
+    a.out_nodes = q.nodes.as<rtx::NodeDev>();
+    RTX_HIP(rtxp::launch_pose(a, stream));
+    q.n_ref_nodes = 0u;
+    q.valid = true;
+    return RTX_OK;
+}
+
+// ... and the fields of a posed call's copy of the scene's argument block that the ray-batch kernels read geometry through
+// (rtx_ray_walk.hpp).  The pipeline's fields (primary_nodes, planes) are not the pose's: it has no posed form.
+void pose_swap(const DeviceState &st, rtx::DeviceScene *S)
+{
+    S->nodes = st.pose.nodes.as<const rtx::NodeRec>();
+    S->tris = st.pose.tris.as<const rtx::TriRec>();
+    S->shade = st.pose.shade.as<const rtx::ShadeRec>();
+    S->ref_nodes = st.pose.ref_nodes.as<const rtx::NodeRec>();
+    S->n_ref_nodes = st.pose.n_ref_nodes;
+}
+
 // key + sort + kernel of one batch on `stream`, the light kernel of a lit one ahead of them; caller holds the slot's lock,
 // has the device current and the scene uploaded
 int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *d_first, const float *d_second,
@@ -732,7 +837,9 @@ int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *
     rtxq::SortBuffers sort{};
     const bool regroup = batch_regroups(b);
     if (regroup) RTX_TRY(reserve_query_sort(st, b.n, &sort));
+    if (b.posed && !st.pose.valid) return RTX_ERR_BAD_ARG;      // this device holds no pose
     rtx::DeviceScene S = device_scene(scene, st);
+    if (b.posed) pose_swap(st, &S);
     if (b.lit) {
         RTX_TRY(reserve_light(scene, st, *b.lit, false));
         RTX_TRY(light_launch(scene, st, *b.lit, false, stream));
@@ -761,6 +868,7 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
     for (int k = 0; k < kBatchOuts; ++k) d_out[k] = b.out_bytes[k] ? st.q_out.as<uint8_t>() + offset[k] : nullptr;
     RTX_TRY(wait_for(st.q_sorted, st.stream));              // a device-resident call may still be sorting
     if (b.lit) RTX_TRY(wait_for(st.lit.used, st.stream));   // ... or reading its light's points
+    if (b.posed) RTX_TRY(wait_for(st.pose.used, st.stream));    // ... or making the pose
     if (in_bytes) {
         RTX_HIP(hipMemcpyAsync(st.q_first.as<void>(), first, in_bytes, hipMemcpyHostToDevice, st.stream));
         RTX_HIP(hipMemcpyAsync(st.q_second.as<void>(), second, in_bytes, hipMemcpyHostToDevice, st.stream));
@@ -791,6 +899,7 @@ int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_firs
                          static_cast<hipStream_t>(stream)));
     if (batch_regroups(b)) RTX_TRY(mark_busy(st.q_sorted, static_cast<hipStream_t>(stream)));
     if (b.lit) RTX_TRY(mark_busy(st.lit.used, static_cast<hipStream_t>(stream)));
+    if (b.posed) RTX_TRY(mark_busy(st.pose.used, static_cast<hipStream_t>(stream)));
     return RTX_OK;
 }
 
@@ -806,20 +915,20 @@ bool shade_args_ok(const RtxScene *scene, const void *first, const void *second,
     return n_pixels == 0u || shade_ray_count(scene, n_pixels) != 0u;
 }
 
-Batch query_batch(bool occlusion, uint32_t n_rays, uint32_t flags)
+Batch query_batch(bool occlusion, uint32_t n_rays, uint32_t flags, bool posed)
 {
     return Batch{n_rays, n_rays, flags, {static_cast<size_t>(n_rays) * (occlusion ? 1u : sizeof(RtxRayHit)), 0u, 0u}, 0u,
-                 occlusion ? launch_queried<true> : launch_queried<false>, nullptr, nullptr};
+                 occlusion ? launch_queried<true> : launch_queried<false>, nullptr, nullptr, posed};
 }
 
 // Caller has checked n_pixels (shade_args_ok).  lit, here and below: NULL for the scene's light, else the call's (lit_of):
 // the light kernel runs ahead of the batch's kernel, and the statistics count the light's samples per hit.
-Batch shade_batch(const RtxScene *scene, uint32_t n_pixels, uint32_t flags, const Lit *lit, bool want_hits)
+Batch shade_batch(const RtxScene *scene, uint32_t n_pixels, uint32_t flags, const Lit *lit, bool posed, bool want_hits)
 {
     const uint32_t n_rays = shade_ray_count(scene, n_pixels);
     return Batch{n_pixels, n_rays, flags,
                  {static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade), want_hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u, 0u},
-                 lit ? lit->count : scene->prep.nb_light_sample, launch_shaded, nullptr, lit};
+                 lit ? lit->count : scene->prep.nb_light_sample, launch_shaded, nullptr, lit, posed};
 }
 
 // a frame has pixels, and fewer than 2^31 of them
@@ -837,10 +946,12 @@ bool view_args_ok(const RtxScene *scene, const RtxView *v, const void *rgb, cons
 }
 
 // caller has checked the view (view_args_ok); the rays are made tile by tile: no regrouping pass
-Batch view_batch(const RtxScene *scene, const RtxView *v, const Lit *lit, const void *rgb, const void *shade, const void *hits)
+Batch view_batch(const RtxScene *scene, const RtxView *v, const Lit *lit, bool posed, const void *rgb, const void *shade,
+                 const void *hits)
 {
     const uint32_t n_pixels = v->nx * v->ny, n_rays = n_pixels * scene->prep.nb_ray;
-    Batch b{n_pixels, n_rays, RTX_RAYS_KEEP_ORDER, {0u, 0u, 0u}, lit ? lit->count : scene->prep.nb_light_sample, launch_viewed, v, lit};
+    Batch b{n_pixels, n_rays, RTX_RAYS_KEEP_ORDER, {0u, 0u, 0u}, lit ? lit->count : scene->prep.nb_light_sample, launch_viewed, v, lit,
+            posed};
     b.out_bytes[kViewShade] = shade ? static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade) : 0u;
     b.out_bytes[kViewHits] = hits ? static_cast<size_t>(n_rays) * sizeof(RtxRayHit) : 0u;
     b.out_bytes[kViewRgb] = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
@@ -871,33 +982,34 @@ bool lit_of(const RtxScene *scene, const RtxLight *light, Lit *out)
 // The bodies of rtx_render_view and rtx_shade_rays, each with its _lit twin's light as an argument.  A view's outputs in
 // Batch::out_bytes' order: {shade, hits, rgb}.
 static_assert(kViewShade == 0 && kViewHits == 1 && kViewRgb == 2, "view_host and view_device list a view's outputs in this order");
-int view_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, uint8_t *rgb, RtxPixelShade *shade, RtxRayHit *hits,
-              RtxStats *stats)
+int view_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, uint8_t *rgb, RtxPixelShade *shade,
+              RtxRayHit *hits, RtxStats *stats)
 {
     if (!view_args_ok(scene, view, rgb, shade, hits)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, view_batch(scene, view, lit, rgb, shade, hits), nullptr, nullptr, {shade, hits, rgb}, stats);
+    return batch_host(scene, device, view_batch(scene, view, lit, posed, rgb, shade, hits), nullptr, nullptr, {shade, hits, rgb}, stats);
 }
 
-int view_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, void *d_rgb, void *d_shade, void *d_hits, void *stream)
+int view_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, void *d_rgb, void *d_shade, void *d_hits,
+                void *stream)
 {
     if (!view_args_ok(scene, view, d_rgb, d_shade, d_hits) || !aligned16(d_shade, d_hits)) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, view_batch(scene, view, lit, d_rgb, d_shade, d_hits), nullptr, nullptr, {d_shade, d_hits, d_rgb},
-                        stream);
+    return batch_device(scene, device, view_batch(scene, view, lit, posed, d_rgb, d_shade, d_hits), nullptr, nullptr,
+                        {d_shade, d_hits, d_rgb}, stream);
 }
 
 int shade_host(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions, uint32_t flags,
-               const Lit *lit, RtxPixelShade *shade, RtxRayHit *hits, RtxStats *stats)
+               const Lit *lit, bool posed, RtxPixelShade *shade, RtxRayHit *hits, RtxStats *stats)
 {
     if (!shade_args_ok(scene, origins, directions, shade, flags, n_pixels)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, shade_batch(scene, n_pixels, flags, lit, hits != nullptr), origins, directions,
+    return batch_host(scene, device, shade_batch(scene, n_pixels, flags, lit, posed, hits != nullptr), origins, directions,
                       {shade, hits, nullptr}, stats);
 }
 
 int shade_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions, uint32_t flags,
-                 const Lit *lit, void *d_shade, void *d_hits, void *stream)
+                 const Lit *lit, bool posed, void *d_shade, void *d_hits, void *stream)
 {
     if (!shade_args_ok(scene, d_origins, d_directions, d_shade, flags, n_pixels) || !aligned16(d_shade, d_hits)) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, shade_batch(scene, n_pixels, flags, lit, d_hits != nullptr), d_origins, d_directions,
+    return batch_device(scene, device, shade_batch(scene, n_pixels, flags, lit, posed, d_hits != nullptr), d_origins, d_directions,
                         {d_shade, d_hits, nullptr}, stream);
 }
 
@@ -1274,40 +1386,40 @@ int rtx_trace_rays(RtxScene *scene, int device, uint32_t n_rays, const float *or
                    uint32_t flags, RtxRayHit *out_hits, RtxStats *stats)
 {
     if (!query_args_ok(scene, origins, directions, out_hits, flags, n_rays)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, query_batch(false, n_rays, flags), origins, directions, {out_hits, nullptr, nullptr}, stats);
+    return batch_host(scene, device, query_batch(false, n_rays, flags, false), origins, directions, {out_hits, nullptr, nullptr}, stats);
 }
 
 int rtx_occluded_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
                       uint32_t flags, uint8_t *out_occluded, RtxStats *stats)
 {
     if (!query_args_ok(scene, origins, targets, out_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
-    return batch_host(scene, device, query_batch(true, n_rays, flags), origins, targets, {out_occluded, nullptr, nullptr}, stats);
+    return batch_host(scene, device, query_batch(true, n_rays, flags, false), origins, targets, {out_occluded, nullptr, nullptr}, stats);
 }
 
 int rtx_trace_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
                           uint32_t flags, void *d_hits, void *stream)
 {
     if (!query_args_ok(scene, d_origins, d_directions, d_hits, flags, n_rays) || !aligned16(d_hits)) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, query_batch(false, n_rays, flags), d_origins, d_directions, {d_hits, nullptr, nullptr}, stream);
+    return batch_device(scene, device, query_batch(false, n_rays, flags, false), d_origins, d_directions, {d_hits, nullptr, nullptr}, stream);
 }
 
 int rtx_occluded_rays_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
                              uint32_t flags, void *d_occluded, void *stream)
 {
     if (!query_args_ok(scene, d_origins, d_targets, d_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
-    return batch_device(scene, device, query_batch(true, n_rays, flags), d_origins, d_targets, {d_occluded, nullptr, nullptr}, stream);
+    return batch_device(scene, device, query_batch(true, n_rays, flags, false), d_origins, d_targets, {d_occluded, nullptr, nullptr}, stream);
 }
 
 int rtx_shade_rays(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
                    uint32_t flags, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
-    return shade_host(scene, device, n_pixels, origins, directions, flags, nullptr, out_shade, out_hits, stats);
+    return shade_host(scene, device, n_pixels, origins, directions, flags, nullptr, false, out_shade, out_hits, stats);
 }
 
 int rtx_shade_rays_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
                           uint32_t flags, void *d_shade, void *d_hits, void *stream)
 {
-    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, nullptr, d_shade, d_hits, stream);
+    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, nullptr, false, d_shade, d_hits, stream);
 }
 
 int rtx_scene_view(const RtxScene *scene, RtxView *out)
@@ -1328,13 +1440,13 @@ int rtx_scene_view(const RtxScene *scene, RtxView *out)
 int rtx_render_view(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxPixelShade *out_shade,
                     RtxRayHit *out_hits, RtxStats *stats)
 {
-    return view_host(scene, device, view, nullptr, out_rgb, out_shade, out_hits, stats);
+    return view_host(scene, device, view, nullptr, false, out_rgb, out_shade, out_hits, stats);
 }
 
 int rtx_render_view_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, void *d_shade, void *d_hits,
                            void *stream)
 {
-    return view_device(scene, device, view, nullptr, d_rgb, d_shade, d_hits, stream);
+    return view_device(scene, device, view, nullptr, false, d_rgb, d_shade, d_hits, stream);
 }
 
 int rtx_scene_light(const RtxScene *scene, RtxLight *out)
@@ -1353,7 +1465,7 @@ int rtx_render_view_lit(RtxScene *scene, int device, const RtxView *view, const 
 {
     Lit lit;
     if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_host(scene, device, view, &lit, out_rgb, out_shade, out_hits, stats);
+    return view_host(scene, device, view, &lit, false, out_rgb, out_shade, out_hits, stats);
 }
 
 int rtx_render_view_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
@@ -1361,7 +1473,7 @@ int rtx_render_view_lit_device(RtxScene *scene, int device, const RtxView *view,
 {
     Lit lit;
     if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_device(scene, device, view, &lit, d_rgb, d_shade, d_hits, stream);
+    return view_device(scene, device, view, &lit, false, d_rgb, d_shade, d_hits, stream);
 }
 
 int rtx_shade_rays_lit(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
@@ -1369,7 +1481,7 @@ int rtx_shade_rays_lit(RtxScene *scene, int device, uint32_t n_pixels, const flo
 {
     Lit lit;
     if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return shade_host(scene, device, n_pixels, origins, directions, flags, &lit, out_shade, out_hits, stats);
+    return shade_host(scene, device, n_pixels, origins, directions, flags, &lit, false, out_shade, out_hits, stats);
 }
 
 int rtx_shade_rays_lit_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
@@ -1377,7 +1489,7 @@ int rtx_shade_rays_lit_device(RtxScene *scene, int device, uint32_t n_pixels, co
 {
     Lit lit;
     if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, &lit, d_shade, d_hits, stream);
+    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, &lit, false, d_shade, d_hits, stream);
 }
 
 int rtx_scene_light_points_for(const RtxScene *scene, const RtxLight *light, float *out)
@@ -1465,6 +1577,178 @@ int rtx_debug_light_walk(RtxScene *scene, int device, const RtxLight *light, flo
     }
     RTX_HIP(hipStreamSynchronize(st.stream));
     return RTX_OK;
+}
+
+int rtx_scene_pose_bound(const RtxScene *scene, float *out)
+{
+    if (!scene || !out) return RTX_ERR_BAD_ARG;
+    *out = scene->prep.scene_magnitude;
+    return RTX_OK;
+}
+
+int rtx_scene_posed_records(const RtxScene *scene, const float *v0v1v2, const uint32_t *tie_rank, uint32_t *out_tris,
+                            uint32_t *out_shade, uint32_t *out_nodes)
+{
+    if (!scene || !v0v1v2) return RTX_ERR_BAD_ARG;
+    try {
+        const rtx::PoseTables &t = pose_tables_of(const_cast<RtxScene *>(scene));      // (the tables are a cache under the scene's lock)
+        rtx::posed_records(scene->prep, t, v0v1v2, tie_rank, reinterpret_cast<rtx::TriRec *>(out_tris),
+                           reinterpret_cast<rtx::ShadeRec *>(out_shade), reinterpret_cast<rtx::NodeRec *>(out_nodes));
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_scene_pose(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
+                   RtxStats *stats)
+{
+    if (!scene || !v0v1v2 || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
+    const rtx::PreparedScene &p = scene->prep;
+    if (!rtx::pose_in_range(p, v0v1v2)) return RTX_ERR_UNSUPPORTED;
+    const Timed timed(stats);
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const size_t n_prims = p.tris.size();
+    const bool want_ref = reference_tree == RTX_REFTREE_ALWAYS || (reference_tree == RTX_REFTREE_AUTO && n_prims <= rtx::kRefTreeAutoMax);
+    std::vector<uint32_t> ref_rank;
+    std::vector<rtx::NodeDev> ref_stream;
+    try {
+        if (want_ref) {
+            std::vector<rtx::NodeRec> stream;
+            RTX_TRY(rtx::posed_ref_tree(p, pose_tables_of(scene), v0v1v2, ref_rank, stream));
+            ref_stream = rtx::nodes_in_device_order(stream);
+        }
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    const uint32_t *rank = tie_rank ? tie_rank : (want_ref ? ref_rank.data() : nullptr);
+    RTX_TRY(reserve_pose(scene, st, true, ref_stream.size()));
+    RTX_TRY(wait_for(st.pose.used, st.stream));      // a device-resident call may still read the pose this one replaces
+    const size_t v_bytes = static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
+    hipError_t he = hipSuccess;
+    if (v_bytes) he = hipMemcpyAsync(st.pose.v.as<void>(), v0v1v2, v_bytes, hipMemcpyHostToDevice, st.stream);
+    if (he == hipSuccess && rank)
+        he = hipMemcpyAsync(st.pose.rank.as<void>(), rank, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
+    if (he == hipSuccess && !ref_stream.empty()) {
+        he = hipMemcpyAsync(st.pose.ref_nodes.as<void>(), ref_stream.data(), ref_stream.size() * sizeof(rtx::NodeDev),
+                            hipMemcpyHostToDevice, st.stream);
+        if (he == hipSuccess)
+            he = hipMemsetAsync(st.pose.ref_nodes.as<rtx::NodeDev>() + ref_stream.size(), 0, sizeof(rtx::NodeDev), st.stream);
+    }
+    int rc = hip_rc(he);
+    if (rc == RTX_OK) rc = timed.begin(st);
+    if (rc == RTX_OK) rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, st.stream);
+    if (rc == RTX_OK) rc = timed.end(st);
+    if (rc != RTX_OK) {
+        st.pose.valid = false;
+        (void)hipStreamSynchronize(st.stream);      // the copies above read the caller's arrays and this call's vectors
+        return rc;
+    }
+    st.pose.n_ref_nodes = static_cast<uint32_t>(ref_stream.size());
+    return timed.gather(st, 0u, 0u);
+}
+
+int rtx_scene_pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream)
+{
+    if (!scene || !d_v0v1v2) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_v0v1v2) | reinterpret_cast<uintptr_t>(d_tie_rank)) & 3u) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    RTX_TRY(reserve_pose(scene, st, false, 0u));
+    RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank),
+                        static_cast<hipStream_t>(stream)));
+    return mark_busy(st.pose.used, static_cast<hipStream_t>(stream));
+}
+
+int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
+{
+    if (!scene) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    if (!st.pose.valid) return RTX_ERR_BAD_ARG;
+    const size_t n_prims = scene->prep.tris.size(), n = scene->prep.nodes.size();
+    std::vector<rtx::NodeDev> dev;
+    try {
+        dev.resize(out_nodes ? n : 0u);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    RTX_TRY(wait_for(st.pose.used, st.stream));
+    if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, st.pose.tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
+    if (out_shade)
+        RTX_HIP(hipMemcpyAsync(out_shade, st.pose.shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
+    if (!dev.empty()) RTX_HIP(hipMemcpyAsync(dev.data(), st.pose.nodes.as<void>(), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    for (size_t i = 0; i < dev.size(); ++i) {         // NodeDev word order -> NodeRec's
+        const rtx::NodeDev &d = dev[i];
+        const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
+        std::memcpy(out_nodes + 8u * i, &r, sizeof r);
+    }
+    return RTX_OK;
+}
+
+int rtx_trace_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
+                         uint32_t flags, RtxRayHit *out_hits, RtxStats *stats)
+{
+    if (!query_args_ok(scene, origins, directions, out_hits, flags, n_rays)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, query_batch(false, n_rays, flags, true), origins, directions, {out_hits, nullptr, nullptr}, stats);
+}
+
+int rtx_occluded_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
+                            uint32_t flags, uint8_t *out_occluded, RtxStats *stats)
+{
+    if (!query_args_ok(scene, origins, targets, out_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
+    return batch_host(scene, device, query_batch(true, n_rays, flags, true), origins, targets, {out_occluded, nullptr, nullptr}, stats);
+}
+
+int rtx_trace_rays_posed_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_directions,
+                                uint32_t flags, void *d_hits, void *stream)
+{
+    if (!query_args_ok(scene, d_origins, d_directions, d_hits, flags, n_rays) || !aligned16(d_hits)) return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, query_batch(false, n_rays, flags, true), d_origins, d_directions, {d_hits, nullptr, nullptr}, stream);
+}
+
+int rtx_occluded_rays_posed_device(RtxScene *scene, int device, uint32_t n_rays, const void *d_origins, const void *d_targets,
+                                   uint32_t flags, void *d_occluded, void *stream)
+{
+    if (!query_args_ok(scene, d_origins, d_targets, d_occluded, flags, n_rays)) return RTX_ERR_BAD_ARG;
+    return batch_device(scene, device, query_batch(true, n_rays, flags, true), d_origins, d_targets, {d_occluded, nullptr, nullptr}, stream);
+}
+
+int rtx_shade_rays_posed(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
+                         uint32_t flags, const RtxLight *light, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
+{
+    Lit lit;
+    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return shade_host(scene, device, n_pixels, origins, directions, flags, light ? &lit : nullptr, true, out_shade, out_hits, stats);
+}
+
+int rtx_shade_rays_posed_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
+                                uint32_t flags, const RtxLight *light, void *d_shade, void *d_hits, void *stream)
+{
+    Lit lit;
+    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, light ? &lit : nullptr, true, d_shade, d_hits, stream);
+}
+
+int rtx_render_view_posed(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
+                          RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
+{
+    Lit lit;
+    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_host(scene, device, view, light ? &lit : nullptr, true, out_rgb, out_shade, out_hits, stats);
+}
+
+int rtx_render_view_posed_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
+                                 void *d_shade, void *d_hits, void *stream)
+{
+    Lit lit;
+    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_device(scene, device, view, light ? &lit : nullptr, true, d_rgb, d_shade, d_hits, stream);
 }
 
 int rtx_scene_aimed_nodes(const RtxScene *scene, const float eye[3], uint32_t *out_dwords)

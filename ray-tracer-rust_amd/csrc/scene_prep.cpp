@@ -66,15 +66,7 @@ void camera_new(const float eye[3], const float look_at[3], const float up[3],
 void triangle_derive(const float v0[3], const float v1[3], const float v2[3],
                      float e1[3], float e2[3], float normal[3], float bmin[3], float bmax[3])
 {
-    const V3 a = load3(v0), b = load3(v1), c = load3(v2);
-    const V3 ea = b - a, eb = c - a;
-    store3(e1, ea);
-    store3(e2, eb);
-    store3(normal, unit3(cross3(ea, eb)));
-    for (int k = 0; k < 3; ++k) {
-        bmin[k] = lesser(lesser(v0[k], v1[k]), v2[k]);
-        bmax[k] = greater(greater(v0[k], v1[k]), v2[k]);
-    }
+    triangle_statement(v0, v1, v2, e1, e2, normal, bmin, bmax);   // scene_prep.h: the statement the device compiles too
 }
 
 // Triangle::get_sample — triangle.rs:113-127: scene_prep.h's light_sample_point, the statement the device compiles too
@@ -905,6 +897,111 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
     } catch (const std::bad_alloc &) {
         return RTX_ERR_OOM;
     }
+    return RTX_OK;
+}
+
+// ---- posing (scene_prep.h) ----------------------------------------------------------------------------------------------
+
+void pose_tables(const PreparedScene &s, PoseTables &out)
+{
+    const size_t n_nodes = s.nodes.size(), n_prims = s.shade.size();
+    out.ranges.assign(2u * n_nodes, 0u);
+    for (size_t i = n_nodes; i-- > 0;) {        // pre-order: both children of an inner node lie behind it
+        const NodeRec &n = s.nodes[i];
+        uint32_t first, end;
+        if (n.info & kLeafFlag) {
+            first = n.info & kLeafIndexMask;
+            end = first + n.link;
+        } else {
+            const size_t a = i + 1u, b = n.info;
+            first = std::min(out.ranges[2u * a], out.ranges[2u * b]);
+            end = std::max(out.ranges[2u * a] + out.ranges[2u * a + 1u], out.ranges[2u * b] + out.ranges[2u * b + 1u]);
+        }
+        out.ranges[2u * i] = first;
+        out.ranges[2u * i + 1u] = end - first;
+    }
+    out.tri_of.assign(n_prims, kPoseNoTriangle);
+    uint32_t next = 0;
+    for (size_t i = 0; i < n_prims; ++i)
+        if (s.shade[i].kind == 0u) out.tri_of[i] = next++;
+    out.order.clear();
+    out.order.reserve(n_nodes);
+    for (uint32_t i = 0; i < n_nodes; ++i)
+        if (out.ranges[2u * i + 1u] > kPoseLaneMax) out.order.push_back(i);
+    out.n_long = static_cast<uint32_t>(out.order.size());
+    for (uint32_t i = 0; i < n_nodes; ++i)
+        if (out.ranges[2u * i + 1u] <= kPoseLaneMax) out.order.push_back(i);
+}
+
+bool pose_in_range(const PreparedScene &s, const float *pose)
+{
+    const size_t n = 9u * static_cast<size_t>(s.n_tris - s.n_spheres);
+    for (size_t k = 0; k < n; ++k)
+        if (!(std::fabs(pose[k]) <= s.scene_magnitude)) return false;      // (false for a NaN)
+    return true;
+}
+
+void posed_records(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *rank, TriRec *tris,
+                   ShadeRec *shade, NodeRec *nodes)
+{
+    const size_t n_prims = s.tris.size();
+    std::vector<TriRec> own;
+    if (!tris) {
+        own.resize(n_prims);
+        tris = own.data();
+    }
+    for (size_t j = 0; j < n_prims; ++j) {
+        TriRec r = s.tris[j];
+        ShadeRec sh = s.shade[r.idx];
+        if (sh.kind == 0u) {
+            const float *v = pose + 9u * static_cast<size_t>(t.tri_of[r.idx]);
+            std::memcpy(r.v0, v, 12);
+            triangle_statement(v, v + 3, v + 6, r.e1, r.e2, sh.normal, r.bmin, r.bmax);
+        }
+        sh.rank = rank ? rank[r.idx] : r.idx;
+        tris[j] = r;
+        if (shade) shade[r.idx] = sh;
+    }
+    if (!nodes) return;
+    const float inf = std::numeric_limits<float>::infinity();
+    for (size_t i = 0; i < s.nodes.size(); ++i) {
+        NodeRec n = s.nodes[i];
+        const uint32_t first = t.ranges[2u * i], count = t.ranges[2u * i + 1u];
+        for (int k = 0; k < 3; ++k) {
+            float lo = inf, hi = -inf;
+            for (uint32_t j = first; j < first + count; ++j) {
+                lo = fminf(lo, tris[j].bmin[k]);
+                hi = fmaxf(hi, tris[j].bmax[k]);
+            }
+            n.bmin[k] = lo - s.cull_delta;
+            n.bmax[k] = hi + s.cull_delta;
+        }
+        nodes[i] = n;
+    }
+}
+
+int posed_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, std::vector<uint32_t> &rank,
+                   std::vector<NodeRec> &stream)
+{
+    const size_t n_prims = s.tris.size();
+    std::vector<TriRec> tris(n_prims);
+    posed_records(s, t, pose, nullptr, tris.data(), nullptr, nullptr);
+    std::vector<float> boxes(6u * n_prims);
+    std::vector<uint32_t> pos_of(n_prims);
+    for (size_t j = 0; j < n_prims; ++j) {
+        const uint32_t idx = tris[j].idx;
+        std::memcpy(&boxes[6u * idx], tris[j].bmin, 12);
+        std::memcpy(&boxes[6u * idx + 3u], tris[j].bmax, 12);
+        pos_of[idx] = static_cast<uint32_t>(j);
+    }
+    rank.assign(n_prims, 0u);
+    const int rc = ref_tree_build_boxes(static_cast<uint32_t>(n_prims), boxes.data(), rank.data(), &stream);
+    if (rc != RTX_OK) return rc;
+    for (NodeRec &nd : stream)
+        if (nd.info & kLeafFlag) {
+            const uint32_t prim = nd.info & kLeafIndexMask;
+            nd.info = kLeafFlag | (s.shade[prim].kind ? kSphereFlag : 0u) | pos_of[prim];
+        }
     return RTX_OK;
 }
 

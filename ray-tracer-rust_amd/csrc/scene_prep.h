@@ -49,6 +49,36 @@ RTX_HOST_DEVICE inline float tour_distance(const float a[3], const float b[3])
 }
 // a call's light may have at most this many points (nb_ray x its sample count): rtx_*_lit, rtx_scene_light_points_for
 constexpr uint64_t kMaxCallLightPoints = 1ull << 20;
+// Triangle::new + get_bounding_box — triangle.rs:22-34, :45-56: e1 = v1 - v0, e2 = v2 - v0, normal = unit(cross(e1, e2))
+// (nalgebra's dot: the accumulator starts at zero, x, y, z in turn; Unit::new_normalize: each component divided by the
+// square root), the box by min_float / max_float (`a < b ? a : b`, `a < b ? b : a`, triangle.rs:37-43).  One text for both
+// compilers, as light_sample_point is: triangle_derive (scene_prep.cpp) on the host, rtxp::pose_records_kernel
+// (rtx_pose.hip) on the device, the same bits with -ffp-contract=off and the correctly rounded divide and square root.
+RTX_HOST_DEVICE inline void triangle_statement(const float v0[3], const float v1[3], const float v2[3], float e1[3],
+                                               float e2[3], float normal[3], float bmin[3], float bmax[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        e1[k] = v1[k] - v0[k];
+        e2[k] = v2[k] - v0[k];
+    }
+    const float cx = e1[1] * e2[2] - e1[2] * e2[1];
+    const float cy = e1[2] * e2[0] - e1[0] * e2[2];
+    const float cz = e1[0] * e2[1] - e1[1] * e2[0];
+    float acc = 0.0f;
+    acc = acc + cx * cx;
+    acc = acc + cy * cy;
+    acc = acc + cz * cz;
+    const float n = sqrtf(acc);
+    normal[0] = cx / n;
+    normal[1] = cy / n;
+    normal[2] = cz / n;
+    for (int k = 0; k < 3; ++k) {
+        const float lo = v0[k] < v1[k] ? v0[k] : v1[k];
+        const float hi = v0[k] < v1[k] ? v1[k] : v0[k];
+        bmin[k] = lo < v2[k] ? lo : v2[k];
+        bmax[k] = hi < v2[k] ? v2[k] : hi;
+    }
+}
 
 // One node of the threaded (pre-order, skip-linked) BVH stream: 8 dwords, fetched
 // by the kernel with one scalar 32-byte load.
@@ -210,5 +240,35 @@ int  ref_tree_build(uint32_t n_tris, const float *v0v1v2, uint32_t *out_rank, st
 int  ref_tree_build_boxes(uint32_t n, const float *lo_hi, uint32_t *out_rank, std::vector<NodeRec> *out_stream);
 // above this many primitives RTX_REFTREE_AUTO skips the O(n^2) reference tree (the reference itself could not build it)
 constexpr uint32_t kRefTreeAutoMax = 50000u;
+
+// ---- posing an uploaded scene's triangles (rtx_scene_pose; the kernels: rtx_pose.hip) ----
+// A pose is n_tris x 9 floats in RtxSceneDesc.v0v1v2's layout: the Vec's triangles in Vec order, spheres skipped (they do
+// not move).  The tree keeps its shape: every record of `nodes` holds the exact union of the primitives' own boxes over a
+// contiguous run of the primitive array (TreeBuilder::build, the global leaf, the root over all, both RTX_ACCEL_BRUTE
+// shapes), so record i's posed box is a min/max fold over records [first_i, first_i + count_i), independent of every
+// other node.  The refit kernels fold each range directly, a range of at most kPoseLaneMax records by one work-item and a
+// longer one by one workgroup of kPoseBlock work-items: `order` lists the nodes, the n_long long ranges first.
+constexpr uint32_t kPoseLaneMax = 32u;
+constexpr uint32_t kPoseBlock = 256u;
+constexpr uint32_t kPoseNoTriangle = 0xFFFFFFFFu;
+struct PoseTables {
+    std::vector<uint32_t> ranges;      // n_nodes x {first, count}
+    std::vector<uint32_t> tri_of;      // Vec position -> triangle number in the pose; a sphere: kPoseNoTriangle
+    std::vector<uint32_t> order;       // the nodes: those with count > kPoseLaneMax (ascending), then the others (ascending)
+    uint32_t n_long = 0;
+};
+void pose_tables(const PreparedScene &s, PoseTables &out);
+// what PreparedScene::cull_delta and origin_bound were sized for bounds the pose: every coordinate finite and of
+// magnitude at most scene_magnitude
+bool pose_in_range(const PreparedScene &s, const float *pose);
+// The host statement of what the pose kernels make.  rank: per Vec position, or NULL for the position itself.  tris:
+// n_prims records in leaf order; shade: n_prims in Vec order; nodes: n_nodes records in NodeRec's word order, the planes
+// moved outwards by cull_delta in f32 as nodes_in_device_order moves them.  Each output may be NULL.
+void posed_records(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *rank, TriRec *tris,
+                   ShadeRec *shade, NodeRec *nodes);
+// The reference's own tree over the posed primitives (ref_tree_build_boxes, O(n^2)): its leaf ranks per Vec position and
+// its stream, the leaves naming positions of the primitive array as PreparedScene::ref_nodes' do.
+int posed_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, std::vector<uint32_t> &rank,
+                   std::vector<NodeRec> &stream);
 
 }  // namespace rtx

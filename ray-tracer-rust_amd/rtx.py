@@ -93,6 +93,9 @@ class RayHit(C.Structure):
 
 NO_HIT = 0xFFFFFFFF
 RAYS_KEEP_ORDER, RAYS_FORCE_REGROUP = 1, 2
+# the refit kernels' size thresholds (scene_prep.h: kPoseLaneMax, kPoseBlock): a node whose run of records is longer than
+# POSE_LANE_MAX is folded by one workgroup of POSE_BLOCK work-items, a shorter one by one work-item
+POSE_LANE_MAX, POSE_BLOCK = 32, 256
 # the same 32 bytes as a numpy record: what Scene.trace_rays returns
 RAY_HIT_DTYPE = np.dtype([("prim", np.uint32), ("t", np.float32), ("p_hit", np.float32, 3), ("normal", np.float32, 3)])
 assert RAY_HIT_DTYPE.itemsize == C.sizeof(RayHit) == 32
@@ -175,6 +178,25 @@ _SIGS = {
                                      C.POINTER(PixelShade), C.POINTER(RayHit), C.POINTER(Stats)]),
     "rtx_shade_rays_lit_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.POINTER(RtxLight), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_scene_pose_bound": (C.c_int, [C.c_void_p, f32p]),
+    "rtx_scene_pose": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, C.c_uint32, C.POINTER(Stats)]),
+    "rtx_scene_pose_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_scene_posed_records": (C.c_int, [C.c_void_p, f32p, u32p, u32p, u32p, u32p]),
+    "rtx_debug_pose": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, u32p]),
+    "rtx_trace_rays_posed": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, C.POINTER(RayHit), C.POINTER(Stats)]),
+    "rtx_occluded_rays_posed": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, u8p, C.POINTER(Stats)]),
+    "rtx_trace_rays_posed_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                              C.c_void_p]),
+    "rtx_occluded_rays_posed_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p]),
+    "rtx_shade_rays_posed": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, f32p, f32p, C.c_uint32, C.POINTER(RtxLight),
+                                       C.POINTER(PixelShade), C.POINTER(RayHit), C.POINTER(Stats)]),
+    "rtx_shade_rays_posed_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                              C.POINTER(RtxLight), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_render_view_posed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
+                                        C.POINTER(PixelShade), C.POINTER(RayHit), C.POINTER(Stats)]),
+    "rtx_render_view_posed_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -540,43 +562,47 @@ class Scene:
             raise ValueError("the two ray arrays disagree in length")
         return a, b
 
-    def trace_rays(self, origins, directions, device=0, keep_order=False, stats=False, force_regroup=False):
+    def trace_rays(self, origins, directions, device=0, keep_order=False, stats=False, force_regroup=False, posed=False):
         """bvh.intersect(&Ray::new(origin, direction)) per ray -> structured array (RAY_HIT_DTYPE) of n records
         {prim, t, p_hit, normal}; prim == NO_HIT is a miss.  Directions may have any length.  keep_order traces in the
         given order (no regrouping pass); the results are the same bytes either way."""
         o, d = self._ray_arrays(origins, directions)
         out = np.zeros(len(o), RAY_HIT_DTYPE)
         st = Stats()
-        _check(_lib.rtx_trace_rays(self._h, device, len(o), _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup),
-                                   out.ctypes.data_as(C.POINTER(RayHit)), C.byref(st) if stats else None), "rtx_trace_rays")
+        fn = _lib.rtx_trace_rays_posed if posed else _lib.rtx_trace_rays      # posed: against the device's pose (pose())
+        _check(fn(self._h, device, len(o), _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup),
+                  out.ctypes.data_as(C.POINTER(RayHit)), C.byref(st) if stats else None), "rtx_trace_rays")
         return (out, st.asdict()) if stats else out
 
-    def occluded_rays(self, origins, targets, device=0, keep_order=False, stats=False, force_regroup=False):
+    def occluded_rays(self, origins, targets, device=0, keep_order=False, stats=False, force_regroup=False, posed=False):
         """The decision of main.rs:201-231 per (origin, target) pair -> uint8 [n], 1 = occluded, 0 = lit."""
         o, t = self._ray_arrays(origins, targets)
         out = np.zeros(len(o), np.uint8)
         st = Stats()
-        _check(_lib.rtx_occluded_rays(self._h, device, len(o), _fp(o), _fp(t), self._ray_flags(keep_order, force_regroup),
-                                      out.ctypes.data_as(u8p), C.byref(st) if stats else None), "rtx_occluded_rays")
+        fn = _lib.rtx_occluded_rays_posed if posed else _lib.rtx_occluded_rays
+        _check(fn(self._h, device, len(o), _fp(o), _fp(t), self._ray_flags(keep_order, force_regroup),
+                  out.ctypes.data_as(u8p), C.byref(st) if stats else None), "rtx_occluded_rays")
         return (out, st.asdict()) if stats else out
 
     def trace_rays_device(self, device, n_rays, d_origins_ptr, d_directions_ptr, d_hits_ptr, stream=None,
-                          keep_order=False, force_regroup=False):
+                          keep_order=False, force_regroup=False, posed=False):
         """Asynchronous closest-hit launch on device buffers the caller owns (n x 3 float32 twice, n x 32 bytes out)."""
-        _check(_lib.rtx_trace_rays_device(self._h, device, n_rays, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
-                                          self._ray_flags(keep_order, force_regroup), C.c_void_p(d_hits_ptr),
-                                          C.c_void_p(stream) if stream else None), "rtx_trace_rays_device")
+        fn = _lib.rtx_trace_rays_posed_device if posed else _lib.rtx_trace_rays_device
+        _check(fn(self._h, device, n_rays, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
+                  self._ray_flags(keep_order, force_regroup), C.c_void_p(d_hits_ptr),
+                  C.c_void_p(stream) if stream else None), "rtx_trace_rays_device")
 
     def occluded_rays_device(self, device, n_rays, d_origins_ptr, d_targets_ptr, d_occluded_ptr, stream=None,
-                             keep_order=False, force_regroup=False):
+                             keep_order=False, force_regroup=False, posed=False):
         """Asynchronous occlusion launch on device buffers the caller owns (n x 3 float32 twice, n bytes out)."""
-        _check(_lib.rtx_occluded_rays_device(self._h, device, n_rays, C.c_void_p(d_origins_ptr), C.c_void_p(d_targets_ptr),
-                                             self._ray_flags(keep_order, force_regroup), C.c_void_p(d_occluded_ptr),
-                                             C.c_void_p(stream) if stream else None), "rtx_occluded_rays_device")
+        fn = _lib.rtx_occluded_rays_posed_device if posed else _lib.rtx_occluded_rays_device
+        _check(fn(self._h, device, n_rays, C.c_void_p(d_origins_ptr), C.c_void_p(d_targets_ptr),
+                  self._ray_flags(keep_order, force_regroup), C.c_void_p(d_occluded_ptr),
+                  C.c_void_p(stream) if stream else None), "rtx_occluded_rays_device")
 
     # -- shading rays the caller supplies (GPU only)
     def shade_rays(self, origins, directions, device=0, keep_order=False, stats=False, force_regroup=False,
-                   want_hits=False, light=None):
+                   want_hits=False, light=None, posed=False):
         """render_pixel's body (main.rs:182-239) per pixel of nb_ray consecutive rays -> structured array
         (PIXEL_SHADE_DTYPE) of n / nb_ray records {linear, rgb8, hits}.  want_hits adds the rays' closest hits
         (RAY_HIT_DTYPE, n records, what trace_rays returns); stats adds the statistics, last.  Directions may have any
@@ -592,7 +618,9 @@ class Scene:
         tail = (out.ctypes.data_as(C.POINTER(PixelShade)), hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None,
                 C.byref(st) if stats else None)
         head = (self._h, device, n, _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup))
-        if light is None:
+        if posed:
+            _check(_lib.rtx_shade_rays_posed(*head, C.byref(light) if light is not None else None, *tail), "rtx_shade_rays_posed")
+        elif light is None:
             _check(_lib.rtx_shade_rays(*head, *tail), "rtx_shade_rays")
         else:
             _check(_lib.rtx_shade_rays_lit(*head, C.byref(light), *tail), "rtx_shade_rays_lit")
@@ -600,13 +628,16 @@ class Scene:
         return res if len(res) > 1 else out
 
     def shade_rays_device(self, device, n_pixels, d_origins_ptr, d_directions_ptr, d_shade_ptr, d_hits_ptr=None,
-                          stream=None, keep_order=False, force_regroup=False, light=None):
+                          stream=None, keep_order=False, force_regroup=False, light=None, posed=False):
         """Asynchronous shading launch on device buffers the caller owns (n_pixels * nb_ray x 3 float32 twice,
         n_pixels x 16 bytes out, optionally n_pixels * nb_ray x 32 bytes of hit records)."""
         head = (self._h, device, n_pixels, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
                 self._ray_flags(keep_order, force_regroup))
         tail = (C.c_void_p(d_shade_ptr), C.c_void_p(d_hits_ptr) if d_hits_ptr else None, C.c_void_p(stream) if stream else None)
-        if light is None:
+        if posed:
+            _check(_lib.rtx_shade_rays_posed_device(*head, C.byref(light) if light is not None else None, *tail),
+                   "rtx_shade_rays_posed_device")
+        elif light is None:
             _check(_lib.rtx_shade_rays_device(*head, *tail), "rtx_shade_rays_device")
         else:
             _check(_lib.rtx_shade_rays_lit_device(*head, C.byref(light), *tail), "rtx_shade_rays_lit_device")
@@ -628,7 +659,7 @@ class Scene:
         _check(_lib.rtx_scene_view(self._h, C.byref(out)), "rtx_scene_view")
         return out
 
-    def render_view(self, view, device=0, stats=False, want_shade=False, want_hits=False, light=None):
+    def render_view(self, view, device=0, stats=False, want_shade=False, want_hits=False, light=None, posed=False):
         """render_pixel for every pixel of the view's rectangle -> uint8 [ny, nx, 3]; want_shade adds the pixels' records
         (PIXEL_SHADE_DTYPE [ny, nx]: what shade_rays returns for the view's rays), want_hits the rays' closest hits
         (RAY_HIT_DTYPE [ny, nx, nb_ray]: trace_rays'), stats the statistics, last.  light (an RtxLight: make_light, light())
@@ -639,23 +670,83 @@ class Scene:
         st = Stats()
         tail = (out.ctypes.data, shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
                 hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None, C.byref(st) if stats else None)
-        if light is None:
+        if posed:
+            _check(_lib.rtx_render_view_posed(self._h, device, C.byref(view), C.byref(light) if light is not None else None, *tail),
+                   "rtx_render_view_posed")
+        elif light is None:
             _check(_lib.rtx_render_view(self._h, device, C.byref(view), *tail), "rtx_render_view")
         else:
             _check(_lib.rtx_render_view_lit(self._h, device, C.byref(view), C.byref(light), *tail), "rtx_render_view_lit")
         res = (out,) + ((shade,) if want_shade else ()) + ((hits,) if want_hits else ()) + ((st.asdict(),) if stats else ())
         return res if len(res) > 1 else out
 
-    def render_view_device(self, device, view, d_rgb_ptr=None, d_shade_ptr=None, d_hits_ptr=None, stream=None, light=None):
+    def render_view_device(self, device, view, d_rgb_ptr=None, d_shade_ptr=None, d_hits_ptr=None, stream=None, light=None,
+                           posed=False):
         """Asynchronous view launch into device buffers the caller owns, each optional: ny*nx*3 bytes, ny*nx x 16 bytes,
         ny*nx*nb_ray x 32 bytes."""
         tail = (C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None, C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
                 C.c_void_p(d_hits_ptr) if d_hits_ptr else None, C.c_void_p(stream) if stream else None)
-        if light is None:
+        if posed:
+            _check(_lib.rtx_render_view_posed_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                                     *tail), "rtx_render_view_posed_device")
+        elif light is None:
             _check(_lib.rtx_render_view_device(self._h, device, C.byref(view), *tail), "rtx_render_view_device")
         else:
             _check(_lib.rtx_render_view_lit_device(self._h, device, C.byref(view), C.byref(light), *tail),
                    "rtx_render_view_lit_device")
+
+    # -- posing the scene's triangles (GPU only, posed_records and pose_bound aside): the posed= keyword of trace_rays*,
+    #    occluded_rays*, shade_rays* and render_view* then works on the device's pose
+    def pose_bound(self):
+        """The largest coordinate magnitude a pose may hold (rtx_scene_pose_bound)."""
+        out = C.c_float(0.0)
+        _check(_lib.rtx_scene_pose_bound(self._h, C.byref(out)), "rtx_scene_pose_bound")
+        return np.float32(out.value)
+
+    def _pose_arrays(self, v0v1v2, tie_rank):
+        v = np.ascontiguousarray(v0v1v2, dtype=np.float32).reshape(-1, 9)
+        if len(v) != len(self.tris):
+            raise ValueError("a pose has one entry per triangle of the scene")
+        rank = None if tie_rank is None else np.ascontiguousarray(tie_rank, dtype=np.uint32).reshape(-1)
+        if rank is not None and len(rank) != self.n_prims:
+            raise ValueError("tie_rank must have one entry per primitive")
+        return v, rank
+
+    def pose(self, v0v1v2, device=0, tie_rank=None, reference_tree=REFTREE_NEVER, stats=False):
+        """Moves the scene's triangles on `device` to v0v1v2 (float32 [n_tris, 9], Vec order, spheres skipped): one pose per
+        scene and device, replaced by the next (rtx_scene_pose).  stats: kernel_ms is the pose kernels' time."""
+        v, rank = self._pose_arrays(v0v1v2, tie_rank)
+        st = Stats()
+        _check(_lib.rtx_scene_pose(self._h, device, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
+                                   int(reference_tree), C.byref(st) if stats else None), "rtx_scene_pose")
+        return st.asdict() if stats else None
+
+    def pose_device(self, device, d_v0v1v2_ptr, d_tie_rank_ptr=None, stream=None):
+        """Asynchronous pose from device arrays the caller owns (n_tris x 9 float32; n_prims uint32 or None)."""
+        _check(_lib.rtx_scene_pose_device(self._h, device, C.c_void_p(d_v0v1v2_ptr),
+                                          C.c_void_p(d_tie_rank_ptr) if d_tie_rank_ptr else None,
+                                          C.c_void_p(stream) if stream else None), "rtx_scene_pose_device")
+
+    def _pose_outputs(self):
+        i = self.info()
+        return np.zeros((self.n_prims, 16), np.uint32), np.zeros((self.n_prims, 8), np.uint32), np.zeros((i["n_nodes"], 8), np.uint32)
+
+    def posed_records(self, v0v1v2, tie_rank=None):
+        """Host only: the words the pose kernels make -> (tris uint32 [n_prims, 16] in leaf order, shade uint32 [n_prims, 8]
+        in Vec order, nodes uint32 [n_nodes, 8] in nodes()' word order with the planes moved by cull_delta)."""
+        v, rank = self._pose_arrays(v0v1v2, tie_rank)
+        t, s, n = self._pose_outputs()
+        _check(_lib.rtx_scene_posed_records(self._h, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
+                                            t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)),
+               "rtx_scene_posed_records")
+        return t, s, n
+
+    def debug_pose(self, device=0):
+        """Diagnostics: the pose `device` holds, copied back, in posed_records' layout."""
+        t, s, n = self._pose_outputs()
+        _check(_lib.rtx_debug_pose(self._h, device, t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)),
+               "rtx_debug_pose")
+        return t, s, n
 
     # -- another light for views and shaded rays: the light= keyword of render_view* and shade_rays*
     @staticmethod
