@@ -497,7 +497,7 @@ int rtx_scene_pose_device(RtxScene *scene, int device, const void *d_v0v1v2, con
  * _device forms — in every respect (argument checks, outputs, flags, regrouping, alignment, stats), and launches the
  * kernels its twin launches, with the geometry pointers of its argument block swapped for the pose's.  light: NULL for the
  * scene's light, else the call is its _lit twin.  RTX_ERR_BAD_ARG when `device` holds no pose of this scene.  A posed call
- * leaves every later unposed call unchanged.  The render pipeline (rtx_render_view_rows) has no posed form yet. */
+ * leaves every later unposed call unchanged.  The render pipeline's posed form is rtx_render_view_rows_posed, below. */
 int rtx_trace_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
                          uint32_t flags, RtxRayHit *out_hits, RtxStats *stats);
 int rtx_occluded_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *targets,
@@ -525,6 +525,40 @@ int rtx_scene_posed_records(const RtxScene *scene, const float *v0v1v2, const ui
 /* Diagnostic: blocks and copies the pose `device` holds back, in rtx_scene_posed_records' layout; each output may be NULL.
  * RTX_ERR_BAD_ARG when the device holds no pose. */
 int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes);
+
+/* The pose through the render pipeline.  Each call is its twin in every respect — rtx_render_view_rows / _device for a NULL
+ * light, rtx_render_view_rows_lit / _device otherwise: the argument checks, full width only, the eye's range rule before
+ * a device is looked for, ny == 0, d_bytes, stats, rtx_launch_timings, rtx_debug_tile_descs, no capture and replay, the
+ * light's rules — and launches the kernels its twin launches.  What differs is what they read: pose_swap's geometry
+ * pointers, and the two things the pipeline keeps beside them:
+ *   the plane records of the global triangles, made by every pose behind its records (one 16-word record per global
+ *     triangle from its posed record: N = e1 x e2 and W = |e1| x |e2| with plus signs in double, N rounded to nearest, W
+ *     to the f32 above; K_d = 2^-19 * 2 * (Wx + Wy + Wz) + 2^-100 in double over the rounded W, to the f32 above, or
+ *     infinity when a W is not below 2^100) — the words rtx_scene_create makes for the created triangles;
+ *   the primary rays' stream, aimed at the view's eye over the pose's refitted stream by rtx_render_view_rows' aim kernels,
+ *     in a buffer of the pose's own: it is kept for (eye, stream, pose) and every rtx_scene_pose / rtx_scene_pose_device
+ *     takes it away; the unposed calls' aimed stream is neither read nor written, so posed and unposed views of one eye
+ *     alternate without aiming either again.  A scene without a primary stream of its own (RTX_ACCEL_BRUTE, or nothing
+ *     beside the global triangles) aims nothing: its posed primary rays walk the pose's stream.
+ * The margin of the shaft test is the twin's: it is folded from the bound M of the range rule, not from the extent of the
+ * geometry.  RTX_ERR_BAD_ARG when `device` holds no pose of this scene.  Ordering: the pose's rule
+ * (the host call waits, by an event, for the device-resident poses and posed launches before it; the device-resident one
+ * marks the pose busy) and the pipeline's (launches on one device are ordered on one stream).  Parity: the frame of
+ * rtx_render_view_rows on a scene created with the posed vertices, byte for byte, under rtx_scene_pose's tie rule. */
+int rtx_render_view_rows_posed(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                               uint8_t *out_rgb, RtxStats *stats);
+int rtx_render_view_rows_posed_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                                      void *d_rgb, size_t d_bytes, void *stream, uint64_t *d_counters);
+/* Host only, no device: the words a pose makes for the pipeline.  out_planes: n_global x 16 words (v0, N, W, K_d, five
+ * zeros, idx: the created scene's plane records, for the posed triangles); out_aimed: n_nodes x 8 words, NodeRec
+ * word order: rtx_scene_posed_records' node words (their planes moved by cull_delta once, there) in rtx_scene_aimed_nodes'
+ * order for `eye`.  Each output may be NULL; eye may be NULL when out_aimed is.  RTX_ERR_BAD_ARG otherwise for a NULL. */
+int rtx_scene_posed_pipeline_records(const RtxScene *scene, const float *v0v1v2, const float eye[3], uint32_t *out_planes,
+                                     uint32_t *out_aimed);
+/* Diagnostic: the plane records of the pose `device` holds (nothing is written for a scene without global triangles), and
+ * the aim kernels run over that pose for `eye` (a scene that aims nothing: the pose's stream), in the layout above;
+ * blocks.  Each output may be NULL; eye may be NULL when out_aimed is.  RTX_ERR_BAD_ARG when the device holds no pose. */
+int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uint32_t *out_planes, uint32_t *out_aimed);
 
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),

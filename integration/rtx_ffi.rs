@@ -231,6 +231,19 @@ extern "C" {
                                    out_shade: *mut u32, out_nodes: *mut u32) -> c_int;
     pub fn rtx_debug_pose(scene: *mut RtxScene, device: c_int, out_tris: *mut u32, out_shade: *mut u32,
                           out_nodes: *mut u32) -> c_int;
+    /// The pose through the render pipeline: `rtx_render_view_rows` / `_device` (NULL light) or `rtx_render_view_rows_lit`
+    /// / `_device` with the device's pose in place of the uploaded triangles; `RTX_ERR_BAD_ARG` when it holds none.
+    pub fn rtx_render_view_rows_posed(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                      out_rgb: *mut u8, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_rows_posed_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                             d_rgb: *mut c_void, d_bytes: usize, stream: *mut c_void,
+                                             d_counters: *mut u64) -> c_int;
+    /// Host only: the plane records (n_global x 16 words) and the aimed stream (n_nodes x 8 words) a pose makes for the
+    /// pipeline; each output may be NULL, `eye` when `out_aimed` is.  `rtx_debug_pose_pipeline` reads the device's back.
+    pub fn rtx_scene_posed_pipeline_records(scene: *const RtxScene, v0v1v2: *const f32, eye: *const f32, out_planes: *mut u32,
+                                            out_aimed: *mut u32) -> c_int;
+    pub fn rtx_debug_pose_pipeline(scene: *mut RtxScene, device: c_int, eye: *const f32, out_planes: *mut u32,
+                                   out_aimed: *mut u32) -> c_int;
     /// Host only: the points of `light` on this scene (`out` may be NULL); returns their number or a negative error.
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.

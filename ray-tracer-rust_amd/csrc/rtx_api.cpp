@@ -23,6 +23,7 @@
 #include "rtx_aim.h"
 #include "rtx_device.h"
 #include "rtx_light.h"
+#include "rtx_planes.h"
 #include "rtx_pose.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
@@ -142,6 +143,17 @@ int reserve_all(std::initializer_list<Sized> list)
     return RTX_OK;
 }
 
+// A primary rays' stream aimed on the device (rtx_aim.hip): (n_nodes + 1) records, the last one the zeroed sentinel, the aim
+// kernels' scratch, and what the stream was aimed at, on and over — the eye's 12 bytes, the stream, and which pose's nodes
+// (DeviceState::pose's `made`; 0: the uploaded scene's).  A call with the same three walks it as it stands.
+struct AimedStream {
+    DeviceBuffer nodes, links;
+    float eye[3] = {0.0f, 0.0f, 0.0f};
+    hipStream_t on = nullptr;
+    unsigned long long over = 0;
+    bool valid = false;
+};
+
 // What a scene keeps on one device.  The argument blocks the launchers read (rtx::DeviceScene, rtx::StreamWorkspace,
 // rtxq::SortBuffers) are built from these owners where a launch needs them.
 class DeviceState {
@@ -172,15 +184,9 @@ public:
     // regrouping pass's (key, ray number) buffers and the sort's temporary storage; none shared with the render workspace
     DeviceBuffer q_first, q_second, q_out;
     struct { DeviceBuffer keys, keys_sorted, index, index_sorted, temp; } q_sort;
-    // rtx_render_view_rows (rtx_aim.hip): the primary rays' stream of the most recent view's eye — (n_nodes + 1) records,
-    // the last one the zeroed sentinel — the aim kernels' scratch, and what the stream was aimed at and on: a call with the
-    // same eye on the same stream walks it as it stands
-    struct {
-        DeviceBuffer nodes, links;
-        float eye[3] = {0.0f, 0.0f, 0.0f};
-        hipStream_t on = nullptr;
-        bool valid = false;
-    } aimed;
+    // rtx_render_view_rows (rtx_aim.hip): the primary rays' stream of the most recent unposed view's eye, aimed over the
+    // uploaded shadow stream; posed calls neither read nor write it (theirs is pose.aimed)
+    AimedStream aimed;
     // rtx_*_lit (rtx_light.hip): the points of the most recent lit call's light, made on that call's stream ahead of its
     // view or shade kernel; rtx_render_view_rows_lit (rtx_tour.hip) adds the tour and the boxes of that light.  One owner
     // (reserve_light, light_launch), one guard: `used` (mark_busy / wait_for)
@@ -190,14 +196,19 @@ public:
     } lit;
     // rtx_scene_pose (rtx_pose.hip): the host tables (rtx::PoseTables, uploaded with the first pose), the host variant's
     // copies of the caller's arrays, and the one pose this device holds: posed primitive and shading records, the refitted
-    // stream, and — host variant with a reference tree — that tree's stream.  One guard: `used` (mark_busy / wait_for)
+    // stream, and — host variant with a reference tree — that tree's stream.  For rtx_render_view_rows_posed: the plane
+    // records of the pose's global triangles (rtx_planes.hip, made with the pose) and the primary rays' stream of the most
+    // recent posed view's eye, aimed over the pose's nodes; `made` counts the poses launched, and every one of them takes
+    // the aimed stream's validity away.  One guard: `used` (mark_busy / wait_for)
     struct {
         DeviceBuffer tri_of, ranges, order;
         bool tables = false;
         DeviceBuffer v, rank;
-        DeviceBuffer tris, shade, nodes, ref_nodes;
+        DeviceBuffer tris, shade, nodes, ref_nodes, planes;
         uint32_t n_ref_nodes = 0;
         bool valid = false;
+        unsigned long long made = 0;
+        AimedStream aimed;
         Event used;
     } pose;
 private:
@@ -766,12 +777,14 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
     const size_t nodes = (n_nodes + 1u) * sizeof(rtx::NodeDev), ref = n_ref ? (n_ref + 1u) * sizeof(rtx::NodeDev) : 0u;
     const size_t v = host_copies ? std::max<size_t>(static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float), 16u) : 0u;
     const size_t rank = host_copies ? std::max<size_t>(n_prims * sizeof(uint32_t), 16u) : 0u;
+    const size_t planes = static_cast<size_t>(p.n_global) * sizeof(rtx::TriRec);      // (no global triangle: no buffer)
     auto &q = st.pose;
     if (q.tris.capacity() < tris || q.shade.capacity() < shade || q.nodes.capacity() < nodes || q.ref_nodes.capacity() < ref ||
-        q.v.capacity() < v || q.rank.capacity() < rank) {
+        q.v.capacity() < v || q.rank.capacity() < rank || q.planes.capacity() < planes) {
         q.valid = false;
         RTX_HIP(hipDeviceSynchronize());
-        RTX_TRY(reserve_all({{q.tris, tris}, {q.shade, shade}, {q.nodes, nodes}, {q.ref_nodes, ref}, {q.v, v}, {q.rank, rank}}));
+        RTX_TRY(reserve_all({{q.tris, tris}, {q.shade, shade}, {q.nodes, nodes}, {q.ref_nodes, ref}, {q.v, v}, {q.rank, rank},
+                             {q.planes, planes}}));
     }
     if (q.tables) return RTX_OK;
     try {
@@ -787,13 +800,17 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
 }
 
 // the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
-// copies of them; the records behind the last one (upload_all pads the scene's with the same) are zeroed on the same stream
+// copies of them; the records behind the last one (upload_all pads the scene's with the same) are zeroed on the same stream.
+// The plane kernel follows them over the posed global triangles (none: no launch), and whatever was aimed over the
+// previous pose no longer stands.
 int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, hipStream_t stream)
 {
     const rtx::PreparedScene &p = scene->prep;
     const uint32_t n_prims = static_cast<uint32_t>(p.tris.size()), n_nodes = static_cast<uint32_t>(p.nodes.size());
     auto &q = st.pose;
     q.valid = false;
+    q.aimed.valid = false;
+    ++q.made;
     RTX_HIP(hipMemsetAsync(q.tris.as<rtx::TriRec>() + n_prims, 0, sizeof(rtx::TriRec), stream));
     RTX_HIP(hipMemsetAsync(q.nodes.as<rtx::NodeDev>() + n_nodes, 0, sizeof(rtx::NodeDev), stream));
     rtxp::PoseArgs a{};
@@ -813,13 +830,15 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
     a.out_shade = q.shade.as<rtx::ShadeRec>();
     a.out_nodes = q.nodes.as<rtx::NodeDev>();
     RTX_HIP(rtxp::launch_pose(a, stream));
+    RTX_HIP(rtxg::launch_global_planes(q.tris.as<const rtx::TriRec>(), p.n_global, q.planes.as<rtx::TriRec>(), stream));
     q.n_ref_nodes = 0u;
     q.valid = true;
     return RTX_OK;
 }
 
 // ... and the fields of a posed call's copy of the scene's argument block that the ray-batch kernels read geometry through
-// (rtx_ray_walk.hpp).  The pipeline's fields (primary_nodes, planes) are not the pose's: it has no posed form.
+// (rtx_ray_walk.hpp).  The pipeline's own fields (primary_nodes, planes) are not swapped here: a posed pipeline call sets
+// them beside this (view_rows_launch).
 void pose_swap(const DeviceState &st, rtx::DeviceScene *S)
 {
     S->nodes = st.pose.nodes.as<const rtx::NodeRec>();
@@ -1035,48 +1054,66 @@ bool view_rows_args_ok(const RtxScene *scene, const RtxView *v, const void *out)
 // The stream the view's primary rays walk, on `stream`: the scene's shadow stream when it has no primary stream of its own
 // (nothing is aimed then), else the device's aimed buffer, the aim kernels run first unless it stands for this eye on this
 // stream.  Caller holds the slot's lock and has the device current and the scene uploaded; reserve_aimed() comes first.
-int reserve_aimed(RtxScene *scene, DeviceState &st)
+// posed: the same over the pose — its refitted shadow stream, its own aimed buffer (DeviceState::pose's), so that posed
+// and unposed views of one eye alternate without aiming either again, and neither is handed the other's stream.  The
+// tree keeps its shape under a pose: tree_root and the record count hold.
+AimedStream &aimed_of(DeviceState &st, bool posed) { return posed ? st.pose.aimed : st.aimed; }
+
+int reserve_aimed(RtxScene *scene, DeviceState &st, bool posed)
 {
     if (scene->prep.primary_nodes.empty()) return RTX_OK;
+    AimedStream &a = aimed_of(st, posed);
     const size_t n = scene->prep.nodes.size();
-    const size_t had = st.aimed.nodes.capacity();
-    const int rc = reserve_all({{st.aimed.nodes, (n + 1u) * sizeof(rtx::NodeDev)}, {st.aimed.links, n * sizeof(rtxa::AimLink)}});
-    if (rc != RTX_OK || st.aimed.nodes.capacity() != had) st.aimed.valid = false;
+    const size_t had = a.nodes.capacity();
+    const int rc = reserve_all({{a.nodes, (n + 1u) * sizeof(rtx::NodeDev)}, {a.links, n * sizeof(rtxa::AimLink)}});
+    if (rc != RTX_OK || a.nodes.capacity() != had) a.valid = false;
     return rc;
 }
 
-const rtx::NodeRec *aimed_stream(const RtxScene *scene, const DeviceState &st)
+const rtx::NodeRec *aimed_stream(const RtxScene *scene, DeviceState &st, bool posed)
 {
-    return (scene->prep.primary_nodes.empty() ? st.nodes : st.aimed.nodes).as<const rtx::NodeRec>();
+    if (scene->prep.primary_nodes.empty()) return (posed ? st.pose.nodes : st.nodes).as<const rtx::NodeRec>();
+    return aimed_of(st, posed).nodes.as<const rtx::NodeRec>();
 }
 
-int aim_at(RtxScene *scene, DeviceState &st, const float eye[3], hipStream_t stream)
+int aim_at(RtxScene *scene, DeviceState &st, bool posed, const float eye[3], hipStream_t stream)
 {
     const rtx::PreparedScene &p = scene->prep;
     if (p.primary_nodes.empty()) return RTX_OK;
-    if (st.aimed.valid && st.aimed.on == stream && std::memcmp(st.aimed.eye, eye, 12) == 0) return RTX_OK;
-    st.aimed.valid = false;
+    AimedStream &a = aimed_of(st, posed);
+    const unsigned long long over = posed ? st.pose.made : 0ull;
+    if (a.valid && a.on == stream && a.over == over && std::memcmp(a.eye, eye, 12) == 0) return RTX_OK;
+    a.valid = false;
     const uint32_t n = static_cast<uint32_t>(p.nodes.size());
-    RTX_HIP(hipMemsetAsync(st.aimed.nodes.as<rtx::NodeDev>() + n, 0, sizeof(rtx::NodeDev), stream));      // the sentinel
-    RTX_HIP(rtxa::launch_aim(st.nodes.as<const rtx::NodeDev>(), n, tree_root(p), eye, st.aimed.links.as<rtxa::AimLink>(),
-                             st.aimed.nodes.as<rtx::NodeDev>(), stream));
-    std::memcpy(st.aimed.eye, eye, 12);
-    st.aimed.on = stream;
-    st.aimed.valid = true;
+    RTX_HIP(hipMemsetAsync(a.nodes.as<rtx::NodeDev>() + n, 0, sizeof(rtx::NodeDev), stream));      // the sentinel
+    RTX_HIP(rtxa::launch_aim((posed ? st.pose.nodes : st.nodes).as<const rtx::NodeDev>(), n, tree_root(p), eye,
+                             a.links.as<rtxa::AimLink>(), a.nodes.as<rtx::NodeDev>(), stream));
+    std::memcpy(a.eye, eye, 12);
+    a.on = stream;
+    a.over = over;
+    a.valid = true;
     return RTX_OK;
 }
 
 // rtx_render_rows / rtx_render_tiles_device for a view: device_scene() with the view's frame and camera and the aimed
 // stream, rows [y0, y0 + ny) as one share.  `before`: as render_launch's; the aim kernels follow it on the stream.  lit:
 // NULL, or the call's light with its margin (lit_rows_margin): the light kernels follow the aim kernels, and the pipeline's
-// kernels are handed that light's five fields.
+// kernels are handed that light's five fields.  posed: the device's pose in place of the uploaded geometry — pose_swap's
+// fields, the pose's plane records and the stream aimed over the pose's nodes; no field of the block is added or moved,
+// and the kernels are the unposed call's.  The shaft margin is the unposed call's too: it is folded from the bound M every
+// posed coordinate respects, not from the geometry's extent.  RTX_ERR_BAD_ARG: no pose on this device.
 template <class Before>
 int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t *d_out, unsigned long long *d_counters,
-                     hipStream_t stream, Before before, const Lit *lit, float shaft_delta)
+                     hipStream_t stream, Before before, const Lit *lit, float shaft_delta, bool posed)
 {
-    RTX_TRY(reserve_aimed(scene, st));
+    if (posed && !st.pose.valid) return RTX_ERR_BAD_ARG;
+    RTX_TRY(reserve_aimed(scene, st, posed));
     if (lit) RTX_TRY(reserve_light(scene, st, *lit, true));
     rtx::DeviceScene S = device_scene(scene, st);
+    if (posed) {
+        pose_swap(st, &S);
+        S.planes = scene->prep.n_global ? st.pose.planes.as<const rtx::TriRec>() : nullptr;
+    }
     if (lit) light_swap(st, *lit, true, shaft_delta, &S);
     S.width = v.width;
     S.height = v.height;
@@ -1085,11 +1122,11 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t
     std::memcpy(S.cv, v.v, 12);
     std::memcpy(S.cw, v.w, 12);
     S.distance = v.distance;
-    S.primary_nodes = aimed_stream(scene, st);
+    S.primary_nodes = aimed_stream(scene, st, posed);
     const rtx::TileSpec ts{v.y0, v.ny, v.ny, v.ny};
     return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
         RTX_TRY(before());
-        RTX_TRY(aim_at(scene, st, v.eye, stream));
+        RTX_TRY(aim_at(scene, st, posed, v.eye, stream));
         return lit ? light_launch(scene, st, *lit, true, stream) : RTX_OK;
     });
 }
@@ -1103,8 +1140,9 @@ int view_rows_supported(const RtxScene *scene, const RtxView *view, const Lit *l
 }
 
 // The bodies of rtx_render_view_rows and rtx_render_view_rows_device, each with its _lit twin's light as an argument (NULL:
-// the scene's, nothing swapped).  The host one renders into d_out on the library's stream and copies the rows back.
-int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, uint8_t *out_rgb, RtxStats *stats)
+// the scene's, nothing swapped) and its _posed twin's switch.  The host one renders into d_out on the library's stream and
+// copies the rows back.
+int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, uint8_t *out_rgb, RtxStats *stats)
 {
     if (!view_rows_args_ok(scene, view, out_rgb)) return RTX_ERR_BAD_ARG;
     const Timed timed(stats);
@@ -1118,16 +1156,17 @@ int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *
     const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
     RTX_TRY(st.d_out.reserve(bytes));
     if (lit) RTX_TRY(wait_for(st.lit.used, st.stream));      // a device-resident call may still read its light
+    if (posed) RTX_TRY(wait_for(st.pose.used, st.stream));   // ... or make the pose, or walk what was aimed over it
     RTX_TRY(view_rows_launch(scene, st, v, st.d_out.as<uint8_t>(), timed.counters(st), st.stream, [&] { return timed.begin(st); }, lit,
-                             shaft_delta));
+                             shaft_delta, posed));
     RTX_TRY(timed.end(st));
     RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
     return timed.gather(st, static_cast<uint64_t>(v.ny) * v.width * scene->prep.nb_ray, lit ? lit->count : scene->prep.nb_light_sample);
 }
 
 // ... the device-resident one into the caller's buffer on the caller's stream, nothing waited for
-int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, void *d_rgb, size_t d_bytes, void *stream,
-                     uint64_t *d_counters)
+int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, void *d_rgb, size_t d_bytes,
+                     void *stream, uint64_t *d_counters)
 {
     if (!view_rows_args_ok(scene, view, d_rgb)) return RTX_ERR_BAD_ARG;
     if (d_bytes < static_cast<size_t>(view->ny) * view->width * 3u) return RTX_ERR_BAD_ARG;
@@ -1137,8 +1176,30 @@ int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     RTX_TRY(view_rows_launch(scene, e.state(), *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
-                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta));
-    return lit ? mark_busy(e.state().lit.used, static_cast<hipStream_t>(stream)) : RTX_OK;
+                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta, posed));
+    if (lit) RTX_TRY(mark_busy(e.state().lit.used, static_cast<hipStream_t>(stream)));
+    return posed ? mark_busy(e.state().pose.used, static_cast<hipStream_t>(stream)) : RTX_OK;
+}
+
+// host statement of the plane kernel and of the aim kernels over a pose: global_plane_statement over the posed records of
+// the global triangles; stream_nearest_first over posed_records' node words, whose planes cull_delta has moved already
+// (a scene without a primary stream of its own: those words as they are).  Each output may be NULL.  May throw.
+void posed_pipeline_on_host(RtxScene *scene, const float *pose, const float *eye, rtx::TriRec *planes, rtx::NodeRec *aimed)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const rtx::PoseTables &t = pose_tables_of(scene);
+    std::vector<rtx::TriRec> tris(p.tris.size());
+    std::vector<rtx::NodeRec> nodes(aimed ? p.nodes.size() : 0u);
+    rtx::posed_records(p, t, pose, nullptr, tris.data(), nullptr, aimed ? nodes.data() : nullptr);
+    if (planes)
+        for (uint32_t i = 0; i < p.n_global; ++i) rtx::global_plane_statement(tris[i], planes + i);
+    if (!aimed) return;
+    if (!p.primary_nodes.empty()) {
+        std::vector<rtx::NodeRec> out;
+        rtx::stream_nearest_first(nodes, tree_root(p), eye, out);
+        nodes.swap(out);
+    }
+    std::memcpy(aimed, nodes.data(), nodes.size() * sizeof(rtx::NodeRec));
 }
 
 // host statement of the aim kernels: stream_nearest_first over the shadow stream with its planes moved as
@@ -1520,13 +1581,13 @@ int rtx_debug_light_points(RtxScene *scene, int device, const RtxLight *light, f
 
 int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats)
 {
-    return view_rows_host(scene, device, view, nullptr, out_rgb, stats);
+    return view_rows_host(scene, device, view, nullptr, false, out_rgb, stats);
 }
 
 int rtx_render_view_rows_device(RtxScene *scene, int device, const RtxView *view, void *d_rgb, size_t d_bytes, void *stream,
                                 uint64_t *d_counters)
 {
-    return view_rows_device(scene, device, view, nullptr, d_rgb, d_bytes, stream, d_counters);
+    return view_rows_device(scene, device, view, nullptr, false, d_rgb, d_bytes, stream, d_counters);
 }
 
 int rtx_render_view_rows_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
@@ -1534,7 +1595,7 @@ int rtx_render_view_rows_lit(RtxScene *scene, int device, const RtxView *view, c
 {
     Lit lit;
     if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_rows_host(scene, device, view, &lit, out_rgb, stats);
+    return view_rows_host(scene, device, view, &lit, false, out_rgb, stats);
 }
 
 int rtx_render_view_rows_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
@@ -1542,7 +1603,7 @@ int rtx_render_view_rows_lit_device(RtxScene *scene, int device, const RtxView *
 {
     Lit lit;
     if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_rows_device(scene, device, view, &lit, d_rgb, d_bytes, stream, d_counters);
+    return view_rows_device(scene, device, view, &lit, false, d_rgb, d_bytes, stream, d_counters);
 }
 
 int rtx_scene_light_walk_for(const RtxScene *scene, const RtxLight *light, uint32_t *out_order, float *out_boxes,
@@ -1769,10 +1830,10 @@ int rtx_debug_aimed_nodes(RtxScene *scene, int device, const float eye[3], uint3
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    int rc = reserve_aimed(scene, st);
+    int rc = reserve_aimed(scene, st, false);
     if (rc != RTX_OK) return rc;
     st.aimed.valid = false;                  // the kernels run whatever the buffer holds
-    if ((rc = aim_at(scene, st, eye, st.stream)) != RTX_OK) return rc;
+    if ((rc = aim_at(scene, st, false, eye, st.stream)) != RTX_OK) return rc;
     const size_t n = scene->prep.nodes.size();
     std::vector<rtx::NodeDev> dev;
     try {
@@ -1780,12 +1841,73 @@ int rtx_debug_aimed_nodes(RtxScene *scene, int device, const float eye[3], uint3
     } catch (...) {
         return RTX_ERR_OOM;
     }
-    if (n) RTX_HIP(hipMemcpyAsync(dev.data(), aimed_stream(scene, st), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
+    if (n) RTX_HIP(hipMemcpyAsync(dev.data(), aimed_stream(scene, st, false), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
     RTX_HIP(hipStreamSynchronize(st.stream));
     for (size_t i = 0; i < n; ++i) {         // NodeDev word order -> NodeRec's
         const rtx::NodeDev &d = dev[i];
         const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
         std::memcpy(out_dwords + 8u * i, &r, sizeof r);
+    }
+    return RTX_OK;
+}
+
+int rtx_render_view_rows_posed(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
+                               RtxStats *stats)
+{
+    Lit lit;
+    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_rows_host(scene, device, view, light ? &lit : nullptr, true, out_rgb, stats);
+}
+
+int rtx_render_view_rows_posed_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
+                                      size_t d_bytes, void *stream, uint64_t *d_counters)
+{
+    Lit lit;
+    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
+    return view_rows_device(scene, device, view, light ? &lit : nullptr, true, d_rgb, d_bytes, stream, d_counters);
+}
+
+int rtx_scene_posed_pipeline_records(const RtxScene *scene, const float *v0v1v2, const float eye[3], uint32_t *out_planes,
+                                     uint32_t *out_aimed)
+{
+    if (!scene || !v0v1v2 || (out_aimed && !eye)) return RTX_ERR_BAD_ARG;
+    try {
+        posed_pipeline_on_host(const_cast<RtxScene *>(scene), v0v1v2, eye, reinterpret_cast<rtx::TriRec *>(out_planes),
+                               reinterpret_cast<rtx::NodeRec *>(out_aimed));      // (the tables are a cache under the scene's lock)
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uint32_t *out_planes, uint32_t *out_aimed)
+{
+    if (!scene || (out_aimed && !eye)) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    if (!st.pose.valid) return RTX_ERR_BAD_ARG;
+    const size_t n = scene->prep.nodes.size(), n_global = scene->prep.n_global;
+    std::vector<rtx::NodeDev> dev;
+    try {
+        dev.resize(out_aimed ? n : 0u);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    RTX_TRY(wait_for(st.pose.used, st.stream));
+    if (out_planes && n_global)
+        RTX_HIP(hipMemcpyAsync(out_planes, st.pose.planes.as<void>(), n_global * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
+    if (!dev.empty()) {
+        RTX_TRY(reserve_aimed(scene, st, true));
+        st.pose.aimed.valid = false;         // the kernels run whatever the buffer holds
+        RTX_TRY(aim_at(scene, st, true, eye, st.stream));
+        RTX_HIP(hipMemcpyAsync(dev.data(), aimed_stream(scene, st, true), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
+    }
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    for (size_t i = 0; i < dev.size(); ++i) {         // NodeDev word order -> NodeRec's
+        const rtx::NodeDev &d = dev[i];
+        const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
+        std::memcpy(out_aimed + 8u * i, &r, sizeof r);
     }
     return RTX_OK;
 }

@@ -133,6 +133,45 @@ struct TriRec {
 };
 static_assert(sizeof(TriRec) == 64, "TriRec must be 64 bytes");
 
+// The f32 after x towards +infinity, for x >= +0.0: one more in the bit pattern (nextafterf there, which host and device
+// cannot state differently: +0.0 gives the smallest subnormal); +infinity and a NaN come back as they are.
+RTX_HOST_DEVICE inline float f32_successor(float x)
+{
+    if (!(x < __builtin_inff())) return x;
+    uint32_t bits;
+    __builtin_memcpy(&bits, &x, 4);
+    ++bits;
+    __builtin_memcpy(&x, &bits, 4);
+    return x;
+}
+// Plane data of a global triangle (PreparedScene::global_planes; rtx_traverse.hpp: plane_rules_out) from its primitive
+// record: v0 = v0, e1 = N, e2 = W, bmin[0] = K_d, idx = idx, every other word zero.  N and W in double from the f32 edges
+// (the products of two f32 are exact there, so a fused form gives the same bits), N rounded to nearest, W upwards;
+// K_d = 2^-19 * 2 * (Wx + Wy + Wz) + 2^-100 over the ROUNDED W in double, upwards.  Anything not comfortably finite
+// switches the shortcut off for that triangle (K_d = inf).  One text for both compilers, as triangle_statement is:
+// prepare_scene on the host, rtxg::global_planes_kernel (rtx_planes.hip) on the device for a pose's triangles.
+RTX_HOST_DEVICE inline void global_plane_statement(const TriRec &t, TriRec *out)
+{
+    TriRec g = {};
+    const double e1[3] = {t.e1[0], t.e1[1], t.e1[2]}, e2[3] = {t.e2[0], t.e2[1], t.e2[2]};
+    double sum_w = 0.0;
+    bool fine = true;
+    for (int a = 0; a < 3; ++a) {
+        const int b = (a + 1) % 3, c = (a + 2) % 3;
+        const double n = e1[b] * e2[c] - e1[c] * e2[b];
+        const double w = fabs(e1[b] * e2[c]) + fabs(e1[c] * e2[b]);
+        g.v0[a] = t.v0[a];
+        g.e1[a] = static_cast<float>(n);
+        g.e2[a] = f32_successor(static_cast<float>(w));
+        fine = fine && w < 0x1p100;                    // (false for a NaN and for infinity)
+        sum_w += static_cast<double>(g.e2[a]);
+    }
+    const double kd = 0x1p-19 * 2.0 * sum_w + 0x1p-100;
+    g.bmin[0] = fine ? f32_successor(static_cast<float>(kd)) : __builtin_inff();
+    g.idx = t.idx;
+    *out = g;
+}
+
 // Shading data of a primitive, indexed by its position in the caller's Vec<Primitive> (read once per hit).
 struct ShadeRec {
     float    normal[3];   // triangle: Triangle::new, triangle.rs:29; sphere: its origin (normal = normalize(p_hit - origin), sphere.rs:93-95)

@@ -197,6 +197,12 @@ _SIGS = {
                                         C.POINTER(PixelShade), C.POINTER(RayHit), C.POINTER(Stats)]),
     "rtx_render_view_posed_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
+    "rtx_render_view_rows_posed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
+                                             C.POINTER(Stats)]),
+    "rtx_render_view_rows_posed_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
+                                                    C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rtx_scene_posed_pipeline_records": (C.c_int, [C.c_void_p, f32p, f32p, u32p, u32p]),
+    "rtx_debug_pose_pipeline": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, u32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -808,13 +814,17 @@ class Scene:
         return tour[:n], boxes
 
     # -- any view through the render pipeline (GPU only); light=: under another light (rtx_render_view_rows_lit)
-    def render_view_rows(self, view, device=0, stats=False, light=None):
+    def render_view_rows(self, view, device=0, stats=False, light=None, posed=False):
         """Rows [y0, y0 + ny) of the view's frame through the render pipeline, full width (x0 = 0, nx = width)
         -> uint8 [ny, width, 3]: render_view's bytes at the pipeline's speed.  An eye beyond the scene's largest
-        coordinate raises RtxError(ERR_UNSUPPORTED): render_view serves it."""
+        coordinate raises RtxError(ERR_UNSUPPORTED): render_view serves it.  posed: the device's pose (pose()) in place of
+        the uploaded triangles (rtx_render_view_rows_posed)."""
         out = np.zeros((view.ny, view.width, 3), np.uint8)
         st = Stats()
-        if light is None:
+        if posed:
+            _check(_lib.rtx_render_view_rows_posed(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                                   out.ctypes.data, C.byref(st) if stats else None), "rtx_render_view_rows_posed")
+        elif light is None:
             _check(_lib.rtx_render_view_rows(self._h, device, C.byref(view), out.ctypes.data, C.byref(st) if stats else None),
                    "rtx_render_view_rows")
         else:
@@ -822,11 +832,14 @@ class Scene:
                                                  C.byref(st) if stats else None), "rtx_render_view_rows_lit")
         return (out, st.asdict()) if stats else out
 
-    def render_view_rows_device(self, device, view, d_rgb_ptr, d_bytes, stream=None, d_counters_ptr=None, light=None):
+    def render_view_rows_device(self, device, view, d_rgb_ptr, d_bytes, stream=None, d_counters_ptr=None, light=None, posed=False):
         """Asynchronous pipeline launch of the view's rows into a device buffer the caller owns (ny*width*3 bytes)."""
         tail = (C.c_void_p(d_rgb_ptr), d_bytes, C.c_void_p(stream) if stream else None,
                 C.c_void_p(d_counters_ptr) if d_counters_ptr else None)
-        if light is None:
+        if posed:
+            _check(_lib.rtx_render_view_rows_posed_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                                          *tail), "rtx_render_view_rows_posed_device")
+        elif light is None:
             _check(_lib.rtx_render_view_rows_device(self._h, device, C.byref(view), *tail), "rtx_render_view_rows_device")
         else:
             _check(_lib.rtx_render_view_rows_lit_device(self._h, device, C.byref(view), C.byref(light), *tail),
@@ -844,6 +857,31 @@ class Scene:
         nd = np.zeros((self.info()["n_nodes"], 8), np.uint32)
         _check(_lib.rtx_debug_aimed_nodes(self._h, device, _fp(_f3(eye)), nd.ctypes.data_as(u32p)), "rtx_debug_aimed_nodes")
         return nd
+
+    # -- the pose through the render pipeline: the posed= keyword of render_view_rows*; what it reads beside the pose
+    def _pipeline_outputs(self):
+        i = self.info()
+        return np.zeros((i["n_global"], 16), np.uint32), np.zeros((i["n_nodes"], 8), np.uint32)
+
+    def posed_pipeline_records(self, v0v1v2, eye=None):
+        """Host only: the words a pose makes for the pipeline -> (planes uint32 [n_global, 16], aimed uint32 [n_nodes, 8] in
+        aimed_nodes()' word order, or None without an eye)."""
+        v, _ = self._pose_arrays(v0v1v2, None)
+        planes, aimed = self._pipeline_outputs()
+        _check(_lib.rtx_scene_posed_pipeline_records(self._h, _fp(v), _fp(_f3(eye)) if eye is not None else None,
+                                                     planes.ctypes.data_as(u32p),
+                                                     aimed.ctypes.data_as(u32p) if eye is not None else None),
+               "rtx_scene_posed_pipeline_records")
+        return planes, (aimed if eye is not None else None)
+
+    def debug_pose_pipeline(self, eye=None, device=0):
+        """Diagnostics: the plane records of the pose `device` holds and the aim kernels run over it for `eye`, copied back,
+        in posed_pipeline_records' layout."""
+        planes, aimed = self._pipeline_outputs()
+        _check(_lib.rtx_debug_pose_pipeline(self._h, device, _fp(_f3(eye)) if eye is not None else None,
+                                            planes.ctypes.data_as(u32p), aimed.ctypes.data_as(u32p) if eye is not None else None),
+               "rtx_debug_pose_pipeline")
+        return planes, (aimed if eye is not None else None)
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
