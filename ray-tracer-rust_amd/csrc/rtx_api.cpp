@@ -144,14 +144,25 @@ int reserve_all(std::initializer_list<Sized> list)
 }
 
 // A primary rays' stream aimed on the device (rtx_aim.hip): (n_nodes + 1) records, the last one the zeroed sentinel, the aim
-// kernels' scratch, and what the stream was aimed at, on and over — the eye's 12 bytes, the stream, and which pose's nodes
-// (DeviceState::pose's `made`; 0: the uploaded scene's).  A call with the same three walks it as it stands.
+// kernels' scratch, and what the stream was aimed at and on — the eye's 12 bytes and the stream.  A call with the same two
+// walks it as it stands.  Nothing states which nodes it was aimed over: it belongs to one DeviceGeometry and is aimed over
+// that geometry's nodes only.  The uploaded scene's nodes are written once, before anything is aimed.  The pose's nodes have
+// one writer, pose_launch, which takes `valid` away before it launches: a valid stream is over the nodes as they stand.
 struct AimedStream {
     DeviceBuffer nodes, links;
     float eye[3] = {0.0f, 0.0f, 0.0f};
     hipStream_t on = nullptr;
-    unsigned long long over = 0;
     bool valid = false;
+};
+
+// The geometry a walk reads: the node stream, the reference tree's stream and its record count, the primitive and the
+// shading records, the plane records of the global triangles (none: never reserved), and the primary rays' stream aimed
+// over these nodes (rtx_render_view_rows).  A DeviceState holds two: the uploaded scene's (upload_all) and its pose's
+// (reserve_pose, pose_launch); geometry_of picks the one a call walks, and device_scene reads all six fields from it.
+struct DeviceGeometry {
+    DeviceBuffer nodes, ref_nodes, tris, shade, planes;
+    uint32_t n_ref_nodes = 0;
+    AimedStream aimed;
 };
 
 // What a scene keeps on one device.  The argument blocks the launchers read (rtx::DeviceScene, rtx::StreamWorkspace,
@@ -167,8 +178,11 @@ public:
     Stream stream;
     Event ev0, ev1;
     Event ring[RTX_TIMING_RING][3];      // launch start / end of the scheduling pass / launch end (rtx_launch_timings)
-    Event q_sorted;                      // guards q_sort (mark_busy / wait_for)
-    DeviceBuffer nodes, primary_nodes, ref_nodes, tris, shade, samples, lights, light_tour, thr, planes, light_boxes;
+    Event q_sorted;                      // guards q_sort (kUsesSort)
+    // the uploaded scene's geometry; its aimed stream is that of the most recent unposed rtx_render_view_rows' eye.
+    // primary_nodes: the scene's own eye's stream, which only the calls that render the scene's own view walk
+    DeviceGeometry geo;
+    DeviceBuffer primary_nodes, samples, lights, light_tour, thr, light_boxes;
     DeviceBuffer d_out, d_counters;
     DeviceBuffer d_redo;                 // queue of tiles for reference_tiles_kernel
     // The two-pass pipeline zeroes its counting words (d_redo's headers, ws.buckets) for the NEXT launch inside each
@@ -184,31 +198,24 @@ public:
     // regrouping pass's (key, ray number) buffers and the sort's temporary storage; none shared with the render workspace
     DeviceBuffer q_first, q_second, q_out;
     struct { DeviceBuffer keys, keys_sorted, index, index_sorted, temp; } q_sort;
-    // rtx_render_view_rows (rtx_aim.hip): the primary rays' stream of the most recent unposed view's eye, aimed over the
-    // uploaded shadow stream; posed calls neither read nor write it (theirs is pose.aimed)
-    AimedStream aimed;
     // rtx_*_lit (rtx_light.hip): the points of the most recent lit call's light, made on that call's stream ahead of its
     // view or shade kernel; rtx_render_view_rows_lit (rtx_tour.hip) adds the tour and the boxes of that light.  One owner
-    // (reserve_light, light_launch), one guard: `used` (mark_busy / wait_for)
+    // (reserve_light, light_launch), one guard: `used` (kUsesLight)
     struct {
         DeviceBuffer points, tour, boxes;
         Event used;
     } lit;
     // rtx_scene_pose (rtx_pose.hip): the host tables (rtx::PoseTables, uploaded with the first pose), the host variant's
-    // copies of the caller's arrays, and the one pose this device holds: posed primitive and shading records, the refitted
-    // stream, and — host variant with a reference tree — that tree's stream.  For rtx_render_view_rows_posed: the plane
-    // records of the pose's global triangles (rtx_planes.hip, made with the pose) and the primary rays' stream of the most
-    // recent posed view's eye, aimed over the pose's nodes; `made` counts the poses launched, and every one of them takes
-    // the aimed stream's validity away.  One guard: `used` (mark_busy / wait_for)
+    // copies of the caller's arrays, and the one pose this device holds, as a geometry: posed primitive and shading
+    // records, the refitted stream, — host variant with a reference tree — that tree's stream, the plane records of the
+    // pose's global triangles (rtx_planes.hip, made with the pose) and the primary rays' stream of the most recent posed
+    // view's eye, which posed and unposed views of one eye do not share.  One guard: `used` (kUsesPose)
     struct {
         DeviceBuffer tri_of, ranges, order;
         bool tables = false;
         DeviceBuffer v, rank;
-        DeviceBuffer tris, shade, nodes, ref_nodes, planes;
-        uint32_t n_ref_nodes = 0;
+        DeviceGeometry geo;
         bool valid = false;
-        unsigned long long made = 0;
-        AimedStream aimed;
         Event used;
     } pose;
 private:
@@ -235,6 +242,29 @@ struct DeviceSlot {
     std::mutex mu;
     std::unique_ptr<DeviceState, ReleaseOnDevice> st;
 };
+
+// The one rule for the library-owned buffer groups an event guards.  A call states the groups it uses — the regrouping
+// buffers (q_sort), the light buffers (lit), the pose (pose: its geometry, aimed stream included) — as a set of these bits.
+// A call that uses them on the library's stream (the host bodies, the rtx_debug_* read-backs, rtx_scene_pose) waits for
+// all of them first: wait_for_uses.  A device-resident call marks all of them behind its kernels on the caller's stream:
+// mark_uses.  A new guarded group is one bit, one event and one line in each of the two.
+enum : unsigned { kUsesSort = 1u, kUsesLight = 2u, kUsesPose = 4u };
+
+int wait_for_uses(DeviceState &st, unsigned uses)
+{
+    if (uses & kUsesSort) RTX_TRY(wait_for(st.q_sorted, st.stream));
+    if (uses & kUsesLight) RTX_TRY(wait_for(st.lit.used, st.stream));
+    if (uses & kUsesPose) RTX_TRY(wait_for(st.pose.used, st.stream));
+    return RTX_OK;
+}
+
+int mark_uses(DeviceState &st, unsigned uses, hipStream_t callers)
+{
+    if (uses & kUsesSort) RTX_TRY(mark_busy(st.q_sorted, callers));
+    if (uses & kUsesLight) RTX_TRY(mark_busy(st.lit.used, callers));
+    if (uses & kUsesPose) RTX_TRY(mark_busy(st.pose.used, callers));
+    return RTX_OK;
+}
 
 double wall_ms()
 {
@@ -309,18 +339,20 @@ int upload_all(RtxScene *scene, DeviceState &st)
     const rtx::PreparedScene &p = scene->prep;
     int rc;
     const float inflate = p.cull_delta;   // the culling planes move outwards: rtx_traverse.hpp, box_mask
-    if ((rc = upload_vec(st.nodes, rtx::nodes_in_device_order(p.nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
+    DeviceGeometry &g = st.geo;
+    if ((rc = upload_vec(g.nodes, rtx::nodes_in_device_order(p.nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
     if (!p.primary_nodes.empty() &&
         (rc = upload_vec(st.primary_nodes, rtx::nodes_in_device_order(p.primary_nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
     if (!p.ref_nodes.empty() &&
-        (rc = upload_vec(st.ref_nodes, rtx::nodes_in_device_order(p.ref_nodes), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
+        (rc = upload_vec(g.ref_nodes, rtx::nodes_in_device_order(p.ref_nodes), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
+    g.n_ref_nodes = static_cast<uint32_t>(p.ref_nodes.size());
     // one spare record of zeros behind the primitive records (no walk requests the record after the one it tests any more)
-    if ((rc = upload_vec(st.tris, p.tris, sizeof(rtx::TriRec))) != RTX_OK) return rc;
-    if ((rc = upload_vec(st.shade, p.shade)) != RTX_OK) return rc;
+    if ((rc = upload_vec(g.tris, p.tris, sizeof(rtx::TriRec))) != RTX_OK) return rc;
+    if ((rc = upload_vec(g.shade, p.shade)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.samples, p.samples)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.lights, p.light_points)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.light_tour, p.light_tour)) != RTX_OK) return rc;
-    if (!p.global_planes.empty() && (rc = upload_vec(st.planes, p.global_planes)) != RTX_OK) return rc;
+    if (!p.global_planes.empty() && (rc = upload_vec(g.planes, p.global_planes)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.light_boxes, p.light_boxes)) != RTX_OK) return rc;
     if ((rc = st.thr.reserve(sizeof(p.gamma_thr))) != RTX_OK) return rc;
     RTX_HIP(hipMemcpy(st.thr.as<void>(), p.gamma_thr, sizeof(p.gamma_thr), hipMemcpyHostToDevice));
@@ -368,21 +400,35 @@ private:
     DeviceGuard guard_;
 };
 
-rtx::DeviceScene device_scene(const RtxScene *scene, const DeviceState &st)
+// Which geometry a call walks: the uploaded scene's, or (posed) the pose's.  The one place that answers a posed call on
+// a device that holds no pose: RTX_ERR_BAD_ARG.  The tree keeps its shape under a pose: tree_root, the record counts
+// and the number of global triangles hold for both.
+int geometry_of(DeviceState &st, bool posed, DeviceGeometry **out)
+{
+    *out = &st.geo;
+    if (!posed) return RTX_OK;
+    if (!st.pose.valid) return RTX_ERR_BAD_ARG;
+    *out = &st.pose.geo;
+    return RTX_OK;
+}
+
+// The launchers' argument block over geometry `g` of the device.  primary_nodes is the scene's own eye's stream over the
+// uploaded nodes; only the pipeline reads it, and a pipeline view puts its aimed stream there (view_rows_launch).
+rtx::DeviceScene device_scene(const RtxScene *scene, const DeviceState &st, const DeviceGeometry &g)
 {
     const rtx::PreparedScene &p = scene->prep;
     rtx::DeviceScene S;
-    S.nodes = st.nodes.as<const rtx::NodeRec>();
-    S.primary_nodes = st.primary_nodes.capacity() ? st.primary_nodes.as<const rtx::NodeRec>() : S.nodes;
+    S.nodes = g.nodes.as<const rtx::NodeRec>();
+    S.primary_nodes = st.primary_nodes.capacity() ? st.primary_nodes.as<const rtx::NodeRec>() : st.geo.nodes.as<const rtx::NodeRec>();
     S.light_tour = st.light_tour.as<const float>();
     S.n_wide = 0u;
-    S.ref_nodes = st.ref_nodes.as<const rtx::NodeRec>();
-    S.n_ref_nodes = static_cast<uint32_t>(p.ref_nodes.size());
-    S.tris = st.tris.as<const rtx::TriRec>();
-    S.shade = st.shade.as<const rtx::ShadeRec>();
+    S.ref_nodes = g.ref_nodes.as<const rtx::NodeRec>();
+    S.n_ref_nodes = g.n_ref_nodes;
+    S.tris = g.tris.as<const rtx::TriRec>();
+    S.shade = g.shade.as<const rtx::ShadeRec>();
     S.samples = st.samples.as<const float2>();
     S.light_points = st.lights.as<const float>();
-    S.planes = st.planes.as<const rtx::TriRec>();
+    S.planes = g.planes.as<const rtx::TriRec>();
     S.gamma_thr = st.thr.as<const float>();
     S.light_boxes = st.light_boxes.as<const float>();
     S.shaft_delta = p.shaft_delta;
@@ -539,7 +585,7 @@ int launch_on(RtxScene *scene, DeviceSlot &slot, const rtx::TileSpec &ts, const 
     DeviceState &st = *slot.st;
     const size_t bytes = static_cast<size_t>(ts.local_rows) * scene->prep.width * 3u;
     RTX_TRY(st.d_out.reserve(bytes ? bytes : 16));
-    RTX_TRY(render_launch(st, device_scene(scene, st), ts, st.d_out.as<uint8_t>(), timed.counters(st), nullptr, st.stream,
+    RTX_TRY(render_launch(st, device_scene(scene, st, st.geo), ts, st.d_out.as<uint8_t>(), timed.counters(st), nullptr, st.stream,
                           [&] { return timed.begin(st); }));
     return timed.end(st);
 }
@@ -655,8 +701,17 @@ struct Batch {
     hipError_t (*launch)(const BatchArgs &);
     const RtxView *view;           // rtx_render_view: the caller's, read while the call runs; else NULL
     const Lit *lit;                // the lit twins: the call's light (shadow_rays_per_hit is its count); else NULL
-    bool posed;                    // the posed twins: the device's pose in place of the uploaded geometry (pose_swap)
+    bool posed;                    // the posed twins: the device's pose in place of the uploaded geometry (geometry_of)
 };
+
+// the guarded groups a call with this light (or NULL) and this switch uses, the regrouping buffers aside
+unsigned uses_of(const Lit *lit, bool posed)
+{
+    unsigned uses = 0u;
+    if (lit) uses |= kUsesLight;
+    if (posed) uses |= kUsesPose;
+    return uses;
+}
 
 bool batch_regroups(const Batch &b)
 {
@@ -779,12 +834,13 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
     const size_t rank = host_copies ? std::max<size_t>(n_prims * sizeof(uint32_t), 16u) : 0u;
     const size_t planes = static_cast<size_t>(p.n_global) * sizeof(rtx::TriRec);      // (no global triangle: no buffer)
     auto &q = st.pose;
-    if (q.tris.capacity() < tris || q.shade.capacity() < shade || q.nodes.capacity() < nodes || q.ref_nodes.capacity() < ref ||
-        q.v.capacity() < v || q.rank.capacity() < rank || q.planes.capacity() < planes) {
+    DeviceGeometry &g = q.geo;
+    if (g.tris.capacity() < tris || g.shade.capacity() < shade || g.nodes.capacity() < nodes || g.ref_nodes.capacity() < ref ||
+        q.v.capacity() < v || q.rank.capacity() < rank || g.planes.capacity() < planes) {
         q.valid = false;
         RTX_HIP(hipDeviceSynchronize());
-        RTX_TRY(reserve_all({{q.tris, tris}, {q.shade, shade}, {q.nodes, nodes}, {q.ref_nodes, ref}, {q.v, v}, {q.rank, rank},
-                             {q.planes, planes}}));
+        RTX_TRY(reserve_all({{g.tris, tris}, {g.shade, shade}, {g.nodes, nodes}, {g.ref_nodes, ref}, {q.v, v}, {q.rank, rank},
+                             {g.planes, planes}}));
     }
     if (q.tables) return RTX_OK;
     try {
@@ -801,25 +857,24 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
 
 // the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
 // copies of them; the records behind the last one (upload_all pads the scene's with the same) are zeroed on the same stream.
-// The plane kernel follows them over the posed global triangles (none: no launch), and whatever was aimed over the
-// previous pose no longer stands.
+// The plane kernel follows them over the posed global triangles (none: no launch).  This is the only writer of the pose's
+// nodes, and it takes the aimed stream's validity away before anything is launched (AimedStream).
 int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, hipStream_t stream)
 {
     const rtx::PreparedScene &p = scene->prep;
     const uint32_t n_prims = static_cast<uint32_t>(p.tris.size()), n_nodes = static_cast<uint32_t>(p.nodes.size());
-    auto &q = st.pose;
-    q.valid = false;
+    DeviceGeometry &q = st.pose.geo;
+    st.pose.valid = false;
     q.aimed.valid = false;
-    ++q.made;
     RTX_HIP(hipMemsetAsync(q.tris.as<rtx::TriRec>() + n_prims, 0, sizeof(rtx::TriRec), stream));
     RTX_HIP(hipMemsetAsync(q.nodes.as<rtx::NodeDev>() + n_nodes, 0, sizeof(rtx::NodeDev), stream));
     rtxp::PoseArgs a{};
-    a.tris = st.tris.as<const rtx::TriRec>();
-    a.shade = st.shade.as<const rtx::ShadeRec>();
-    a.nodes = st.nodes.as<const rtx::NodeDev>();
-    a.tri_of = q.tri_of.as<const uint32_t>();
-    a.ranges = q.ranges.as<const uint2>();
-    a.order = q.order.as<const uint32_t>();
+    a.tris = st.geo.tris.as<const rtx::TriRec>();
+    a.shade = st.geo.shade.as<const rtx::ShadeRec>();
+    a.nodes = st.geo.nodes.as<const rtx::NodeDev>();
+    a.tri_of = st.pose.tri_of.as<const uint32_t>();
+    a.ranges = st.pose.ranges.as<const uint2>();
+    a.order = st.pose.order.as<const uint32_t>();
     a.n_prims = n_prims;
     a.n_nodes = n_nodes;
     a.n_long = scene->pose_tables.n_long;      // (made: reserve_pose)
@@ -832,20 +887,8 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
     RTX_HIP(rtxp::launch_pose(a, stream));
     RTX_HIP(rtxg::launch_global_planes(q.tris.as<const rtx::TriRec>(), p.n_global, q.planes.as<rtx::TriRec>(), stream));
     q.n_ref_nodes = 0u;
-    q.valid = true;
+    st.pose.valid = true;
     return RTX_OK;
-}
-
-// ... and the fields of a posed call's copy of the scene's argument block that the ray-batch kernels read geometry through
-// (rtx_ray_walk.hpp).  The pipeline's own fields (primary_nodes, planes) are not swapped here: a posed pipeline call sets
-// them beside this (view_rows_launch).
-void pose_swap(const DeviceState &st, rtx::DeviceScene *S)
-{
-    S->nodes = st.pose.nodes.as<const rtx::NodeRec>();
-    S->tris = st.pose.tris.as<const rtx::TriRec>();
-    S->shade = st.pose.shade.as<const rtx::ShadeRec>();
-    S->ref_nodes = st.pose.ref_nodes.as<const rtx::NodeRec>();
-    S->n_ref_nodes = st.pose.n_ref_nodes;
 }
 
 // key + sort + kernel of one batch on `stream`, the light kernel of a lit one ahead of them; caller holds the slot's lock,
@@ -856,9 +899,9 @@ int batch_launch(RtxScene *scene, DeviceState &st, const Batch &b, const float *
     rtxq::SortBuffers sort{};
     const bool regroup = batch_regroups(b);
     if (regroup) RTX_TRY(reserve_query_sort(st, b.n, &sort));
-    if (b.posed && !st.pose.valid) return RTX_ERR_BAD_ARG;      // this device holds no pose
-    rtx::DeviceScene S = device_scene(scene, st);
-    if (b.posed) pose_swap(st, &S);
+    DeviceGeometry *geo;
+    RTX_TRY(geometry_of(st, b.posed, &geo));
+    rtx::DeviceScene S = device_scene(scene, st, *geo);
     if (b.lit) {
         RTX_TRY(reserve_light(scene, st, *b.lit, false));
         RTX_TRY(light_launch(scene, st, *b.lit, false, stream));
@@ -885,9 +928,9 @@ int batch_host(RtxScene *scene, int device, const Batch &b, const float *first, 
     RTX_TRY(reserve_all({{st.q_first, in_bytes}, {st.q_second, in_bytes}, {st.q_out, offset[kBatchOuts]}}));
     void *d_out[kBatchOuts];
     for (int k = 0; k < kBatchOuts; ++k) d_out[k] = b.out_bytes[k] ? st.q_out.as<uint8_t>() + offset[k] : nullptr;
-    RTX_TRY(wait_for(st.q_sorted, st.stream));              // a device-resident call may still be sorting
-    if (b.lit) RTX_TRY(wait_for(st.lit.used, st.stream));   // ... or reading its light's points
-    if (b.posed) RTX_TRY(wait_for(st.pose.used, st.stream));    // ... or making the pose
+    // a device-resident call may still be sorting (waited for whether this batch regroups or not), reading its light's
+    // points, or making the pose
+    RTX_TRY(wait_for_uses(st, kUsesSort | uses_of(b.lit, b.posed)));
     if (in_bytes) {
         RTX_HIP(hipMemcpyAsync(st.q_first.as<void>(), first, in_bytes, hipMemcpyHostToDevice, st.stream));
         RTX_HIP(hipMemcpyAsync(st.q_second.as<void>(), second, in_bytes, hipMemcpyHostToDevice, st.stream));
@@ -916,10 +959,8 @@ int batch_device(RtxScene *scene, int device, const Batch &b, const void *d_firs
     DeviceState &st = e.state();
     RTX_TRY(batch_launch(scene, st, b, static_cast<const float *>(d_first), static_cast<const float *>(d_second), d_out, nullptr,
                          static_cast<hipStream_t>(stream)));
-    if (batch_regroups(b)) RTX_TRY(mark_busy(st.q_sorted, static_cast<hipStream_t>(stream)));
-    if (b.lit) RTX_TRY(mark_busy(st.lit.used, static_cast<hipStream_t>(stream)));
-    if (b.posed) RTX_TRY(mark_busy(st.pose.used, static_cast<hipStream_t>(stream)));
-    return RTX_OK;
+    const unsigned sorts = batch_regroups(b) ? kUsesSort : 0u;
+    return mark_uses(st, sorts | uses_of(b.lit, b.posed), static_cast<hipStream_t>(stream));
 }
 
 // the argument checks a family's host and device-resident entry points share
@@ -998,6 +1039,18 @@ bool lit_of(const RtxScene *scene, const RtxLight *light, Lit *out)
     return static_cast<uint64_t>(scene->prep.nb_ray) * out->count <= rtx::kMaxCallLightPoints;
 }
 
+// The light of a call that takes an RtxLight, checked before everything else of the call (lit_of's rules).  kRequired (the
+// _lit entry points): a NULL light fails.  kOptional (the _posed ones): a NULL light is the scene's own, lit == NULL.
+// !ok: the call answers RTX_ERR_BAD_ARG.
+struct CallLight {
+    enum Need { kRequired, kOptional };
+    CallLight(const RtxScene *scene, const RtxLight *light, Need need)
+        : ok((!light && need == kOptional) || lit_of(scene, light, &copy)), lit(light && ok ? &copy : nullptr) {}
+    Lit copy;
+    const bool ok;
+    const Lit *const lit;
+};
+
 // The bodies of rtx_render_view and rtx_shade_rays, each with its _lit twin's light as an argument.  A view's outputs in
 // Batch::out_bytes' order: {shade, hits, rgb}.
 static_assert(kViewShade == 0 && kViewHits == 1 && kViewRgb == 2, "view_host and view_device list a view's outputs in this order");
@@ -1051,18 +1104,15 @@ bool view_rows_args_ok(const RtxScene *scene, const RtxView *v, const void *out)
     return static_cast<uint64_t>(v->y0) + v->ny <= v->height;
 }
 
-// The stream the view's primary rays walk, on `stream`: the scene's shadow stream when it has no primary stream of its own
-// (nothing is aimed then), else the device's aimed buffer, the aim kernels run first unless it stands for this eye on this
-// stream.  Caller holds the slot's lock and has the device current and the scene uploaded; reserve_aimed() comes first.
-// posed: the same over the pose — its refitted shadow stream, its own aimed buffer (DeviceState::pose's), so that posed
-// and unposed views of one eye alternate without aiming either again, and neither is handed the other's stream.  The
-// tree keeps its shape under a pose: tree_root and the record count hold.
-AimedStream &aimed_of(DeviceState &st, bool posed) { return posed ? st.pose.aimed : st.aimed; }
-
-int reserve_aimed(RtxScene *scene, DeviceState &st, bool posed)
+// The stream the view's primary rays walk over geometry `g`, on `stream`: g's shadow stream when the scene has no primary
+// stream of its own (nothing is aimed then), else g's aimed buffer, the aim kernels run first unless it stands for this eye
+// on this stream.  Caller holds the slot's lock and has the device current and the scene uploaded; reserve_aimed() comes
+// first.  Each geometry has its own aimed buffer, so that posed and unposed views of one eye alternate without aiming
+// either again, and neither is handed the other's stream.
+int reserve_aimed(const RtxScene *scene, DeviceGeometry &g)
 {
     if (scene->prep.primary_nodes.empty()) return RTX_OK;
-    AimedStream &a = aimed_of(st, posed);
+    AimedStream &a = g.aimed;
     const size_t n = scene->prep.nodes.size();
     const size_t had = a.nodes.capacity();
     const int rc = reserve_all({{a.nodes, (n + 1u) * sizeof(rtx::NodeDev)}, {a.links, n * sizeof(rtxa::AimLink)}});
@@ -1070,50 +1120,41 @@ int reserve_aimed(RtxScene *scene, DeviceState &st, bool posed)
     return rc;
 }
 
-const rtx::NodeRec *aimed_stream(const RtxScene *scene, DeviceState &st, bool posed)
+const rtx::NodeRec *aimed_stream(const RtxScene *scene, const DeviceGeometry &g)
 {
-    if (scene->prep.primary_nodes.empty()) return (posed ? st.pose.nodes : st.nodes).as<const rtx::NodeRec>();
-    return aimed_of(st, posed).nodes.as<const rtx::NodeRec>();
+    return (scene->prep.primary_nodes.empty() ? g.nodes : g.aimed.nodes).as<const rtx::NodeRec>();
 }
 
-int aim_at(RtxScene *scene, DeviceState &st, bool posed, const float eye[3], hipStream_t stream)
+int aim_at(const RtxScene *scene, DeviceGeometry &g, const float eye[3], hipStream_t stream)
 {
     const rtx::PreparedScene &p = scene->prep;
     if (p.primary_nodes.empty()) return RTX_OK;
-    AimedStream &a = aimed_of(st, posed);
-    const unsigned long long over = posed ? st.pose.made : 0ull;
-    if (a.valid && a.on == stream && a.over == over && std::memcmp(a.eye, eye, 12) == 0) return RTX_OK;
+    AimedStream &a = g.aimed;
+    if (a.valid && a.on == stream && std::memcmp(a.eye, eye, 12) == 0) return RTX_OK;
     a.valid = false;
     const uint32_t n = static_cast<uint32_t>(p.nodes.size());
     RTX_HIP(hipMemsetAsync(a.nodes.as<rtx::NodeDev>() + n, 0, sizeof(rtx::NodeDev), stream));      // the sentinel
-    RTX_HIP(rtxa::launch_aim((posed ? st.pose.nodes : st.nodes).as<const rtx::NodeDev>(), n, tree_root(p), eye,
-                             a.links.as<rtxa::AimLink>(), a.nodes.as<rtx::NodeDev>(), stream));
+    RTX_HIP(rtxa::launch_aim(g.nodes.as<const rtx::NodeDev>(), n, tree_root(p), eye, a.links.as<rtxa::AimLink>(),
+                             a.nodes.as<rtx::NodeDev>(), stream));
     std::memcpy(a.eye, eye, 12);
     a.on = stream;
-    a.over = over;
     a.valid = true;
     return RTX_OK;
 }
 
-// rtx_render_rows / rtx_render_tiles_device for a view: device_scene() with the view's frame and camera and the aimed
-// stream, rows [y0, y0 + ny) as one share.  `before`: as render_launch's; the aim kernels follow it on the stream.  lit:
-// NULL, or the call's light with its margin (lit_rows_margin): the light kernels follow the aim kernels, and the pipeline's
-// kernels are handed that light's five fields.  posed: the device's pose in place of the uploaded geometry — pose_swap's
-// fields, the pose's plane records and the stream aimed over the pose's nodes; no field of the block is added or moved,
-// and the kernels are the unposed call's.  The shaft margin is the unposed call's too: it is folded from the bound M every
-// posed coordinate respects, not from the geometry's extent.  RTX_ERR_BAD_ARG: no pose on this device.
+// rtx_render_rows / rtx_render_tiles_device for a view: device_scene() over geometry `g` (geometry_of) with the view's
+// frame and camera and the stream aimed over g's nodes, rows [y0, y0 + ny) as one share.  `before`: as render_launch's; the
+// aim kernels follow it on the stream.  lit: NULL, or the call's light with its margin (lit_rows_margin): the light kernels
+// follow the aim kernels, and the pipeline's kernels are handed that light's five fields.  Whichever geometry it is, no
+// field of the block is added or moved, and the kernels are the same.  So is the shaft margin: it is folded from the bound M
+// every posed coordinate respects, not from the geometry's extent.
 template <class Before>
-int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t *d_out, unsigned long long *d_counters,
-                     hipStream_t stream, Before before, const Lit *lit, float shaft_delta, bool posed)
+int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const RtxView &v, uint8_t *d_out,
+                     unsigned long long *d_counters, hipStream_t stream, Before before, const Lit *lit, float shaft_delta)
 {
-    if (posed && !st.pose.valid) return RTX_ERR_BAD_ARG;
-    RTX_TRY(reserve_aimed(scene, st, posed));
+    RTX_TRY(reserve_aimed(scene, g));
     if (lit) RTX_TRY(reserve_light(scene, st, *lit, true));
-    rtx::DeviceScene S = device_scene(scene, st);
-    if (posed) {
-        pose_swap(st, &S);
-        S.planes = scene->prep.n_global ? st.pose.planes.as<const rtx::TriRec>() : nullptr;
-    }
+    rtx::DeviceScene S = device_scene(scene, st, g);
     if (lit) light_swap(st, *lit, true, shaft_delta, &S);
     S.width = v.width;
     S.height = v.height;
@@ -1122,11 +1163,11 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, const RtxView &v, uint8_t
     std::memcpy(S.cv, v.v, 12);
     std::memcpy(S.cw, v.w, 12);
     S.distance = v.distance;
-    S.primary_nodes = aimed_stream(scene, st, posed);
+    S.primary_nodes = aimed_stream(scene, g);
     const rtx::TileSpec ts{v.y0, v.ny, v.ny, v.ny};
     return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
         RTX_TRY(before());
-        RTX_TRY(aim_at(scene, st, posed, v.eye, stream));
+        RTX_TRY(aim_at(scene, g, v.eye, stream));
         return lit ? light_launch(scene, st, *lit, true, stream) : RTX_OK;
     });
 }
@@ -1155,10 +1196,12 @@ int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *
     const RtxView v = *view;                 // (the caller's may change while the call runs)
     const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
     RTX_TRY(st.d_out.reserve(bytes));
-    if (lit) RTX_TRY(wait_for(st.lit.used, st.stream));      // a device-resident call may still read its light
-    if (posed) RTX_TRY(wait_for(st.pose.used, st.stream));   // ... or make the pose, or walk what was aimed over it
-    RTX_TRY(view_rows_launch(scene, st, v, st.d_out.as<uint8_t>(), timed.counters(st), st.stream, [&] { return timed.begin(st); }, lit,
-                             shaft_delta, posed));
+    DeviceGeometry *geo;
+    RTX_TRY(geometry_of(st, posed, &geo));
+    // a device-resident call may still read its light, make the pose, or walk what was aimed over it
+    RTX_TRY(wait_for_uses(st, uses_of(lit, posed)));
+    RTX_TRY(view_rows_launch(scene, st, *geo, v, st.d_out.as<uint8_t>(), timed.counters(st), st.stream, [&] { return timed.begin(st); },
+                             lit, shaft_delta));
     RTX_TRY(timed.end(st));
     RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
     return timed.gather(st, static_cast<uint64_t>(v.ny) * v.width * scene->prep.nb_ray, lit ? lit->count : scene->prep.nb_light_sample);
@@ -1175,10 +1218,11 @@ int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit
     RTX_TRY(view_rows_supported(scene, view, lit, &shaft_delta));
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
-    RTX_TRY(view_rows_launch(scene, e.state(), *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
-                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta, posed));
-    if (lit) RTX_TRY(mark_busy(e.state().lit.used, static_cast<hipStream_t>(stream)));
-    return posed ? mark_busy(e.state().pose.used, static_cast<hipStream_t>(stream)) : RTX_OK;
+    DeviceGeometry *geo;
+    RTX_TRY(geometry_of(e.state(), posed, &geo));
+    RTX_TRY(view_rows_launch(scene, e.state(), *geo, *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
+                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta));
+    return mark_uses(e.state(), uses_of(lit, posed), static_cast<hipStream_t>(stream));
 }
 
 // host statement of the plane kernel and of the aim kernels over a pose: global_plane_statement over the posed records of
@@ -1217,6 +1261,28 @@ std::vector<rtx::NodeRec> aimed_on_host(const rtx::PreparedScene &p, const float
     std::vector<rtx::NodeRec> out;
     rtx::stream_nearest_first(moved, tree_root(p), eye, out);
     return out;
+}
+
+// The end of a read-back on the library's stream: n records of a node stream on the device (a geometry's nodes or its
+// aimed stream) are copied behind what the call has enqueued, the stream is drained, and the records are stated in
+// NodeRec word order, 8 words each.  out == NULL: no records, the stream is drained all the same.
+int read_back_nodes(const DeviceState &st, const void *d_nodes, size_t n, uint32_t *out)
+{
+    std::vector<rtx::NodeDev> dev;
+    try {
+        dev.resize(out ? n : 0u);
+    } catch (...) {
+        (void)hipStreamSynchronize(st.stream);      // what the call has enqueued writes the caller's arrays
+        return RTX_ERR_OOM;
+    }
+    if (!dev.empty()) RTX_HIP(hipMemcpyAsync(dev.data(), d_nodes, n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    for (size_t i = 0; i < dev.size(); ++i) {
+        const rtx::NodeDev &d = dev[i];
+        const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
+        std::memcpy(out + 8u * i, &r, sizeof r);
+    }
+    return RTX_OK;
 }
 
 }  // namespace
@@ -1438,7 +1504,7 @@ int rtx_render_tiles_device(RtxScene *scene, int device, uint32_t first_tile, ui
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     const rtx::TileSpec ts{first_tile * tile_rows, tile_rows, tile_stride * tile_rows, rows};
-    return render_launch(e.state(), device_scene(scene, e.state()), ts, static_cast<uint8_t *>(d_out_rgb),
+    return render_launch(e.state(), device_scene(scene, e.state(), e.state().geo), ts, static_cast<uint8_t *>(d_out_rgb),
                          reinterpret_cast<unsigned long long *>(d_counters), nullptr, static_cast<hipStream_t>(stream),
                          [] { return static_cast<int>(RTX_OK); });
 }
@@ -1524,33 +1590,29 @@ int rtx_scene_light(const RtxScene *scene, RtxLight *out)
 int rtx_render_view_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
                         RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
-    Lit lit;
-    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_host(scene, device, view, &lit, false, out_rgb, out_shade, out_hits, stats);
+    const CallLight l(scene, light, CallLight::kRequired);
+    return l.ok ? view_host(scene, device, view, l.lit, false, out_rgb, out_shade, out_hits, stats) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_render_view_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
                                void *d_shade, void *d_hits, void *stream)
 {
-    Lit lit;
-    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_device(scene, device, view, &lit, false, d_rgb, d_shade, d_hits, stream);
+    const CallLight l(scene, light, CallLight::kRequired);
+    return l.ok ? view_device(scene, device, view, l.lit, false, d_rgb, d_shade, d_hits, stream) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_shade_rays_lit(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
                        uint32_t flags, const RtxLight *light, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
-    Lit lit;
-    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return shade_host(scene, device, n_pixels, origins, directions, flags, &lit, false, out_shade, out_hits, stats);
+    const CallLight l(scene, light, CallLight::kRequired);
+    return l.ok ? shade_host(scene, device, n_pixels, origins, directions, flags, l.lit, false, out_shade, out_hits, stats) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_shade_rays_lit_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
                               uint32_t flags, const RtxLight *light, void *d_shade, void *d_hits, void *stream)
 {
-    Lit lit;
-    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, &lit, false, d_shade, d_hits, stream);
+    const CallLight l(scene, light, CallLight::kRequired);
+    return l.ok ? shade_device(scene, device, n_pixels, d_origins, d_directions, flags, l.lit, false, d_shade, d_hits, stream) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_scene_light_points_for(const RtxScene *scene, const RtxLight *light, float *out)
@@ -1571,7 +1633,7 @@ int rtx_debug_light_points(RtxScene *scene, int device, const RtxLight *light, f
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
     RTX_TRY(reserve_light(scene, st, lit, false));
-    RTX_TRY(wait_for(st.lit.used, st.stream));
+    RTX_TRY(wait_for_uses(st, kUsesLight));
     RTX_TRY(light_launch(scene, st, lit, false, st.stream));
     const size_t bytes = static_cast<size_t>(scene->prep.nb_ray) * lit.count * 3u * sizeof(float);
     if (bytes) RTX_HIP(hipMemcpyAsync(out, st.lit.points.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
@@ -1593,17 +1655,15 @@ int rtx_render_view_rows_device(RtxScene *scene, int device, const RtxView *view
 int rtx_render_view_rows_lit(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
                              RtxStats *stats)
 {
-    Lit lit;
-    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_rows_host(scene, device, view, &lit, false, out_rgb, stats);
+    const CallLight l(scene, light, CallLight::kRequired);
+    return l.ok ? view_rows_host(scene, device, view, l.lit, false, out_rgb, stats) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_render_view_rows_lit_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
                                     size_t d_bytes, void *stream, uint64_t *d_counters)
 {
-    Lit lit;
-    if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_rows_device(scene, device, view, &lit, false, d_rgb, d_bytes, stream, d_counters);
+    const CallLight l(scene, light, CallLight::kRequired);
+    return l.ok ? view_rows_device(scene, device, view, l.lit, false, d_rgb, d_bytes, stream, d_counters) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_scene_light_walk_for(const RtxScene *scene, const RtxLight *light, uint32_t *out_order, float *out_boxes,
@@ -1628,7 +1688,7 @@ int rtx_debug_light_walk(RtxScene *scene, int device, const RtxLight *light, flo
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
     RTX_TRY(reserve_light(scene, st, lit, true));
-    RTX_TRY(wait_for(st.lit.used, st.stream));
+    RTX_TRY(wait_for_uses(st, kUsesLight));
     RTX_TRY(light_launch(scene, st, lit, true, st.stream));
     const size_t n = static_cast<size_t>(scene->prep.nb_ray) * lit.count;
     if (n) {
@@ -1686,17 +1746,17 @@ int rtx_scene_pose(RtxScene *scene, int device, const float *v0v1v2, const uint3
     }
     const uint32_t *rank = tie_rank ? tie_rank : (want_ref ? ref_rank.data() : nullptr);
     RTX_TRY(reserve_pose(scene, st, true, ref_stream.size()));
-    RTX_TRY(wait_for(st.pose.used, st.stream));      // a device-resident call may still read the pose this one replaces
+    RTX_TRY(wait_for_uses(st, kUsesPose));      // a device-resident call may still read the pose this one replaces
     const size_t v_bytes = static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
     hipError_t he = hipSuccess;
     if (v_bytes) he = hipMemcpyAsync(st.pose.v.as<void>(), v0v1v2, v_bytes, hipMemcpyHostToDevice, st.stream);
     if (he == hipSuccess && rank)
         he = hipMemcpyAsync(st.pose.rank.as<void>(), rank, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
     if (he == hipSuccess && !ref_stream.empty()) {
-        he = hipMemcpyAsync(st.pose.ref_nodes.as<void>(), ref_stream.data(), ref_stream.size() * sizeof(rtx::NodeDev),
+        he = hipMemcpyAsync(st.pose.geo.ref_nodes.as<void>(), ref_stream.data(), ref_stream.size() * sizeof(rtx::NodeDev),
                             hipMemcpyHostToDevice, st.stream);
         if (he == hipSuccess)
-            he = hipMemsetAsync(st.pose.ref_nodes.as<rtx::NodeDev>() + ref_stream.size(), 0, sizeof(rtx::NodeDev), st.stream);
+            he = hipMemsetAsync(st.pose.geo.ref_nodes.as<rtx::NodeDev>() + ref_stream.size(), 0, sizeof(rtx::NodeDev), st.stream);
     }
     int rc = hip_rc(he);
     if (rc == RTX_OK) rc = timed.begin(st);
@@ -1707,7 +1767,7 @@ int rtx_scene_pose(RtxScene *scene, int device, const float *v0v1v2, const uint3
         (void)hipStreamSynchronize(st.stream);      // the copies above read the caller's arrays and this call's vectors
         return rc;
     }
-    st.pose.n_ref_nodes = static_cast<uint32_t>(ref_stream.size());
+    st.pose.geo.n_ref_nodes = static_cast<uint32_t>(ref_stream.size());
     return timed.gather(st, 0u, 0u);
 }
 
@@ -1721,7 +1781,7 @@ int rtx_scene_pose_device(RtxScene *scene, int device, const void *d_v0v1v2, con
     RTX_TRY(reserve_pose(scene, st, false, 0u));
     RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank),
                         static_cast<hipStream_t>(stream)));
-    return mark_busy(st.pose.used, static_cast<hipStream_t>(stream));
+    return mark_uses(st, kUsesPose, static_cast<hipStream_t>(stream));
 }
 
 int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
@@ -1730,26 +1790,14 @@ int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *ou
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    if (!st.pose.valid) return RTX_ERR_BAD_ARG;
-    const size_t n_prims = scene->prep.tris.size(), n = scene->prep.nodes.size();
-    std::vector<rtx::NodeDev> dev;
-    try {
-        dev.resize(out_nodes ? n : 0u);
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    RTX_TRY(wait_for(st.pose.used, st.stream));
-    if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, st.pose.tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
+    DeviceGeometry *g;
+    RTX_TRY(geometry_of(st, true, &g));
+    const size_t n_prims = scene->prep.tris.size();
+    RTX_TRY(wait_for_uses(st, kUsesPose));
+    if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, g->tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
     if (out_shade)
-        RTX_HIP(hipMemcpyAsync(out_shade, st.pose.shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
-    if (!dev.empty()) RTX_HIP(hipMemcpyAsync(dev.data(), st.pose.nodes.as<void>(), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
-    RTX_HIP(hipStreamSynchronize(st.stream));
-    for (size_t i = 0; i < dev.size(); ++i) {         // NodeDev word order -> NodeRec's
-        const rtx::NodeDev &d = dev[i];
-        const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
-        std::memcpy(out_nodes + 8u * i, &r, sizeof r);
-    }
-    return RTX_OK;
+        RTX_HIP(hipMemcpyAsync(out_shade, g->shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
+    return read_back_nodes(st, g->nodes.as<void>(), scene->prep.nodes.size(), out_nodes);
 }
 
 int rtx_trace_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
@@ -1783,33 +1831,29 @@ int rtx_occluded_rays_posed_device(RtxScene *scene, int device, uint32_t n_rays,
 int rtx_shade_rays_posed(RtxScene *scene, int device, uint32_t n_pixels, const float *origins, const float *directions,
                          uint32_t flags, const RtxLight *light, RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
-    Lit lit;
-    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return shade_host(scene, device, n_pixels, origins, directions, flags, light ? &lit : nullptr, true, out_shade, out_hits, stats);
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? shade_host(scene, device, n_pixels, origins, directions, flags, l.lit, true, out_shade, out_hits, stats) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_shade_rays_posed_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_origins, const void *d_directions,
                                 uint32_t flags, const RtxLight *light, void *d_shade, void *d_hits, void *stream)
 {
-    Lit lit;
-    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return shade_device(scene, device, n_pixels, d_origins, d_directions, flags, light ? &lit : nullptr, true, d_shade, d_hits, stream);
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? shade_device(scene, device, n_pixels, d_origins, d_directions, flags, l.lit, true, d_shade, d_hits, stream) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_render_view_posed(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
                           RtxPixelShade *out_shade, RtxRayHit *out_hits, RtxStats *stats)
 {
-    Lit lit;
-    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_host(scene, device, view, light ? &lit : nullptr, true, out_rgb, out_shade, out_hits, stats);
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? view_host(scene, device, view, l.lit, true, out_rgb, out_shade, out_hits, stats) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_render_view_posed_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
                                  void *d_shade, void *d_hits, void *stream)
 {
-    Lit lit;
-    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_device(scene, device, view, light ? &lit : nullptr, true, d_rgb, d_shade, d_hits, stream);
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? view_device(scene, device, view, l.lit, true, d_rgb, d_shade, d_hits, stream) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_scene_aimed_nodes(const RtxScene *scene, const float eye[3], uint32_t *out_dwords)
@@ -1830,41 +1874,25 @@ int rtx_debug_aimed_nodes(RtxScene *scene, int device, const float eye[3], uint3
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    int rc = reserve_aimed(scene, st, false);
+    int rc = reserve_aimed(scene, st.geo);
     if (rc != RTX_OK) return rc;
-    st.aimed.valid = false;                  // the kernels run whatever the buffer holds
-    if ((rc = aim_at(scene, st, false, eye, st.stream)) != RTX_OK) return rc;
-    const size_t n = scene->prep.nodes.size();
-    std::vector<rtx::NodeDev> dev;
-    try {
-        dev.resize(n);
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    if (n) RTX_HIP(hipMemcpyAsync(dev.data(), aimed_stream(scene, st, false), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
-    RTX_HIP(hipStreamSynchronize(st.stream));
-    for (size_t i = 0; i < n; ++i) {         // NodeDev word order -> NodeRec's
-        const rtx::NodeDev &d = dev[i];
-        const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
-        std::memcpy(out_dwords + 8u * i, &r, sizeof r);
-    }
-    return RTX_OK;
+    st.geo.aimed.valid = false;              // the kernels run whatever the buffer holds
+    if ((rc = aim_at(scene, st.geo, eye, st.stream)) != RTX_OK) return rc;
+    return read_back_nodes(st, aimed_stream(scene, st.geo), scene->prep.nodes.size(), out_dwords);
 }
 
 int rtx_render_view_rows_posed(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint8_t *out_rgb,
                                RtxStats *stats)
 {
-    Lit lit;
-    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_rows_host(scene, device, view, light ? &lit : nullptr, true, out_rgb, stats);
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? view_rows_host(scene, device, view, l.lit, true, out_rgb, stats) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_render_view_rows_posed_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, void *d_rgb,
                                       size_t d_bytes, void *stream, uint64_t *d_counters)
 {
-    Lit lit;
-    if (light && !lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
-    return view_rows_device(scene, device, view, light ? &lit : nullptr, true, d_rgb, d_bytes, stream, d_counters);
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? view_rows_device(scene, device, view, l.lit, true, d_rgb, d_bytes, stream, d_counters) : RTX_ERR_BAD_ARG;
 }
 
 int rtx_scene_posed_pipeline_records(const RtxScene *scene, const float *v0v1v2, const float eye[3], uint32_t *out_planes,
@@ -1886,30 +1914,18 @@ int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uin
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    if (!st.pose.valid) return RTX_ERR_BAD_ARG;
+    DeviceGeometry *g;
+    RTX_TRY(geometry_of(st, true, &g));
     const size_t n = scene->prep.nodes.size(), n_global = scene->prep.n_global;
-    std::vector<rtx::NodeDev> dev;
-    try {
-        dev.resize(out_aimed ? n : 0u);
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    RTX_TRY(wait_for(st.pose.used, st.stream));
+    RTX_TRY(wait_for_uses(st, kUsesPose));
     if (out_planes && n_global)
-        RTX_HIP(hipMemcpyAsync(out_planes, st.pose.planes.as<void>(), n_global * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
-    if (!dev.empty()) {
-        RTX_TRY(reserve_aimed(scene, st, true));
-        st.pose.aimed.valid = false;         // the kernels run whatever the buffer holds
-        RTX_TRY(aim_at(scene, st, true, eye, st.stream));
-        RTX_HIP(hipMemcpyAsync(dev.data(), aimed_stream(scene, st, true), n * sizeof(rtx::NodeDev), hipMemcpyDeviceToHost, st.stream));
+        RTX_HIP(hipMemcpyAsync(out_planes, g->planes.as<void>(), n_global * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
+    if (out_aimed && n) {
+        RTX_TRY(reserve_aimed(scene, *g));
+        g->aimed.valid = false;              // the kernels run whatever the buffer holds
+        RTX_TRY(aim_at(scene, *g, eye, st.stream));
     }
-    RTX_HIP(hipStreamSynchronize(st.stream));
-    for (size_t i = 0; i < dev.size(); ++i) {         // NodeDev word order -> NodeRec's
-        const rtx::NodeDev &d = dev[i];
-        const rtx::NodeRec r{{d.lox, d.loy, d.loz}, d.link, {d.hix, d.hiy, d.hiz}, d.info};
-        std::memcpy(out_aimed + 8u * i, &r, sizeof r);
-    }
-    return RTX_OK;
+    return read_back_nodes(st, aimed_stream(scene, *g), n, out_aimed);
 }
 
 int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint64_t *out,
@@ -1926,7 +1942,7 @@ int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t 
     Entry en(scene, device, Entry::kUploaded);
     if (en.rc != RTX_OK) return en.rc;
     DeviceState &st = en.state();
-    const rtx::DeviceScene S = device_scene(scene, st);
+    const rtx::DeviceScene S = device_scene(scene, st, st.geo);
     *tiles_x = rtx::trace_tiles_x(S, kernel_variant());
     *tiles_y = (nrows + 7u) / 8u;
     const size_t n = static_cast<size_t>(*tiles_x) * *tiles_y;

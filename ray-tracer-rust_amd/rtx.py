@@ -607,6 +607,18 @@ class Scene:
                   C.c_void_p(stream) if stream else None), "rtx_occluded_rays_device")
 
     # -- shading rays the caller supplies (GPU only)
+    @staticmethod
+    def _lit_or_posed(stem, form, head, tail, light, posed):
+        """Calls stem + form (form: "" or "_device"), its _lit twin under a light, or its _posed twin (whose light is
+        optional: None is the scene's), with the light between head and tail."""
+        if posed:
+            name, mid = stem + "_posed" + form, (C.byref(light) if light is not None else None,)
+        elif light is None:
+            name, mid = stem + form, ()
+        else:
+            name, mid = stem + "_lit" + form, (C.byref(light),)
+        _check(getattr(_lib, name)(*head, *mid, *tail), name)
+
     def shade_rays(self, origins, directions, device=0, keep_order=False, stats=False, force_regroup=False,
                    want_hits=False, light=None, posed=False):
         """render_pixel's body (main.rs:182-239) per pixel of nb_ray consecutive rays -> structured array
@@ -624,12 +636,7 @@ class Scene:
         tail = (out.ctypes.data_as(C.POINTER(PixelShade)), hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None,
                 C.byref(st) if stats else None)
         head = (self._h, device, n, _fp(o), _fp(d), self._ray_flags(keep_order, force_regroup))
-        if posed:
-            _check(_lib.rtx_shade_rays_posed(*head, C.byref(light) if light is not None else None, *tail), "rtx_shade_rays_posed")
-        elif light is None:
-            _check(_lib.rtx_shade_rays(*head, *tail), "rtx_shade_rays")
-        else:
-            _check(_lib.rtx_shade_rays_lit(*head, C.byref(light), *tail), "rtx_shade_rays_lit")
+        self._lit_or_posed("rtx_shade_rays", "", head, tail, light, posed)
         res = (out,) + ((hits,) if want_hits else ()) + ((st.asdict(),) if stats else ())
         return res if len(res) > 1 else out
 
@@ -640,13 +647,7 @@ class Scene:
         head = (self._h, device, n_pixels, C.c_void_p(d_origins_ptr), C.c_void_p(d_directions_ptr),
                 self._ray_flags(keep_order, force_regroup))
         tail = (C.c_void_p(d_shade_ptr), C.c_void_p(d_hits_ptr) if d_hits_ptr else None, C.c_void_p(stream) if stream else None)
-        if posed:
-            _check(_lib.rtx_shade_rays_posed_device(*head, C.byref(light) if light is not None else None, *tail),
-                   "rtx_shade_rays_posed_device")
-        elif light is None:
-            _check(_lib.rtx_shade_rays_device(*head, *tail), "rtx_shade_rays_device")
-        else:
-            _check(_lib.rtx_shade_rays_lit_device(*head, C.byref(light), *tail), "rtx_shade_rays_lit_device")
+        self._lit_or_posed("rtx_shade_rays", "_device", head, tail, light, posed)
 
     # -- any pinhole view of the uploaded scene (GPU only)
     @staticmethod
@@ -676,13 +677,7 @@ class Scene:
         st = Stats()
         tail = (out.ctypes.data, shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
                 hits.ctypes.data_as(C.POINTER(RayHit)) if want_hits else None, C.byref(st) if stats else None)
-        if posed:
-            _check(_lib.rtx_render_view_posed(self._h, device, C.byref(view), C.byref(light) if light is not None else None, *tail),
-                   "rtx_render_view_posed")
-        elif light is None:
-            _check(_lib.rtx_render_view(self._h, device, C.byref(view), *tail), "rtx_render_view")
-        else:
-            _check(_lib.rtx_render_view_lit(self._h, device, C.byref(view), C.byref(light), *tail), "rtx_render_view_lit")
+        self._lit_or_posed("rtx_render_view", "", (self._h, device, C.byref(view)), tail, light, posed)
         res = (out,) + ((shade,) if want_shade else ()) + ((hits,) if want_hits else ()) + ((st.asdict(),) if stats else ())
         return res if len(res) > 1 else out
 
@@ -692,14 +687,7 @@ class Scene:
         ny*nx*nb_ray x 32 bytes."""
         tail = (C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None, C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
                 C.c_void_p(d_hits_ptr) if d_hits_ptr else None, C.c_void_p(stream) if stream else None)
-        if posed:
-            _check(_lib.rtx_render_view_posed_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                                                     *tail), "rtx_render_view_posed_device")
-        elif light is None:
-            _check(_lib.rtx_render_view_device(self._h, device, C.byref(view), *tail), "rtx_render_view_device")
-        else:
-            _check(_lib.rtx_render_view_lit_device(self._h, device, C.byref(view), C.byref(light), *tail),
-                   "rtx_render_view_lit_device")
+        self._lit_or_posed("rtx_render_view", "_device", (self._h, device, C.byref(view)), tail, light, posed)
 
     # -- posing the scene's triangles (GPU only, posed_records and pose_bound aside): the posed= keyword of trace_rays*,
     #    occluded_rays*, shade_rays* and render_view* then works on the device's pose
@@ -821,29 +809,15 @@ class Scene:
         the uploaded triangles (rtx_render_view_rows_posed)."""
         out = np.zeros((view.ny, view.width, 3), np.uint8)
         st = Stats()
-        if posed:
-            _check(_lib.rtx_render_view_rows_posed(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                                                   out.ctypes.data, C.byref(st) if stats else None), "rtx_render_view_rows_posed")
-        elif light is None:
-            _check(_lib.rtx_render_view_rows(self._h, device, C.byref(view), out.ctypes.data, C.byref(st) if stats else None),
-                   "rtx_render_view_rows")
-        else:
-            _check(_lib.rtx_render_view_rows_lit(self._h, device, C.byref(view), C.byref(light), out.ctypes.data,
-                                                 C.byref(st) if stats else None), "rtx_render_view_rows_lit")
+        self._lit_or_posed("rtx_render_view_rows", "", (self._h, device, C.byref(view)),
+                           (out.ctypes.data, C.byref(st) if stats else None), light, posed)
         return (out, st.asdict()) if stats else out
 
     def render_view_rows_device(self, device, view, d_rgb_ptr, d_bytes, stream=None, d_counters_ptr=None, light=None, posed=False):
         """Asynchronous pipeline launch of the view's rows into a device buffer the caller owns (ny*width*3 bytes)."""
         tail = (C.c_void_p(d_rgb_ptr), d_bytes, C.c_void_p(stream) if stream else None,
                 C.c_void_p(d_counters_ptr) if d_counters_ptr else None)
-        if posed:
-            _check(_lib.rtx_render_view_rows_posed_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                                                          *tail), "rtx_render_view_rows_posed_device")
-        elif light is None:
-            _check(_lib.rtx_render_view_rows_device(self._h, device, C.byref(view), *tail), "rtx_render_view_rows_device")
-        else:
-            _check(_lib.rtx_render_view_rows_lit_device(self._h, device, C.byref(view), C.byref(light), *tail),
-                   "rtx_render_view_rows_lit_device")
+        self._lit_or_posed("rtx_render_view_rows", "_device", (self._h, device, C.byref(view)), tail, light, posed)
 
     def aimed_nodes(self, eye):
         """Host only: records [n_nodes, 8] of the stream the primary rays of a view with this eye walk (planes moved by

@@ -322,6 +322,35 @@ def test_device_resident_pose_and_two_posed_launches_on_one_stream(rtx, orc, sam
     assert np.array_equal(bunny.render_view_rows(view), ps.posed(orc, samples_seeded, "identity")["frame"])
 
 
+def test_a_host_pose_and_a_host_lit_call_behind_device_resident_posed_lit_rows(rtx, orc, samples_seeded, bunny):
+    """the host calls overwrite the pose and the light buffers the launch on the caller's stream still reads: both wait"""
+    torch = pytest.importorskip("torch")
+    assert torch.cuda.is_available(), "torch sees no GPU"
+    turn, shift = (ps.posed(orc, samples_seeded, n) for n in ("turn", "shift"))
+    light = rtx.Scene.make_light(*ls.SIDE_LIGHTS[ps.POSE_LIGHT])
+    other = ls.side(orc, samples_seeded, "point")
+    assert other["v"] == ps.SIDE and ps.POSE_LIGHT != "point"
+    view = lib_view(rtx, ps.SIDE)
+    n = view.ny * view.width * 3
+    stream = torch.cuda.Stream(device="cuda:0")
+    assert stream.cuda_stream != torch.cuda.default_stream().cuda_stream
+    with torch.cuda.stream(stream):
+        d_turn = torch.from_numpy(turn["pose"].copy()).to("cuda:0")
+        buf = torch.full((n + 16,), GUARD, dtype=torch.uint8, device="cuda:0")
+        stream.synchronize()
+        bunny.pose_device(0, d_turn.data_ptr(), None, stream.cuda_stream)
+        bunny.render_view_rows_device(0, view, buf.data_ptr(), buf.numel(), stream.cuda_stream, posed=True, light=light)
+        # nothing waited for: another pose and another light, on the library's stream
+        bunny.pose(shift["pose"])
+        host = bunny.render_view_rows(view, light=rtx.Scene.make_light(*ls.SIDE_LIGHTS["point"]))
+        stream.synchronize()
+        out = buf.cpu().numpy()
+        want = ps.lit_frame(orc, samples_seeded, "turn", ps.POSE_LIGHT)[0]
+        assert out[:n].tobytes() == want.tobytes() and (out[n:] == GUARD).all()
+        assert np.array_equal(host, other["frame"]), "host lit rows differ at %s" % where(host, other["frame"])
+    assert np.array_equal(bunny.render_view_rows(view, posed=True), shift["frame"])          # the host pose stands
+
+
 # ---------------------------------------------------------------------------------------------- 11: a turntable
 def test_four_turns_of_the_mesh(rtx, orc, samples_seeded, bunny):
     view = lib_view(rtx, ps.TURNTABLE_VIEW)
