@@ -560,6 +560,55 @@ int rtx_scene_posed_pipeline_records(const RtxScene *scene, const float *v0v1v2,
  * blocks.  Each output may be NULL; eye may be NULL when out_aimed is.  RTX_ERR_BAD_ARG when the device holds no pose. */
 int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uint32_t *out_planes, uint32_t *out_aimed);
 
+/* ---- A pose whose tree is rebuilt on the device --------------------------------------------------------------------------
+ * rtx_scene_pose_rebuilt / _device are rtx_scene_pose / _device in every respect — the argument checks, the range rule
+ * decided on the host before a device is looked for, one pose per scene and device (a new pose of either kind replaces
+ * the previous one and takes the pose's aimed stream away), the ordering, stats (kernel_ms: the key kernel, the sort, the
+ * record kernel, the refit and the plane kernel) — except the tree: instead of keeping the splits made for the created
+ * geometry, the records of the tree proper (every record but the global triangles', which stay records [0, n_global) in
+ * their order) are sorted on the device by a 64-bit key, and a balanced tree is laid over the sorted runs.
+ *   key: bit 63 the arm (0 triangle, 1 sphere: spheres sort behind all triangles, a leaf never mixes arms); bits 62..0
+ *     the 3 x 21-bit Morton interleave (x highest in each triple) of the cells of the centre of the primitive's own posed
+ *     box: c = 0.5f * (bmin + bmax), cell = (uint32)((c + M) * S) held to [0, 2^21 - 1], a NaN to cell 0; M is
+ *     rtx_scene_pose_bound's, S = 2^21 / (2 M) rounded to f32 once.  A sphere's key comes from its uploaded record.
+ *   sort: stable — equal keys keep uploaded order.
+ *   shape: pre-order, skip-linked, as rtx_scene_nodes: with global triangles and a tree proper, record 0 is the root and
+ *     record 1 the global leaf; the tree proper is the balanced subtree over the triangle run, or an inner node over that
+ *     and the balanced subtree over the sphere run when both exist; a run of more than leaf_max records (the scene's,
+ *     default 4) splits at begin + count / 2.  The shape depends on n_global, the two run lengths and leaf_max only; the
+ *     rebuilt stream has its own node count (rtx_scene_rebuilt_counts).
+ *   boxes: every node's box is the fold of the own boxes of its run, moved outwards by cull_delta, as for rtx_scene_pose.
+ * Every posed call then runs over the rebuilt pose unchanged, and for rays without a zero direction component returns what
+ * it returns over the refitted pose: only speed changes (DESIGN.md section 19 has which tree wins where).  Ties and hard
+ * groups: rtx_scene_pose's rule over the rebuilt stream; with a reference tree (host variant) its leaves name positions of
+ * the sorted array.  rtx_scene_pose_rebuilt_device outside the range rule: keys saturate, the permutation is still a
+ * permutation and the shape is fixed, so the calls terminate; the values are unspecified.  Spheres do not move and the
+ * primitive count does not change. */
+int rtx_scene_pose_rebuilt(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank /* may be NULL */,
+                           uint32_t reference_tree, RtxStats *stats);
+int rtx_scene_pose_rebuilt_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank /* may be NULL */,
+                                  void *stream);
+/* Host only, no device: the node count of the rebuilt stream. */
+int rtx_scene_rebuilt_counts(const RtxScene *scene, uint32_t *out_n_nodes);
+/* Host only, no device: the words a rebuilt pose makes.  out_keys, out_perm: one per record of the tree proper
+ * (n_prims - n_global), in sorted order: the key, and the position in the uploaded array (rtx_scene_nodes' out_tri_order)
+ * of the record that sorted position n_global + p holds; out_tris: n_prims x 16 words in sorted order; out_shade:
+ * n_prims x 8 in Vec order, as rtx_scene_posed_records'; out_nodes: rtx_scene_rebuilt_counts' x 8, NodeRec word order, the
+ * planes moved by cull_delta.  Each output may be NULL.  The vertices are not checked against the range rule. */
+int rtx_scene_rebuilt_records(const RtxScene *scene, const float *v0v1v2, const uint32_t *tie_rank, uint64_t *out_keys,
+                              uint32_t *out_perm, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes);
+/* Host only, no device: the aim kernels' output over a rebuilt pose for `eye`: rtx_scene_rebuilt_records' node words (their
+ * planes moved by cull_delta once, there) in rtx_scene_aimed_nodes' order; a scene that aims nothing: those words as they
+ * are.  out_aimed: rtx_scene_rebuilt_counts' x 8 words.  RTX_ERR_BAD_ARG for a NULL. */
+int rtx_scene_rebuilt_aimed(const RtxScene *scene, const float *v0v1v2, const float eye[3], uint32_t *out_aimed);
+/* Diagnostic: blocks and copies the rebuilt pose `device` holds back, in rtx_scene_rebuilt_records' layout, and the aim
+ * kernels' output over it for `eye` (out_aimed: the rebuilt node count x 8; a scene that aims nothing: the pose's stream).
+ * Each output may be NULL; eye may be NULL when out_aimed is.  RTX_ERR_BAD_ARG when the device holds no rebuilt pose.
+ * On a rebuilt pose rtx_debug_pose's out_nodes and rtx_debug_pose_pipeline's out_aimed — sized by the uploaded node
+ * count — do not apply: RTX_ERR_BAD_ARG when they are not NULL. */
+int rtx_debug_pose_rebuilt(RtxScene *scene, int device, const float eye[3], uint32_t *out_perm, uint32_t *out_tris,
+                           uint32_t *out_shade, uint32_t *out_nodes, uint32_t *out_aimed);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

@@ -244,6 +244,21 @@ extern "C" {
                                             out_aimed: *mut u32) -> c_int;
     pub fn rtx_debug_pose_pipeline(scene: *mut RtxScene, device: c_int, eye: *const f32, out_planes: *mut u32,
                                    out_aimed: *mut u32) -> c_int;
+    /// A pose whose tree is rebuilt on the device: `rtx_scene_pose` / `_device` in every respect except the tree — the
+    /// tree proper's records sorted by a 64-bit Morton key, a balanced tree over the sorted runs, boxes by the refit.
+    /// Every posed call then runs over it unchanged.
+    pub fn rtx_scene_pose_rebuilt(scene: *mut RtxScene, device: c_int, v0v1v2: *const f32, tie_rank: *const u32,
+                                  reference_tree: u32, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_scene_pose_rebuilt_device(scene: *mut RtxScene, device: c_int, d_v0v1v2: *const c_void, d_tie_rank: *const c_void,
+                                         stream: *mut c_void) -> c_int;
+    /// Host only: the rebuilt stream's node count, and the words a rebuilt pose makes (each output may be NULL).
+    pub fn rtx_scene_rebuilt_counts(scene: *const RtxScene, out_n_nodes: *mut u32) -> c_int;
+    pub fn rtx_scene_rebuilt_records(scene: *const RtxScene, v0v1v2: *const f32, tie_rank: *const u32, out_keys: *mut u64,
+                                     out_perm: *mut u32, out_tris: *mut u32, out_shade: *mut u32, out_nodes: *mut u32) -> c_int;
+    pub fn rtx_scene_rebuilt_aimed(scene: *const RtxScene, v0v1v2: *const f32, eye: *const f32, out_aimed: *mut u32) -> c_int;
+    /// Diagnostic: the rebuilt pose the device holds, and the aim kernels' output over it for `eye`; blocks.
+    pub fn rtx_debug_pose_rebuilt(scene: *mut RtxScene, device: c_int, eye: *const f32, out_perm: *mut u32, out_tris: *mut u32,
+                                  out_shade: *mut u32, out_nodes: *mut u32, out_aimed: *mut u32) -> c_int;
     /// Host only: the points of `light` on this scene (`out` may be NULL); returns their number or a negative error.
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.

@@ -25,6 +25,7 @@
 #include "rtx_light.h"
 #include "rtx_planes.h"
 #include "rtx_pose.h"
+#include "rtx_rebuild.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
 #include "rtx_tour.h"
@@ -161,6 +162,7 @@ struct AimedStream {
 // (reserve_pose, pose_launch); geometry_of picks the one a call walks, and device_scene reads all six fields from it.
 struct DeviceGeometry {
     DeviceBuffer nodes, ref_nodes, tris, shade, planes;
+    uint32_t n_nodes = 0;                // records of `nodes` (a sentinel follows): the scene's, or a rebuilt pose's own count
     uint32_t n_ref_nodes = 0;
     AimedStream aimed;
 };
@@ -217,6 +219,15 @@ public:
         DeviceGeometry geo;
         bool valid = false;
         Event used;
+        // rtx_scene_pose_rebuilt (rtx_rebuild.hip): the rebuilt stream's host tables (rtx::RebuildTables, uploaded with the
+        // first rebuilt pose: link and info as node records, ranges, order), the sort's buffers and the permutation.
+        // rebuilt: the pose that stands is a rebuilt one (geo.n_nodes is then the rebuilt stream's count)
+        struct {
+            DeviceBuffer nodes, ranges, order;
+            bool tables = false;
+            DeviceBuffer keys, keys_sorted, index, perm, temp;
+        } b;
+        bool rebuilt = false;
     } pose;
 private:
     ~DeviceState() = default;
@@ -279,6 +290,8 @@ struct RtxScene {
     std::mutex mu;
     rtx::PoseTables pose_tables;     // made by the first call that poses (pose_tables_of), under mu
     bool pose_tables_made = false;
+    rtx::RebuildTables rebuild_tables;   // made by the first call that asks for a rebuilt pose (rebuild_tables_of), under mu
+    bool rebuild_tables_made = false;
     std::map<int, DeviceSlot> dev;
 };
 
@@ -345,6 +358,7 @@ int upload_all(RtxScene *scene, DeviceState &st)
         (rc = upload_vec(st.primary_nodes, rtx::nodes_in_device_order(p.primary_nodes, inflate), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
     if (!p.ref_nodes.empty() &&
         (rc = upload_vec(g.ref_nodes, rtx::nodes_in_device_order(p.ref_nodes), sizeof(rtx::NodeRec))) != RTX_OK) return rc;
+    g.n_nodes = static_cast<uint32_t>(p.nodes.size());
     g.n_ref_nodes = static_cast<uint32_t>(p.ref_nodes.size());
     // one spare record of zeros behind the primitive records (no walk requests the record after the one it tests any more)
     if ((rc = upload_vec(g.tris, p.tris, sizeof(rtx::TriRec))) != RTX_OK) return rc;
@@ -401,8 +415,8 @@ private:
 };
 
 // Which geometry a call walks: the uploaded scene's, or (posed) the pose's.  The one place that answers a posed call on
-// a device that holds no pose: RTX_ERR_BAD_ARG.  The tree keeps its shape under a pose: tree_root, the record counts
-// and the number of global triangles hold for both.
+// a device that holds no pose: RTX_ERR_BAD_ARG.  The primitive count and the number of global triangles hold for both; the
+// node count is the geometry's own (a rebuilt pose's tree has another one).
 int geometry_of(DeviceState &st, bool posed, DeviceGeometry **out)
 {
     *out = &st.geo;
@@ -432,7 +446,7 @@ rtx::DeviceScene device_scene(const RtxScene *scene, const DeviceState &st, cons
     S.gamma_thr = st.thr.as<const float>();
     S.light_boxes = st.light_boxes.as<const float>();
     S.shaft_delta = p.shaft_delta;
-    S.n_nodes = static_cast<uint32_t>(p.nodes.size());
+    S.n_nodes = g.n_nodes;
     S.n_samples = p.n_samples;
     S.width = p.width;
     S.height = p.height;
@@ -593,10 +607,11 @@ int launch_on(RtxScene *scene, DeviceSlot &slot, const rtx::TileSpec &ts, const 
 // ---- ray batches: the queries (rtx_query.hip), shading (rtx_shade.hip) and views (rtx_view.hip) -------------------------
 
 // first record of the tree proper: behind the root and the leaf of the global triangles when there are any
-uint32_t tree_root(const rtx::PreparedScene &p)
+uint32_t tree_root(const rtx::PreparedScene &p, size_t n_nodes)
 {
-    return (p.n_global != 0u && p.nodes.size() > 2u) ? 2u : 0u;
+    return (p.n_global != 0u && n_nodes > 2u) ? 2u : 0u;
 }
+uint32_t tree_root(const rtx::PreparedScene &p) { return tree_root(p, p.nodes.size()); }
 
 // The multiply-based culling of the walks is proven for origins whose coordinates stay within the magnitude behind
 // cull_delta (scene_prep.cpp): the bound the ray-batch kernels are handed, and the one a pipeline view's eye is held to.
@@ -821,70 +836,135 @@ const rtx::PoseTables &pose_tables_of(RtxScene *scene)
 
 uint32_t posed_triangles(const RtxScene *scene) { return scene->prep.n_tris - scene->prep.n_spheres; }
 
+// the rebuilt stream's host tables, made once; may throw std::bad_alloc
+const rtx::RebuildTables &rebuild_tables_of(RtxScene *scene)
+{
+    std::lock_guard<std::mutex> lk(scene->mu);
+    if (!scene->rebuild_tables_made) {
+        rtx::rebuild_tables(scene->prep, scene->rebuild_tables);
+        scene->rebuild_tables_made = true;
+    }
+    return scene->rebuild_tables;
+}
+
 // The pose's buffers, library-owned per device and grow-only, and the tables' upload with the first pose.  Growing a buffer
 // waits for the device first, since an earlier launch may still read it.  n_ref: records of the reference tree's stream that
-// goes beside the pose (host variant), or 0.  Caller holds the slot's lock and has the device current and the scene uploaded.
-int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_ref)
+// goes beside the pose (host variant), or 0.  rebuilt: the node records are sized for the rebuilt stream, and the sort's
+// buffers and the rebuilt stream's tables come with them (uploaded with the first rebuilt pose).  Caller holds the slot's
+// lock and has the device current and the scene uploaded.
+int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_ref, bool rebuilt)
 {
     const rtx::PreparedScene &p = scene->prep;
-    const size_t n_prims = p.tris.size(), n_nodes = p.nodes.size();
+    const rtx::RebuildTables *bt = nullptr;
+    try {
+        if (rebuilt) bt = &rebuild_tables_of(scene);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    const size_t n_prims = p.tris.size(), n_nodes = bt ? bt->nodes.size() : p.nodes.size();
     const size_t tris = (n_prims + 1u) * sizeof(rtx::TriRec), shade = std::max<size_t>(n_prims * sizeof(rtx::ShadeRec), 16u);
     const size_t nodes = (n_nodes + 1u) * sizeof(rtx::NodeDev), ref = n_ref ? (n_ref + 1u) * sizeof(rtx::NodeDev) : 0u;
     const size_t v = host_copies ? std::max<size_t>(static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float), 16u) : 0u;
     const size_t rank = host_copies ? std::max<size_t>(n_prims * sizeof(uint32_t), 16u) : 0u;
     const size_t planes = static_cast<size_t>(p.n_global) * sizeof(rtx::TriRec);      // (no global triangle: no buffer)
+    const size_t n_tree = n_prims - p.n_global;
+    const size_t keys = rebuilt ? std::max<size_t>(n_tree * sizeof(uint64_t), 16u) : 0u;
+    const size_t index = rebuilt ? std::max<size_t>(n_tree * sizeof(uint32_t), 16u) : 0u;
+    size_t temp = 0;
+    if (rebuilt) {
+        RTX_HIP(rtxb::sort_temp_bytes(static_cast<uint32_t>(n_tree), &temp));
+        if (temp < 16u) temp = 16u;
+    }
     auto &q = st.pose;
     DeviceGeometry &g = q.geo;
     if (g.tris.capacity() < tris || g.shade.capacity() < shade || g.nodes.capacity() < nodes || g.ref_nodes.capacity() < ref ||
-        q.v.capacity() < v || q.rank.capacity() < rank || g.planes.capacity() < planes) {
+        q.v.capacity() < v || q.rank.capacity() < rank || g.planes.capacity() < planes || q.b.keys.capacity() < keys ||
+        q.b.keys_sorted.capacity() < keys || q.b.index.capacity() < index || q.b.perm.capacity() < index ||
+        q.b.temp.capacity() < temp) {
         q.valid = false;
         RTX_HIP(hipDeviceSynchronize());
         RTX_TRY(reserve_all({{g.tris, tris}, {g.shade, shade}, {g.nodes, nodes}, {g.ref_nodes, ref}, {q.v, v}, {q.rank, rank},
-                             {g.planes, planes}}));
+                             {g.planes, planes}, {q.b.keys, keys}, {q.b.keys_sorted, keys}, {q.b.index, index},
+                             {q.b.perm, index}, {q.b.temp, temp}}));
     }
-    if (q.tables) return RTX_OK;
     try {
-        const rtx::PoseTables &t = pose_tables_of(scene);
-        RTX_TRY(upload_vec(q.tri_of, t.tri_of));
-        RTX_TRY(upload_vec(q.ranges, t.ranges));
-        RTX_TRY(upload_vec(q.order, t.order));
+        if (!q.tables) {
+            const rtx::PoseTables &t = pose_tables_of(scene);
+            RTX_TRY(upload_vec(q.tri_of, t.tri_of));
+            RTX_TRY(upload_vec(q.ranges, t.ranges));
+            RTX_TRY(upload_vec(q.order, t.order));
+            q.tables = true;
+        }
+        if (bt && !q.b.tables) {
+            RTX_TRY(upload_vec(q.b.nodes, rtx::nodes_in_device_order(bt->nodes)));
+            RTX_TRY(upload_vec(q.b.ranges, bt->ranges));
+            RTX_TRY(upload_vec(q.b.order, bt->order));
+            q.b.tables = true;
+        }
     } catch (...) {
         return RTX_ERR_OOM;
     }
-    q.tables = true;
     return RTX_OK;
 }
 
 // the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
 // copies of them; the records behind the last one (upload_all pads the scene's with the same) are zeroed on the same stream.
+// rebuilt: the rebuild kernels and the sort make the records in sorted order, and the refit runs alone over the rebuilt
+// stream's tables; the geometry's node count becomes that stream's.
 // The plane kernel follows them over the posed global triangles (none: no launch).  This is the only writer of the pose's
 // nodes, and it takes the aimed stream's validity away before anything is launched (AimedStream).
-int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, hipStream_t stream)
+int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, hipStream_t stream, bool rebuilt)
 {
     const rtx::PreparedScene &p = scene->prep;
-    const uint32_t n_prims = static_cast<uint32_t>(p.tris.size()), n_nodes = static_cast<uint32_t>(p.nodes.size());
+    const uint32_t n_prims = static_cast<uint32_t>(p.tris.size());
+    const uint32_t n_nodes = static_cast<uint32_t>(rebuilt ? scene->rebuild_tables.nodes.size() : p.nodes.size());   // (made: reserve_pose)
     DeviceGeometry &q = st.pose.geo;
     st.pose.valid = false;
     q.aimed.valid = false;
+    q.n_nodes = n_nodes;
+    st.pose.rebuilt = rebuilt;
     RTX_HIP(hipMemsetAsync(q.tris.as<rtx::TriRec>() + n_prims, 0, sizeof(rtx::TriRec), stream));
     RTX_HIP(hipMemsetAsync(q.nodes.as<rtx::NodeDev>() + n_nodes, 0, sizeof(rtx::NodeDev), stream));
     rtxp::PoseArgs a{};
     a.tris = st.geo.tris.as<const rtx::TriRec>();
     a.shade = st.geo.shade.as<const rtx::ShadeRec>();
-    a.nodes = st.geo.nodes.as<const rtx::NodeDev>();
+    a.nodes = (rebuilt ? st.pose.b.nodes : st.geo.nodes).as<const rtx::NodeDev>();
     a.tri_of = st.pose.tri_of.as<const uint32_t>();
-    a.ranges = st.pose.ranges.as<const uint2>();
-    a.order = st.pose.order.as<const uint32_t>();
+    a.ranges = (rebuilt ? st.pose.b.ranges : st.pose.ranges).as<const uint2>();
+    a.order = (rebuilt ? st.pose.b.order : st.pose.order).as<const uint32_t>();
     a.n_prims = n_prims;
     a.n_nodes = n_nodes;
-    a.n_long = scene->pose_tables.n_long;      // (made: reserve_pose)
+    a.n_long = rebuilt ? scene->rebuild_tables.n_long : scene->pose_tables.n_long;      // (made: reserve_pose)
     a.cull_delta = p.cull_delta;
     a.pose = d_pose;
     a.rank = d_rank;
     a.out_tris = q.tris.as<rtx::TriRec>();
     a.out_shade = q.shade.as<rtx::ShadeRec>();
     a.out_nodes = q.nodes.as<rtx::NodeDev>();
-    RTX_HIP(rtxp::launch_pose(a, stream));
+    if (rebuilt) {
+        rtxb::RebuildArgs r{};
+        r.tris = a.tris;
+        r.shade = a.shade;
+        r.tri_of = a.tri_of;
+        r.n_prims = n_prims;
+        r.n_global = p.n_global;
+        r.bound = p.scene_magnitude;
+        r.scale = rtx::rebuild_key_scale(p.scene_magnitude);
+        r.pose = d_pose;
+        r.rank = d_rank;
+        r.keys = st.pose.b.keys.as<uint64_t>();
+        r.keys_sorted = st.pose.b.keys_sorted.as<uint64_t>();
+        r.index = st.pose.b.index.as<uint32_t>();
+        r.perm = st.pose.b.perm.as<uint32_t>();
+        r.temp = st.pose.b.temp.as<void>();
+        r.temp_bytes = st.pose.b.temp.capacity();
+        r.out_tris = a.out_tris;
+        r.out_shade = a.out_shade;
+        RTX_HIP(rtxb::launch_rebuild(r, stream));
+        RTX_HIP(rtxp::launch_refit(a, stream));
+    } else {
+        RTX_HIP(rtxp::launch_pose(a, stream));
+    }
     RTX_HIP(rtxg::launch_global_planes(q.tris.as<const rtx::TriRec>(), p.n_global, q.planes.as<rtx::TriRec>(), stream));
     q.n_ref_nodes = 0u;
     st.pose.valid = true;
@@ -1113,7 +1193,7 @@ int reserve_aimed(const RtxScene *scene, DeviceGeometry &g)
 {
     if (scene->prep.primary_nodes.empty()) return RTX_OK;
     AimedStream &a = g.aimed;
-    const size_t n = scene->prep.nodes.size();
+    const size_t n = g.n_nodes;
     const size_t had = a.nodes.capacity();
     const int rc = reserve_all({{a.nodes, (n + 1u) * sizeof(rtx::NodeDev)}, {a.links, n * sizeof(rtxa::AimLink)}});
     if (rc != RTX_OK || a.nodes.capacity() != had) a.valid = false;
@@ -1132,9 +1212,9 @@ int aim_at(const RtxScene *scene, DeviceGeometry &g, const float eye[3], hipStre
     AimedStream &a = g.aimed;
     if (a.valid && a.on == stream && std::memcmp(a.eye, eye, 12) == 0) return RTX_OK;
     a.valid = false;
-    const uint32_t n = static_cast<uint32_t>(p.nodes.size());
+    const uint32_t n = g.n_nodes;
     RTX_HIP(hipMemsetAsync(a.nodes.as<rtx::NodeDev>() + n, 0, sizeof(rtx::NodeDev), stream));      // the sentinel
-    RTX_HIP(rtxa::launch_aim(g.nodes.as<const rtx::NodeDev>(), n, tree_root(p), eye, a.links.as<rtxa::AimLink>(),
+    RTX_HIP(rtxa::launch_aim(g.nodes.as<const rtx::NodeDev>(), n, tree_root(p, n), eye, a.links.as<rtxa::AimLink>(),
                              a.nodes.as<rtx::NodeDev>(), stream));
     std::memcpy(a.eye, eye, 12);
     a.on = stream;
@@ -1283,6 +1363,78 @@ int read_back_nodes(const DeviceState &st, const void *d_nodes, size_t n, uint32
         std::memcpy(out + 8u * i, &r, sizeof r);
     }
     return RTX_OK;
+}
+
+// The bodies of rtx_scene_pose / rtx_scene_pose_device and of their _rebuilt twins: everything but the tree is the same.
+int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
+              RtxStats *stats, bool rebuilt)
+{
+    if (!scene || !v0v1v2 || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
+    const rtx::PreparedScene &p = scene->prep;
+    if (!rtx::pose_in_range(p, v0v1v2)) return RTX_ERR_UNSUPPORTED;
+    const Timed timed(stats);
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const size_t n_prims = p.tris.size();
+    const bool want_ref = reference_tree == RTX_REFTREE_ALWAYS || (reference_tree == RTX_REFTREE_AUTO && n_prims <= rtx::kRefTreeAutoMax);
+    std::vector<uint32_t> ref_rank;
+    std::vector<rtx::NodeDev> ref_stream;
+    try {
+        if (want_ref) {
+            std::vector<rtx::NodeRec> stream;
+            if (rebuilt) {      // the leaves name positions of the sorted array: through the host statement's permutation
+                std::vector<uint32_t> perm(n_prims - p.n_global);
+                rtx::rebuilt_records(p, pose_tables_of(scene), rebuild_tables_of(scene), v0v1v2, nullptr, nullptr, perm.data(),
+                                     nullptr, nullptr, nullptr);
+                RTX_TRY(rtx::rebuilt_ref_tree(p, pose_tables_of(scene), v0v1v2, perm.data(), ref_rank, stream));
+            } else {
+                RTX_TRY(rtx::posed_ref_tree(p, pose_tables_of(scene), v0v1v2, ref_rank, stream));
+            }
+            ref_stream = rtx::nodes_in_device_order(stream);
+        }
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    const uint32_t *rank = tie_rank ? tie_rank : (want_ref ? ref_rank.data() : nullptr);
+    RTX_TRY(reserve_pose(scene, st, true, ref_stream.size(), rebuilt));
+    RTX_TRY(wait_for_uses(st, kUsesPose));      // a device-resident call may still read the pose this one replaces
+    const size_t v_bytes = static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
+    hipError_t he = hipSuccess;
+    if (v_bytes) he = hipMemcpyAsync(st.pose.v.as<void>(), v0v1v2, v_bytes, hipMemcpyHostToDevice, st.stream);
+    if (he == hipSuccess && rank)
+        he = hipMemcpyAsync(st.pose.rank.as<void>(), rank, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
+    if (he == hipSuccess && !ref_stream.empty()) {
+        he = hipMemcpyAsync(st.pose.geo.ref_nodes.as<void>(), ref_stream.data(), ref_stream.size() * sizeof(rtx::NodeDev),
+                            hipMemcpyHostToDevice, st.stream);
+        if (he == hipSuccess)
+            he = hipMemsetAsync(st.pose.geo.ref_nodes.as<rtx::NodeDev>() + ref_stream.size(), 0, sizeof(rtx::NodeDev), st.stream);
+    }
+    int rc = hip_rc(he);
+    if (rc == RTX_OK) rc = timed.begin(st);
+    if (rc == RTX_OK)
+        rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, st.stream, rebuilt);
+    if (rc == RTX_OK) rc = timed.end(st);
+    if (rc != RTX_OK) {
+        st.pose.valid = false;
+        (void)hipStreamSynchronize(st.stream);      // the copies above read the caller's arrays and this call's vectors
+        return rc;
+    }
+    st.pose.geo.n_ref_nodes = static_cast<uint32_t>(ref_stream.size());
+    return timed.gather(st, 0u, 0u);
+}
+
+int pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream, bool rebuilt)
+{
+    if (!scene || !d_v0v1v2) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_v0v1v2) | reinterpret_cast<uintptr_t>(d_tie_rank)) & 3u) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    RTX_TRY(reserve_pose(scene, st, false, 0u, rebuilt));
+    RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank),
+                        static_cast<hipStream_t>(stream), rebuilt));
+    return mark_uses(st, kUsesPose, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -1724,64 +1876,97 @@ int rtx_scene_posed_records(const RtxScene *scene, const float *v0v1v2, const ui
 int rtx_scene_pose(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
                    RtxStats *stats)
 {
-    if (!scene || !v0v1v2 || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
-    const rtx::PreparedScene &p = scene->prep;
-    if (!rtx::pose_in_range(p, v0v1v2)) return RTX_ERR_UNSUPPORTED;
-    const Timed timed(stats);
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    const size_t n_prims = p.tris.size();
-    const bool want_ref = reference_tree == RTX_REFTREE_ALWAYS || (reference_tree == RTX_REFTREE_AUTO && n_prims <= rtx::kRefTreeAutoMax);
-    std::vector<uint32_t> ref_rank;
-    std::vector<rtx::NodeDev> ref_stream;
-    try {
-        if (want_ref) {
-            std::vector<rtx::NodeRec> stream;
-            RTX_TRY(rtx::posed_ref_tree(p, pose_tables_of(scene), v0v1v2, ref_rank, stream));
-            ref_stream = rtx::nodes_in_device_order(stream);
-        }
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    const uint32_t *rank = tie_rank ? tie_rank : (want_ref ? ref_rank.data() : nullptr);
-    RTX_TRY(reserve_pose(scene, st, true, ref_stream.size()));
-    RTX_TRY(wait_for_uses(st, kUsesPose));      // a device-resident call may still read the pose this one replaces
-    const size_t v_bytes = static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
-    hipError_t he = hipSuccess;
-    if (v_bytes) he = hipMemcpyAsync(st.pose.v.as<void>(), v0v1v2, v_bytes, hipMemcpyHostToDevice, st.stream);
-    if (he == hipSuccess && rank)
-        he = hipMemcpyAsync(st.pose.rank.as<void>(), rank, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
-    if (he == hipSuccess && !ref_stream.empty()) {
-        he = hipMemcpyAsync(st.pose.geo.ref_nodes.as<void>(), ref_stream.data(), ref_stream.size() * sizeof(rtx::NodeDev),
-                            hipMemcpyHostToDevice, st.stream);
-        if (he == hipSuccess)
-            he = hipMemsetAsync(st.pose.geo.ref_nodes.as<rtx::NodeDev>() + ref_stream.size(), 0, sizeof(rtx::NodeDev), st.stream);
-    }
-    int rc = hip_rc(he);
-    if (rc == RTX_OK) rc = timed.begin(st);
-    if (rc == RTX_OK) rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, st.stream);
-    if (rc == RTX_OK) rc = timed.end(st);
-    if (rc != RTX_OK) {
-        st.pose.valid = false;
-        (void)hipStreamSynchronize(st.stream);      // the copies above read the caller's arrays and this call's vectors
-        return rc;
-    }
-    st.pose.geo.n_ref_nodes = static_cast<uint32_t>(ref_stream.size());
-    return timed.gather(st, 0u, 0u);
+    return pose_host(scene, device, v0v1v2, tie_rank, reference_tree, stats, false);
 }
 
 int rtx_scene_pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream)
 {
-    if (!scene || !d_v0v1v2) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_v0v1v2) | reinterpret_cast<uintptr_t>(d_tie_rank)) & 3u) return RTX_ERR_BAD_ARG;
+    return pose_device(scene, device, d_v0v1v2, d_tie_rank, stream, false);
+}
+
+int rtx_scene_pose_rebuilt(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
+                           RtxStats *stats)
+{
+    return pose_host(scene, device, v0v1v2, tie_rank, reference_tree, stats, true);
+}
+
+int rtx_scene_pose_rebuilt_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream)
+{
+    return pose_device(scene, device, d_v0v1v2, d_tie_rank, stream, true);
+}
+
+int rtx_scene_rebuilt_counts(const RtxScene *scene, uint32_t *out_n_nodes)
+{
+    if (!scene || !out_n_nodes) return RTX_ERR_BAD_ARG;
+    try {
+        *out_n_nodes = static_cast<uint32_t>(rebuild_tables_of(const_cast<RtxScene *>(scene)).nodes.size());   // (a cache under the scene's lock)
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_scene_rebuilt_records(const RtxScene *scene, const float *v0v1v2, const uint32_t *tie_rank, uint64_t *out_keys,
+                              uint32_t *out_perm, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
+{
+    if (!scene || !v0v1v2) return RTX_ERR_BAD_ARG;
+    try {
+        RtxScene *sc = const_cast<RtxScene *>(scene);      // (the tables are caches under the scene's lock)
+        const rtx::PoseTables &t = pose_tables_of(sc);
+        rtx::rebuilt_records(scene->prep, t, rebuild_tables_of(sc), v0v1v2, tie_rank, out_keys, out_perm,
+                             reinterpret_cast<rtx::TriRec *>(out_tris), reinterpret_cast<rtx::ShadeRec *>(out_shade),
+                             reinterpret_cast<rtx::NodeRec *>(out_nodes));
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_scene_rebuilt_aimed(const RtxScene *scene, const float *v0v1v2, const float eye[3], uint32_t *out_aimed)
+{
+    if (!scene || !v0v1v2 || !eye || !out_aimed) return RTX_ERR_BAD_ARG;
+    try {
+        RtxScene *sc = const_cast<RtxScene *>(scene);      // (the tables are caches under the scene's lock)
+        const rtx::PreparedScene &p = scene->prep;
+        const rtx::RebuildTables &b = rebuild_tables_of(sc);
+        std::vector<rtx::NodeRec> nodes(b.nodes.size());
+        rtx::rebuilt_records(p, pose_tables_of(sc), b, v0v1v2, nullptr, nullptr, nullptr, nullptr, nullptr, nodes.data());
+        if (!p.primary_nodes.empty()) {                    // (a scene that aims nothing: the pose's stream as it is)
+            std::vector<rtx::NodeRec> out;
+            rtx::stream_nearest_first(nodes, tree_root(p, nodes.size()), eye, out);
+            nodes.swap(out);
+        }
+        std::memcpy(out_aimed, nodes.data(), nodes.size() * sizeof(rtx::NodeRec));
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_debug_pose_rebuilt(RtxScene *scene, int device, const float eye[3], uint32_t *out_perm, uint32_t *out_tris,
+                           uint32_t *out_shade, uint32_t *out_nodes, uint32_t *out_aimed)
+{
+    if (!scene || (out_aimed && !eye)) return RTX_ERR_BAD_ARG;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    RTX_TRY(reserve_pose(scene, st, false, 0u));
-    RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank),
-                        static_cast<hipStream_t>(stream)));
-    return mark_uses(st, kUsesPose, static_cast<hipStream_t>(stream));
+    DeviceGeometry *g;
+    RTX_TRY(geometry_of(st, true, &g));
+    if (!st.pose.rebuilt) return RTX_ERR_BAD_ARG;
+    const size_t n_prims = scene->prep.tris.size(), n_tree = n_prims - scene->prep.n_global, n = g->n_nodes;
+    RTX_TRY(wait_for_uses(st, kUsesPose));
+    if (out_perm && n_tree)
+        RTX_HIP(hipMemcpyAsync(out_perm, st.pose.b.perm.as<void>(), n_tree * sizeof(uint32_t), hipMemcpyDeviceToHost, st.stream));
+    if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, g->tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
+    if (out_shade)
+        RTX_HIP(hipMemcpyAsync(out_shade, g->shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
+    RTX_TRY(read_back_nodes(st, g->nodes.as<void>(), n, out_nodes));
+    if (out_aimed && n) {
+        RTX_TRY(reserve_aimed(scene, *g));
+        g->aimed.valid = false;              // the kernels run whatever the buffer holds
+        RTX_TRY(aim_at(scene, *g, eye, st.stream));
+    }
+    return read_back_nodes(st, aimed_stream(scene, *g), n, out_aimed);
 }
 
 int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
@@ -1792,12 +1977,13 @@ int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *ou
     DeviceState &st = e.state();
     DeviceGeometry *g;
     RTX_TRY(geometry_of(st, true, &g));
+    if (st.pose.rebuilt && out_nodes) return RTX_ERR_BAD_ARG;      // sized by the uploaded node count: rtx_debug_pose_rebuilt
     const size_t n_prims = scene->prep.tris.size();
     RTX_TRY(wait_for_uses(st, kUsesPose));
     if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, g->tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
     if (out_shade)
         RTX_HIP(hipMemcpyAsync(out_shade, g->shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
-    return read_back_nodes(st, g->nodes.as<void>(), scene->prep.nodes.size(), out_nodes);
+    return read_back_nodes(st, g->nodes.as<void>(), out_nodes ? scene->prep.nodes.size() : 0u, out_nodes);
 }
 
 int rtx_trace_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
@@ -1916,6 +2102,7 @@ int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uin
     DeviceState &st = e.state();
     DeviceGeometry *g;
     RTX_TRY(geometry_of(st, true, &g));
+    if (st.pose.rebuilt && out_aimed) return RTX_ERR_BAD_ARG;      // sized by the uploaded node count: rtx_debug_pose_rebuilt
     const size_t n = scene->prep.nodes.size(), n_global = scene->prep.n_global;
     RTX_TRY(wait_for_uses(st, kUsesPose));
     if (out_planes && n_global)

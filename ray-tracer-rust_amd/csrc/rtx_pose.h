@@ -39,5 +39,9 @@ struct PoseArgs {
 // records (one workgroup of rtx::kPoseBlock per node) and one for the others (one work-item per node).  No work-item reads
 // a box another workgroup wrote in the same launch.  All on `stream`; nothing is waited for.
 hipError_t launch_pose(const PoseArgs &a, hipStream_t stream);
+// The refit alone, over records something else has put into out_tris on `stream` (rtx_rebuild.hip: a rebuilt pose's sorted
+// records): nodes, ranges, order, n_long and n_nodes are then the rebuilt stream's tables.  Reads nodes (link and info),
+// ranges, order and out_tris; writes out_nodes.
+hipError_t launch_refit(const PoseArgs &a, hipStream_t stream);
 
 }  // namespace rtxp

@@ -101,6 +101,17 @@ __global__ void __launch_bounds__(kPoseBlock) refit_long_kernel(PoseArgs a)
     write_node(a, i, lo, hi);
 }
 
+hipError_t launch_refit(const PoseArgs &a, hipStream_t stream)
+{
+    if (a.n_prims == 0u || a.n_nodes == 0u) return hipSuccess;
+    if (!a.nodes || !a.ranges || !a.order || !a.out_tris || !a.out_nodes || a.n_long > a.n_nodes) return hipErrorInvalidValue;
+    if (a.n_long != 0u) hipLaunchKernelGGL(refit_long_kernel, dim3(a.n_long), dim3(kPoseBlock), 0, stream, a);
+    const uint32_t n_short = a.n_nodes - a.n_long;
+    if (n_short != 0u)
+        hipLaunchKernelGGL(refit_short_kernel, dim3((n_short + kPoseBlock - 1u) / kPoseBlock), dim3(kPoseBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_pose(const PoseArgs &a, hipStream_t stream)
 {
     if (a.n_prims == 0u || a.n_nodes == 0u) return hipSuccess;
@@ -108,11 +119,7 @@ hipError_t launch_pose(const PoseArgs &a, hipStream_t stream)
         !a.out_nodes || a.n_long > a.n_nodes)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(pose_records_kernel, dim3((a.n_prims + kPoseBlock - 1u) / kPoseBlock), dim3(kPoseBlock), 0, stream, a);
-    if (a.n_long != 0u) hipLaunchKernelGGL(refit_long_kernel, dim3(a.n_long), dim3(kPoseBlock), 0, stream, a);
-    const uint32_t n_short = a.n_nodes - a.n_long;
-    if (n_short != 0u)
-        hipLaunchKernelGGL(refit_short_kernel, dim3((n_short + kPoseBlock - 1u) / kPoseBlock), dim3(kPoseBlock), 0, stream, a);
-    return hipGetLastError();
+    return launch_refit(a, stream);
 }
 
 }  // namespace rtxp

@@ -738,6 +738,7 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
         s.nodes.clear();
         s.primary_nodes.clear();
         s.nodes.reserve(2 * static_cast<size_t>(n_prims));
+        s.leaf_max = d.leaf_max ? d.leaf_max : 4;          // (a rebuilt pose's: rebuild_tables)
         if (d.accel == RTX_ACCEL_BRUTE) {
             // one leaf per arm (a leaf holds one arm only), under a root when both are present
             auto it = std::stable_partition(prims.begin(), prims.end(), [](const Prim &p) { return p.kind == 0u; });
@@ -981,6 +982,153 @@ int posed_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pos
             const uint32_t prim = nd.info & kLeafIndexMask;
             nd.info = kLeafFlag | (s.shade[prim].kind ? kSphereFlag : 0u) | pos_of[prim];
         }
+    return RTX_OK;
+}
+
+
+// ---- a pose whose tree is rebuilt (scene_prep.h) ---------------------------------------------------------------------------
+
+namespace {
+
+// pre-order, balanced: a run of more than leaf_max records splits at begin + count / 2
+void rebuild_subtree(std::vector<NodeRec> &nodes, std::vector<uint32_t> &ranges, uint32_t begin, uint32_t count, bool sphere,
+                     uint32_t leaf_max)
+{
+    const size_t self = nodes.size();
+    nodes.push_back(NodeRec{});
+    ranges.push_back(begin);
+    ranges.push_back(count);
+    if (count <= leaf_max) {
+        nodes[self].info = kLeafFlag | (sphere ? kSphereFlag : 0u) | begin;
+        nodes[self].link = count;
+        return;
+    }
+    const uint32_t half = count / 2u;
+    rebuild_subtree(nodes, ranges, begin, half, sphere, leaf_max);
+    nodes[self].info = static_cast<uint32_t>(nodes.size());
+    rebuild_subtree(nodes, ranges, begin + half, count - half, sphere, leaf_max);
+    nodes[self].link = static_cast<uint32_t>(nodes.size());
+}
+
+}  // namespace
+
+void rebuild_tables(const PreparedScene &s, RebuildTables &out)
+{
+    const uint32_t n_prims = static_cast<uint32_t>(s.tris.size()), n_global = s.n_global;
+    const uint32_t leaf_max = s.leaf_max ? s.leaf_max : 1u;
+    uint32_t n_spheres = 0;
+    for (uint32_t j = n_global; j < n_prims; ++j) n_spheres += s.shade[s.tris[j].idx].kind != 0u;
+    const uint32_t n_tris = n_prims - n_global - n_spheres;
+    out.n_tree_tris = n_tris;
+    out.n_tree_spheres = n_spheres;
+    out.nodes.clear();
+    out.ranges.clear();
+    auto proper = [&]() {
+        if (n_tris != 0u && n_spheres != 0u) {
+            const size_t self = out.nodes.size();
+            out.nodes.push_back(NodeRec{});
+            out.ranges.push_back(n_global);
+            out.ranges.push_back(n_tris + n_spheres);
+            rebuild_subtree(out.nodes, out.ranges, n_global, n_tris, false, leaf_max);
+            out.nodes[self].info = static_cast<uint32_t>(out.nodes.size());
+            rebuild_subtree(out.nodes, out.ranges, n_global + n_tris, n_spheres, true, leaf_max);
+            out.nodes[self].link = static_cast<uint32_t>(out.nodes.size());
+        } else if (n_tris != 0u) {
+            rebuild_subtree(out.nodes, out.ranges, n_global, n_tris, false, leaf_max);
+        } else if (n_spheres != 0u) {
+            rebuild_subtree(out.nodes, out.ranges, n_global, n_spheres, true, leaf_max);
+        }
+    };
+    if (n_global != 0u) {               // as prepare_scene lays them out: the root, the global leaf, the tree proper
+        NodeRec leaf{};
+        leaf.info = kLeafFlag | 0u;
+        leaf.link = n_global;
+        if (n_global < n_prims) {
+            NodeRec root{};
+            root.info = 2u;
+            out.nodes.push_back(root);
+            out.ranges.push_back(0u);
+            out.ranges.push_back(n_prims);
+            out.nodes.push_back(leaf);
+            out.ranges.push_back(0u);
+            out.ranges.push_back(n_global);
+            proper();
+            out.nodes[0].link = static_cast<uint32_t>(out.nodes.size());
+        } else {
+            out.nodes.push_back(leaf);
+            out.ranges.push_back(0u);
+            out.ranges.push_back(n_global);
+        }
+    } else {
+        proper();
+    }
+    const uint32_t n_nodes = static_cast<uint32_t>(out.nodes.size());
+    out.order.clear();
+    out.order.reserve(n_nodes);
+    for (uint32_t i = 0; i < n_nodes; ++i)
+        if (out.ranges[2u * i + 1u] > kPoseLaneMax) out.order.push_back(i);
+    out.n_long = static_cast<uint32_t>(out.order.size());
+    for (uint32_t i = 0; i < n_nodes; ++i)
+        if (out.ranges[2u * i + 1u] <= kPoseLaneMax) out.order.push_back(i);
+}
+
+void rebuilt_records(const PreparedScene &s, const PoseTables &t, const RebuildTables &b, const float *pose,
+                     const uint32_t *rank, uint64_t *keys, uint32_t *perm, TriRec *tris, ShadeRec *shade, NodeRec *nodes)
+{
+    const size_t n_prims = s.tris.size(), n_global = s.n_global, n_tree = n_prims - n_global;
+    std::vector<TriRec> posed(n_prims);
+    posed_records(s, t, pose, rank, posed.data(), shade, nullptr);
+    const float scale = rebuild_key_scale(s.scene_magnitude);
+    std::vector<uint64_t> key_of(n_tree);
+    for (size_t p = 0; p < n_tree; ++p) {
+        const TriRec &r = posed[n_global + p];
+        key_of[p] = rebuild_key_statement(r.bmin, r.bmax, s.shade[r.idx].kind != 0u, s.scene_magnitude, scale);
+    }
+    std::vector<uint32_t> at(n_tree);
+    for (size_t p = 0; p < n_tree; ++p) at[p] = static_cast<uint32_t>(p);
+    std::stable_sort(at.begin(), at.end(), [&](uint32_t x, uint32_t y) { return key_of[x] < key_of[y]; });
+    std::vector<TriRec> own;
+    if (!tris && nodes) {
+        own.resize(n_prims);
+        tris = own.data();
+    }
+    for (size_t p = 0; p < n_tree; ++p) {
+        if (keys) keys[p] = key_of[at[p]];
+        if (perm) perm[p] = static_cast<uint32_t>(n_global) + at[p];
+    }
+    if (tris) {
+        for (size_t j = 0; j < n_global; ++j) tris[j] = posed[j];
+        for (size_t p = 0; p < n_tree; ++p) tris[n_global + p] = posed[n_global + at[p]];
+    }
+    if (!nodes) return;
+    const float inf = std::numeric_limits<float>::infinity();
+    for (size_t i = 0; i < b.nodes.size(); ++i) {
+        NodeRec n = b.nodes[i];
+        const uint32_t first = b.ranges[2u * i], count = b.ranges[2u * i + 1u];
+        for (int k = 0; k < 3; ++k) {
+            float lo = inf, hi = -inf;
+            for (uint32_t j = first; j < first + count; ++j) {
+                lo = fminf(lo, tris[j].bmin[k]);
+                hi = fmaxf(hi, tris[j].bmax[k]);
+            }
+            n.bmin[k] = lo - s.cull_delta;
+            n.bmax[k] = hi + s.cull_delta;
+        }
+        nodes[i] = n;
+    }
+}
+
+int rebuilt_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *perm,
+                     std::vector<uint32_t> &rank, std::vector<NodeRec> &stream)
+{
+    const int rc = posed_ref_tree(s, t, pose, rank, stream);      // its leaves name positions of the uploaded array
+    if (rc != RTX_OK) return rc;
+    const size_t n_prims = s.tris.size(), n_global = s.n_global;
+    std::vector<uint32_t> sorted_of(n_prims);
+    for (size_t j = 0; j < n_global; ++j) sorted_of[j] = static_cast<uint32_t>(j);
+    for (size_t p = 0; p + n_global < n_prims; ++p) sorted_of[perm[p]] = static_cast<uint32_t>(n_global + p);
+    for (NodeRec &nd : stream)
+        if (nd.info & kLeafFlag) nd.info = (nd.info & ~kLeafIndexMask) | sorted_of[nd.info & kLeafIndexMask];
     return RTX_OK;
 }
 

@@ -222,6 +222,7 @@ struct PreparedScene {
     // what shaft_delta is folded from beside the light boxes: the largest coordinate magnitude of the scene and the eye
     // (shaft_delta_of; a call's light folds its own boxes onto it)
     float scene_magnitude = 0.0f;
+    uint32_t leaf_max = 4;   // records a leaf of a tree built for this scene may hold (RtxSceneDesc.leaf_max, 0: 4)
     uint32_t n_global = 0;   // > 0: records [0, n_global) are the "global" triangles, stream = root, their leaf, the tree proper
     // one per global triangle, in TriRec clothing: v0 = v0, e1 = fl(e1 x e2), e2 = (|e1| x |e2| with plus signs, rounded
     // up), bmin[0] = the denominator's error allowance — what rtx_traverse.hpp: plane_rules_out needs
@@ -309,5 +310,57 @@ void posed_records(const PreparedScene &s, const PoseTables &t, const float *pos
 // its stream, the leaves naming positions of the primitive array as PreparedScene::ref_nodes' do.
 int posed_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, std::vector<uint32_t> &rank,
                    std::vector<NodeRec> &stream);
+
+
+// ---- a pose whose tree is rebuilt (rtx_scene_pose_rebuilt; the kernels: rtx_rebuild.hip) ----
+// The records of the tree proper — [n_global, n_prims) of the uploaded array — are sorted by a 64-bit key of their posed
+// own boxes, and a balanced tree is laid over the sorted runs.  Its shape depends on n_global, the two run lengths and
+// leaf_max alone, so every word of link / info, every node's (first, count) and the refit kernels' order are made once per
+// scene (rebuild_tables); only the permutation, the records and the boxes (the refit kernels' fold) are per pose.
+constexpr uint32_t kRebuildCellBits = 21u;
+constexpr uint32_t kRebuildCellMax = (1u << kRebuildCellBits) - 1u;
+// S of rebuild_key_statement for the pose bound M: 2^21 / (2 M), rounded to f32 once
+inline float rebuild_key_scale(float bound) { return static_cast<float>(2097152.0 / (2.0 * static_cast<double>(bound))); }
+// The key of a record from its own (posed) box: bit 63 the arm (1: sphere), bits 62..0 the Morton interleave of the cells
+// of the box centre, x in the highest bit of every triple.  c = 0.5f * (bmin + bmax); cell = (uint32)((c + M) * S) held to
+// [0, 2^21 - 1], a NaN to 0.  One text for both compilers, as triangle_statement is: rebuilt_records on the host,
+// rtxb::key_kernel (rtx_rebuild.hip) on the device; two additions and two multiplications, each rounded once.
+RTX_HOST_DEVICE inline uint64_t rebuild_key_statement(const float bmin[3], const float bmax[3], bool sphere, float bound,
+                                                      float scale)
+{
+    uint64_t key = sphere ? 1ull << 63 : 0ull;
+    for (int k = 0; k < 3; ++k) {
+        const float c = 0.5f * (bmin[k] + bmax[k]);
+        const float f = (c + bound) * scale;
+        uint32_t q = 0u;                                   // (a NaN, and anything below the frame)
+        if (f >= 2097151.0f) q = kRebuildCellMax;
+        else if (f >= 0.0f) q = static_cast<uint32_t>(f);
+        uint64_t x = q;                                    // 21 bits, two zeros between each
+        x = (x | x << 32) & 0x1F00000000FFFFull;
+        x = (x | x << 16) & 0x1F0000FF0000FFull;
+        x = (x | x << 8) & 0x100F00F00F00F00Full;
+        x = (x | x << 4) & 0x10C30C30C30C30C3ull;
+        x = (x | x << 2) & 0x1249249249249249ull;
+        key |= x << (2 - k);
+    }
+    return key;
+}
+struct RebuildTables {
+    std::vector<NodeRec>  nodes;       // the rebuilt stream's link and info; the boxes are zero
+    std::vector<uint32_t> ranges;      // n_nodes x {first, count}, positions of the SORTED primitive array
+    std::vector<uint32_t> order;       // as PoseTables::order
+    uint32_t n_long = 0;
+    uint32_t n_tree_tris = 0, n_tree_spheres = 0;      // the two runs of the tree proper
+};
+void rebuild_tables(const PreparedScene &s, RebuildTables &out);
+// The host statement of a rebuilt pose.  keys, perm: one per record of the tree proper, in sorted order; perm[p] is the
+// position in the uploaded array of the record that sorted position n_global + p holds (std::stable_sort by key: equal
+// keys keep uploaded order).  tris: n_prims records in sorted order; shade: n_prims in Vec order, as posed_records makes
+// them; nodes: the rebuilt stream in NodeRec's word order, the planes moved outwards by cull_delta.  Each may be NULL.
+void rebuilt_records(const PreparedScene &s, const PoseTables &t, const RebuildTables &b, const float *pose,
+                     const uint32_t *rank, uint64_t *keys, uint32_t *perm, TriRec *tris, ShadeRec *shade, NodeRec *nodes);
+// posed_ref_tree with its leaves naming positions of the SORTED primitive array (perm: rebuilt_records')
+int rebuilt_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *perm,
+                     std::vector<uint32_t> &rank, std::vector<NodeRec> &stream);
 
 }  // namespace rtx

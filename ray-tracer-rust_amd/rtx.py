@@ -203,6 +203,12 @@ _SIGS = {
                                                     C.c_size_t, C.c_void_p, C.c_void_p]),
     "rtx_scene_posed_pipeline_records": (C.c_int, [C.c_void_p, f32p, f32p, u32p, u32p]),
     "rtx_debug_pose_pipeline": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, u32p]),
+    "rtx_scene_pose_rebuilt": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, C.c_uint32, C.POINTER(Stats)]),
+    "rtx_scene_pose_rebuilt_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_scene_rebuilt_counts": (C.c_int, [C.c_void_p, u32p]),
+    "rtx_scene_rebuilt_records": (C.c_int, [C.c_void_p, f32p, u32p, C.POINTER(C.c_uint64), u32p, u32p, u32p, u32p]),
+    "rtx_scene_rebuilt_aimed": (C.c_int, [C.c_void_p, f32p, f32p, u32p]),
+    "rtx_debug_pose_rebuilt": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, u32p, u32p, u32p, u32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -856,6 +862,63 @@ class Scene:
                                             planes.ctypes.data_as(u32p), aimed.ctypes.data_as(u32p) if eye is not None else None),
                "rtx_debug_pose_pipeline")
         return planes, (aimed if eye is not None else None)
+
+    # -- a pose whose tree is rebuilt on the device: every posed= call then runs over it unchanged
+    def pose_rebuilt(self, v0v1v2, device=0, tie_rank=None, reference_tree=REFTREE_NEVER, stats=False):
+        """pose() with the tree rebuilt on the device: the tree proper's records sorted by Morton key, a balanced tree over
+        the sorted runs, boxes by the refit kernels (rtx_scene_pose_rebuilt).  stats: kernel_ms is the kernels' time."""
+        v, rank = self._pose_arrays(v0v1v2, tie_rank)
+        st = Stats()
+        _check(_lib.rtx_scene_pose_rebuilt(self._h, device, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
+                                           int(reference_tree), C.byref(st) if stats else None), "rtx_scene_pose_rebuilt")
+        return st.asdict() if stats else None
+
+    def pose_rebuilt_device(self, device, d_v0v1v2_ptr, d_tie_rank_ptr=None, stream=None):
+        """Asynchronous rebuilt pose from device arrays the caller owns (n_tris x 9 float32; n_prims uint32 or None)."""
+        _check(_lib.rtx_scene_pose_rebuilt_device(self._h, device, C.c_void_p(d_v0v1v2_ptr),
+                                                  C.c_void_p(d_tie_rank_ptr) if d_tie_rank_ptr else None,
+                                                  C.c_void_p(stream) if stream else None), "rtx_scene_pose_rebuilt_device")
+
+    def rebuilt_counts(self):
+        """Node records of the rebuilt stream (rtx_scene_rebuilt_counts)."""
+        out = C.c_uint32(0)
+        _check(_lib.rtx_scene_rebuilt_counts(self._h, C.byref(out)), "rtx_scene_rebuilt_counts")
+        return int(out.value)
+
+    def _rebuilt_outputs(self):
+        n_tree = self.n_prims - self.info()["n_global"]
+        return (np.zeros(n_tree, np.uint32), np.zeros((self.n_prims, 16), np.uint32), np.zeros((self.n_prims, 8), np.uint32),
+                np.zeros((self.rebuilt_counts(), 8), np.uint32))
+
+    def rebuilt_records(self, v0v1v2, tie_rank=None):
+        """Host only: the words a rebuilt pose makes -> (keys uint64 [n_tree], perm uint32 [n_tree] — positions of the
+        uploaded primitive array in sorted order —, tris uint32 [n_prims, 16] in sorted order, shade uint32 [n_prims, 8] in
+        Vec order, nodes uint32 [rebuilt_counts(), 8] with the planes moved by cull_delta)."""
+        v, rank = self._pose_arrays(v0v1v2, tie_rank)
+        perm, t, s, n = self._rebuilt_outputs()
+        keys = np.zeros(len(perm), np.uint64)
+        _check(_lib.rtx_scene_rebuilt_records(self._h, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
+                                              keys.ctypes.data_as(C.POINTER(C.c_uint64)), perm.ctypes.data_as(u32p),
+                                              t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)),
+               "rtx_scene_rebuilt_records")
+        return keys, perm, t, s, n
+
+    def rebuilt_aimed(self, v0v1v2, eye):
+        """Host only: the aim kernels' output over the rebuilt pose for `eye` -> uint32 [rebuilt_counts(), 8]."""
+        v, _ = self._pose_arrays(v0v1v2, None)
+        aimed = np.zeros((self.rebuilt_counts(), 8), np.uint32)
+        _check(_lib.rtx_scene_rebuilt_aimed(self._h, _fp(v), _fp(_f3(eye)), aimed.ctypes.data_as(u32p)), "rtx_scene_rebuilt_aimed")
+        return aimed
+
+    def debug_pose_rebuilt(self, eye=None, device=0):
+        """Diagnostics: the rebuilt pose `device` holds, copied back -> (perm, tris, shade, nodes, aimed or None without an
+        eye), in rebuilt_records' layout; aimed: the aim kernels run over it for `eye`."""
+        perm, t, s, n = self._rebuilt_outputs()
+        aimed = np.zeros_like(n)
+        _check(_lib.rtx_debug_pose_rebuilt(self._h, device, _fp(_f3(eye)) if eye is not None else None, perm.ctypes.data_as(u32p),
+                                           t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p),
+                                           aimed.ctypes.data_as(u32p) if eye is not None else None), "rtx_debug_pose_rebuilt")
+        return perm, t, s, n, (aimed if eye is not None else None)
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
