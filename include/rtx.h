@@ -635,6 +635,37 @@ int rtx_launch_timings(RtxScene *scene, int device, int max_launches, float *sch
  * cut), reserved}.  Call with out == NULL to get the count.  Blocks until the device is idle.  Returns the number of
  * tiles written (<= max_tiles) or a negative RtxError. */
 int rtx_debug_tile_descs(RtxScene *scene, int device, uint32_t *out, size_t max_tiles);
+/* Diagnostics: what the scheduling pass of the most recent launch on `device` left beside the descriptors, in
+ * rtx_debug_tile_descs' tile numbering: out_hits, 64 x 12 words per tile (a tile's compacted hit records, or their compact
+ * form when the descriptor's flags say so; words no hit of that launch wrote hold what earlier launches left), and
+ * out_pix_slots, 64 words per tile (the hit record of each pixel, 0xFFFFFFFF: none; written for tiles with a hit).  Either
+ * may be NULL; both NULL: the tile count.  Blocks until the device is idle.  Returns the tiles written or a negative RtxError. */
+int rtx_debug_probe_records(RtxScene *scene, int device, uint32_t *out_hits, uint32_t *out_pix_slots, size_t max_tiles);
+
+/* The long primary walks.  rtx_scene_create predicts, per 8 x 8 pixel tile of the scene's own frame (tile t = tile_y *
+ * ceil(width / 8) + tile_x), how much of the primary rays' stream the tile's rays can pass: the weight of the records whose
+ * stored box meets the frustum of the eye and the tile's pixels (widened by the sample table's range and one pixel), an
+ * inner record 1, a leaf 1 + 3 x its primitive records.  Tiles of at least the threshold weight form the long list,
+ * costliest first, at most min(tiles / 32, 1024); a list of fewer than 8 tiles is dropped.  The scheduling pass starts those tiles first, a workgroup each, and
+ * walks their primary rays as four 4 x 4 pixel beams.  An ordering hint: every byte is what it is without it.  It applies
+ * to rtx_render_rows, rtx_render_frame and rtx_render_tiles_device where the launch's tiles are tiles of the frame (the
+ * share starts on a multiple of 8 rows and, unless it is one band, tile_rows is a multiple of 8); not to scenes of more
+ * than 2^16 stream records, not to launches of more than 65,536 tiles (whose scheduling pass is bound by throughput), not
+ * to the view calls and not to posed geometry.
+ * rtx_scene_probe_long: host only; copies up to max_entries tile numbers and weights (either may be NULL; both NULL: the
+ *   count) and the threshold; returns the entries written.
+ * rtx_scene_probe_tile: host only; the weight of one tile and, out_met != NULL, one byte per record of
+ *   rtx_scene_primary_nodes' stream, 1 where the tile's frustum meets the record (the root and the global triangles' leaf,
+ *   which every walk takes untested, always).  Returns 1, or 0 when the scene predicts nothing (*out_weight = 0).  A call
+ *   for tests: each one sets the stream's boxes up anew (time linear in the stream, whatever the tile).
+ * rtx_debug_probe_split: for tests and A/B runs.  mode 0: the prediction (default); 1: no tile is long; 2: every tile of
+ *   the frame is long.  Holds for the scene's later launches.  Returns the number of long-list workgroups the scene's most
+ *   recent pipeline launch was handed (0: it ran one wavefront per tile throughout), or a negative RtxError. */
+int rtx_scene_probe_long(const RtxScene *scene, uint32_t *out_tiles, uint32_t *out_weights, size_t max_entries,
+                         uint32_t *out_threshold);
+int rtx_scene_probe_tile(const RtxScene *scene, uint32_t tile_x, uint32_t tile_y, uint8_t *out_met /* n_nodes */,
+                         uint32_t *out_weight);
+int rtx_debug_probe_split(RtxScene *scene, uint32_t mode);
 
 const char *rtx_strerror(int err);
 int rtx_last_hip_error(void);

@@ -279,6 +279,15 @@ extern "C" {
                                 out_boxes: *mut f32) -> c_int;
     pub fn rtx_launch_timings(scene: *mut RtxScene, device: c_int, max_launches: c_int, schedule_ms: *mut f32,
                               shade_ms: *mut f32) -> c_int;
+    /// The long primary walks (include/rtx.h): the scene's long list, one tile's weight and met records, and the
+    /// debug switch (0 = predicted, 1 = no tile long, 2 = every tile long).
+    pub fn rtx_scene_probe_long(scene: *const RtxScene, out_tiles: *mut u32, out_weights: *mut u32, max_entries: usize,
+                                out_threshold: *mut u32) -> c_int;
+    pub fn rtx_scene_probe_tile(scene: *const RtxScene, tile_x: u32, tile_y: u32, out_met: *mut u8,
+                                out_weight: *mut u32) -> c_int;
+    pub fn rtx_debug_probe_split(scene: *mut RtxScene, mode: u32) -> c_int;
+    pub fn rtx_debug_probe_records(scene: *mut RtxScene, device: c_int, out_hits: *mut u32, out_pix_slots: *mut u32,
+                                   max_tiles: usize) -> c_int;
     pub fn rtx_strerror(err: c_int) -> *const c_char;
     pub fn rtx_last_hip_error() -> c_int;
     pub fn rtxh_scatter_tiles(frame: *mut u8, height: u32, width: u32, packed: *const u8, first_tile: u32,

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <atomic>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -185,6 +186,10 @@ public:
     // primary_nodes: the scene's own eye's stream, which only the calls that render the scene's own view walk
     DeviceGeometry geo;
     DeviceBuffer primary_nodes, samples, lights, light_tour, thr, light_boxes;
+    // the scene's long list as probe_kernel reads it (rtx::ProbeSplit: the tiles, then the bits), uploaded with the scene
+    // when it predicts any; long_all: every tile of the frame listed (rtx_debug_probe_split, mode 2), made at first use
+    DeviceBuffer long_words, long_all;
+    uint32_t n_long_all = 0;
     DeviceBuffer d_out, d_counters;
     DeviceBuffer d_redo;                 // queue of tiles for reference_tiles_kernel
     // The two-pass pipeline zeroes its counting words (d_redo's headers, ws.buckets) for the NEXT launch inside each
@@ -293,6 +298,9 @@ struct RtxScene {
     rtx::RebuildTables rebuild_tables;   // made by the first call that asks for a rebuilt pose (rebuild_tables_of), under mu
     bool rebuild_tables_made = false;
     std::map<int, DeviceSlot> dev;
+    // rtx_debug_probe_split: which tiles the scheduling pass treats as long (0: the prediction), and how many workgroups of
+    // the long list the scene's most recent pipeline launch was handed
+    std::atomic<uint32_t> split_mode{0u}, last_long{0u};
 };
 
 namespace {
@@ -368,6 +376,11 @@ int upload_all(RtxScene *scene, DeviceState &st)
     if ((rc = upload_vec(st.light_tour, p.light_tour)) != RTX_OK) return rc;
     if (!p.global_planes.empty() && (rc = upload_vec(g.planes, p.global_planes)) != RTX_OK) return rc;
     if ((rc = upload_vec(st.light_boxes, p.light_boxes)) != RTX_OK) return rc;
+    if (!p.long_tiles.empty()) {
+        std::vector<uint32_t> words(p.long_tiles);
+        words.insert(words.end(), p.long_bits.begin(), p.long_bits.end());
+        if ((rc = upload_vec(st.long_words, words)) != RTX_OK) return rc;
+    }
     if ((rc = st.thr.reserve(sizeof(p.gamma_thr))) != RTX_OK) return rc;
     RTX_HIP(hipMemcpy(st.thr.as<void>(), p.gamma_thr, sizeof(p.gamma_thr), hipMemcpyHostToDevice));
     if ((rc = st.d_counters.reserve(rtx::kNumCounters * sizeof(unsigned long long))) != RTX_OK) return rc;
@@ -561,9 +574,11 @@ struct Timed {
 // profile (d_wave_prof, ablation build) is the fused kernel's: no workspace, no slot.  Caller holds the slot's lock and
 // has the device current and the scene uploaded.  The redo queue is library-owned per device: launches on one device
 // must be ordered on one stream.
+// split: the long list of the scene's own view (probe_split_of), or none.
 template <class Before>
 int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpec &ts, uint8_t *d_out,
-                  unsigned long long *d_counters, unsigned long long *d_wave_prof, hipStream_t stream, Before before)
+                  unsigned long long *d_counters, unsigned long long *d_wave_prof, hipStream_t stream, Before before,
+                  const rtx::ProbeSplit &split = rtx::ProbeSplit{nullptr, 0u, 0u, 0u})
 {
     int rc;
     const size_t redo_cap = st.d_redo.capacity(), buckets_cap = st.ws.buckets.capacity();
@@ -581,13 +596,46 @@ int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpe
     }
     if (ts.local_rows) st.launch_words_ready = false;     // until this launch is known to have gone out whole
     RTX_HIP(rtx::launch_trace_shade(S, ts, d_out, st.d_redo.as<uint32_t>(), use_ws ? &ws : nullptr, d_counters, d_wave_prof,
-                                    kernel_variant(), stream, d_wave_prof ? nullptr : phases, st.words_launches, st.words_passes));
+                                    kernel_variant(), stream, d_wave_prof ? nullptr : phases, st.words_launches, st.words_passes, split));
     if (two_pass) {
         st.launch_words_ready = true;
         ++st.words_launches;
         st.words_passes += S.nb_ray;
     }
     if (!d_wave_prof && ts.local_rows) ++st.launches;
+    return RTX_OK;
+}
+
+// The long list a launch of the scene's own view over its uploaded geometry is handed (rtx_render_rows, rtx_render_frame,
+// rtx_render_tiles_device), by the scene's mode: the prediction, none, or every tile of the frame.  None as well where
+// the launcher would drop it (probe_split_applies): the whole-stream form, a share whose tiles are not the frame's, a launch of
+// more than 65,536 tiles.  The view calls and the
+// posed ones never ask: their stream is aimed from another eye, their boxes are not the ones the prediction weighed.
+// Records what it answers (rtx_debug_probe_split).  Caller holds the slot's lock and has the device current and the scene
+// uploaded.
+int probe_split_of(RtxScene *scene, DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpec &ts, rtx::ProbeSplit *out)
+{
+    *out = rtx::ProbeSplit{nullptr, 0u, 0u, 0u};
+    scene->last_long = 0u;
+    const uint32_t mode = scene->split_mode;
+    if (mode == 1u || !rtx::probe_split_applies(S, ts)) return RTX_OK;
+    if (mode == 2u) {
+        if (!st.n_long_all) {
+            const uint32_t n = ((S.width + 7u) / 8u) * ((S.height + 7u) / 8u);
+            std::vector<uint32_t> words(n + (n + 31u) / 32u, 0xFFFFFFFFu);
+            for (uint32_t t = 0; t < n; ++t) words[t] = t;
+            RTX_TRY(upload_vec(st.long_all, words));
+            st.n_long_all = n;
+        }
+        const uint32_t tx = (S.width + 7u) / 8u, ty = (S.height + 7u) / 8u;
+        if (tx - 1u <= 0xFFFFu && ty - 1u <= 0xFFFFu)
+            *out = rtx::ProbeSplit{st.long_all.as<const uint32_t>(), st.n_long_all, (tx - 1u) << 16, (ty - 1u) << 16};
+    } else if (!scene->prep.long_tiles.empty()) {
+        const std::vector<uint32_t> &tiles = scene->prep.long_tiles;
+        rtx::ProbeSplit listed{st.long_words.as<const uint32_t>(), static_cast<uint32_t>(tiles.size()), 0u, 0u};
+        if (rtx::probe_split_ranges(tiles.data(), listed.n_long, (S.width + 7u) / 8u, &listed)) *out = listed;
+    }
+    scene->last_long = out->n_long;
     return RTX_OK;
 }
 
@@ -599,8 +647,11 @@ int launch_on(RtxScene *scene, DeviceSlot &slot, const rtx::TileSpec &ts, const 
     DeviceState &st = *slot.st;
     const size_t bytes = static_cast<size_t>(ts.local_rows) * scene->prep.width * 3u;
     RTX_TRY(st.d_out.reserve(bytes ? bytes : 16));
-    RTX_TRY(render_launch(st, device_scene(scene, st, st.geo), ts, st.d_out.as<uint8_t>(), timed.counters(st), nullptr, st.stream,
-                          [&] { return timed.begin(st); }));
+    const rtx::DeviceScene S = device_scene(scene, st, st.geo);
+    rtx::ProbeSplit split;
+    RTX_TRY(probe_split_of(scene, st, S, ts, &split));
+    RTX_TRY(render_launch(st, S, ts, st.d_out.as<uint8_t>(), timed.counters(st), nullptr, st.stream,
+                          [&] { return timed.begin(st); }, split));
     return timed.end(st);
 }
 
@@ -1245,6 +1296,7 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const 
     S.distance = v.distance;
     S.primary_nodes = aimed_stream(scene, g);
     const rtx::TileSpec ts{v.y0, v.ny, v.ny, v.ny};
+    scene->last_long = 0u;      // (a view's launch is handed no long list: probe_split_of)
     return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
         RTX_TRY(before());
         RTX_TRY(aim_at(scene, g, v.eye, stream));
@@ -1656,9 +1708,12 @@ int rtx_render_tiles_device(RtxScene *scene, int device, uint32_t first_tile, ui
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     const rtx::TileSpec ts{first_tile * tile_rows, tile_rows, tile_stride * tile_rows, rows};
-    return render_launch(e.state(), device_scene(scene, e.state(), e.state().geo), ts, static_cast<uint8_t *>(d_out_rgb),
+    const rtx::DeviceScene S = device_scene(scene, e.state(), e.state().geo);
+    rtx::ProbeSplit split;
+    RTX_TRY(probe_split_of(scene, e.state(), S, ts, &split));
+    return render_launch(e.state(), S, ts, static_cast<uint8_t *>(d_out_rgb),
                          reinterpret_cast<unsigned long long *>(d_counters), nullptr, static_cast<hipStream_t>(stream),
-                         [] { return static_cast<int>(RTX_OK); });
+                         [] { return static_cast<int>(RTX_OK); }, split);
 }
 
 int rtx_trace_rays(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
@@ -2166,6 +2221,51 @@ int rtx_debug_tile_descs(RtxScene *scene, int device, uint32_t *out, size_t max_
     RTX_HIP(hipDeviceSynchronize());
     if (n) RTX_HIP(hipMemcpy(out, st.ws.tiles.as<void>(), n * sizeof(rtx::TileDesc), hipMemcpyDeviceToHost));
     return static_cast<int>(n);
+}
+
+int rtx_debug_probe_records(RtxScene *scene, int device, uint32_t *out_hits, uint32_t *out_pix_slots, size_t max_tiles)
+{
+    if (!scene) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kLocked);
+    if (e.rc != RTX_OK) return e.rc;
+    const DeviceState &st = e.state();
+    if (!out_hits && !out_pix_slots) return static_cast<int>(st.last_tiles);
+    const int rc = e.make_current();
+    if (rc != RTX_OK) return rc;
+    const size_t n = st.last_tiles < max_tiles ? st.last_tiles : max_tiles;
+    RTX_HIP(hipDeviceSynchronize());
+    if (n && out_hits) RTX_HIP(hipMemcpy(out_hits, st.ws.hits.as<void>(), n * 64u * sizeof(rtx::HitRec), hipMemcpyDeviceToHost));
+    if (n && out_pix_slots) RTX_HIP(hipMemcpy(out_pix_slots, st.ws.pix_slot.as<void>(), n * 64u * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return static_cast<int>(n);
+}
+
+int rtx_debug_probe_split(RtxScene *scene, uint32_t mode)
+{
+    if (!scene || mode > 2u) return RTX_ERR_BAD_ARG;
+    scene->split_mode = mode;
+    return static_cast<int>(scene->last_long.load());
+}
+
+int rtx_scene_probe_long(const RtxScene *scene, uint32_t *out_tiles, uint32_t *out_weights, size_t max_entries, uint32_t *out_threshold)
+{
+    if (!scene) return RTX_ERR_BAD_ARG;
+    const rtx::PreparedScene &p = scene->prep;
+    const size_t n = p.long_tiles.size() < max_entries ? p.long_tiles.size() : max_entries;
+    if (out_tiles && n) std::memcpy(out_tiles, p.long_tiles.data(), n * sizeof(uint32_t));
+    if (out_weights && n) std::memcpy(out_weights, p.long_weights.data(), n * sizeof(uint32_t));
+    if (out_threshold) *out_threshold = rtx::kProbeLongWeight;
+    return static_cast<int>(out_tiles || out_weights ? n : p.long_tiles.size());
+}
+
+int rtx_scene_probe_tile(const RtxScene *scene, uint32_t tile_x, uint32_t tile_y, uint8_t *out_met, uint32_t *out_weight)
+{
+    if (!scene || !out_weight) return RTX_ERR_BAD_ARG;
+    const rtx::PreparedScene &p = scene->prep;
+    if (tile_x >= (p.width + 7u) / 8u || tile_y >= (p.height + 7u) / 8u) return RTX_ERR_BAD_ARG;
+    if (out_met) std::memset(out_met, 0, p.nodes.size());
+    bool valid = false;
+    *out_weight = rtx::probe_tile_weight(p, tile_x, tile_y, out_met, &valid);
+    return valid ? 1 : 0;
 }
 
 int rtx_launch_timings(RtxScene *scene, int device, int max_launches, float *schedule_ms, float *shade_ms)

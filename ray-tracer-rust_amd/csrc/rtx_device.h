@@ -49,6 +49,33 @@ struct DeviceScene {
     uint32_t j1_mode;              // librtx_ablation.so only (RTX_J1, rtx_j1_ablation.hpp): 0 = the shipped pipeline; librtx.so: 0
 };
 constexpr uint32_t kCutMaxNodes = 1u << 16;
+static_assert(kCutMaxNodes == kProbeSplitMaxNodes, "a scene predicts long tiles exactly when it cuts per tile");
+
+// The scene's prediction of its long primary walks (PreparedScene::long_tiles, long_bits) on the device: n_long tile
+// numbers of the scene's own frame, costliest first, then a bit per frame tile.  probe_kernel's argument alone, behind its
+// others, and not a field of DeviceScene: the block every kernel is handed keeps its layout, and with it every other
+// kernel its code.  n_long = 0 (words is not read): the pass runs one wavefront per tile throughout.  x_range, y_range:
+// the rectangle of frame tiles around the listed ones, lowest | highest << 16 (probe_split_ranges): a tile outside it does
+// not look its bit up.
+struct ProbeSplit {
+    const uint32_t *words;
+    uint32_t n_long;
+    uint32_t x_range, y_range;
+};
+// fills x_range and y_range for a list of n frame tile numbers; false (nothing split) when a tile coordinate needs more than 16 bits
+inline bool probe_split_ranges(const uint32_t *tiles, uint32_t n, uint32_t tiles_x, ProbeSplit *out)
+{
+    uint32_t x0 = 0xFFFFu, x1 = 0u, y0 = 0xFFFFu, y1 = 0u;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t y = tiles[i] / tiles_x, x = tiles[i] - y * tiles_x;
+        if (x > 0xFFFFu || y > 0xFFFFu) return false;
+        x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1;
+        y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
+    }
+    out->x_range = x0 | x1 << 16;
+    out->y_range = y0 | y1 << 16;
+    return n != 0u;
+}
 
 // Which rows a launch renders: local row ly (0 <= ly < local_rows) is row
 //   first_row + (ly / tile_rows) * tile_stride_rows + ly % tile_rows
@@ -172,10 +199,32 @@ size_t trace_redo_bytes(const DeviceScene &S, const TileSpec &ts);
 // d_redo and this workspace have served since their counting words were last zeroed (zero_launch_words) — by the caller, when
 // either buffer is allocated or grown and after any other pipeline used them.  Their parities select the queue and the
 // histogram a launch works on.
+// split (two-pass pipeline): the scene's long list for launches that render the scene's own view of its uploaded geometry;
+// the launcher drops it where probe_split_applies says no.
 hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
                               const StreamWorkspace *ws, unsigned long long *d_counters,
                               unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
-                              hipEvent_t *phase_events = nullptr, uint32_t launch_no = 0u, uint32_t pass_no = 0u);
+                              hipEvent_t *phase_events = nullptr, uint32_t launch_no = 0u, uint32_t pass_no = 0u,
+                              const ProbeSplit &split = ProbeSplit{nullptr, 0u, 0u, 0u});
+// Whether a launch's tiles are tiles of the frame, so that the scene's long list names them: the share starts on a tile
+// row, and every band of it but a single one is whole tile rows.  (Otherwise a tile of the launch straddles two of the frame.)
+inline bool tiles_frame_aligned(const TileSpec &ts)
+{
+    return ts.first_row % 8u == 0u && ts.tile_stride_rows != 0u && ts.tile_rows != 0u &&
+           ((ts.tile_rows % 8u == 0u && ts.tile_stride_rows % 8u == 0u) || ts.local_rows <= ts.tile_rows);
+}
+// Whether a launch is handed the scene's long list at all: the scene cuts per tile, the launch's tiles are the frame's, and
+// the scheduling pass is bound by its longest wavefronts, not by throughput — up to kProbeSplitMaxTiles tiles, eight rounds
+// of the device's 8,192 wavefront slots (a 4096 x 4096 frame's 262,144 tiles gain nothing from the list and paid +3.4 %
+// of the pass for it: profiles/r08/e_ab_without_a_list.log).  Measured on either side of it: a 2560 x 1440 frame, 57,600
+// tiles, gains (the pass 0.1003 ... 0.1011 -> 0.0941 ... 0.0946 ms); a 3840 x 2160 one, 129,600 tiles, would lose (0.1514 ...
+// 0.1525 -> 0.1574 ... 0.1588); where between the two the sign changes is not measured (profiles/r08/h_ab_rectangle_gate_c5.log).
+constexpr uint32_t kProbeSplitMaxTiles = 65536u;
+inline bool probe_split_applies(const DeviceScene &S, const TileSpec &ts)
+{
+    const uint64_t tiles = static_cast<uint64_t>((S.width + 7u) / 8u) * ((ts.local_rows + 7u) / 8u);
+    return S.n_nodes <= S.cut_max_nodes && ts.local_rows != 0u && tiles_frame_aligned(ts) && tiles <= kProbeSplitMaxTiles;
+}
 // zeroes those counting words (both queues' headers, the workspace's order words in front of its job list) on `stream`
 hipError_t zero_launch_words(uint32_t *d_redo, const StreamWorkspace &ws, hipStream_t stream);
 

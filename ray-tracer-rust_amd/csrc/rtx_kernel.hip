@@ -146,7 +146,7 @@ float split_share()
 template <bool COUNT, bool FAST, bool SPHERES>
 hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
                         const StreamWorkspace &W, unsigned long long *d_counters, hipStream_t stream, hipEvent_t *ev,
-                        uint32_t launch_no, uint32_t pass_no)
+                        uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split_in)
 {
 #ifndef RTX_SHADE_NW
 #define RTX_SHADE_NW 8
@@ -154,7 +154,6 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
     constexpr int NW = RTX_SHADE_NW;     // wavefronts per workgroup of shade_tiles_kernel
     // the form of the two kernels that have two: per-tile cuts, or — a scene too large for them — the whole stream
     const bool whole = S.n_nodes > S.cut_max_nodes;
-    const auto probe = whole ? probe_kernel<COUNT, FAST, SPHERES, true> : probe_kernel<COUNT, FAST, SPHERES, false>;
     const auto shade = whole ? shade_tiles_kernel<COUNT, FAST, NW, SPHERES, true> : shade_tiles_kernel<COUNT, FAST, NW, SPHERES, false>;
     const uint32_t batch = S.nb_light < kMaxLightBatch ? (S.nb_light ? S.nb_light : 1u) : kMaxLightBatch;
 #if RTX_ABLATION
@@ -164,6 +163,14 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
 #endif
     const uint32_t tiles_x = (S.width + 7u) / 8u, tiles_y = (ts.local_rows + 7u) / 8u;
     const uint32_t n_tiles = numbered_tiles(tiles_x, tiles_y);
+    // The long list, where it applies (rtx_device.h: probe_split_applies).  With a list: its workgroups first, padded to whole
+    // rounds of the XCDs, then one workgroup per four tiles.  Without: one workgroup per tile, in whole runs of 64 tile numbers
+    // over the 8 XCDs.
+    const ProbeSplit split = (split_in.n_long != 0u && split_in.words && probe_split_applies(S, ts)) ? split_in : ProbeSplit{nullptr, 0u, 0u, 0u};
+    const uint32_t probe_waves = split.n_long != 0u ? 4u : 1u;
+    const uint32_t probe_grid = split.n_long != 0u ? ((split.n_long + 7u) & ~7u) + 128u * ((n_tiles + 511u) / 512u) : 512u * ((n_tiles + 511u) / 512u);
+    const auto probe = whole ? probe_kernel<COUNT, FAST, SPHERES, true, 1u>
+                     : split.n_long != 0u ? probe_kernel<COUNT, FAST, SPHERES, false, 4u> : probe_kernel<COUNT, FAST, SPHERES, false, 1u>;
     // persistent grid = what the device keeps resident of the form that is launched (the two forms differ in registers)
     static thread_local int cached_dev = -1, cached_blocks = 0;
     static thread_local size_t cached_lds = 0;
@@ -190,8 +197,8 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
         // one that only counts (the table in front of kOrderList)
         const uint32_t hist_set = (pass_no + r) & 1u;
         const StreamWorkspace Wp = counting_set(W, hist_set);      // what the kernels that count are handed
-        hipLaunchKernelGGL(probe, dim3(512u * ((n_tiles + 511u) / 512u)), dim3(64 * kProbeWaves), 0, stream,   // whole runs of 64 tile numbers, 8 XCDs
-                           S, ts, tiles_x, n_tiles, r, Wp, d_out, queue, d_counters);
+        hipLaunchKernelGGL(probe, dim3(probe_grid), dim3(64 * probe_waves), 0, stream,
+                           S, ts, tiles_x, n_tiles, r, Wp, d_out, queue, d_counters, split);
         if (whole) hipLaunchKernelGGL(count_classes_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, Wp);
         hipLaunchKernelGGL(order_tiles_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, W, grid, split_share(),
                            hist_set, whole ? 0u : grid, queue, next_redo_count);
@@ -246,7 +253,7 @@ StreamWorkspaceBytes stream_workspace_bytes(const DeviceScene &S, const TileSpec
 static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
                                   const StreamWorkspace *ws, unsigned long long *d_counters,
                                   unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream, hipEvent_t *ev,
-                                  uint32_t launch_no, uint32_t pass_no)
+                                  uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split)
 {
     // the two-pass pipeline: launch_probe<COUNT, FAST, SPHERES> for the caller's counters and the scene's primitives
     auto two_pass = [&](auto fast) {
@@ -254,7 +261,7 @@ static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, uint
         const bool count = d_counters != nullptr, spheres = S.n_spheres != 0u;
         const auto launch = count ? (spheres ? launch_probe<true, FAST, true> : launch_probe<true, FAST, false>)
                                   : (spheres ? launch_probe<false, FAST, true> : launch_probe<false, FAST, false>);
-        return launch(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no);
+        return launch(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no, split);
     };
 #if RTX_ABLATION
     if (!((variant & kVariantProbe) && ws && !d_wave_prof))
@@ -269,14 +276,14 @@ static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, uint
 hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
                               const StreamWorkspace *ws, unsigned long long *d_counters,
                               unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
-                              hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no)
+                              hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split)
 {
     if (ts.local_rows == 0) return hipSuccess;
     hipError_t e;
     if (phase_events && (e = hipEventRecord(phase_events[0], stream)) != hipSuccess) return e;
     const bool probe = (variant & kVariantProbe) && ws && !d_wave_prof;
     if (phase_events && !probe && (e = hipEventRecord(phase_events[1], stream)) != hipSuccess) return e;
-    e = launch_dispatch(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream, probe ? phase_events : nullptr, launch_no, pass_no);
+    e = launch_dispatch(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream, probe ? phase_events : nullptr, launch_no, pass_no, split);
     if (e != hipSuccess) return e;
     if (phase_events && (e = hipEventRecord(phase_events[2], stream)) != hipSuccess) return e;
     return hipSuccess;
@@ -295,7 +302,7 @@ hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t 
 #define RTX_SW(x) " " #x "=" RTX_SW_STR(x)
 extern "C" __attribute__((used, visibility("hidden"))) const char rtx_build_switches_text[] = "rtx-build-switches:"
     RTX_SW(RTX_CLAIM_RUN_LOG) RTX_SW(RTX_CUT_DRAW_MIN) RTX_SW(RTX_CUT_UNION_MIN) RTX_SW(RTX_LIGHT_BATCH) RTX_SW(RTX_MAX_CUT)
-    RTX_SW(RTX_PACKED_WAVES_PER_SIMD) RTX_SW(RTX_PROBE_VISIT_SCALE) RTX_SW(RTX_PROBE_WAVES_PER_SIMD)
+    RTX_SW(RTX_PACKED_WAVES_PER_SIMD) RTX_SW(RTX_PROBE_LONG_WEIGHT) RTX_SW(RTX_PROBE_VISIT_SCALE) RTX_SW(RTX_PROBE_WAVES_PER_SIMD)
     RTX_SW(RTX_SHADE_CUT_WAVES_PER_SIMD) RTX_SW(RTX_SHADE_NW) RTX_SW(RTX_SHADE_WAVES_PER_SIMD)
     RTX_SW(RTX_SPLIT_SHARE_PERCENT) RTX_SW(RTX_TILE_PARTS_MAX) RTX_SW(RTX_WAVES_PER_SIMD)
     RTX_SW(RTX_EXPERIMENT_TIMELINE) RTX_SW(RTX_EXPERIMENT_PHASES) RTX_SW(RTX_EXPERIMENT_PROBE_PHASES) RTX_SW(RTX_ABLATION);

@@ -1,5 +1,6 @@
 // rtx_pass_schedule.hpp — the render pipeline's scheduling pass (rtx_kernel.hip): probe_kernel, one wavefront per tile —
 // primary rays, hit records, the tile's cut (its shaft against the tree) and its cost estimate — with what it is made of.
+// The tiles the scene predicts long (ProbeSplit) start first, a workgroup each, their primary rays walked as four beams.
 #pragma once
 #include "rtx_probes.hpp"
 #include "rtx_pass_helpers.hpp"
@@ -44,8 +45,10 @@ constexpr uint32_t kChunkFixedCost = 8u;
 #endif
 // the entry form of a tile's cut (CutEntry, staged in LDS by a job) is read by the ablation library's variants only
 constexpr bool kCutEntriesUsed = RTX_ABLATION != 0;
-// independent wavefronts (tiles) per workgroup of probe_kernel: 1, 4 and 8 measured the same (m_ab_probewaves.log)
-constexpr uint32_t kProbeWaves = 1u;
+// wavefronts per workgroup of probe_kernel, its template parameter WAVES.  1: one tile per workgroup, the form of every
+// launch without a long list.  4: a launch with a long list — four independent tiles, or the four beams of one long tile.
+// (Four tiles per workgroup alone measured the same in round 2, j_ab_probe_tiles_per_workgroup.log; in round 7 it is +1.3 %
+// on the pass of a 4096 x 4096 frame, profiles/r08/e_ab_without_a_list.log: only the launches that gain from the list pay it.)
 // Wavefronts per SIMD probe_kernel's register allocation must allow: a 4096 x 4096 frame's 262,144 one-wavefront workgroups
 // are bound by how many of them are resident (the probing walk of cut tiles brought the kernel to 106 scalar registers: 7)
 #ifndef RTX_PROBE_WAVES_PER_SIMD
@@ -264,47 +267,111 @@ __host__ __device__ inline StreamWorkspace counting_set(StreamWorkspace W, uint3
 
 // WHOLE: the scene does not cut per tile (S.n_nodes > S.cut_max_nodes: shade_tiles_kernel's whole-stream form follows) — an
 // instantiation of its own, so that each carries one probing walk only (the kernel is short of scalar registers)
-template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE>
-__global__ void __launch_bounds__(64 * kProbeWaves, RTX_PROBE_WAVES_PER_SIMD) probe_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
+template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE, uint32_t WAVES>
+__global__ void __launch_bounds__(64 * WAVES, RTX_PROBE_WAVES_PER_SIMD) probe_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
                                                    uint32_t r, StreamWorkspace W, uint8_t *__restrict__ out,
-                                                   uint32_t *__restrict__ queue, unsigned long long *__restrict__ counters)
+                                                   uint32_t *__restrict__ queue, unsigned long long *__restrict__ counters,
+                                                   ProbeSplit split)
 {
     const NodeRec RTX_CONSTANT *nodes = (const NodeRec RTX_CONSTANT *)S.nodes;
     const TriRec RTX_CONSTANT *tris = (const TriRec RTX_CONSTANT *)S.tris;
-    // one wavefront per tile, kProbeWaves independent wavefronts per workgroup (no barrier; LDS only inside shaft_cut_binary
-    // and the probing walk)
-    __shared__ uint32_t l_front_all[kProbeWaves][128];           // the cut's next frontier
-    __shared__ CutEntry l_entries_all[kProbeWaves][kMaxCut];     // the tile's cut in its entry form, for the probing walk
+    // one wavefront per tile, WAVES independent wavefronts per workgroup (no barrier; LDS only inside shaft_cut_binary
+    // and the probing walk) — or, in the workgroups of the long list, the four beams of one tile, one barrier
+    static_assert(WAVES == 1u || WAVES == 4u, "one tile per workgroup, or four tiles / the four beams of a long tile");
+    constexpr bool kSplits = WAVES == 4u;                        // this form is handed a long list
+    __shared__ uint32_t l_front_all[WAVES][128];                 // the cut's next frontier
+    __shared__ CutEntry l_entries_all[WAVES][kMaxCut];           // the tile's cut in its entry form, for the probing walk
+    __shared__ float l_beam_t[kSplits ? 64 : 1];                 // long mode: the four beams' answers, by lane of the tile
+    __shared__ uint32_t l_beam_idx[kSplits ? 64 : 1];
+    __shared__ uint32_t l_beam_ok[WAVES];
 #if RTX_ABLATION
-    __shared__ __align__(16) uint32_t l_j1_block[kProbeWaves][kJ1BlockWords];   // RTX_J1=2: a block of 64 primitive records
+    __shared__ __align__(16) uint32_t l_j1_block[WAVES][kJ1BlockWords];   // RTX_J1=2: a block of 64 primitive records
 #endif
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_in_group = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t *const l_front = l_front_all[wave_in_group];
-    // workgroups b, b + 8, ... share an XCD (MI355X_MICROARCH.md, workgroup dispatch): the XCDs are dealt runs of 64
-    // consecutive tile numbers — one 64 x 64 pixel block each — so that an L2 serves neighbouring tiles' walks.  (One
-    // contiguous eighth of the frame per XCD was 25-35 % slower: the upper half of a frame is sky.)
-    static_assert(kProbeWaves == 1u, "the XCD mapping assumes one tile per workgroup");
-    const uint32_t k = blockIdx.x >> 3;
-    const uint32_t tile_id = ((((k >> 6) << 3) + (blockIdx.x & 7u)) << 6) + (k & 63u);
-    if (tile_id >= n_tiles) return;
-    uint32_t px, py, ly, tile_x, tile_y;
-    tile_xy(tile_id, tiles_x, true, tile_x, tile_y);
+    // Workgroups [0, n_long): the long list in order, costliest first — those tiles start in the kernel's first microsecond.
+    // (Up to seven idle workgroups follow, so that the ordinary ones keep their XCDs.)  An entry is a tile of the FRAME; a
+    // launch that renders a share of the rows finds the tile among its own or leaves (the launcher hands a list only to
+    // launches whose tiles are the frame's: rtx_kernel.hip, launch_probe).
+    const uint32_t n_long = kSplits ? split.n_long : 0u, long_groups = (n_long + 7u) & ~7u;
+    const bool long_mode = kSplits && blockIdx.x < n_long;
+    uint32_t tile_id, tile_x, tile_y;
+    if (long_mode) {
+        const uint32_t entry = __builtin_amdgcn_readfirstlane(split.words[blockIdx.x]);
+        const uint32_t fy = entry / tiles_x;
+        tile_x = entry - fy * tiles_x;
+        const uint32_t row = fy * 8u;
+        if (row < ts.first_row) return;
+        const uint32_t band = (row - ts.first_row) / ts.tile_stride_rows, off = (row - ts.first_row) - band * ts.tile_stride_rows;
+        const uint32_t ly0 = band * ts.tile_rows + off;
+        if (off >= ts.tile_rows || ly0 >= ts.local_rows) return;
+        tile_y = ly0 >> 3;
+        tile_id = ((((tile_y >> 3) * ((tiles_x + 7u) >> 3)) + (tile_x >> 3)) << 6) + ((tile_y & 7u) << 3) + (tile_x & 7u);
+        if (tile_id >= n_tiles) return;
+        if (COUNT && wave_in_group != 0u) return;     // the counted form walks a tile as one wavefront (RtxStats stays what it is)
+    } else if (!kSplits) {
+        // workgroups b, b + 8, ... share an XCD (MI355X_MICROARCH.md, workgroup dispatch): the XCDs are dealt runs of 64
+        // consecutive tile numbers — one 64 x 64 pixel block each — so that an L2 serves neighbouring tiles' walks.  (One
+        // contiguous eighth of the frame per XCD was 25-35 % slower: the upper half of a frame is sky.)
+        const uint32_t k = blockIdx.x >> 3;
+        tile_id = ((((k >> 6) << 3) + (blockIdx.x & 7u)) << 6) + (k & 63u);
+        if (tile_id >= n_tiles) return;
+        tile_xy(tile_id, tiles_x, true, tile_x, tile_y);
+    } else {
+        if (blockIdx.x < long_groups) return;
+        // the same dealing, sixteen workgroups of four consecutive tiles per run of 64
+        const uint32_t g = blockIdx.x - long_groups, k = g >> 3;
+        tile_id = ((((k >> 4) << 3) + (g & 7u)) << 6) + ((k & 15u) << 2) + wave_in_group;
+        if (tile_id >= n_tiles) return;
+        tile_xy(tile_id, tiles_x, true, tile_x, tile_y);
+        // A tile of the long list has a workgroup of its own.  Only a tile inside the rectangle around the listed ones reads
+        // its bit (one dependent scalar load in front of everything else: paid by every tile of a 4096 x 4096 frame it was
+        // +2.5 % on the pass; of a 1920 x 1080 frame +1 us, 1.3 %: profiles/r08/h_ab_rectangle_gate_c5.log).
+        if (n_long != 0u) {
+            const uint32_t ly0 = tile_y * 8u, band = ly0 < ts.tile_rows ? 0u : ly0 / ts.tile_rows;
+            const uint32_t fy = (ts.first_row + band * ts.tile_stride_rows + (ly0 - band * ts.tile_rows)) >> 3;
+            if (tile_x >= (split.x_range & 0xFFFFu) && tile_x <= (split.x_range >> 16) && fy >= (split.y_range & 0xFFFFu) &&
+                fy <= (split.y_range >> 16) && ly0 < ts.local_rows) {
+                const uint32_t t = fy * tiles_x + tile_x;
+                if ((split.words[n_long + (t >> 5)] >> (t & 31u)) & 1u) return;
+            }
+        }
+    }
+    uint32_t px, py, ly;
     const bool in_frame = tile_pixel(S, ts, tile_x, tile_y, lane, px, py, ly);
     WaveCounters wc;
     float dx, dy, dz;
     primary_ray(S, in_frame, px, py, r, dx, dy, dz);
-    LaneRay pr = make_ray(in_frame, S.eye[0], S.eye[1], S.eye[2], dx, dy, dz);
-    ProbePhaseClock phases;   // (rtx_probes.hpp: nothing in the product)
+    // long mode: every wavefront forms the tile's 64 rays, wavefront w walks the 4 x 4 pixel quadrant w — a beam half as
+    // wide meets fewer boxes and leaves.  A ray's closest hit does not depend on which rays share its wavefront (the walk
+    // culls by superset, each lane tests its own candidates), so the answers are the ones one wavefront would find.
+    const bool beams = long_mode && !COUNT;
+    const bool walks = in_frame && (!beams || (((lane >> 5) << 1) | ((lane >> 2) & 1u)) == wave_in_group);
+    LaneRay pr = make_ray(walks, S.eye[0], S.eye[1], S.eye[2], dx, dy, dz);
+    ProbePhaseClock phases;   // (rtx_probes.hpp: nothing in the product; long mode: wavefront 0's, the barrier included)
     phases.mark(0);
+    bool ok = true;
+    if (!beams || ballot(walks) != 0ull) {      // (a beam without a pixel in the frame does not walk)
 #if RTX_ABLATION
-    const bool ok = (S.j1_mode == 2u || S.j1_mode == 3u)
-        ? j1_closest_hit_blocks<COUNT>(S.j1_mode, S.tris, S.shade, S.n_prims, pr, wc, lane, l_j1_block[wave_in_group])
-        : closest_hit<COUNT, FAST, SPHERES>((const NodeRec RTX_CONSTANT *)S.primary_nodes, tris, S.shade, S.n_nodes, pr, wc, S.n_global);   // main.rs:187
+        ok = (S.j1_mode == 2u || S.j1_mode == 3u)
+            ? j1_closest_hit_blocks<COUNT>(S.j1_mode, S.tris, S.shade, S.n_prims, pr, wc, lane, l_j1_block[wave_in_group])
+            : closest_hit<COUNT, FAST, SPHERES>((const NodeRec RTX_CONSTANT *)S.primary_nodes, tris, S.shade, S.n_nodes, pr, wc, S.n_global);   // main.rs:187
 #else
-    // (the primary rays' own stream of the tree, nearest-to-the-eye child first: scene_prep.h, PreparedScene::primary_nodes)
-    const bool ok = closest_hit<COUNT, FAST, SPHERES>((const NodeRec RTX_CONSTANT *)S.primary_nodes, tris, S.shade, S.n_nodes, pr, wc, S.n_global);   // main.rs:187
+        // (the primary rays' own stream of the tree, nearest-to-the-eye child first: scene_prep.h, PreparedScene::primary_nodes)
+        ok = closest_hit<COUNT, FAST, SPHERES>((const NodeRec RTX_CONSTANT *)S.primary_nodes, tris, S.shade, S.n_nodes, pr, wc, S.n_global);   // main.rs:187
 #endif
+    }
+    if (beams) {      // the four answers meet in LDS; wavefront 0 goes on with all 64 as if it had walked them
+        if (walks) { l_beam_t[lane] = pr.best_t; l_beam_idx[lane] = pr.best_idx; }
+        else if ((((lane >> 5) << 1) | ((lane >> 2) & 1u)) == wave_in_group) { l_beam_t[lane] = __builtin_inff(); l_beam_idx[lane] = kNone; }
+        if (lane == 0) l_beam_ok[wave_in_group] = ok ? 1u : 0u;
+        __syncthreads();
+        if (wave_in_group != 0u) return;
+        pr.best_t = l_beam_t[lane];
+        pr.best_idx = l_beam_idx[lane];
+        ok = (l_beam_ok[0] & l_beam_ok[1] & l_beam_ok[2] & l_beam_ok[3]) != 0u;
+    }
     phases.mark(1);
     const bool hit = ok && in_frame && pr.best_idx != kNone;
     const unsigned long long hit_mask = ballot(hit);

@@ -874,10 +874,155 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
                 const uint32_t prim = nd.info & kLeafIndexMask;
                 nd.info = kLeafFlag | (s.shade[prim].kind ? kSphereFlag : 0u) | pos_of[prim];
             }
+        // range of the sample table (the jitter of the primary rays), then the long primary walks (scene_prep.h)
+        for (int c = 0; c < 2; ++c) {
+            float lo = d.samples[c], hi = d.samples[c];
+            bool finite = true;
+            for (size_t i = 0; i < d.n_samples; ++i) {
+                const float v = d.samples[2 * i + c];
+                finite = finite && std::isfinite(v);
+                lo = v < lo ? v : lo;
+                hi = v > hi ? v : hi;
+            }
+            s.sample_lo[c] = finite ? lo : std::nanf("");
+            s.sample_hi[c] = finite ? hi : std::nanf("");
+        }
+        predict_long_tiles(s, kProbeLongWeight);
     } catch (const std::bad_alloc &) {
         return RTX_ERR_OOM;
     }
     return RTX_OK;
+}
+
+// ---- the long primary walks (scene_prep.h) ------------------------------------------------------------------------------
+
+namespace {
+
+// The primary stream's boxes as uploaded (nodes_in_device_order: each plane moved by cull_delta in f32), in double, and
+// the walk of the stream against one tile's frustum.
+struct ProbePredictor {
+    const PreparedScene &s;
+    const std::vector<NodeRec> &stream;
+    std::vector<double> box;           // n x {lo xyz, hi xyz}, relative to the eye
+    uint32_t root = 0;
+    bool usable = false;
+    explicit ProbePredictor(const PreparedScene &scene)
+        : s(scene), stream(scene.primary_nodes.empty() ? scene.nodes : scene.primary_nodes)
+    {
+        root = (s.n_global != 0u && stream.size() > 2u) ? 2u : (s.n_global != 0u ? static_cast<uint32_t>(stream.size()) : 0u);
+        usable = stream.size() <= kProbeSplitMaxNodes && s.width && s.height;
+        for (int c = 0; c < 2; ++c) usable = usable && std::isfinite(s.sample_lo[c]) && std::isfinite(s.sample_hi[c]);
+        if (!usable) return;
+        box.resize(6 * stream.size());
+        for (size_t i = 0; i < stream.size(); ++i)
+            for (int k = 0; k < 3; ++k) {
+                box[6 * i + k] = static_cast<double>(stream[i].bmin[k] - s.cull_delta) - static_cast<double>(s.eye[k]);
+                box[6 * i + 3 + k] = static_cast<double>(stream[i].bmax[k] + s.cull_delta) - static_cast<double>(s.eye[k]);
+            }
+    }
+    // the four planes through the eye around the tile's rays, normals pointing inwards; false: no proper frustum
+    bool planes_of(uint32_t tile_x, uint32_t tile_y, double n[4][3]) const
+    {
+        // create_rays: a = px - W / 2 + s0, b = py - H / 2 + s1 over the tile's pixels and the table's range, one more
+        // pixel each side (the kernel rounds a and b to f32: 2^-12 of a pixel at most)
+        const double lo0 = std::fmin(static_cast<double>(s.sample_lo[0]), 0.0), hi0 = std::fmax(static_cast<double>(s.sample_hi[0]), 1.0);
+        const double lo1 = std::fmin(static_cast<double>(s.sample_lo[1]), 0.0), hi1 = std::fmax(static_cast<double>(s.sample_hi[1]), 1.0);
+        const double a0 = 8.0 * tile_x - 0.5 * s.width + lo0 - 1.0, a1 = 8.0 * tile_x + 7.0 - 0.5 * s.width + hi0 + 1.0;
+        const double b0 = 8.0 * tile_y - 0.5 * s.height + lo1 - 1.0, b1 = 8.0 * tile_y + 7.0 - 0.5 * s.height + hi1 + 1.0;
+        auto dir = [&](double a, double b, double out[3]) {
+            for (int k = 0; k < 3; ++k)
+                out[k] = a * s.cam_u[k] + b * s.cam_v[k] - static_cast<double>(s.distance) * s.cam_w[k];
+        };
+        double c[4][3], mid[3];
+        dir(a0, b0, c[0]); dir(a1, b0, c[1]); dir(a1, b1, c[2]); dir(a0, b1, c[3]);
+        dir(0.5 * (a0 + a1), 0.5 * (b0 + b1), mid);
+        for (int e = 0; e < 4; ++e) {
+            const double *p = c[e], *q = c[(e + 1) % 4];
+            n[e][0] = p[1] * q[2] - p[2] * q[1];
+            n[e][1] = p[2] * q[0] - p[0] * q[2];
+            n[e][2] = p[0] * q[1] - p[1] * q[0];
+            double inside = n[e][0] * mid[0] + n[e][1] * mid[1] + n[e][2] * mid[2];
+            if (inside < 0.0) {
+                for (int k = 0; k < 3; ++k) n[e][k] = -n[e][k];
+                inside = -inside;
+            }
+            if (!(inside > 0.0) || !std::isfinite(inside)) return false;
+        }
+        return true;
+    }
+    // a box lies outside when all of it is behind one plane: its corner farthest along the normal decides
+    bool meets(const double n[4][3], size_t i) const
+    {
+        const double *b = &box[6 * i];
+        for (int e = 0; e < 4; ++e) {
+            double far = 0.0;
+            for (int k = 0; k < 3; ++k) far += n[e][k] * (n[e][k] > 0.0 ? b[3 + k] : b[k]);
+            if (far < 0.0) return false;        // (a NaN keeps the box)
+        }
+        return true;
+    }
+    uint32_t weigh(uint32_t tile_x, uint32_t tile_y, uint8_t *met, bool *valid) const
+    {
+        double n[4][3];
+        *valid = usable && planes_of(tile_x, tile_y, n);
+        if (!*valid) return 0u;
+        if (met)
+            for (uint32_t i = 0; i < root && i < stream.size(); ++i) met[i] = 1;
+        uint64_t w = 0;
+        for (size_t i = root; i < stream.size();) {
+            const NodeRec &nd = stream[i];
+            const bool leaf = (nd.info & kLeafFlag) != 0u;
+            const bool pass = meets(n, i);
+            if (pass) {
+                w += leaf ? 1u + 3ull * nd.link : 1u;
+                if (met) met[i] = 1;
+            }
+            i = (leaf || pass) ? i + 1 : (nd.link > i ? nd.link : stream.size());
+        }
+        return w > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(w);
+    }
+};
+
+}  // namespace
+
+uint32_t probe_tile_weight(const PreparedScene &s, uint32_t tile_x, uint32_t tile_y, uint8_t *met, bool *valid)
+{
+    const ProbePredictor p(s);
+    return p.weigh(tile_x, tile_y, met, valid);
+}
+
+void predict_long_tiles(PreparedScene &s, uint32_t threshold)
+{
+    s.long_tiles.clear();
+    s.long_weights.clear();
+    s.long_bits.clear();
+    const ProbePredictor p(s);
+    if (!p.usable) return;
+    const uint32_t tiles_x = (s.width + 7u) / 8u, tiles_y = (s.height + 7u) / 8u;
+    const uint64_t n_tiles64 = static_cast<uint64_t>(tiles_x) * tiles_y;
+    if (n_tiles64 > 0x7FFFFFFFull) return;
+    const uint32_t n_tiles = static_cast<uint32_t>(n_tiles64), cap = probe_long_cap(n_tiles);
+    if (cap == 0u) return;
+    std::vector<std::pair<uint32_t, uint32_t>> found;     // (weight, tile)
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            bool valid = false;
+            const uint32_t w = p.weigh(tx, ty, nullptr, &valid);
+            if (!valid) return;                            // one improper frustum: no prediction for the scene
+            if (w >= threshold) found.emplace_back(w, ty * tiles_x + tx);
+        }
+    // costliest first, equal weights by tile number: one order whatever the sort does with ties
+    std::sort(found.begin(), found.end(), [](const std::pair<uint32_t, uint32_t> &a, const std::pair<uint32_t, uint32_t> &b) {
+        return a.first != b.first ? a.first > b.first : a.second < b.second;
+    });
+    if (found.size() > cap) found.resize(cap);
+    if (found.size() < kProbeLongMinTiles) return;
+    s.long_bits.assign((n_tiles + 31u) / 32u, 0u);
+    for (const auto &f : found) {
+        s.long_tiles.push_back(f.second);
+        s.long_weights.push_back(f.first);
+        s.long_bits[f.second >> 5] |= 1u << (f.second & 31u);
+    }
 }
 
 // ---- posing (scene_prep.h) ----------------------------------------------------------------------------------------------

@@ -227,7 +227,42 @@ struct PreparedScene {
     // one per global triangle, in TriRec clothing: v0 = v0, e1 = fl(e1 x e2), e2 = (|e1| x |e2| with plus signs, rounded
     // up), bmin[0] = the denominator's error allowance — what rtx_traverse.hpp: plane_rules_out needs
     std::vector<TriRec>   global_planes;
+    // The scheduling pass's prediction of the long primary walks (predict_long_tiles): the 8 x 8 pixel tiles of the
+    // scene's own frame, numbered row-major (tile_y * tiles_x + tile_x), whose predicted primary walk weighs at least
+    // kProbeLongWeight — costliest first, at most probe_long_cap of them — their weights, and a bit per frame tile
+    // (word t / 32, bit t % 32) that is set for the listed ones.  An ordering hint: it never decides a pixel.  All
+    // three are empty for a scene that does not cut per tile (more than kProbeSplitMaxNodes records) or whose camera or
+    // sample table gives no proper frustum.
+    std::vector<uint32_t> long_tiles, long_weights, long_bits;
+    float sample_lo[2] = {0.0f, 0.0f}, sample_hi[2] = {0.0f, 0.0f};   // range of the sample table's two columns (NaN: not finite)
 };
+// A tile is long when the records its frustum meets weigh at least this much (an inner record 1, a leaf 1 + 3 x its
+// primitive records: the proxy of rtx_pass_schedule.hpp's cut).  Chosen by measurement (the
+// weight follows a tile's measured primary walk with a correlation of 0.985; swept over 150 ... 400, the scheduling pass is
+// shortest at 300, where a 1080p frame of the default scene lists its 52 costliest tiles).
+#ifndef RTX_PROBE_LONG_WEIGHT
+#define RTX_PROBE_LONG_WEIGHT 300
+#endif
+constexpr uint32_t kProbeLongWeight = RTX_PROBE_LONG_WEIGHT;
+// scenes of more stream records do not cut per tile (rtx_device.h: kCutMaxNodes, the same number) and predict nothing
+constexpr uint32_t kProbeSplitMaxNodes = 1u << 16;
+// A list of fewer tiles is dropped.  Such a scene's tail is not a dozen silhouette tiles but the whole mesh in a tile or two
+// (the small bunny in a 1080p frame: 2 tiles of weight 18,399), where each of the four beams still meets all of it: measured
+// with the list +2 % on that frame's pass (profiles/r08/e_ab_without_a_list.log, C2).
+constexpr uint32_t kProbeLongMinTiles = 8u;
+inline uint32_t probe_long_cap(uint32_t n_tiles) { return n_tiles / 32u < 1024u ? n_tiles / 32u : 1024u; }
+// Weight of the primary-stream records whose stored box (planes moved outwards by cull_delta, as uploaded) meets the
+// frustum of frame tile (tile_x, tile_y): the eye and the tile's pixel rectangle, widened by the sample table's range
+// and one more pixel on each side.  A superset count: a record that any primary ray of the tile can pass is met.  The
+// tree proper only (the root and the global triangles' leaf, which every walk takes untested, weigh nothing and count as
+// met).  met: NULL, or one byte per record of the stream, set to 1 for the records met.  *valid = false (and 0): no
+// prediction for this scene.
+uint32_t probe_tile_weight(const PreparedScene &s, uint32_t tile_x, uint32_t tile_y, uint8_t *met, bool *valid);
+// fills long_tiles, long_weights and long_bits for `threshold` (prepare_scene: kProbeLongWeight).  Weighs every tile of the
+// frame, also of a frame whose full launch is too large for the list (rtx_device.h: kProbeSplitMaxTiles): a share of its rows
+// is not.  A tile beside the mesh ends at the first records, so the cost follows the mesh more than the frame: measured on
+// the host 0.03 s of a scene creation of 0.11 s (big_bunny, 1920 x 1080) and of 0.13 s (4096 x 4096).
+void predict_long_tiles(PreparedScene &s, uint32_t threshold);
 constexpr uint32_t kMaxGlobalPrims = 8u;
 // the walk addresses primitive records by 32-bit byte offsets, 64 B each
 constexpr uint64_t kMaxPrimitives = 1ull << 26;

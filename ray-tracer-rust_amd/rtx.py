@@ -212,6 +212,10 @@ _SIGS = {
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
+    "rtx_debug_probe_records": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_size_t]),
+    "rtx_scene_probe_long": (C.c_int, [C.c_void_p, u32p, u32p, C.c_size_t, u32p]),
+    "rtx_scene_probe_tile": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u8p, u32p]),
+    "rtx_debug_probe_split": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rtx_strerror": (C.c_char_p, [C.c_int]),
     "rtx_last_hip_error": (C.c_int, []),
     "rtx_scene_light_points": (C.c_int, [C.c_void_p, f32p]),
@@ -545,6 +549,47 @@ class Scene:
         if m < 0:
             raise RtxError(m, "rtx_debug_tile_descs")
         return out[:m]
+
+    def probe_records(self, device=0):
+        """Diagnostics: (hit words uint32 [tiles, 768], pixel slots uint32 [tiles, 64]) of the most recent launch's
+        scheduling pass, in tile_descs' numbering."""
+        n = _lib.rtx_debug_probe_records(self._h, device, None, None, 0)
+        if n < 0:
+            raise RtxError(n, "rtx_debug_probe_records")
+        hits, slots = np.zeros((n, 768), np.uint32), np.zeros((n, 64), np.uint32)
+        m = _lib.rtx_debug_probe_records(self._h, device, hits.ctypes.data_as(u32p), slots.ctypes.data_as(u32p), n)
+        if m < 0:
+            raise RtxError(m, "rtx_debug_probe_records")
+        return hits[:m], slots[:m]
+
+    def probe_long(self):
+        """-> (long list: frame tile numbers costliest first, their weights, the threshold); host only."""
+        n = _lib.rtx_scene_probe_long(self._h, None, None, 0, None)
+        if n < 0:
+            raise RtxError(n, "rtx_scene_probe_long")
+        tiles, weights, thr = np.zeros(n, np.uint32), np.zeros(n, np.uint32), C.c_uint32(0)
+        m = _lib.rtx_scene_probe_long(self._h, tiles.ctypes.data_as(u32p), weights.ctypes.data_as(u32p), n,
+                                      C.cast(C.byref(thr), u32p))
+        if m < 0:
+            raise RtxError(m, "rtx_scene_probe_long")
+        return tiles[:m], weights[:m], thr.value
+
+    def probe_tile(self, tile_x, tile_y):
+        """-> (weight, uint8 [n_nodes]: 1 where the tile's frustum meets the record of primary_nodes(), predicted?)"""
+        met = np.zeros(self.info()["n_nodes"], np.uint8)
+        w = C.c_uint32(0)
+        rc = _lib.rtx_scene_probe_tile(self._h, tile_x, tile_y, met.ctypes.data_as(u8p), C.cast(C.byref(w), u32p))
+        if rc < 0:
+            raise RtxError(rc, "rtx_scene_probe_tile")
+        return w.value, met, bool(rc)
+
+    def debug_probe_split(self, mode):
+        """0: the predicted long tiles (default), 1: none, 2: every tile -> long-list workgroups of the scene's most
+        recent pipeline launch."""
+        n = _lib.rtx_debug_probe_split(self._h, mode)
+        if n < 0:
+            raise RtxError(n, "rtx_debug_probe_split")
+        return n
 
     def tiles_rows(self, first_tile, tile_stride, tile_rows):
         return _lib.rtx_tiles_rows(self._h, first_tile, tile_stride, tile_rows)
