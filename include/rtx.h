@@ -448,8 +448,8 @@ int rtx_debug_light_walk(RtxScene *scene, int device, const RtxLight *light, flo
 
 /* ---- posing an uploaded scene's triangles ----------------------------------------- */
 /* Geometry that moves without a new scene, a tree build or an upload.  A pose is n_tris x 9 floats in the layout of
- * RtxSceneDesc.v0v1v2: one entry per triangle of the Vec<Primitive>, in Vec order with spheres skipped.  Spheres do not
- * move, and the triangle count does not change.
+ * RtxSceneDesc.v0v1v2: one entry per triangle of the Vec<Primitive>, in Vec order with spheres skipped.  Spheres and
+ * colours stay as uploaded (rtx_scene_pose_prims, below, poses them too), and the triangle count does not change.
  *
  * What a pose makes, on the device, on the call's stream, in buffers of the library's own (grow-only; growing waits for
  * the device; ONE pose per scene per device: a new pose replaces the previous one; the uploaded scene is never written):
@@ -570,7 +570,8 @@ int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uin
  *   key: bit 63 the arm (0 triangle, 1 sphere: spheres sort behind all triangles, a leaf never mixes arms); bits 62..0
  *     the 3 x 21-bit Morton interleave (x highest in each triple) of the cells of the centre of the primitive's own posed
  *     box: c = 0.5f * (bmin + bmax), cell = (uint32)((c + M) * S) held to [0, 2^21 - 1], a NaN to cell 0; M is
- *     rtx_scene_pose_bound's, S = 2^21 / (2 M) rounded to f32 once.  A sphere's key comes from its uploaded record.
+ *     rtx_scene_pose_bound's, S = 2^21 / (2 M) rounded to f32 once.  A sphere's key comes from its uploaded record
+ *     (rtx_scene_pose_prims: from its posed one).
  *   sort: stable — equal keys keep uploaded order.
  *   shape: pre-order, skip-linked, as rtx_scene_nodes: with global triangles and a tree proper, record 0 is the root and
  *     record 1 the global leaf; the tree proper is the balanced subtree over the triangle run, or an inner node over that
@@ -582,8 +583,8 @@ int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uin
  * it returns over the refitted pose: only speed changes (DESIGN.md section 19 has which tree wins where).  Ties and hard
  * groups: rtx_scene_pose's rule over the rebuilt stream; with a reference tree (host variant) its leaves name positions of
  * the sorted array.  rtx_scene_pose_rebuilt_device outside the range rule: keys saturate, the permutation is still a
- * permutation and the shape is fixed, so the calls terminate; the values are unspecified.  Spheres do not move and the
- * primitive count does not change. */
+ * permutation and the shape is fixed, so the calls terminate; the values are unspecified.  Spheres stay as uploaded
+ * (rtx_scene_pose_prims moves them) and the primitive count does not change. */
 int rtx_scene_pose_rebuilt(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank /* may be NULL */,
                            uint32_t reference_tree, RtxStats *stats);
 int rtx_scene_pose_rebuilt_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank /* may be NULL */,
@@ -608,6 +609,52 @@ int rtx_scene_rebuilt_aimed(const RtxScene *scene, const float *v0v1v2, const fl
  * count — do not apply: RTX_ERR_BAD_ARG when they are not NULL. */
 int rtx_debug_pose_rebuilt(RtxScene *scene, int device, const float eye[3], uint32_t *out_perm, uint32_t *out_tris,
                            uint32_t *out_shade, uint32_t *out_nodes, uint32_t *out_aimed);
+
+/* ---- A pose that states every field of a primitive: spheres move, colours change ------------------------------------------
+ * rtx_scene_pose_prims / _device are rtx_scene_pose / _device — under RTX_POSE_REBUILT rtx_scene_pose_rebuilt / _device —
+ * in every respect: one pose per scene and device (a new pose of any kind replaces the previous one and takes the pose's
+ * aimed stream away), the ordering, the tie rule and reference_tree (the reference's own tree clusters the POSED sphere
+ * boxes), stats (kernel_ms now includes the overlay kernel), every posed call over it unchanged, rtx_debug_pose /
+ * rtx_debug_pose_rebuilt / rtx_debug_pose_pipeline to read it back.  Beside the triangles' vertices the pose may state
+ *   spheres:    every sphere's origin and radius.  Its primitive record and the `normal` words of its shading record are
+ *               restated by Sphere::new and get_bounding_box (sphere.rs:21-41) — the one text rtx_scene_create runs on the
+ *               host: v0 = origin, e1[0] = radius * radius, e1[1] = radius, the own box = origin -+ radius, each rounded
+ *               once; every other word is the uploaded record's.  Node boxes fold the posed boxes; under
+ *               RTX_POSE_REBUILT a sphere's key comes from its posed box.
+ *   rgb, sphere_rgb: the colour of every triangle / every sphere (the rgb words of the shading record).
+ * Only the primitive count and the order of arms in the Vec stay fixed.  A NULL array means "as UPLOADED", never "as the
+ * previous pose": a plain rtx_scene_pose after such a pose puts spheres and colours back.  Arrays of an arm the scene does
+ * not have are not read (v0v1v2 may be NULL for a scene without triangles).  The struct and, for the host variant, the
+ * arrays are read before the call returns; the device variant's arrays (device pointers, 4-byte aligned) must stay valid
+ * until the kernels have run.
+ * On the device one kernel runs ahead of the pose's own: it writes an overlay of the uploaded records (library-owned,
+ * grow-only buffers beside the pose's) which the pose or rebuild kernels read where they read the uploaded ones.  Without
+ * spheres only the shading half is made; with vertices alone nothing is launched.  rtx_scene_pose* never touch it.
+ * RTX_ERR_BAD_ARG: a NULL scene or struct, a NULL v0v1v2 with triangles present, an unknown flag or reference_tree.
+ * Range rule (host variant: RTX_ERR_UNSUPPORTED, decided before a device is looked for; device variant: a stated
+ * precondition): the triangles' as rtx_scene_pose's; for a sphere all four values finite and all six box words
+ * origin -+ radius, as rounded above, of magnitude at most rtx_scene_pose_bound.  A negative radius is taken as
+ * rtx_scene_create takes it.  Colours are not checked, as rtx_scene_create does not check them. */
+#define RTX_POSE_REBUILT 1u             /* the tree as rtx_scene_pose_rebuilt makes it; 0: refitted as rtx_scene_pose */
+typedef struct RtxPosePrims {           /* pointers: host for rtx_scene_pose_prims, device for _device */
+    const float *v0v1v2;                /* n_tris x 9, required when the scene has triangles */
+    const float *spheres;               /* NULL (as uploaded) or n_spheres x 4: origin x,y,z, radius */
+    const float *rgb;                   /* NULL (as uploaded) or n_tris x 3 */
+    const float *sphere_rgb;            /* NULL (as uploaded) or n_spheres x 3 */
+    const uint32_t *tie_rank;           /* NULL or one per Vec position, as rtx_scene_pose's */
+} RtxPosePrims;
+int rtx_scene_pose_prims(RtxScene *scene, int device, const RtxPosePrims *prims, uint32_t flags, uint32_t reference_tree,
+                         RtxStats *stats);
+int rtx_scene_pose_prims_device(RtxScene *scene, int device, const RtxPosePrims *prims, uint32_t flags, void *stream);
+/* Host only, no device: the words such a pose makes.  flags 0: rtx_scene_posed_records' layout, out_keys and out_perm must
+ * be NULL (RTX_ERR_BAD_ARG); RTX_POSE_REBUILT: rtx_scene_rebuilt_records' layout.  Each output may be NULL.  Nothing is
+ * checked against the range rule. */
+int rtx_scene_pose_prims_records(const RtxScene *scene, const RtxPosePrims *prims, uint32_t flags, uint64_t *out_keys,
+                                 uint32_t *out_perm, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes);
+/* Host only, no device: the aim kernels' output over such a pose for `eye`: rtx_scene_posed_pipeline_records' out_aimed
+ * (flags 0) or rtx_scene_rebuilt_aimed's (RTX_POSE_REBUILT).  RTX_ERR_BAD_ARG for a NULL. */
+int rtx_scene_pose_prims_aimed(const RtxScene *scene, const RtxPosePrims *prims, uint32_t flags, const float eye[3],
+                               uint32_t *out_aimed);
 
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),

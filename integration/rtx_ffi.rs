@@ -128,6 +128,19 @@ pub struct RtxLight {
     pub v2: [f32; 3],
     pub nb_light_sample: u32,
 }
+/// What `rtx_scene_pose_prims` states: host pointers for the host variant, device pointers for `_device`.  `v0v1v2` is
+/// required when the scene has triangles; a NULL `spheres` (`n_spheres x 4`: origin, radius), `rgb` (`n_tris x 3`) or
+/// `sphere_rgb` (`n_spheres x 3`) means "as uploaded"; `tie_rank` as `rtx_scene_pose`'s.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtxPosePrims {
+    pub v0v1v2: *const f32,
+    pub spheres: *const f32,
+    pub rgb: *const f32,
+    pub sphere_rgb: *const f32,
+    pub tie_rank: *const u32,
+}
+pub const RTX_POSE_REBUILT: u32 = 1;
 pub const RTX_NO_HIT: u32 = 0xFFFF_FFFF;
 pub const RTX_RAYS_KEEP_ORDER: u32 = 1;
 pub const RTX_RAYS_FORCE_REGROUP: u32 = 2;
@@ -259,6 +272,19 @@ extern "C" {
     /// Diagnostic: the rebuilt pose the device holds, and the aim kernels' output over it for `eye`; blocks.
     pub fn rtx_debug_pose_rebuilt(scene: *mut RtxScene, device: c_int, eye: *const f32, out_perm: *mut u32, out_tris: *mut u32,
                                   out_shade: *mut u32, out_nodes: *mut u32, out_aimed: *mut u32) -> c_int;
+    /// A pose that states every field of a primitive: `rtx_scene_pose` / `_device` (flags 0) or `rtx_scene_pose_rebuilt`
+    /// / `_device` (`RTX_POSE_REBUILT`) with the spheres' origins and radii and both arms' colours stated too; NULL
+    /// arrays are as uploaded.  A sphere's box words beyond `rtx_scene_pose_bound`: `RTX_ERR_UNSUPPORTED` (host variant).
+    pub fn rtx_scene_pose_prims(scene: *mut RtxScene, device: c_int, prims: *const RtxPosePrims, flags: u32,
+                                reference_tree: u32, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_scene_pose_prims_device(scene: *mut RtxScene, device: c_int, prims: *const RtxPosePrims, flags: u32,
+                                       stream: *mut c_void) -> c_int;
+    /// Host only: the words such a pose makes, in `rtx_scene_posed_records`' layout (flags 0: `out_keys` and `out_perm`
+    /// must be NULL) or `rtx_scene_rebuilt_records`'; and the aim kernels' output over it for `eye`.
+    pub fn rtx_scene_pose_prims_records(scene: *const RtxScene, prims: *const RtxPosePrims, flags: u32, out_keys: *mut u64,
+                                        out_perm: *mut u32, out_tris: *mut u32, out_shade: *mut u32, out_nodes: *mut u32) -> c_int;
+    pub fn rtx_scene_pose_prims_aimed(scene: *const RtxScene, prims: *const RtxPosePrims, flags: u32, eye: *const f32,
+                                      out_aimed: *mut u32) -> c_int;
     /// Host only: the points of `light` on this scene (`out` may be NULL); returns their number or a negative error.
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.

@@ -26,6 +26,7 @@
 #include "rtx_light.h"
 #include "rtx_planes.h"
 #include "rtx_pose.h"
+#include "rtx_prims.h"
 #include "rtx_rebuild.h"
 #include "rtx_query.h"
 #include "rtx_shade.h"
@@ -233,6 +234,15 @@ public:
             DeviceBuffer keys, keys_sorted, index, perm, temp;
         } b;
         bool rebuilt = false;
+        // rtx_scene_pose_prims (rtx_prims.hip): the host table (rtx::PoseTables::sphere_of, uploaded with the first such
+        // pose), the host variant's copies of the caller's sphere and colour arrays, and the overlay the pose or rebuild
+        // kernels of such a pose read in place of the uploaded records.  No other pose touches any of them.
+        struct {
+            DeviceBuffer sphere_of;
+            bool tables = false;
+            DeviceBuffer spheres, rgb, sphere_rgb;
+            DeviceBuffer tris, shade;
+        } m;
     } pose;
 private:
     ~DeviceState() = default;
@@ -958,13 +968,48 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
     return RTX_OK;
 }
 
+// The overlay's buffers of a pose that states spheres or colours (rtx_scene_pose_prims), beside reserve_pose's and by its
+// rule: library-owned per device, grow-only, growing waits for the device; sphere_of is uploaded with the first such pose.
+// host_copies: room for the host variant's copies of the arrays `ov` gives.  Caller holds the slot's lock and has the
+// device current and the scene uploaded.
+int reserve_prims(RtxScene *scene, DeviceState &st, bool host_copies, const rtx::PrimsOverlay &ov)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const size_t n_prims = p.tris.size(), n_spheres = p.n_spheres, n_triangles = posed_triangles(scene);
+    const size_t tris = ov.spheres ? std::max<size_t>(n_prims * sizeof(rtx::TriRec), 16u) : 0u;
+    const size_t shade = std::max<size_t>(n_prims * sizeof(rtx::ShadeRec), 16u);
+    const size_t spheres = host_copies && ov.spheres ? std::max<size_t>(n_spheres * 4u * sizeof(float), 16u) : 0u;
+    const size_t rgb = host_copies && ov.rgb ? std::max<size_t>(n_triangles * 3u * sizeof(float), 16u) : 0u;
+    const size_t sphere_rgb = host_copies && ov.sphere_rgb ? std::max<size_t>(n_spheres * 3u * sizeof(float), 16u) : 0u;
+    auto &m = st.pose.m;
+    if (m.tris.capacity() < tris || m.shade.capacity() < shade || m.spheres.capacity() < spheres || m.rgb.capacity() < rgb ||
+        m.sphere_rgb.capacity() < sphere_rgb) {
+        st.pose.valid = false;
+        RTX_HIP(hipDeviceSynchronize());
+        RTX_TRY(reserve_all({{m.tris, tris}, {m.shade, shade}, {m.spheres, spheres}, {m.rgb, rgb}, {m.sphere_rgb, sphere_rgb}}));
+    }
+    try {
+        if (!m.tables) {
+            RTX_TRY(upload_vec(m.sphere_of, pose_tables_of(scene).sphere_of));
+            m.tables = true;
+        }
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
 // the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
-// copies of them; the records behind the last one (upload_all pads the scene's with the same) are zeroed on the same stream.
+// copies of them; d_ov: the sphere and colour arrays of a pose that states them (after reserve_prims), in the same sense:
+// the overlay kernel then runs ahead of the others, which read its records where they read the uploaded ones — the primitive
+// records only with spheres given; nothing given: no launch, no buffer of the overlay's touched.  The records behind the
+// last one (upload_all pads the scene's with the same) are zeroed on the same stream.
 // rebuilt: the rebuild kernels and the sort make the records in sorted order, and the refit runs alone over the rebuilt
 // stream's tables; the geometry's node count becomes that stream's.
 // The plane kernel follows them over the posed global triangles (none: no launch).  This is the only writer of the pose's
 // nodes, and it takes the aimed stream's validity away before anything is launched (AimedStream).
-int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, hipStream_t stream, bool rebuilt)
+int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, const rtx::PrimsOverlay &d_ov,
+                hipStream_t stream, bool rebuilt)
 {
     const rtx::PreparedScene &p = scene->prep;
     const uint32_t n_prims = static_cast<uint32_t>(p.tris.size());
@@ -979,6 +1024,24 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
     rtxp::PoseArgs a{};
     a.tris = st.geo.tris.as<const rtx::TriRec>();
     a.shade = st.geo.shade.as<const rtx::ShadeRec>();
+    if (d_ov.any()) {
+        rtxm::OverlayArgs o{};
+        o.tris = a.tris;
+        o.shade = a.shade;
+        o.tri_of = st.pose.tri_of.as<const uint32_t>();
+        o.sphere_of = st.pose.m.sphere_of.as<const uint32_t>();
+        o.n_prims = n_prims;
+        o.spheres = d_ov.spheres;
+        o.rgb = d_ov.rgb;
+        o.sphere_rgb = d_ov.sphere_rgb;
+        o.ov_tris = d_ov.spheres ? st.pose.m.tris.as<rtx::TriRec>() : nullptr;
+        o.ov_shade = st.pose.m.shade.as<rtx::ShadeRec>();
+        RTX_HIP(rtxm::launch_overlay(o, stream));
+        if (o.ov_tris) a.tris = o.ov_tris;
+        a.shade = o.ov_shade;
+    }
+    // a scene without triangles reads no vertex: the launchers still want a pointer
+    if (!d_pose && posed_triangles(scene) == 0u) d_pose = reinterpret_cast<const float *>(a.tris);
     a.nodes = (rebuilt ? st.pose.b.nodes : st.geo.nodes).as<const rtx::NodeDev>();
     a.tri_of = st.pose.tri_of.as<const uint32_t>();
     a.ranges = (rebuilt ? st.pose.b.ranges : st.pose.ranges).as<const uint2>();
@@ -1360,19 +1423,36 @@ int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit
 // host statement of the plane kernel and of the aim kernels over a pose: global_plane_statement over the posed records of
 // the global triangles; stream_nearest_first over posed_records' node words, whose planes cull_delta has moved already
 // (a scene without a primary stream of its own: those words as they are).  Each output may be NULL.  May throw.
-void posed_pipeline_on_host(RtxScene *scene, const float *pose, const float *eye, rtx::TriRec *planes, rtx::NodeRec *aimed)
+void posed_pipeline_on_host(RtxScene *scene, const float *pose, const float *eye, rtx::TriRec *planes, rtx::NodeRec *aimed,
+                            const rtx::PrimsOverlay *ov = nullptr)
 {
     const rtx::PreparedScene &p = scene->prep;
     const rtx::PoseTables &t = pose_tables_of(scene);
     std::vector<rtx::TriRec> tris(p.tris.size());
     std::vector<rtx::NodeRec> nodes(aimed ? p.nodes.size() : 0u);
-    rtx::posed_records(p, t, pose, nullptr, tris.data(), nullptr, aimed ? nodes.data() : nullptr);
+    rtx::posed_records(p, t, pose, nullptr, tris.data(), nullptr, aimed ? nodes.data() : nullptr, ov);
     if (planes)
         for (uint32_t i = 0; i < p.n_global; ++i) rtx::global_plane_statement(tris[i], planes + i);
     if (!aimed) return;
     if (!p.primary_nodes.empty()) {
         std::vector<rtx::NodeRec> out;
         rtx::stream_nearest_first(nodes, tree_root(p), eye, out);
+        nodes.swap(out);
+    }
+    std::memcpy(aimed, nodes.data(), nodes.size() * sizeof(rtx::NodeRec));
+}
+
+// the same over a rebuilt pose: rebuilt_records' node words in rtx_scene_aimed_nodes' order (a scene that aims nothing: the
+// pose's stream as it is).  aimed: the rebuilt stream's count of records.  May throw.
+void rebuilt_aimed_on_host(RtxScene *scene, const float *pose, const float *eye, rtx::NodeRec *aimed, const rtx::PrimsOverlay *ov)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const rtx::RebuildTables &b = rebuild_tables_of(scene);
+    std::vector<rtx::NodeRec> nodes(b.nodes.size());
+    rtx::rebuilt_records(p, pose_tables_of(scene), b, pose, nullptr, nullptr, nullptr, nullptr, nullptr, nodes.data(), ov);
+    if (!p.primary_nodes.empty()) {
+        std::vector<rtx::NodeRec> out;
+        rtx::stream_nearest_first(nodes, tree_root(p, nodes.size()), eye, out);
         nodes.swap(out);
     }
     std::memcpy(aimed, nodes.data(), nodes.size() * sizeof(rtx::NodeRec));
@@ -1417,13 +1497,30 @@ int read_back_nodes(const DeviceState &st, const void *d_nodes, size_t n, uint32
     return RTX_OK;
 }
 
-// The bodies of rtx_scene_pose / rtx_scene_pose_device and of their _rebuilt twins: everything but the tree is the same.
-int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
-              RtxStats *stats, bool rebuilt)
+// What rtx_scene_pose_prims reads of its struct for `scene`: the arrays of an arm the scene does not have are not read.
+// RTX_ERR_BAD_ARG for vertices missing with triangles present.
+int prims_of(const RtxScene *scene, const RtxPosePrims *in, const float **v0v1v2, rtx::PrimsOverlay *ov)
 {
-    if (!scene || !v0v1v2 || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
+    const bool triangles = posed_triangles(scene) != 0u, spheres = scene->prep.n_spheres != 0u;
+    if (triangles && !in->v0v1v2) return RTX_ERR_BAD_ARG;
+    *v0v1v2 = triangles ? in->v0v1v2 : nullptr;
+    ov->rgb = triangles ? in->rgb : nullptr;
+    ov->spheres = spheres ? in->spheres : nullptr;
+    ov->sphere_rgb = spheres ? in->sphere_rgb : nullptr;
+    return RTX_OK;
+}
+
+// The bodies of rtx_scene_pose / rtx_scene_pose_device and of their _rebuilt twins: everything but the tree is the same.
+// prims: rtx_scene_pose_prims' bodies — v0v1v2 may be NULL for a scene without triangles, and ov is what the call states
+// beside the vertices; the other entry points give none, and nothing of the overlay's is then reserved, copied or launched.
+int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
+              RtxStats *stats, bool rebuilt, bool prims = false, const rtx::PrimsOverlay &ov = rtx::PrimsOverlay())
+{
+    if (!scene || (!v0v1v2 && (!prims || posed_triangles(scene) != 0u)) || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
     const rtx::PreparedScene &p = scene->prep;
-    if (!rtx::pose_in_range(p, v0v1v2)) return RTX_ERR_UNSUPPORTED;
+    if (v0v1v2 && !rtx::pose_in_range(p, v0v1v2)) return RTX_ERR_UNSUPPORTED;
+    if (ov.spheres && !rtx::spheres_in_range(p, ov.spheres)) return RTX_ERR_UNSUPPORTED;
+    const rtx::PrimsOverlay *pov = ov.any() ? &ov : nullptr;
     const Timed timed(stats);
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
@@ -1438,10 +1535,10 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
             if (rebuilt) {      // the leaves name positions of the sorted array: through the host statement's permutation
                 std::vector<uint32_t> perm(n_prims - p.n_global);
                 rtx::rebuilt_records(p, pose_tables_of(scene), rebuild_tables_of(scene), v0v1v2, nullptr, nullptr, perm.data(),
-                                     nullptr, nullptr, nullptr);
-                RTX_TRY(rtx::rebuilt_ref_tree(p, pose_tables_of(scene), v0v1v2, perm.data(), ref_rank, stream));
+                                     nullptr, nullptr, nullptr, pov);
+                RTX_TRY(rtx::rebuilt_ref_tree(p, pose_tables_of(scene), v0v1v2, perm.data(), ref_rank, stream, pov));
             } else {
-                RTX_TRY(rtx::posed_ref_tree(p, pose_tables_of(scene), v0v1v2, ref_rank, stream));
+                RTX_TRY(rtx::posed_ref_tree(p, pose_tables_of(scene), v0v1v2, ref_rank, stream, pov));
             }
             ref_stream = rtx::nodes_in_device_order(stream);
         }
@@ -1450,10 +1547,20 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     }
     const uint32_t *rank = tie_rank ? tie_rank : (want_ref ? ref_rank.data() : nullptr);
     RTX_TRY(reserve_pose(scene, st, true, ref_stream.size(), rebuilt));
+    if (pov) RTX_TRY(reserve_prims(scene, st, true, ov));
     RTX_TRY(wait_for_uses(st, kUsesPose));      // a device-resident call may still read the pose this one replaces
     const size_t v_bytes = static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
     hipError_t he = hipSuccess;
     if (v_bytes) he = hipMemcpyAsync(st.pose.v.as<void>(), v0v1v2, v_bytes, hipMemcpyHostToDevice, st.stream);
+    rtx::PrimsOverlay d_ov;
+    auto copy_in = [&](const float *from, DeviceBuffer &to, size_t floats, const float *&d) {      // (an array not given: nothing)
+        if (he != hipSuccess || !from) return;
+        he = hipMemcpyAsync(to.as<void>(), from, floats * sizeof(float), hipMemcpyHostToDevice, st.stream);
+        d = to.as<const float>();
+    };
+    copy_in(ov.spheres, st.pose.m.spheres, static_cast<size_t>(p.n_spheres) * 4u, d_ov.spheres);
+    copy_in(ov.rgb, st.pose.m.rgb, static_cast<size_t>(posed_triangles(scene)) * 3u, d_ov.rgb);
+    copy_in(ov.sphere_rgb, st.pose.m.sphere_rgb, static_cast<size_t>(p.n_spheres) * 3u, d_ov.sphere_rgb);
     if (he == hipSuccess && rank)
         he = hipMemcpyAsync(st.pose.rank.as<void>(), rank, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
     if (he == hipSuccess && !ref_stream.empty()) {
@@ -1465,7 +1572,8 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     int rc = hip_rc(he);
     if (rc == RTX_OK) rc = timed.begin(st);
     if (rc == RTX_OK)
-        rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, st.stream, rebuilt);
+        rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, d_ov, st.stream,
+                         rebuilt);
     if (rc == RTX_OK) rc = timed.end(st);
     if (rc != RTX_OK) {
         st.pose.valid = false;
@@ -1476,15 +1584,19 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     return timed.gather(st, 0u, 0u);
 }
 
-int pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream, bool rebuilt)
+int pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream, bool rebuilt,
+                bool prims = false, const rtx::PrimsOverlay &d_ov = rtx::PrimsOverlay())
 {
-    if (!scene || !d_v0v1v2) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_v0v1v2) | reinterpret_cast<uintptr_t>(d_tie_rank)) & 3u) return RTX_ERR_BAD_ARG;
+    if (!scene || (!d_v0v1v2 && (!prims || posed_triangles(scene) != 0u))) return RTX_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_v0v1v2) | reinterpret_cast<uintptr_t>(d_tie_rank) | reinterpret_cast<uintptr_t>(d_ov.spheres) |
+         reinterpret_cast<uintptr_t>(d_ov.rgb) | reinterpret_cast<uintptr_t>(d_ov.sphere_rgb)) & 3u)
+        return RTX_ERR_BAD_ARG;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
     RTX_TRY(reserve_pose(scene, st, false, 0u, rebuilt));
-    RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank),
+    if (d_ov.any()) RTX_TRY(reserve_prims(scene, st, false, d_ov));
+    RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank), d_ov,
                         static_cast<hipStream_t>(stream), rebuilt));
     return mark_uses(st, kUsesPose, static_cast<hipStream_t>(stream));
 }
@@ -1981,17 +2093,70 @@ int rtx_scene_rebuilt_aimed(const RtxScene *scene, const float *v0v1v2, const fl
 {
     if (!scene || !v0v1v2 || !eye || !out_aimed) return RTX_ERR_BAD_ARG;
     try {
+        rebuilt_aimed_on_host(const_cast<RtxScene *>(scene), v0v1v2, eye, reinterpret_cast<rtx::NodeRec *>(out_aimed), nullptr);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_scene_pose_prims(RtxScene *scene, int device, const RtxPosePrims *prims, uint32_t flags, uint32_t reference_tree,
+                         RtxStats *stats)
+{
+    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
+    const float *v0v1v2;
+    rtx::PrimsOverlay ov;
+    RTX_TRY(prims_of(scene, prims, &v0v1v2, &ov));
+    return pose_host(scene, device, v0v1v2, prims->tie_rank, reference_tree, stats, (flags & RTX_POSE_REBUILT) != 0u, true, ov);
+}
+
+int rtx_scene_pose_prims_device(RtxScene *scene, int device, const RtxPosePrims *prims, uint32_t flags, void *stream)
+{
+    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
+    const float *d_v0v1v2;
+    rtx::PrimsOverlay d_ov;
+    RTX_TRY(prims_of(scene, prims, &d_v0v1v2, &d_ov));
+    return pose_device(scene, device, d_v0v1v2, prims->tie_rank, stream, (flags & RTX_POSE_REBUILT) != 0u, true, d_ov);
+}
+
+int rtx_scene_pose_prims_records(const RtxScene *scene, const RtxPosePrims *prims, uint32_t flags, uint64_t *out_keys,
+                                 uint32_t *out_perm, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
+{
+    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
+    const bool rebuilt = (flags & RTX_POSE_REBUILT) != 0u;
+    if (!rebuilt && (out_keys || out_perm)) return RTX_ERR_BAD_ARG;
+    const float *v0v1v2;
+    rtx::PrimsOverlay ov;
+    RTX_TRY(prims_of(scene, prims, &v0v1v2, &ov));
+    try {
         RtxScene *sc = const_cast<RtxScene *>(scene);      // (the tables are caches under the scene's lock)
-        const rtx::PreparedScene &p = scene->prep;
-        const rtx::RebuildTables &b = rebuild_tables_of(sc);
-        std::vector<rtx::NodeRec> nodes(b.nodes.size());
-        rtx::rebuilt_records(p, pose_tables_of(sc), b, v0v1v2, nullptr, nullptr, nullptr, nullptr, nullptr, nodes.data());
-        if (!p.primary_nodes.empty()) {                    // (a scene that aims nothing: the pose's stream as it is)
-            std::vector<rtx::NodeRec> out;
-            rtx::stream_nearest_first(nodes, tree_root(p, nodes.size()), eye, out);
-            nodes.swap(out);
-        }
-        std::memcpy(out_aimed, nodes.data(), nodes.size() * sizeof(rtx::NodeRec));
+        const rtx::PoseTables &t = pose_tables_of(sc);
+        rtx::TriRec *tris = reinterpret_cast<rtx::TriRec *>(out_tris);
+        rtx::ShadeRec *shade = reinterpret_cast<rtx::ShadeRec *>(out_shade);
+        rtx::NodeRec *nodes = reinterpret_cast<rtx::NodeRec *>(out_nodes);
+        if (rebuilt)
+            rtx::rebuilt_records(scene->prep, t, rebuild_tables_of(sc), v0v1v2, prims->tie_rank, out_keys, out_perm, tris, shade,
+                                 nodes, &ov);
+        else
+            rtx::posed_records(scene->prep, t, v0v1v2, prims->tie_rank, tris, shade, nodes, &ov);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+int rtx_scene_pose_prims_aimed(const RtxScene *scene, const RtxPosePrims *prims, uint32_t flags, const float eye[3],
+                               uint32_t *out_aimed)
+{
+    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT) || !eye || !out_aimed) return RTX_ERR_BAD_ARG;
+    const float *v0v1v2;
+    rtx::PrimsOverlay ov;
+    RTX_TRY(prims_of(scene, prims, &v0v1v2, &ov));
+    try {
+        RtxScene *sc = const_cast<RtxScene *>(scene);
+        rtx::NodeRec *aimed = reinterpret_cast<rtx::NodeRec *>(out_aimed);
+        if (flags & RTX_POSE_REBUILT) rebuilt_aimed_on_host(sc, v0v1v2, eye, aimed, &ov);
+        else posed_pipeline_on_host(sc, v0v1v2, eye, nullptr, aimed, &ov);
     } catch (...) {
         return RTX_ERR_OOM;
     }

@@ -666,15 +666,7 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
                 const float *p = d.spheres + 4 * static_cast<size_t>(next_sphere);
                 for (int k = 0; k < 4; ++k)
                     if (!std::isfinite(p[k])) return RTX_ERR_UNSUPPORTED;
-                const float radius = p[3];
-                std::memcpy(r.v0, p, 12);
-                r.e1[0] = radius * radius;                                   // Sphere::new, sphere.rs:26
-                r.e1[1] = radius;
-                for (int k = 0; k < 3; ++k) {                                // get_bounding_box, sphere.rs:32-41
-                    r.bmin[k] = p[k] - radius;
-                    r.bmax[k] = p[k] + radius;
-                }
-                std::memcpy(sh.normal, p, 12);                               // the origin; get_normal needs p_hit (sphere.rs:93-95)
+                sphere_statement(p, r.v0, r.e1, r.bmin, r.bmax, sh.normal);  // Sphere::new, get_bounding_box (scene_prep.h)
                 std::memcpy(sh.rgb, d.sphere_rgb + 3 * static_cast<size_t>(next_sphere), 12);
                 sh.kind = 1;
                 ++next_sphere;
@@ -1046,9 +1038,12 @@ void pose_tables(const PreparedScene &s, PoseTables &out)
         out.ranges[2u * i + 1u] = end - first;
     }
     out.tri_of.assign(n_prims, kPoseNoTriangle);
-    uint32_t next = 0;
-    for (size_t i = 0; i < n_prims; ++i)
+    out.sphere_of.assign(n_prims, kPoseNoTriangle);
+    uint32_t next = 0, next_sphere = 0;
+    for (size_t i = 0; i < n_prims; ++i) {
         if (s.shade[i].kind == 0u) out.tri_of[i] = next++;
+        else out.sphere_of[i] = next_sphere++;
+    }
     out.order.clear();
     out.order.reserve(n_nodes);
     for (uint32_t i = 0; i < n_nodes; ++i)
@@ -1066,8 +1061,40 @@ bool pose_in_range(const PreparedScene &s, const float *pose)
     return true;
 }
 
+bool spheres_in_range(const PreparedScene &s, const float *spheres)
+{
+    for (size_t i = 0; i < s.n_spheres; ++i) {
+        const float *p = spheres + 4u * i;
+        float v0[3], e1[3], lo[3], hi[3], origin[3];
+        for (int k = 0; k < 4; ++k)
+            if (!std::isfinite(p[k])) return false;
+        sphere_statement(p, v0, e1, lo, hi, origin);
+        for (int k = 0; k < 3; ++k)
+            if (!(std::fabs(lo[k]) <= s.scene_magnitude) || !(std::fabs(hi[k]) <= s.scene_magnitude)) return false;
+    }
+    return true;
+}
+
+void overlay_records(const PreparedScene &s, const PoseTables &t, const PrimsOverlay &ov, TriRec *tris, ShadeRec *shade)
+{
+    const size_t n_prims = s.tris.size();
+    for (size_t j = 0; j < n_prims; ++j) {
+        TriRec r = s.tris[j];
+        ShadeRec sh = s.shade[r.idx];
+        if (sh.kind != 0u) {
+            const size_t n = t.sphere_of[r.idx];
+            if (ov.spheres) sphere_statement(ov.spheres + 4u * n, r.v0, r.e1, r.bmin, r.bmax, sh.normal);
+            if (ov.sphere_rgb) std::memcpy(sh.rgb, ov.sphere_rgb + 3u * n, 12);
+        } else if (ov.rgb) {
+            std::memcpy(sh.rgb, ov.rgb + 3u * static_cast<size_t>(t.tri_of[r.idx]), 12);
+        }
+        if (tris) tris[j] = r;
+        if (shade) shade[r.idx] = sh;
+    }
+}
+
 void posed_records(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *rank, TriRec *tris,
-                   ShadeRec *shade, NodeRec *nodes)
+                   ShadeRec *shade, NodeRec *nodes, const PrimsOverlay *ov)
 {
     const size_t n_prims = s.tris.size();
     std::vector<TriRec> own;
@@ -1075,9 +1102,21 @@ void posed_records(const PreparedScene &s, const PoseTables &t, const float *pos
         own.resize(n_prims);
         tris = own.data();
     }
+    // what the kernels are handed as the uploaded arrays: the scene's, or the overlay's over them
+    const TriRec *in_tris = s.tris.data();
+    const ShadeRec *in_shade = s.shade.data();
+    std::vector<TriRec> ov_tris;
+    std::vector<ShadeRec> ov_shade;
+    if (ov && ov->any()) {
+        ov_tris.resize(n_prims);
+        ov_shade.resize(n_prims);
+        overlay_records(s, t, *ov, ov_tris.data(), ov_shade.data());
+        in_tris = ov_tris.data();
+        in_shade = ov_shade.data();
+    }
     for (size_t j = 0; j < n_prims; ++j) {
-        TriRec r = s.tris[j];
-        ShadeRec sh = s.shade[r.idx];
+        TriRec r = in_tris[j];
+        ShadeRec sh = in_shade[r.idx];
         if (sh.kind == 0u) {
             const float *v = pose + 9u * static_cast<size_t>(t.tri_of[r.idx]);
             std::memcpy(r.v0, v, 12);
@@ -1106,11 +1145,11 @@ void posed_records(const PreparedScene &s, const PoseTables &t, const float *pos
 }
 
 int posed_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, std::vector<uint32_t> &rank,
-                   std::vector<NodeRec> &stream)
+                   std::vector<NodeRec> &stream, const PrimsOverlay *ov)
 {
     const size_t n_prims = s.tris.size();
     std::vector<TriRec> tris(n_prims);
-    posed_records(s, t, pose, nullptr, tris.data(), nullptr, nullptr);
+    posed_records(s, t, pose, nullptr, tris.data(), nullptr, nullptr, ov);
     std::vector<float> boxes(6u * n_prims);
     std::vector<uint32_t> pos_of(n_prims);
     for (size_t j = 0; j < n_prims; ++j) {
@@ -1218,11 +1257,12 @@ void rebuild_tables(const PreparedScene &s, RebuildTables &out)
 }
 
 void rebuilt_records(const PreparedScene &s, const PoseTables &t, const RebuildTables &b, const float *pose,
-                     const uint32_t *rank, uint64_t *keys, uint32_t *perm, TriRec *tris, ShadeRec *shade, NodeRec *nodes)
+                     const uint32_t *rank, uint64_t *keys, uint32_t *perm, TriRec *tris, ShadeRec *shade, NodeRec *nodes,
+                     const PrimsOverlay *ov)
 {
     const size_t n_prims = s.tris.size(), n_global = s.n_global, n_tree = n_prims - n_global;
     std::vector<TriRec> posed(n_prims);
-    posed_records(s, t, pose, rank, posed.data(), shade, nullptr);
+    posed_records(s, t, pose, rank, posed.data(), shade, nullptr, ov);
     const float scale = rebuild_key_scale(s.scene_magnitude);
     std::vector<uint64_t> key_of(n_tree);
     for (size_t p = 0; p < n_tree; ++p) {
@@ -1264,9 +1304,9 @@ void rebuilt_records(const PreparedScene &s, const PoseTables &t, const RebuildT
 }
 
 int rebuilt_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *perm,
-                     std::vector<uint32_t> &rank, std::vector<NodeRec> &stream)
+                     std::vector<uint32_t> &rank, std::vector<NodeRec> &stream, const PrimsOverlay *ov)
 {
-    const int rc = posed_ref_tree(s, t, pose, rank, stream);      // its leaves name positions of the uploaded array
+    const int rc = posed_ref_tree(s, t, pose, rank, stream, ov);      // its leaves name positions of the uploaded array
     if (rc != RTX_OK) return rc;
     const size_t n_prims = s.tris.size(), n_global = s.n_global;
     std::vector<uint32_t> sorted_of(n_prims);

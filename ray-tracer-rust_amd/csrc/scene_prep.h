@@ -172,6 +172,25 @@ RTX_HOST_DEVICE inline void global_plane_statement(const TriRec &t, TriRec *out)
     *out = g;
 }
 
+// Sphere::new + get_bounding_box — sphere.rs:21-41 — from s = {origin x, y, z, radius}: v0 = the origin, e1[0] = radius *
+// radius, e1[1] = radius, the box = origin -+ radius (each word rounded once), and the origin once more for the shading
+// record's `normal` words (get_normal needs p_hit, sphere.rs:93-95).  Every other word of the 64-byte slot stays what the
+// caller holds there (zero in a prepared record).  One text for both compilers, as triangle_statement is: prepare_scene on
+// the host, rtxm::overlay_kernel (rtx_prims.hip) on the device for a pose's spheres.
+RTX_HOST_DEVICE inline void sphere_statement(const float s[4], float v0[3], float e1[3], float bmin[3], float bmax[3],
+                                             float origin_for_shade[3])
+{
+    const float radius = s[3];
+    e1[0] = radius * radius;
+    e1[1] = radius;
+    for (int k = 0; k < 3; ++k) {
+        v0[k] = s[k];
+        bmin[k] = s[k] - radius;
+        bmax[k] = s[k] + radius;
+        origin_for_shade[k] = s[k];
+    }
+}
+
 // Shading data of a primitive, indexed by its position in the caller's Vec<Primitive> (read once per hit).
 struct ShadeRec {
     float    normal[3];   // triangle: Triangle::new, triangle.rs:29; sphere: its origin (normal = normalize(p_hit - origin), sphere.rs:93-95)
@@ -317,8 +336,8 @@ int  ref_tree_build_boxes(uint32_t n, const float *lo_hi, uint32_t *out_rank, st
 constexpr uint32_t kRefTreeAutoMax = 50000u;
 
 // ---- posing an uploaded scene's triangles (rtx_scene_pose; the kernels: rtx_pose.hip) ----
-// A pose is n_tris x 9 floats in RtxSceneDesc.v0v1v2's layout: the Vec's triangles in Vec order, spheres skipped (they do
-// not move).  The tree keeps its shape: every record of `nodes` holds the exact union of the primitives' own boxes over a
+// A pose is n_tris x 9 floats in RtxSceneDesc.v0v1v2's layout: the Vec's triangles in Vec order, spheres skipped (they
+// move through a PrimsOverlay, below).  The tree keeps its shape: every record of `nodes` holds the exact union of the primitives' own boxes over a
 // contiguous run of the primitive array (TreeBuilder::build, the global leaf, the root over all, both RTX_ACCEL_BRUTE
 // shapes), so record i's posed box is a min/max fold over records [first_i, first_i + count_i), independent of every
 // other node.  The refit kernels fold each range directly, a range of at most kPoseLaneMax records by one work-item and a
@@ -329,6 +348,7 @@ constexpr uint32_t kPoseNoTriangle = 0xFFFFFFFFu;
 struct PoseTables {
     std::vector<uint32_t> ranges;      // n_nodes x {first, count}
     std::vector<uint32_t> tri_of;      // Vec position -> triangle number in the pose; a sphere: kPoseNoTriangle
+    std::vector<uint32_t> sphere_of;   // Vec position -> sphere number (rtx_scene_pose_prims); a triangle: kPoseNoTriangle
     std::vector<uint32_t> order;       // the nodes: those with count > kPoseLaneMax (ascending), then the others (ascending)
     uint32_t n_long = 0;
 };
@@ -336,15 +356,31 @@ void pose_tables(const PreparedScene &s, PoseTables &out);
 // what PreparedScene::cull_delta and origin_bound were sized for bounds the pose: every coordinate finite and of
 // magnitude at most scene_magnitude
 bool pose_in_range(const PreparedScene &s, const float *pose);
+// What a pose states beside the triangles' vertices (rtx_scene_pose_prims; the kernel: rtx_prims.hip): each array is NULL,
+// "as uploaded", or one entry per primitive of its arm in Vec order — spheres: n_spheres x {origin x, y, z, radius};
+// rgb: n_triangles x 3; sphere_rgb: n_spheres x 3.
+struct PrimsOverlay {
+    const float *spheres = nullptr, *rgb = nullptr, *sphere_rgb = nullptr;
+    bool any() const { return spheres || rgb || sphere_rgb; }
+};
+// The host statement of rtxm::overlay_kernel: the uploaded primitive records (leaf order) and shading records (Vec order)
+// with every sphere restated by sphere_statement and every rgb replaced where `ov` gives one, every other word copied.
+// They stand where the uploaded arrays stand for posed_records and rebuilt_records.  Each output may be NULL.
+void overlay_records(const PreparedScene &s, const PoseTables &t, const PrimsOverlay &ov, TriRec *tris, ShadeRec *shade);
+// pose_in_range's rule for posed spheres: all four values finite, and the six box words origin -+ radius, as
+// sphere_statement rounds them, of magnitude at most scene_magnitude
+bool spheres_in_range(const PreparedScene &s, const float *spheres);
 // The host statement of what the pose kernels make.  rank: per Vec position, or NULL for the position itself.  tris:
 // n_prims records in leaf order; shade: n_prims in Vec order; nodes: n_nodes records in NodeRec's word order, the planes
-// moved outwards by cull_delta in f32 as nodes_in_device_order moves them.  Each output may be NULL.
+// moved outwards by cull_delta in f32 as nodes_in_device_order moves them.  Each output may be NULL.  ov: NULL, or what
+// the pose states beside the vertices (overlay_records' words in place of the uploaded ones); pose may be NULL for a scene
+// without triangles.
 void posed_records(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *rank, TriRec *tris,
-                   ShadeRec *shade, NodeRec *nodes);
+                   ShadeRec *shade, NodeRec *nodes, const PrimsOverlay *ov = nullptr);
 // The reference's own tree over the posed primitives (ref_tree_build_boxes, O(n^2)): its leaf ranks per Vec position and
 // its stream, the leaves naming positions of the primitive array as PreparedScene::ref_nodes' do.
 int posed_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, std::vector<uint32_t> &rank,
-                   std::vector<NodeRec> &stream);
+                   std::vector<NodeRec> &stream, const PrimsOverlay *ov = nullptr);
 
 
 // ---- a pose whose tree is rebuilt (rtx_scene_pose_rebuilt; the kernels: rtx_rebuild.hip) ----
@@ -392,10 +428,12 @@ void rebuild_tables(const PreparedScene &s, RebuildTables &out);
 // position in the uploaded array of the record that sorted position n_global + p holds (std::stable_sort by key: equal
 // keys keep uploaded order).  tris: n_prims records in sorted order; shade: n_prims in Vec order, as posed_records makes
 // them; nodes: the rebuilt stream in NodeRec's word order, the planes moved outwards by cull_delta.  Each may be NULL.
+// ov: as posed_records'.
 void rebuilt_records(const PreparedScene &s, const PoseTables &t, const RebuildTables &b, const float *pose,
-                     const uint32_t *rank, uint64_t *keys, uint32_t *perm, TriRec *tris, ShadeRec *shade, NodeRec *nodes);
+                     const uint32_t *rank, uint64_t *keys, uint32_t *perm, TriRec *tris, ShadeRec *shade, NodeRec *nodes,
+                     const PrimsOverlay *ov = nullptr);
 // posed_ref_tree with its leaves naming positions of the SORTED primitive array (perm: rebuilt_records')
 int rebuilt_ref_tree(const PreparedScene &s, const PoseTables &t, const float *pose, const uint32_t *perm,
-                     std::vector<uint32_t> &rank, std::vector<NodeRec> &stream);
+                     std::vector<uint32_t> &rank, std::vector<NodeRec> &stream, const PrimsOverlay *ov = nullptr);
 
 }  // namespace rtx

@@ -130,6 +130,16 @@ class RtxLight(C.Structure):
 assert C.sizeof(RtxLight) == 40 and C.alignment(RtxLight) == 4
 
 
+class RtxPosePrims(C.Structure):
+    """RtxPosePrims: what a pose of every field states — host pointers for rtx_scene_pose_prims, device ones for _device."""
+    _fields_ = [("v0v1v2", C.c_void_p), ("spheres", C.c_void_p), ("rgb", C.c_void_p), ("sphere_rgb", C.c_void_p),
+                ("tie_rank", C.c_void_p)]
+
+
+assert C.sizeof(RtxPosePrims) == 40 and C.alignment(RtxPosePrims) == 8
+POSE_REBUILT = 1
+
+
 # every symbol include/rtx.h declares (tests check the export list against the header)
 _SIGS = {
     "rtx_abi_version": (C.c_int, []),
@@ -209,6 +219,11 @@ _SIGS = {
     "rtx_scene_rebuilt_records": (C.c_int, [C.c_void_p, f32p, u32p, C.POINTER(C.c_uint64), u32p, u32p, u32p, u32p]),
     "rtx_scene_rebuilt_aimed": (C.c_int, [C.c_void_p, f32p, f32p, u32p]),
     "rtx_debug_pose_rebuilt": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, u32p, u32p, u32p, u32p]),
+    "rtx_scene_pose_prims": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPosePrims), C.c_uint32, C.c_uint32, C.POINTER(Stats)]),
+    "rtx_scene_pose_prims_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPosePrims), C.c_uint32, C.c_void_p]),
+    "rtx_scene_pose_prims_records": (C.c_int, [C.c_void_p, C.POINTER(RtxPosePrims), C.c_uint32, C.POINTER(C.c_uint64), u32p, u32p,
+                                              u32p, u32p]),
+    "rtx_scene_pose_prims_aimed": (C.c_int, [C.c_void_p, C.POINTER(RtxPosePrims), C.c_uint32, f32p, u32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -964,6 +979,62 @@ class Scene:
                                            t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p),
                                            aimed.ctypes.data_as(u32p) if eye is not None else None), "rtx_debug_pose_rebuilt")
         return perm, t, s, n, (aimed if eye is not None else None)
+
+    # -- a pose that states every field of a primitive: spheres move, colours change.  None = as uploaded
+    def _prims_struct(self, v0v1v2, spheres, rgb, sphere_rgb, tie_rank):
+        """-> (RtxPosePrims of host pointers, the arrays they point into)"""
+        def shaped(a, rows, cols, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, cols)
+            if len(a) != rows:
+                raise ValueError("a pose has one entry per %s of the scene" % what)
+            return a
+        v, rank = self._pose_arrays(self.tris if v0v1v2 is None else v0v1v2, tie_rank)
+        keep = [v, shaped(spheres, len(self.spheres), 4, "sphere"), shaped(rgb, len(self.tris), 3, "triangle"),
+                shaped(sphere_rgb, len(self.spheres), 3, "sphere"), rank]
+        return RtxPosePrims(*[a.ctypes.data if a is not None and a.size else None for a in keep]), keep
+
+    def pose_prims(self, v0v1v2=None, spheres=None, rgb=None, sphere_rgb=None, device=0, tie_rank=None,
+                   reference_tree=REFTREE_NEVER, rebuilt=False, stats=False):
+        """pose() / pose_rebuilt() with the spheres (float32 [n_spheres, 4]: origin, radius) and the colours of both arms
+        (float32 [n_tris, 3], [n_spheres, 3]) stated too; None: as uploaded (v0v1v2: the scene's own vertices)
+        (rtx_scene_pose_prims).  stats: kernel_ms is the kernels' time, the overlay kernel's included."""
+        prims, keep = self._prims_struct(v0v1v2, spheres, rgb, sphere_rgb, tie_rank)
+        st = Stats()
+        _check(_lib.rtx_scene_pose_prims(self._h, device, C.byref(prims), POSE_REBUILT if rebuilt else 0, int(reference_tree),
+                                         C.byref(st) if stats else None), "rtx_scene_pose_prims")
+        return st.asdict() if stats else None
+
+    def pose_prims_device(self, device, d_v0v1v2_ptr, d_spheres_ptr=None, d_rgb_ptr=None, d_sphere_rgb_ptr=None,
+                          d_tie_rank_ptr=None, rebuilt=False, stream=None):
+        """Asynchronous pose of every field from device arrays the caller owns (None or 0: as uploaded)."""
+        prims = RtxPosePrims(*[p if p else None for p in (d_v0v1v2_ptr, d_spheres_ptr, d_rgb_ptr, d_sphere_rgb_ptr, d_tie_rank_ptr)])
+        _check(_lib.rtx_scene_pose_prims_device(self._h, device, C.byref(prims), POSE_REBUILT if rebuilt else 0,
+                                                C.c_void_p(stream) if stream else None), "rtx_scene_pose_prims_device")
+
+    def pose_prims_records(self, v0v1v2=None, spheres=None, rgb=None, sphere_rgb=None, tie_rank=None, rebuilt=False):
+        """Host only: the words such a pose makes -> posed_records' (tris, shade, nodes), or with rebuilt=True
+        rebuilt_records' (keys, perm, tris, shade, nodes)."""
+        prims, keep = self._prims_struct(v0v1v2, spheres, rgb, sphere_rgb, tie_rank)
+        if rebuilt:
+            perm, t, s, n = self._rebuilt_outputs()
+            keys = np.zeros(len(perm), np.uint64)
+        else:
+            t, s, n = self._pose_outputs()
+        _check(_lib.rtx_scene_pose_prims_records(self._h, C.byref(prims), POSE_REBUILT if rebuilt else 0,
+                                                 keys.ctypes.data_as(C.POINTER(C.c_uint64)) if rebuilt else None,
+                                                 perm.ctypes.data_as(u32p) if rebuilt else None, t.ctypes.data_as(u32p),
+                                                 s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)), "rtx_scene_pose_prims_records")
+        return (keys, perm, t, s, n) if rebuilt else (t, s, n)
+
+    def pose_prims_aimed(self, eye, v0v1v2=None, spheres=None, rgb=None, sphere_rgb=None, rebuilt=False):
+        """Host only: the aim kernels' output over such a pose for `eye` -> uint32 [n_nodes or rebuilt_counts(), 8]."""
+        prims, keep = self._prims_struct(v0v1v2, spheres, rgb, sphere_rgb, None)
+        aimed = np.zeros((self.rebuilt_counts() if rebuilt else self.info()["n_nodes"], 8), np.uint32)
+        _check(_lib.rtx_scene_pose_prims_aimed(self._h, C.byref(prims), POSE_REBUILT if rebuilt else 0, _fp(_f3(eye)),
+                                               aimed.ctypes.data_as(u32p)), "rtx_scene_pose_prims_aimed")
+        return aimed
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
