@@ -20,9 +20,11 @@ __device__ __forceinline__ uint32_t compact_hit_word(uint32_t record, uint32_t w
     return word < 3u ? record * 3u + word : (word < 9u ? 192u + word - 3u : kNone);
 }
 
-// byte of a linear channel: number of thresholds (b >= 1) that are <= x  (color.rs:28-33)
+// byte of a linear channel: number of thresholds (b >= 1) that are <= x  (color.rs:28-33).  -inf counts as +inf: it is
+// the one negative whose power is a number — powf(-inf, 1 / 2.2) = +inf, byte 255; every other negative gives NaN, byte 0
 __device__ __forceinline__ uint32_t quantise(const float *__restrict__ thr, float x)
 {
+    if (x == -__builtin_inff()) x = __builtin_inff();
     uint32_t b = 0;
 #pragma unroll
     for (uint32_t step = 128; step; step >>= 1)

@@ -14,9 +14,11 @@ namespace rtx {
 
 namespace {
 
-// byte of a linear channel: number of thresholds (b >= 1) that are <= x  (color.rs:28-33); the render kernels' search
+// byte of a linear channel: number of thresholds (b >= 1) that are <= x  (color.rs:28-33); the render kernels' search,
+// -inf counted as +inf as there (powf(-inf, 1 / 2.2) = +inf)
 __device__ __forceinline__ uint32_t shade_quantise(const float *__restrict__ thr, float x)
 {
+    if (x == -__builtin_inff()) x = __builtin_inff();
     uint32_t b = 0;
 #pragma unroll
     for (uint32_t step = 128; step; step >>= 1)
