@@ -656,6 +656,56 @@ int rtx_scene_pose_prims_records(const RtxScene *scene, const RtxPosePrims *prim
 int rtx_scene_pose_prims_aimed(const RtxScene *scene, const RtxPosePrims *prims, uint32_t flags, const float eye[3],
                                uint32_t *out_aimed);
 
+/* ---- A pose by affine moves made on the device: the vertices never leave it ---------------------------------------------------
+ * rtx_scene_pose_moved / _device are rtx_scene_pose_prims / _device in every respect not named here: one pose per scene and
+ * device, the pose's aimed stream taken away, the ordering, the tie rule and reference_tree, RTX_POSE_REBUILT, stats
+ * (kernel_ms now includes the move kernel), every posed call over it unchanged.  What differs is where the vertices and the
+ * spheres come from: the device makes them from the scene's geometry AS CREATED (the "rest" geometry: RtxSceneDesc.v0v1v2
+ * and .spheres as given, kept by rtx_scene_create and uploaded once per scene and device with the first such pose) and a
+ * small set of affine maps, "moves"; every primitive names the move it follows, or none.  The per-call input of a rigid
+ * animation is then 48 bytes per move, not 36 bytes per triangle.
+ * The statement (scene_prep.h: move_statement, one text for the host and the device compiler, no contraction):
+ *   a point p under move m (12 floats):  out[r] = ((m[4r] * p0 + m[4r+1] * p1) + m[4r+2] * p2) + m[4r+3]  for r = 0, 1, 2 —
+ *     three products and three sums in this order, each rounded to f32 once;
+ *   a triangle: its three vertices each; a sphere: its origin, and radius * radius_scale[g], one product (radius_scale NULL:
+ *     the radius copied);
+ *   group RTX_MOVE_NONE: the primitive keeps its created words bit for bit.  That is NOT the identity matrix, which turns a
+ *     -0.0 coordinate into +0.0 (-0.0 * 1 + 0 * y + 0 * z + 0 = +0.0); RTX_MOVE_NONE keeps the sign;
+ *   a group value >= n_moves other than RTX_MOVE_NONE: RTX_ERR_BAD_ARG from the host variant, which reads the array; the
+ *     statement and the kernel take it as RTX_MOVE_NONE — `moves` and `radius_scale` are never indexed with a value that
+ *     has not been compared against n_moves, whatever a device array holds.
+ * Triangle::new, get_bounding_box and Sphere::new then run on these values as for any pose: a moved pose is
+ * rtx_scene_pose_prims with the arrays rtx_scene_moved_prims states, word for word.
+ * On the device one kernel runs ahead of the overlay and pose kernels and writes two library-owned grow-only buffers
+ * (n_tris x 9 and n_spheres x 4 floats), which stand where a caller's v0v1v2 and spheres stand.  The host variant copies
+ * moves, group, radius_scale and the colour arrays to the device per call; the device variant's arrays (device pointers,
+ * 4-byte aligned) must stay valid until the kernels have run.
+ * RTX_ERR_BAD_ARG (host variant: all decided before a device is looked for): a NULL scene or struct, a NULL moves, n_moves 0
+ * or above 65,536, an unknown flag or reference_tree, a bad group value (above).  Range rule (host variant:
+ * RTX_ERR_UNSUPPORTED, decided before a device is looked for — the host runs the statement and applies
+ * rtx_scene_pose_prims' rule to its output, so a non-finite entry of a move that is followed fails here, and so does turning
+ * a ground whose corner then leaves rtx_scene_pose_bound; device variant: a stated precondition).  The reference's own
+ * tree (host variant) is built from the statement's output. */
+#define RTX_MOVE_NONE 0xFFFFFFFFu      /* this primitive stays as uploaded: its words are copied, no arithmetic */
+typedef struct RtxPoseMoves {          /* 56 bytes, alignment 8; pointers: host for the host call, device for _device */
+    uint32_t n_moves;                  /* 1 ... 65,536 */
+    const float *moves;                /* n_moves x 12: a 3 x 4 map, row major: rows of A, then the row's translation */
+    const uint32_t *group;             /* NULL (every primitive follows move 0) or one per Vec position */
+    const float *radius_scale;         /* NULL (radii as uploaded) or n_moves: a sphere's radius times this */
+    const float *rgb, *sphere_rgb;     /* as RtxPosePrims': NULL = as uploaded */
+    const uint32_t *tie_rank;          /* as RtxPosePrims' */
+} RtxPoseMoves;
+int rtx_scene_pose_moved(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags /* RTX_POSE_REBUILT or 0 */,
+                         uint32_t reference_tree, RtxStats *stats);
+int rtx_scene_pose_moved_device(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, void *stream);
+/* Host only, no device: the vertices and spheres such a pose makes (either output may be NULL): n_tris x 9 and
+ * n_spheres x 4 floats.  RTX_ERR_BAD_ARG: a NULL scene, struct or moves, n_moves out of range.  Group values are taken as
+ * the statement takes them; nothing is checked against the range rule. */
+int rtx_scene_moved_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres);
+/* Diagnostic: blocks and copies back the arrays the move kernel last wrote on `device` (either may be NULL);
+ * RTX_ERR_BAD_ARG when it never ran there, or when a host pose of another kind has since reused the buffers. */
+int rtx_debug_moved_prims(RtxScene *scene, int device, float *out_v0v1v2, float *out_spheres);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

@@ -141,6 +141,22 @@ pub struct RtxPosePrims {
     pub tie_rank: *const u32,
 }
 pub const RTX_POSE_REBUILT: u32 = 1;
+/// What `rtx_scene_pose_moved` states: `n_moves` (1 ..= 65,536) affine maps of 12 floats (3 x 4, row major: a row of A, then
+/// that row's translation), the move each Vec position follows (`group`: NULL = all follow move 0, `RTX_MOVE_NONE` = the
+/// primitive keeps its created words), a factor per move for a sphere's radius (`radius_scale`, NULL = as uploaded), and
+/// `rgb` / `sphere_rgb` / `tie_rank` as `RtxPosePrims`'.  Host pointers for the host variant, device pointers for `_device`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtxPoseMoves {
+    pub n_moves: u32,
+    pub moves: *const f32,
+    pub group: *const u32,
+    pub radius_scale: *const f32,
+    pub rgb: *const f32,
+    pub sphere_rgb: *const f32,
+    pub tie_rank: *const u32,
+}
+pub const RTX_MOVE_NONE: u32 = 0xFFFF_FFFF;
 pub const RTX_NO_HIT: u32 = 0xFFFF_FFFF;
 pub const RTX_RAYS_KEEP_ORDER: u32 = 1;
 pub const RTX_RAYS_FORCE_REGROUP: u32 = 2;
@@ -285,7 +301,18 @@ extern "C" {
                                         out_perm: *mut u32, out_tris: *mut u32, out_shade: *mut u32, out_nodes: *mut u32) -> c_int;
     pub fn rtx_scene_pose_prims_aimed(scene: *const RtxScene, prims: *const RtxPosePrims, flags: u32, eye: *const f32,
                                       out_aimed: *mut u32) -> c_int;
-    /// Host only: the points of `light` on this scene (`out` may be NULL); returns their number or a negative error.
+    /// A pose whose vertices and spheres the DEVICE makes from the scene's geometry as created and `moves`: everything else
+    /// is `rtx_scene_pose_prims` / `_device`.  A group value that is neither below `n_moves` nor `RTX_MOVE_NONE`:
+    /// `RTX_ERR_BAD_ARG` (host variant); moved primitives beyond `rtx_scene_pose_bound`: `RTX_ERR_UNSUPPORTED` (host variant).
+    pub fn rtx_scene_pose_moved(scene: *mut RtxScene, device: c_int, moves: *const RtxPoseMoves, flags: u32,
+                                reference_tree: u32, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_scene_pose_moved_device(scene: *mut RtxScene, device: c_int, moves: *const RtxPoseMoves, flags: u32,
+                                       stream: *mut c_void) -> c_int;
+    /// Host only: the `n_tris x 9` vertices and `n_spheres x 4` spheres such a pose makes (either may be NULL).
+    pub fn rtx_scene_moved_prims(scene: *const RtxScene, moves: *const RtxPoseMoves, out_v0v1v2: *mut f32,
+                                 out_spheres: *mut f32) -> c_int;
+    /// Diagnostic: the same two arrays as the move kernel last wrote them on `device`; blocks.
+    pub fn rtx_debug_moved_prims(scene: *mut RtxScene, device: c_int, out_v0v1v2: *mut f32, out_spheres: *mut f32) -> c_int;
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.
     pub fn rtx_debug_light_points(scene: *mut RtxScene, device: c_int, light: *const RtxLight, out: *mut f32) -> c_int;

@@ -24,6 +24,7 @@
 #include "rtx_aim.h"
 #include "rtx_device.h"
 #include "rtx_light.h"
+#include "rtx_move.h"
 #include "rtx_planes.h"
 #include "rtx_pose.h"
 #include "rtx_prims.h"
@@ -243,6 +244,17 @@ public:
             DeviceBuffer spheres, rgb, sphere_rgb;
             DeviceBuffer tris, shade;
         } m;
+        // rtx_scene_pose_moved (rtx_move.hip): the scene's rest geometry and its tables (rtx::PreparedScene::rest_*, uploaded
+        // with the first such pose) and the host variant's copies of the caller's moves, groups and radius factors.  The
+        // move kernel writes `v` and `m.spheres` above — the buffers the host poses copy a caller's arrays into — and the
+        // pose reads them from there as it reads those copies.  ran: they hold what the move kernel last wrote
+        // (rtx_debug_moved_prims); a host pose that copies into them takes it away.
+        struct {
+            DeviceBuffer rest_v, rest_spheres, tri_vec, sphere_vec;
+            bool tables = false;
+            DeviceBuffer moves, group, radius_scale;
+            bool ran = false;
+        } f;
     } pose;
 private:
     ~DeviceState() = default;
@@ -999,8 +1011,37 @@ int reserve_prims(RtxScene *scene, DeviceState &st, bool host_copies, const rtx:
     return RTX_OK;
 }
 
+// The buffers of a moved pose (rtx_scene_pose_moved), beside reserve_pose's and by its rule: the rest geometry, uploaded with
+// the first such pose, the two arrays the move kernel writes (pose.v, pose.m.spheres) and, host_copies, room for the host
+// variant's copies of what `mv` gives.  Caller holds the slot's lock and has the device current and the scene uploaded.
+int reserve_moves(RtxScene *scene, DeviceState &st, bool host_copies, const rtx::PoseMoves &mv)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const size_t v = std::max<size_t>(p.rest_v0v1v2.size() * sizeof(float), 16u);
+    const size_t spheres = std::max<size_t>(p.rest_spheres.size() * sizeof(float), 16u);
+    const size_t moves = host_copies ? static_cast<size_t>(mv.n_moves) * 12u * sizeof(float) : 0u;
+    const size_t group = host_copies && mv.group ? std::max<size_t>(p.tris.size() * sizeof(uint32_t), 16u) : 0u;
+    const size_t scale = host_copies && mv.radius_scale ? static_cast<size_t>(mv.n_moves) * sizeof(float) : 0u;
+    auto &q = st.pose;
+    if (q.v.capacity() < v || q.m.spheres.capacity() < spheres || q.f.moves.capacity() < moves || q.f.group.capacity() < group ||
+        q.f.radius_scale.capacity() < scale) {
+        q.valid = false;
+        q.f.ran = false;
+        RTX_HIP(hipDeviceSynchronize());
+        RTX_TRY(reserve_all({{q.v, v}, {q.m.spheres, spheres}, {q.f.moves, moves}, {q.f.group, group}, {q.f.radius_scale, scale}}));
+    }
+    if (!q.f.tables) {
+        RTX_TRY(upload_vec(q.f.rest_v, p.rest_v0v1v2));
+        RTX_TRY(upload_vec(q.f.rest_spheres, p.rest_spheres));
+        RTX_TRY(upload_vec(q.f.tri_vec, p.rest_tri_vec));
+        RTX_TRY(upload_vec(q.f.sphere_vec, p.rest_sphere_vec));
+        q.f.tables = true;
+    }
+    return RTX_OK;
+}
+
 // the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
-// copies of them; d_ov: the sphere and colour arrays of a pose that states them (after reserve_prims), in the same sense:
+// copies of them; ov_in: the sphere and colour arrays of a pose that states them (after reserve_prims), in the same sense:
 // the overlay kernel then runs ahead of the others, which read its records where they read the uploaded ones — the primitive
 // records only with spheres given; nothing given: no launch, no buffer of the overlay's touched.  The records behind the
 // last one (upload_all pads the scene's with the same) are zeroed on the same stream.
@@ -1008,9 +1049,12 @@ int reserve_prims(RtxScene *scene, DeviceState &st, bool host_copies, const rtx:
 // stream's tables; the geometry's node count becomes that stream's.
 // The plane kernel follows them over the posed global triangles (none: no launch).  This is the only writer of the pose's
 // nodes, and it takes the aimed stream's validity away before anything is launched (AimedStream).
-int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, const rtx::PrimsOverlay &d_ov,
-                hipStream_t stream, bool rebuilt)
+// d_moves: a moved pose (after reserve_moves; its arrays on the device): the move kernel runs ahead of all of them and
+// writes pose.v and pose.m.spheres, which then stand where d_pose and d_ov.spheres stand.
+int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, const rtx::PrimsOverlay &ov_in,
+                hipStream_t stream, bool rebuilt, const rtx::PoseMoves *d_moves = nullptr)
 {
+    rtx::PrimsOverlay d_ov = ov_in;
     const rtx::PreparedScene &p = scene->prep;
     const uint32_t n_prims = static_cast<uint32_t>(p.tris.size());
     const uint32_t n_nodes = static_cast<uint32_t>(rebuilt ? scene->rebuild_tables.nodes.size() : p.nodes.size());   // (made: reserve_pose)
@@ -1021,6 +1065,26 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
     st.pose.rebuilt = rebuilt;
     RTX_HIP(hipMemsetAsync(q.tris.as<rtx::TriRec>() + n_prims, 0, sizeof(rtx::TriRec), stream));
     RTX_HIP(hipMemsetAsync(q.nodes.as<rtx::NodeDev>() + n_nodes, 0, sizeof(rtx::NodeDev), stream));
+    if (d_moves) {
+        rtxf::MoveArgs f{};
+        f.rest_v = st.pose.f.rest_v.as<const float>();
+        f.rest_spheres = st.pose.f.rest_spheres.as<const float>();
+        f.tri_vec = st.pose.f.tri_vec.as<const uint32_t>();
+        f.sphere_vec = st.pose.f.sphere_vec.as<const uint32_t>();
+        f.n_triangles = posed_triangles(scene);
+        f.n_spheres = p.n_spheres;
+        f.n_moves = d_moves->n_moves;
+        f.moves = d_moves->moves;
+        f.group = d_moves->group;
+        f.radius_scale = d_moves->radius_scale;
+        f.out_v = st.pose.v.as<float>();
+        f.out_spheres = st.pose.m.spheres.as<float>();
+        st.pose.f.ran = false;
+        RTX_HIP(rtxf::launch_move(f, stream));
+        st.pose.f.ran = true;
+        d_pose = f.n_triangles ? f.out_v : nullptr;
+        d_ov.spheres = f.n_spheres ? f.out_spheres : nullptr;
+    }
     rtxp::PoseArgs a{};
     a.tris = st.geo.tris.as<const rtx::TriRec>();
     a.shade = st.geo.shade.as<const rtx::ShadeRec>();
@@ -1510,16 +1574,38 @@ int prims_of(const RtxScene *scene, const RtxPosePrims *in, const float **v0v1v2
     return RTX_OK;
 }
 
+// What rtx_scene_pose_moved reads of its struct for `scene`, as prims_of: the colours of an arm the scene does not have are
+// not read.  RTX_ERR_BAD_ARG for a NULL `moves` or a count outside 1 ... 65,536.
+int moves_of(const RtxScene *scene, const RtxPoseMoves *in, rtx::PoseMoves *mv, rtx::PrimsOverlay *ov)
+{
+    if (!in->moves || in->n_moves == 0u || in->n_moves > rtx::kMaxMoves) return RTX_ERR_BAD_ARG;
+    mv->n_moves = in->n_moves;
+    mv->moves = in->moves;
+    mv->group = in->group;
+    mv->radius_scale = in->radius_scale;
+    ov->rgb = posed_triangles(scene) != 0u ? in->rgb : nullptr;
+    ov->sphere_rgb = scene->prep.n_spheres != 0u ? in->sphere_rgb : nullptr;
+    return RTX_OK;
+}
+
 // The bodies of rtx_scene_pose / rtx_scene_pose_device and of their _rebuilt twins: everything but the tree is the same.
 // prims: rtx_scene_pose_prims' bodies — v0v1v2 may be NULL for a scene without triangles, and ov is what the call states
 // beside the vertices; the other entry points give none, and nothing of the overlay's is then reserved, copied or launched.
+// moves: rtx_scene_pose_moved's bodies — v0v1v2 is NULL and ov_in states no spheres: the device makes both from the moves,
+// the caller has applied the range rule to the host statement (rtx::moved_in_range), and only the reference's own tree has
+// the statement's output made on the host.
 int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
-              RtxStats *stats, bool rebuilt, bool prims = false, const rtx::PrimsOverlay &ov = rtx::PrimsOverlay())
+              RtxStats *stats, bool rebuilt, bool prims = false, const rtx::PrimsOverlay &ov_in = rtx::PrimsOverlay(),
+              const rtx::PoseMoves *moves = nullptr)
 {
-    if (!scene || (!v0v1v2 && (!prims || posed_triangles(scene) != 0u)) || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
+    if (!scene || (!v0v1v2 && !moves && (!prims || posed_triangles(scene) != 0u)) || reference_tree > RTX_REFTREE_NEVER)
+        return RTX_ERR_BAD_ARG;
     const rtx::PreparedScene &p = scene->prep;
     if (v0v1v2 && !rtx::pose_in_range(p, v0v1v2)) return RTX_ERR_UNSUPPORTED;
-    if (ov.spheres && !rtx::spheres_in_range(p, ov.spheres)) return RTX_ERR_UNSUPPORTED;
+    if (ov_in.spheres && !rtx::spheres_in_range(p, ov_in.spheres)) return RTX_ERR_UNSUPPORTED;
+    rtx::PrimsOverlay ov = ov_in;
+    // a moved pose states spheres wherever the scene has some: the rest array stands for "given" (it is never copied)
+    if (moves && p.n_spheres) ov.spheres = p.rest_spheres.data();
     const rtx::PrimsOverlay *pov = ov.any() ? &ov : nullptr;
     const Timed timed(stats);
     Entry e(scene, device, Entry::kUploaded);
@@ -1529,7 +1615,15 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     const bool want_ref = reference_tree == RTX_REFTREE_ALWAYS || (reference_tree == RTX_REFTREE_AUTO && n_prims <= rtx::kRefTreeAutoMax);
     std::vector<uint32_t> ref_rank;
     std::vector<rtx::NodeDev> ref_stream;
+    std::vector<float> moved_v, moved_spheres;
     try {
+        if (want_ref && moves) {      // the reference's own tree is built from the statement's output
+            moved_v.resize(p.rest_v0v1v2.size());
+            moved_spheres.resize(p.rest_spheres.size());
+            rtx::moved_prims(p, *moves, moved_v.data(), moved_spheres.data());
+            v0v1v2 = moved_v.data();
+            if (p.n_spheres) ov.spheres = moved_spheres.data();
+        }
         if (want_ref) {
             std::vector<rtx::NodeRec> stream;
             if (rebuilt) {      // the leaves name positions of the sorted array: through the host statement's permutation
@@ -1548,17 +1642,36 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     const uint32_t *rank = tie_rank ? tie_rank : (want_ref ? ref_rank.data() : nullptr);
     RTX_TRY(reserve_pose(scene, st, true, ref_stream.size(), rebuilt));
     if (pov) RTX_TRY(reserve_prims(scene, st, true, ov));
+    if (moves) RTX_TRY(reserve_moves(scene, st, true, *moves));
     RTX_TRY(wait_for_uses(st, kUsesPose));      // a device-resident call may still read the pose this one replaces
-    const size_t v_bytes = static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
+    const size_t v_bytes = moves ? 0u : static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
     hipError_t he = hipSuccess;
+    if (!moves) st.pose.f.ran = false;      // (the copies below overwrite what the move kernel wrote)
     if (v_bytes) he = hipMemcpyAsync(st.pose.v.as<void>(), v0v1v2, v_bytes, hipMemcpyHostToDevice, st.stream);
     rtx::PrimsOverlay d_ov;
+    rtx::PoseMoves d_moves;
+    if (moves) {
+        auto &f = st.pose.f;
+        d_moves.n_moves = moves->n_moves;
+        he = hipMemcpyAsync(f.moves.as<void>(), moves->moves, static_cast<size_t>(moves->n_moves) * 12u * sizeof(float),
+                            hipMemcpyHostToDevice, st.stream);
+        d_moves.moves = f.moves.as<const float>();
+        if (he == hipSuccess && moves->group) {
+            he = hipMemcpyAsync(f.group.as<void>(), moves->group, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
+            d_moves.group = f.group.as<const uint32_t>();
+        }
+        if (he == hipSuccess && moves->radius_scale) {
+            he = hipMemcpyAsync(f.radius_scale.as<void>(), moves->radius_scale, static_cast<size_t>(moves->n_moves) * sizeof(float),
+                                hipMemcpyHostToDevice, st.stream);
+            d_moves.radius_scale = f.radius_scale.as<const float>();
+        }
+    }
     auto copy_in = [&](const float *from, DeviceBuffer &to, size_t floats, const float *&d) {      // (an array not given: nothing)
         if (he != hipSuccess || !from) return;
         he = hipMemcpyAsync(to.as<void>(), from, floats * sizeof(float), hipMemcpyHostToDevice, st.stream);
         d = to.as<const float>();
     };
-    copy_in(ov.spheres, st.pose.m.spheres, static_cast<size_t>(p.n_spheres) * 4u, d_ov.spheres);
+    copy_in(moves ? nullptr : ov.spheres, st.pose.m.spheres, static_cast<size_t>(p.n_spheres) * 4u, d_ov.spheres);
     copy_in(ov.rgb, st.pose.m.rgb, static_cast<size_t>(posed_triangles(scene)) * 3u, d_ov.rgb);
     copy_in(ov.sphere_rgb, st.pose.m.sphere_rgb, static_cast<size_t>(p.n_spheres) * 3u, d_ov.sphere_rgb);
     if (he == hipSuccess && rank)
@@ -1573,7 +1686,7 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     if (rc == RTX_OK) rc = timed.begin(st);
     if (rc == RTX_OK)
         rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, d_ov, st.stream,
-                         rebuilt);
+                         rebuilt, moves ? &d_moves : nullptr);
     if (rc == RTX_OK) rc = timed.end(st);
     if (rc != RTX_OK) {
         st.pose.valid = false;
@@ -1585,19 +1698,27 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
 }
 
 int pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream, bool rebuilt,
-                bool prims = false, const rtx::PrimsOverlay &d_ov = rtx::PrimsOverlay())
+                bool prims = false, const rtx::PrimsOverlay &ov_in = rtx::PrimsOverlay(), const rtx::PoseMoves *d_moves = nullptr)
 {
-    if (!scene || (!d_v0v1v2 && (!prims || posed_triangles(scene) != 0u))) return RTX_ERR_BAD_ARG;
+    rtx::PrimsOverlay d_ov = ov_in;
+    if (!scene || (!d_v0v1v2 && !d_moves && (!prims || posed_triangles(scene) != 0u))) return RTX_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(d_v0v1v2) | reinterpret_cast<uintptr_t>(d_tie_rank) | reinterpret_cast<uintptr_t>(d_ov.spheres) |
          reinterpret_cast<uintptr_t>(d_ov.rgb) | reinterpret_cast<uintptr_t>(d_ov.sphere_rgb)) & 3u)
+        return RTX_ERR_BAD_ARG;
+    if (d_moves && ((reinterpret_cast<uintptr_t>(d_moves->moves) | reinterpret_cast<uintptr_t>(d_moves->group) |
+                     reinterpret_cast<uintptr_t>(d_moves->radius_scale)) & 3u))
         return RTX_ERR_BAD_ARG;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
     RTX_TRY(reserve_pose(scene, st, false, 0u, rebuilt));
+    if (d_moves) {      // (the overlay's primitive records are reserved where spheres are stated: the move kernel's)
+        RTX_TRY(reserve_moves(scene, st, false, *d_moves));
+        if (scene->prep.n_spheres) d_ov.spheres = st.pose.m.spheres.as<const float>();
+    }
     if (d_ov.any()) RTX_TRY(reserve_prims(scene, st, false, d_ov));
     RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank), d_ov,
-                        static_cast<hipStream_t>(stream), rebuilt));
+                        static_cast<hipStream_t>(stream), rebuilt, d_moves));
     return mark_uses(st, kUsesPose, static_cast<hipStream_t>(stream));
 }
 
@@ -2161,6 +2282,52 @@ int rtx_scene_pose_prims_aimed(const RtxScene *scene, const RtxPosePrims *prims,
         return RTX_ERR_OOM;
     }
     return RTX_OK;
+}
+
+int rtx_scene_moved_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres)
+{
+    if (!scene || !moves) return RTX_ERR_BAD_ARG;
+    rtx::PoseMoves mv;
+    rtx::PrimsOverlay ov;
+    RTX_TRY(moves_of(scene, moves, &mv, &ov));
+    rtx::moved_prims(scene->prep, mv, out_v0v1v2, out_spheres);
+    return RTX_OK;
+}
+
+int rtx_scene_pose_moved(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, uint32_t reference_tree,
+                         RtxStats *stats)
+{
+    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT) || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
+    rtx::PoseMoves mv;
+    rtx::PrimsOverlay ov;
+    RTX_TRY(moves_of(scene, moves, &mv, &ov));
+    if (!rtx::move_groups_ok(scene->prep, mv)) return RTX_ERR_BAD_ARG;
+    if (!rtx::moved_in_range(scene->prep, mv)) return RTX_ERR_UNSUPPORTED;      // the statement on the host, nothing stored
+    return pose_host(scene, device, nullptr, moves->tie_rank, reference_tree, stats, (flags & RTX_POSE_REBUILT) != 0u, true, ov, &mv);
+}
+
+int rtx_scene_pose_moved_device(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, void *stream)
+{
+    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
+    rtx::PoseMoves d_mv;
+    rtx::PrimsOverlay d_ov;
+    RTX_TRY(moves_of(scene, moves, &d_mv, &d_ov));
+    return pose_device(scene, device, nullptr, moves->tie_rank, stream, (flags & RTX_POSE_REBUILT) != 0u, true, d_ov, &d_mv);
+}
+
+int rtx_debug_moved_prims(RtxScene *scene, int device, float *out_v0v1v2, float *out_spheres)
+{
+    if (!scene) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    if (!st.pose.f.ran) return RTX_ERR_BAD_ARG;
+    const size_t v_bytes = scene->prep.rest_v0v1v2.size() * sizeof(float), s_bytes = scene->prep.rest_spheres.size() * sizeof(float);
+    RTX_TRY(wait_for_uses(st, kUsesPose));
+    if (out_v0v1v2 && v_bytes) RTX_HIP(hipMemcpyAsync(out_v0v1v2, st.pose.v.as<void>(), v_bytes, hipMemcpyDeviceToHost, st.stream));
+    if (out_spheres && s_bytes)
+        RTX_HIP(hipMemcpyAsync(out_spheres, st.pose.m.spheres.as<void>(), s_bytes, hipMemcpyDeviceToHost, st.stream));
+    return read_back_nodes(st, nullptr, 0u, nullptr);
 }
 
 int rtx_debug_pose_rebuilt(RtxScene *scene, int device, const float eye[3], uint32_t *out_perm, uint32_t *out_tris,

@@ -656,9 +656,17 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
         std::vector<TriRec> recs(n_prims);
         std::vector<float> boxes(6 * static_cast<size_t>(n_prims));
         s.shade.resize(n_prims);
+        // the rest geometry of rtx_scene_pose_moved: the arrays as given, and each entry's position in the Vec
+        if (d.n_tris) s.rest_v0v1v2.assign(d.v0v1v2, d.v0v1v2 + 9 * static_cast<size_t>(d.n_tris));
+        if (d.n_spheres) s.rest_spheres.assign(d.spheres, d.spheres + 4 * static_cast<size_t>(d.n_spheres));
+        s.rest_tri_vec.clear();
+        s.rest_sphere_vec.clear();
+        s.rest_tri_vec.reserve(d.n_tris);
+        s.rest_sphere_vec.reserve(d.n_spheres);
         uint32_t next_tri = 0, next_sphere = 0;
         for (uint32_t i = 0; i < n_prims; ++i) {
             const bool sphere = d.kinds ? d.kinds[i] != 0 : i >= d.n_tris;
+            (sphere ? s.rest_sphere_vec : s.rest_tri_vec).push_back(i);
             TriRec &r = recs[i];
             ShadeRec &sh = s.shade[i];
             std::memset(&r, 0, sizeof r);
@@ -1061,17 +1069,65 @@ bool pose_in_range(const PreparedScene &s, const float *pose)
     return true;
 }
 
+namespace {
+bool sphere_in_range(const PreparedScene &s, const float *p)
+{
+    float v0[3], e1[3], lo[3], hi[3], origin[3];
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(p[k])) return false;
+    sphere_statement(p, v0, e1, lo, hi, origin);
+    for (int k = 0; k < 3; ++k)
+        if (!(std::fabs(lo[k]) <= s.scene_magnitude) || !(std::fabs(hi[k]) <= s.scene_magnitude)) return false;
+    return true;
+}
+}  // namespace
+
 bool spheres_in_range(const PreparedScene &s, const float *spheres)
 {
-    for (size_t i = 0; i < s.n_spheres; ++i) {
-        const float *p = spheres + 4u * i;
-        float v0[3], e1[3], lo[3], hi[3], origin[3];
-        for (int k = 0; k < 4; ++k)
-            if (!std::isfinite(p[k])) return false;
-        sphere_statement(p, v0, e1, lo, hi, origin);
-        for (int k = 0; k < 3; ++k)
-            if (!(std::fabs(lo[k]) <= s.scene_magnitude) || !(std::fabs(hi[k]) <= s.scene_magnitude)) return false;
+    for (size_t i = 0; i < s.n_spheres; ++i)
+        if (!sphere_in_range(s, spheres + 4u * i)) return false;
+    return true;
+}
+
+void moved_prims(const PreparedScene &s, const PoseMoves &m, float *out_v0v1v2, float *out_spheres)
+{
+    if (out_v0v1v2)
+        for (size_t t = 0; t < s.rest_tri_vec.size(); ++t) {
+            const uint32_t g = m.group ? m.group[s.rest_tri_vec[t]] : 0u;
+            for (size_t k = 0; k < 3u; ++k)
+                move_statement(m.moves, m.radius_scale, m.n_moves, g, false, &s.rest_v0v1v2[9u * t + 3u * k], out_v0v1v2 + 9u * t + 3u * k);
+        }
+    if (out_spheres)
+        for (size_t i = 0; i < s.rest_sphere_vec.size(); ++i) {
+            const uint32_t g = m.group ? m.group[s.rest_sphere_vec[i]] : 0u;
+            move_statement(m.moves, m.radius_scale, m.n_moves, g, true, &s.rest_spheres[4u * i], out_spheres + 4u * i);
+        }
+}
+
+bool moved_in_range(const PreparedScene &s, const PoseMoves &m)
+{
+    for (size_t t = 0; t < s.rest_tri_vec.size(); ++t) {
+        const uint32_t g = m.group ? m.group[s.rest_tri_vec[t]] : 0u;
+        for (size_t k = 0; k < 3u; ++k) {
+            float out[3];
+            move_statement(m.moves, m.radius_scale, m.n_moves, g, false, &s.rest_v0v1v2[9u * t + 3u * k], out);
+            for (int c = 0; c < 3; ++c)
+                if (!(std::fabs(out[c]) <= s.scene_magnitude)) return false;      // (false for a NaN)
+        }
     }
+    for (size_t i = 0; i < s.rest_sphere_vec.size(); ++i) {
+        float out[4];
+        move_statement(m.moves, m.radius_scale, m.n_moves, m.group ? m.group[s.rest_sphere_vec[i]] : 0u, true, &s.rest_spheres[4u * i], out);
+        if (!sphere_in_range(s, out)) return false;
+    }
+    return true;
+}
+
+bool move_groups_ok(const PreparedScene &s, const PoseMoves &m)
+{
+    if (!m.group) return true;
+    for (size_t i = 0; i < s.n_tris; ++i)
+        if (m.group[i] >= m.n_moves && m.group[i] != kMoveNone) return false;
     return true;
 }
 

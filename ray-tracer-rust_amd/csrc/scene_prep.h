@@ -191,6 +191,30 @@ RTX_HOST_DEVICE inline void sphere_statement(const float s[4], float v0[3], floa
     }
 }
 
+// A pose made from the scene's vertices as created and a set of affine maps (rtx_scene_pose_moved; the kernel:
+// rtx_move.hip).  A move is 12 floats, a 3 x 4 map, row major: the three words of a row of A, then the row's translation.
+// One statement for a vertex (sphere = false: 3 words in, 3 out) and for a sphere's {origin x, y, z, radius} (sphere = true:
+// 4 words): under move g, out[r] = ((m[4r] * p0 + m[4r+1] * p1) + m[4r+2] * p2) + m[4r+3] — three products and three sums in
+// this order, each rounded to f32 once (both compilers run it under -ffp-contract=off) — and a sphere's radius times
+// radius_scale[g], one product, or copied where radius_scale is NULL.  g == kMoveNone, and any other g that is not below
+// n_moves, copies the words as they are: neither `moves` nor `radius_scale` is indexed with a value that has not been
+// compared against n_moves.  The copy keeps the sign of a -0.0, which the identity matrix does not (-0.0 + 0.0 = +0.0).
+// One text for both compilers, as triangle_statement and sphere_statement are: moved_prims on the host,
+// rtxf::move_kernel on the device.
+constexpr uint32_t kMoveNone = 0xFFFFFFFFu;
+constexpr uint32_t kMaxMoves = 65536u;
+RTX_HOST_DEVICE inline void move_statement(const float *moves, const float *radius_scale, uint32_t n_moves, uint32_t g,
+                                           bool sphere, const float *in, float *out)
+{
+    if (g >= n_moves) {
+        for (int k = 0; k < (sphere ? 4 : 3); ++k) out[k] = in[k];
+        return;
+    }
+    const float *m = moves + 12u * static_cast<size_t>(g);
+    for (int r = 0; r < 3; ++r) out[r] = ((m[4 * r] * in[0] + m[4 * r + 1] * in[1]) + m[4 * r + 2] * in[2]) + m[4 * r + 3];
+    if (sphere) out[3] = radius_scale ? in[3] * radius_scale[g] : in[3];
+}
+
 // Shading data of a primitive, indexed by its position in the caller's Vec<Primitive> (read once per hit).
 struct ShadeRec {
     float    normal[3];   // triangle: Triangle::new, triangle.rs:29; sphere: its origin (normal = normalize(p_hit - origin), sphere.rs:93-95)
@@ -254,6 +278,11 @@ struct PreparedScene {
     // sample table gives no proper frustum.
     std::vector<uint32_t> long_tiles, long_weights, long_bits;
     float sample_lo[2] = {0.0f, 0.0f}, sample_hi[2] = {0.0f, 0.0f};   // range of the sample table's two columns (NaN: not finite)
+    // The "rest" geometry of rtx_scene_pose_moved: RtxSceneDesc.v0v1v2 and .spheres as given (a primitive record keeps v0,
+    // e1 and e2, from which v1 and v2 cannot be had exactly), and for every triangle and every sphere its position in the
+    // Vec, where a pose's `group` array names its move.  No record, stream or table above is made from them.
+    std::vector<float>    rest_v0v1v2, rest_spheres;     // n_triangles x 9, n_spheres x 4
+    std::vector<uint32_t> rest_tri_vec, rest_sphere_vec; // n_triangles, n_spheres
 };
 // A tile is long when the records its frustum meets weigh at least this much (an inner record 1, a leaf 1 + 3 x its
 // primitive records: the proxy of rtx_pass_schedule.hpp's cut).  Chosen by measurement (the
@@ -370,6 +399,22 @@ void overlay_records(const PreparedScene &s, const PoseTables &t, const PrimsOve
 // pose_in_range's rule for posed spheres: all four values finite, and the six box words origin -+ radius, as
 // sphere_statement rounds them, of magnitude at most scene_magnitude
 bool spheres_in_range(const PreparedScene &s, const float *spheres);
+// What a moved pose states (rtx_scene_pose_moved): n_moves maps of 12 floats, the move each Vec position follows (group:
+// NULL, every primitive follows move 0; kMoveNone: none) and a factor per move for a sphere's radius (NULL: radii as
+// created).  moved_prims is the host statement of rtxf::move_kernel: move_statement over the rest geometry, into the
+// arrays rtx_scene_pose_prims is then handed as v0v1v2 (n_triangles x 9) and spheres (n_spheres x 4).  Either may be NULL.
+struct PoseMoves {
+    uint32_t n_moves = 0;
+    const float *moves = nullptr;
+    const uint32_t *group = nullptr;
+    const float *radius_scale = nullptr;
+};
+void moved_prims(const PreparedScene &s, const PoseMoves &m, float *out_v0v1v2, float *out_spheres);
+// pose_in_range and spheres_in_range over moved_prims' output, stated without making it: the statement runs once more per
+// vertex and sphere, and nothing is stored (a moved pose's host call touches no array of the pose's size but `group`)
+bool moved_in_range(const PreparedScene &s, const PoseMoves &m);
+// the host variant's rule for `group`: every entry below n_moves or kMoveNone (true for a NULL array)
+bool move_groups_ok(const PreparedScene &s, const PoseMoves &m);
 // The host statement of what the pose kernels make.  rank: per Vec position, or NULL for the position itself.  tris:
 // n_prims records in leaf order; shade: n_prims in Vec order; nodes: n_nodes records in NodeRec's word order, the planes
 // moved outwards by cull_delta in f32 as nodes_in_device_order moves them.  Each output may be NULL.  ov: NULL, or what

@@ -140,6 +140,18 @@ assert C.sizeof(RtxPosePrims) == 40 and C.alignment(RtxPosePrims) == 8
 POSE_REBUILT = 1
 
 
+class RtxPoseMoves(C.Structure):
+    """RtxPoseMoves: the moves of a pose the device makes from the scene's geometry as created — host pointers for
+    rtx_scene_pose_moved, device ones for _device."""
+    _fields_ = [("n_moves", C.c_uint32), ("moves", C.c_void_p), ("group", C.c_void_p), ("radius_scale", C.c_void_p),
+                ("rgb", C.c_void_p), ("sphere_rgb", C.c_void_p), ("tie_rank", C.c_void_p)]
+
+
+assert C.sizeof(RtxPoseMoves) == 56 and C.alignment(RtxPoseMoves) == 8
+MOVE_NONE = 0xFFFFFFFF
+MAX_MOVES = 65536
+
+
 # every symbol include/rtx.h declares (tests check the export list against the header)
 _SIGS = {
     "rtx_abi_version": (C.c_int, []),
@@ -224,6 +236,10 @@ _SIGS = {
     "rtx_scene_pose_prims_records": (C.c_int, [C.c_void_p, C.POINTER(RtxPosePrims), C.c_uint32, C.POINTER(C.c_uint64), u32p, u32p,
                                               u32p, u32p]),
     "rtx_scene_pose_prims_aimed": (C.c_int, [C.c_void_p, C.POINTER(RtxPosePrims), C.c_uint32, f32p, u32p]),
+    "rtx_scene_pose_moved": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPoseMoves), C.c_uint32, C.c_uint32, C.POINTER(Stats)]),
+    "rtx_scene_pose_moved_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPoseMoves), C.c_uint32, C.c_void_p]),
+    "rtx_scene_moved_prims": (C.c_int, [C.c_void_p, C.POINTER(RtxPoseMoves), f32p, f32p]),
+    "rtx_debug_moved_prims": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -1035,6 +1051,54 @@ class Scene:
         _check(_lib.rtx_scene_pose_prims_aimed(self._h, C.byref(prims), POSE_REBUILT if rebuilt else 0, _fp(_f3(eye)),
                                                aimed.ctypes.data_as(u32p)), "rtx_scene_pose_prims_aimed")
         return aimed
+
+    # -- a pose the device makes from the scene's geometry as created and a set of affine moves
+    def _moves_struct(self, moves, group, radius_scale, rgb=None, sphere_rgb=None, tie_rank=None):
+        """-> (RtxPoseMoves of host pointers, the arrays they point into)"""
+        m = np.ascontiguousarray(moves, dtype=np.float32).reshape(-1, 12)
+        g = None if group is None else np.ascontiguousarray(group, dtype=np.uint32).reshape(-1)
+        if g is not None and len(g) != self.n_prims:
+            raise ValueError("group has one entry per primitive of the scene")
+        r = None if radius_scale is None else np.ascontiguousarray(radius_scale, dtype=np.float32).reshape(-1)
+        if r is not None and len(r) != len(m):
+            raise ValueError("radius_scale has one entry per move")
+        prims, keep = self._prims_struct(None, None, rgb, sphere_rgb, tie_rank)
+        keep = [m, g, r] + keep
+        addr = lambda a: a.ctypes.data if a is not None and a.size else None
+        return RtxPoseMoves(len(m), addr(m), addr(g), addr(r), prims.rgb, prims.sphere_rgb, prims.tie_rank), keep
+
+    def pose_moved(self, moves, group=None, radius_scale=None, rgb=None, sphere_rgb=None, device=0, tie_rank=None,
+                   reference_tree=REFTREE_NEVER, rebuilt=False, stats=False):
+        """pose_prims() with the vertices and the spheres made ON THE DEVICE: moves float32 [n_moves, 12] (3 x 4 maps, row
+        major), group uint32 [n_prims] (the move each Vec position follows, MOVE_NONE: none; None: all follow move 0),
+        radius_scale float32 [n_moves] or None (rtx_scene_pose_moved).  stats: kernel_ms includes the move kernel."""
+        mv, keep = self._moves_struct(moves, group, radius_scale, rgb, sphere_rgb, tie_rank)
+        st = Stats()
+        _check(_lib.rtx_scene_pose_moved(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0, int(reference_tree),
+                                         C.byref(st) if stats else None), "rtx_scene_pose_moved")
+        return st.asdict() if stats else None
+
+    def pose_moved_device(self, device, n_moves, d_moves_ptr, d_group_ptr=None, d_radius_scale_ptr=None, d_rgb_ptr=None,
+                          d_sphere_rgb_ptr=None, d_tie_rank_ptr=None, rebuilt=False, stream=None):
+        """Asynchronous moved pose from device arrays the caller owns (None or 0: no such array)."""
+        mv = RtxPoseMoves(int(n_moves), *[p if p else None for p in (d_moves_ptr, d_group_ptr, d_radius_scale_ptr, d_rgb_ptr,
+                                                                     d_sphere_rgb_ptr, d_tie_rank_ptr)])
+        _check(_lib.rtx_scene_pose_moved_device(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0,
+                                                C.c_void_p(stream) if stream else None), "rtx_scene_pose_moved_device")
+
+    def moved_prims(self, moves, group=None, radius_scale=None):
+        """Host only: the arrays such a pose makes -> (v0v1v2 float32 [n_tris, 9], spheres float32 [n_spheres, 4])
+        (rtx_scene_moved_prims)."""
+        mv, keep = self._moves_struct(moves, group, radius_scale)
+        v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
+        _check(_lib.rtx_scene_moved_prims(self._h, C.byref(mv), _fp(v), _fp(sph)), "rtx_scene_moved_prims")
+        return v, sph
+
+    def debug_moved_prims(self, device=0):
+        """Diagnostic: the arrays the move kernel last wrote on `device`, in moved_prims' form (rtx_debug_moved_prims)."""
+        v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
+        _check(_lib.rtx_debug_moved_prims(self._h, device, _fp(v), _fp(sph)), "rtx_debug_moved_prims")
+        return v, sph
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
