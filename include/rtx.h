@@ -702,9 +702,51 @@ int rtx_scene_pose_moved_device(RtxScene *scene, int device, const RtxPoseMoves 
  * n_spheres x 4 floats.  RTX_ERR_BAD_ARG: a NULL scene, struct or moves, n_moves out of range.  Group values are taken as
  * the statement takes them; nothing is checked against the range rule. */
 int rtx_scene_moved_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres);
-/* Diagnostic: blocks and copies back the arrays the move kernel last wrote on `device` (either may be NULL);
- * RTX_ERR_BAD_ARG when it never ran there, or when a host pose of another kind has since reused the buffers. */
+/* Diagnostic: blocks and copies back the arrays the move or skin kernel last wrote on `device` (either may be NULL);
+ * RTX_ERR_BAD_ARG when neither ever ran there, or when a host pose of another kind has since reused the buffers. */
 int rtx_debug_moved_prims(RtxScene *scene, int device, float *out_v0v1v2, float *out_spheres);
+
+/* ---- A skinned pose: weighted moves per triangle corner, made on the device -------------------------------------------------
+ * A moved pose lets a PRIMITIVE follow one move; a mesh that bends needs every CORNER to blend several.  A skin is bound to
+ * the scene once — per triangle corner four move indices ("bones") and four weights, per sphere one move index — and a
+ * skinned pose then takes only the moves: 48 bytes per move and frame, as a moved pose does, and nothing of the scene's size.
+ * The statement for one corner (scene_prep.h: skin_statement, one text for the host and the device compiler, no
+ * contraction), with p the corner as created:
+ *   all four bones >= n_moves (RTX_MOVE_NONE is such a value): the corner keeps its created words bit for bit — no
+ *     arithmetic, so the sign of a -0.0 survives; this is how the ground stays put;
+ *   otherwise q_k = p under move bones[k] by rtx_scene_pose_moved's statement (a bone that is not below n_moves: q_k = p
+ *     itself), and out[r] = ((w0 * q0[r] + w1 * q1[r]) + w2 * q2[r]) + w3 * q3[r] for r = 0, 1, 2 — four products and three
+ *     sums in this order, each rounded to f32 once.  A slot of weight 0 still takes part: 1 * -0.0 + 0 * x is +0.0.
+ *   Weights are taken as given: not normalised, not required to sum to 1; a weighted RTX_MOVE_NONE slot blends towards the
+ *     rest position.  `moves` is never indexed with a value that has not been compared against n_moves.
+ *   A sphere follows sphere_bone[s] exactly as a moved pose's sphere follows group[its position], radius_scale included.
+ * rtx_scene_skin copies the arrays into the scene (host memory kept: 96 bytes per triangle and 4 per sphere — taking the
+ * arrays per call instead would cost more per frame than the vertices they replace), replaces any previous skin and records
+ * the largest bone other than RTX_MOVE_NONE; a NULL skin unbinds.  Like create and destroy it is not re-entrant per handle:
+ * no other call on the scene may run beside it.  It touches no device and no pose that stands on one: each device uploads
+ * the skin (library-owned, grow-only, 16-byte aligned buffers) with its first skinned pose after a bind.
+ * RTX_ERR_BAD_ARG: a NULL scene, NULL bones or weights with triangles present.  RTX_ERR_UNSUPPORTED: a weight that is not
+ * finite.  On an error the previous skin stays bound.
+ * rtx_scene_skin_bound: 1 when a skin is bound, 0 when not (RTX_ERR_BAD_ARG for a NULL scene); *out_max_bone (may be NULL):
+ * the largest bone other than RTX_MOVE_NONE over corners and spheres, 0 when there is none or no skin.
+ * rtx_scene_pose_skinned / _device / rtx_scene_skinned_prims are rtx_scene_pose_moved / _device / rtx_scene_moved_prims in
+ * every respect not named here (stats: kernel_ms includes the skin kernel; rtx_debug_moved_prims reads its arrays).  What
+ * differs: moves->group must be NULL (the skin names the moves) and a skin must be bound, else RTX_ERR_BAD_ARG; the host
+ * variant also returns RTX_ERR_BAD_ARG when n_moves <= the bind's largest bone (an O(1) check) and RTX_ERR_UNSUPPORTED by
+ * the range rule over the statement's output, all before a device is looked for, and copies moves, radius_scale and the
+ * colour arrays per call, nothing else.  For the device variant both are stated preconditions: outside them the call
+ * still terminates and indexes nothing unchecked; the values are unspecified. */
+typedef struct RtxSkin {               /* 24 bytes, alignment 8; host pointers */
+    const uint32_t *bones;             /* n_triangles x 3 x 4: per corner (v0, v1, v2 in RtxSceneDesc.v0v1v2 order, spheres skipped) */
+    const float *weights;              /* n_triangles x 3 x 4 */
+    const uint32_t *sphere_bone;       /* NULL (every sphere RTX_MOVE_NONE) or n_spheres */
+} RtxSkin;
+int rtx_scene_skin(RtxScene *scene, const RtxSkin *skin);
+int rtx_scene_skin_bound(const RtxScene *scene, uint32_t *out_max_bone);
+int rtx_scene_pose_skinned(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags /* RTX_POSE_REBUILT or 0 */,
+                           uint32_t reference_tree, RtxStats *stats);
+int rtx_scene_pose_skinned_device(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, void *stream);
+int rtx_scene_skinned_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres);
 
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),

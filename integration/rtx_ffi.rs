@@ -157,6 +157,16 @@ pub struct RtxPoseMoves {
     pub tie_rank: *const u32,
 }
 pub const RTX_MOVE_NONE: u32 = 0xFFFF_FFFF;
+/// What `rtx_scene_skin` binds (host pointers, copied by the call): per triangle corner four move indices and four weights
+/// (`n_triangles x 3 x 4` each, corners in `RtxSceneDesc.v0v1v2` order), per sphere one move index (`sphere_bone`: NULL =
+/// every sphere `RTX_MOVE_NONE`).  The scene keeps 96 bytes per triangle.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtxSkin {
+    pub bones: *const u32,
+    pub weights: *const f32,
+    pub sphere_bone: *const u32,
+}
 pub const RTX_NO_HIT: u32 = 0xFFFF_FFFF;
 pub const RTX_RAYS_KEEP_ORDER: u32 = 1;
 pub const RTX_RAYS_FORCE_REGROUP: u32 = 2;
@@ -311,8 +321,22 @@ extern "C" {
     /// Host only: the `n_tris x 9` vertices and `n_spheres x 4` spheres such a pose makes (either may be NULL).
     pub fn rtx_scene_moved_prims(scene: *const RtxScene, moves: *const RtxPoseMoves, out_v0v1v2: *mut f32,
                                  out_spheres: *mut f32) -> c_int;
-    /// Diagnostic: the same two arrays as the move kernel last wrote them on `device`; blocks.
+    /// Diagnostic: the same two arrays as the move or skin kernel last wrote them on `device`; blocks.
     pub fn rtx_debug_moved_prims(scene: *mut RtxScene, device: c_int, out_v0v1v2: *mut f32, out_spheres: *mut f32) -> c_int;
+    /// Binds a skin to the scene (NULL: unbinds); host only, no device touched, not re-entrant per handle.
+    /// `RTX_ERR_UNSUPPORTED`: a weight that is not finite.
+    pub fn rtx_scene_skin(scene: *mut RtxScene, skin: *const RtxSkin) -> c_int;
+    /// 1: a skin is bound, 0: none; `out_max_bone` (may be NULL): the largest bone other than `RTX_MOVE_NONE`.
+    pub fn rtx_scene_skin_bound(scene: *const RtxScene, out_max_bone: *mut u32) -> c_int;
+    /// `rtx_scene_pose_moved` / `_device` / `rtx_scene_moved_prims` with the bound skin naming the moves: every triangle
+    /// corner blends up to four of them.  `moves.group` must be NULL and a skin bound, else `RTX_ERR_BAD_ARG`; host variant:
+    /// also `RTX_ERR_BAD_ARG` when `n_moves` is not above the skin's largest bone.
+    pub fn rtx_scene_pose_skinned(scene: *mut RtxScene, device: c_int, moves: *const RtxPoseMoves, flags: u32,
+                                  reference_tree: u32, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_scene_pose_skinned_device(scene: *mut RtxScene, device: c_int, moves: *const RtxPoseMoves, flags: u32,
+                                         stream: *mut c_void) -> c_int;
+    pub fn rtx_scene_skinned_prims(scene: *const RtxScene, moves: *const RtxPoseMoves, out_v0v1v2: *mut f32,
+                                   out_spheres: *mut f32) -> c_int;
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.
     pub fn rtx_debug_light_points(scene: *mut RtxScene, device: c_int, light: *const RtxLight, out: *mut f32) -> c_int;

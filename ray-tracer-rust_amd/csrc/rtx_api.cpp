@@ -25,6 +25,7 @@
 #include "rtx_device.h"
 #include "rtx_light.h"
 #include "rtx_move.h"
+#include "rtx_skin.h"
 #include "rtx_planes.h"
 #include "rtx_pose.h"
 #include "rtx_prims.h"
@@ -255,6 +256,13 @@ public:
             DeviceBuffer moves, group, radius_scale;
             bool ran = false;
         } f;
+        // rtx_scene_pose_skinned (rtx_skin.hip): this device's copy of the scene's skin (RtxScene::skin), uploaded with the
+        // first skinned pose after a bind.  generation: the bind it is a copy of (0: none yet).  The skin kernel reads the
+        // rest geometry of `f` and writes where the move kernel writes, f.ran included.
+        struct {
+            DeviceBuffer bones, weights, sphere_bone;
+            uint64_t generation = 0;
+        } k;
     } pose;
 private:
     ~DeviceState() = default;
@@ -319,6 +327,7 @@ struct RtxScene {
     bool pose_tables_made = false;
     rtx::RebuildTables rebuild_tables;   // made by the first call that asks for a rebuilt pose (rebuild_tables_of), under mu
     bool rebuild_tables_made = false;
+    rtx::Skin skin;                  // rtx_scene_skin, which is not re-entrant per handle: read without a lock
     std::map<int, DeviceSlot> dev;
     // rtx_debug_probe_split: which tiles the scheduling pass treats as long (0: the prediction), and how many workgroups of
     // the long list the scene's most recent pipeline launch was handed
@@ -1040,6 +1049,23 @@ int reserve_moves(RtxScene *scene, DeviceState &st, bool host_copies, const rtx:
     return RTX_OK;
 }
 
+// This device's copy of the scene's skin (rtx_scene_pose_skinned), after reserve_moves and by its rule: library-owned,
+// grow-only, uploaded when the scene's generation is not the copy's.  A device-resident skinned pose may still read the
+// copy a re-bind replaces, so the upload waits for the device; it happens once per bind.  No pose is touched.
+int reserve_skin(RtxScene *scene, DeviceState &st)
+{
+    const rtx::Skin &k = scene->skin;
+    auto &q = st.pose.k;
+    if (q.generation == k.generation) return RTX_OK;
+    RTX_HIP(hipDeviceSynchronize());
+    q.generation = 0u;
+    RTX_TRY(upload_vec(q.bones, k.bones));
+    RTX_TRY(upload_vec(q.weights, k.weights));
+    RTX_TRY(upload_vec(q.sphere_bone, k.sphere_bone));
+    q.generation = k.generation;
+    return RTX_OK;
+}
+
 // the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
 // copies of them; ov_in: the sphere and colour arrays of a pose that states them (after reserve_prims), in the same sense:
 // the overlay kernel then runs ahead of the others, which read its records where they read the uploaded ones — the primitive
@@ -1050,9 +1076,10 @@ int reserve_moves(RtxScene *scene, DeviceState &st, bool host_copies, const rtx:
 // The plane kernel follows them over the posed global triangles (none: no launch).  This is the only writer of the pose's
 // nodes, and it takes the aimed stream's validity away before anything is launched (AimedStream).
 // d_moves: a moved pose (after reserve_moves; its arrays on the device): the move kernel runs ahead of all of them and
-// writes pose.v and pose.m.spheres, which then stand where d_pose and d_ov.spheres stand.
+// writes pose.v and pose.m.spheres, which then stand where d_pose and d_ov.spheres stand.  skinned (after reserve_skin): the
+// skin kernel runs in the move kernel's place and writes the same two buffers.
 int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, const rtx::PrimsOverlay &ov_in,
-                hipStream_t stream, bool rebuilt, const rtx::PoseMoves *d_moves = nullptr)
+                hipStream_t stream, bool rebuilt, const rtx::PoseMoves *d_moves = nullptr, bool skinned = false)
 {
     rtx::PrimsOverlay d_ov = ov_in;
     const rtx::PreparedScene &p = scene->prep;
@@ -1065,7 +1092,26 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
     st.pose.rebuilt = rebuilt;
     RTX_HIP(hipMemsetAsync(q.tris.as<rtx::TriRec>() + n_prims, 0, sizeof(rtx::TriRec), stream));
     RTX_HIP(hipMemsetAsync(q.nodes.as<rtx::NodeDev>() + n_nodes, 0, sizeof(rtx::NodeDev), stream));
-    if (d_moves) {
+    if (d_moves && skinned) {
+        rtxk::SkinArgs k{};
+        k.rest_v = st.pose.f.rest_v.as<const float>();
+        k.rest_spheres = st.pose.f.rest_spheres.as<const float>();
+        k.bones = st.pose.k.bones.as<const uint4>();
+        k.weights = st.pose.k.weights.as<const float4>();
+        k.sphere_bone = st.pose.k.sphere_bone.as<const uint32_t>();
+        k.n_triangles = posed_triangles(scene);
+        k.n_spheres = p.n_spheres;
+        k.n_moves = d_moves->n_moves;
+        k.moves = d_moves->moves;
+        k.radius_scale = d_moves->radius_scale;
+        k.out_v = st.pose.v.as<float>();
+        k.out_spheres = st.pose.m.spheres.as<float>();
+        st.pose.f.ran = false;
+        RTX_HIP(rtxk::launch_skin(k, stream));
+        st.pose.f.ran = true;
+        d_pose = k.n_triangles ? k.out_v : nullptr;
+        d_ov.spheres = k.n_spheres ? k.out_spheres : nullptr;
+    } else if (d_moves) {
         rtxf::MoveArgs f{};
         f.rest_v = st.pose.f.rest_v.as<const float>();
         f.rest_spheres = st.pose.f.rest_spheres.as<const float>();
@@ -1593,10 +1639,11 @@ int moves_of(const RtxScene *scene, const RtxPoseMoves *in, rtx::PoseMoves *mv, 
 // beside the vertices; the other entry points give none, and nothing of the overlay's is then reserved, copied or launched.
 // moves: rtx_scene_pose_moved's bodies — v0v1v2 is NULL and ov_in states no spheres: the device makes both from the moves,
 // the caller has applied the range rule to the host statement (rtx::moved_in_range), and only the reference's own tree has
-// the statement's output made on the host.
+// the statement's output made on the host.  skin: rtx_scene_pose_skinned's — the moves are blended per corner by the scene's
+// skin (rtx::skinned_in_range applied by the caller), everything else as for moves.
 int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
               RtxStats *stats, bool rebuilt, bool prims = false, const rtx::PrimsOverlay &ov_in = rtx::PrimsOverlay(),
-              const rtx::PoseMoves *moves = nullptr)
+              const rtx::PoseMoves *moves = nullptr, const rtx::Skin *skin = nullptr)
 {
     if (!scene || (!v0v1v2 && !moves && (!prims || posed_triangles(scene) != 0u)) || reference_tree > RTX_REFTREE_NEVER)
         return RTX_ERR_BAD_ARG;
@@ -1620,7 +1667,8 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
         if (want_ref && moves) {      // the reference's own tree is built from the statement's output
             moved_v.resize(p.rest_v0v1v2.size());
             moved_spheres.resize(p.rest_spheres.size());
-            rtx::moved_prims(p, *moves, moved_v.data(), moved_spheres.data());
+            if (skin) rtx::skinned_prims(p, *skin, *moves, moved_v.data(), moved_spheres.data());
+            else rtx::moved_prims(p, *moves, moved_v.data(), moved_spheres.data());
             v0v1v2 = moved_v.data();
             if (p.n_spheres) ov.spheres = moved_spheres.data();
         }
@@ -1643,6 +1691,7 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     RTX_TRY(reserve_pose(scene, st, true, ref_stream.size(), rebuilt));
     if (pov) RTX_TRY(reserve_prims(scene, st, true, ov));
     if (moves) RTX_TRY(reserve_moves(scene, st, true, *moves));
+    if (skin) RTX_TRY(reserve_skin(scene, st));
     RTX_TRY(wait_for_uses(st, kUsesPose));      // a device-resident call may still read the pose this one replaces
     const size_t v_bytes = moves ? 0u : static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
     hipError_t he = hipSuccess;
@@ -1686,7 +1735,7 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     if (rc == RTX_OK) rc = timed.begin(st);
     if (rc == RTX_OK)
         rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, d_ov, st.stream,
-                         rebuilt, moves ? &d_moves : nullptr);
+                         rebuilt, moves ? &d_moves : nullptr, skin != nullptr);
     if (rc == RTX_OK) rc = timed.end(st);
     if (rc != RTX_OK) {
         st.pose.valid = false;
@@ -1698,7 +1747,8 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
 }
 
 int pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream, bool rebuilt,
-                bool prims = false, const rtx::PrimsOverlay &ov_in = rtx::PrimsOverlay(), const rtx::PoseMoves *d_moves = nullptr)
+                bool prims = false, const rtx::PrimsOverlay &ov_in = rtx::PrimsOverlay(), const rtx::PoseMoves *d_moves = nullptr,
+                bool skinned = false)
 {
     rtx::PrimsOverlay d_ov = ov_in;
     if (!scene || (!d_v0v1v2 && !d_moves && (!prims || posed_triangles(scene) != 0u))) return RTX_ERR_BAD_ARG;
@@ -1715,10 +1765,11 @@ int pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d
     if (d_moves) {      // (the overlay's primitive records are reserved where spheres are stated: the move kernel's)
         RTX_TRY(reserve_moves(scene, st, false, *d_moves));
         if (scene->prep.n_spheres) d_ov.spheres = st.pose.m.spheres.as<const float>();
+        if (skinned) RTX_TRY(reserve_skin(scene, st));
     }
     if (d_ov.any()) RTX_TRY(reserve_prims(scene, st, false, d_ov));
     RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank), d_ov,
-                        static_cast<hipStream_t>(stream), rebuilt, d_moves));
+                        static_cast<hipStream_t>(stream), rebuilt, d_moves, skinned));
     return mark_uses(st, kUsesPose, static_cast<hipStream_t>(stream));
 }
 
@@ -2313,6 +2364,60 @@ int rtx_scene_pose_moved_device(RtxScene *scene, int device, const RtxPoseMoves 
     rtx::PrimsOverlay d_ov;
     RTX_TRY(moves_of(scene, moves, &d_mv, &d_ov));
     return pose_device(scene, device, nullptr, moves->tie_rank, stream, (flags & RTX_POSE_REBUILT) != 0u, true, d_ov, &d_mv);
+}
+
+int rtx_scene_skin(RtxScene *scene, const RtxSkin *skin)
+{
+    if (!scene) return RTX_ERR_BAD_ARG;
+    if (!skin) {      // unbind: the arrays go, the generation moves on (a device's copy is never taken for a later bind's)
+        const uint64_t next = scene->skin.generation + 1u;
+        scene->skin = rtx::Skin();
+        scene->skin.generation = next;
+        return RTX_OK;
+    }
+    return rtx::skin_bind(scene->prep, skin->bones, skin->weights, skin->sphere_bone, scene->skin);
+}
+
+int rtx_scene_skin_bound(const RtxScene *scene, uint32_t *out_max_bone)
+{
+    if (!scene) return RTX_ERR_BAD_ARG;
+    if (out_max_bone) *out_max_bone = scene->skin.bound ? scene->skin.max_bone : 0u;
+    return scene->skin.bound ? 1 : 0;
+}
+
+int rtx_scene_skinned_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres)
+{
+    if (!scene || !moves) return RTX_ERR_BAD_ARG;
+    rtx::PoseMoves mv;
+    rtx::PrimsOverlay ov;
+    RTX_TRY(moves_of(scene, moves, &mv, &ov));
+    if (mv.group || !scene->skin.bound) return RTX_ERR_BAD_ARG;
+    rtx::skinned_prims(scene->prep, scene->skin, mv, out_v0v1v2, out_spheres);
+    return RTX_OK;
+}
+
+int rtx_scene_pose_skinned(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, uint32_t reference_tree,
+                           RtxStats *stats)
+{
+    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT) || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
+    rtx::PoseMoves mv;
+    rtx::PrimsOverlay ov;
+    RTX_TRY(moves_of(scene, moves, &mv, &ov));
+    const rtx::Skin &skin = scene->skin;
+    if (mv.group || !skin.bound || mv.n_moves <= skin.max_bone) return RTX_ERR_BAD_ARG;      // (O(1): what the bind recorded)
+    if (!rtx::skinned_in_range(scene->prep, skin, mv)) return RTX_ERR_UNSUPPORTED;      // the statement on the host, nothing stored
+    return pose_host(scene, device, nullptr, moves->tie_rank, reference_tree, stats, (flags & RTX_POSE_REBUILT) != 0u, true, ov, &mv,
+                     &skin);
+}
+
+int rtx_scene_pose_skinned_device(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, void *stream)
+{
+    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
+    rtx::PoseMoves d_mv;
+    rtx::PrimsOverlay d_ov;
+    RTX_TRY(moves_of(scene, moves, &d_mv, &d_ov));
+    if (d_mv.group || !scene->skin.bound) return RTX_ERR_BAD_ARG;
+    return pose_device(scene, device, nullptr, moves->tie_rank, stream, (flags & RTX_POSE_REBUILT) != 0u, true, d_ov, &d_mv, true);
 }
 
 int rtx_debug_moved_prims(RtxScene *scene, int device, float *out_v0v1v2, float *out_spheres)

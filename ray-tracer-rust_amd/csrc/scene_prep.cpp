@@ -1131,6 +1131,59 @@ bool move_groups_ok(const PreparedScene &s, const PoseMoves &m)
     return true;
 }
 
+int skin_bind(const PreparedScene &s, const uint32_t *bones, const float *weights, const uint32_t *sphere_bone, Skin &out)
+{
+    const size_t n_corner_words = 12u * s.rest_tri_vec.size(), n_spheres = s.rest_sphere_vec.size();
+    if (n_corner_words && (!bones || !weights)) return RTX_ERR_BAD_ARG;
+    for (size_t k = 0; k < n_corner_words; ++k)
+        if (!std::isfinite(weights[k])) return RTX_ERR_UNSUPPORTED;
+    Skin made;
+    try {
+        if (n_corner_words) {
+            made.bones.assign(bones, bones + n_corner_words);
+            made.weights.assign(weights, weights + n_corner_words);
+        }
+        if (sphere_bone) made.sphere_bone.assign(sphere_bone, sphere_bone + n_spheres);
+        else made.sphere_bone.assign(n_spheres, kMoveNone);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    for (uint32_t b : made.bones)
+        if (b != kMoveNone && b > made.max_bone) made.max_bone = b;
+    for (uint32_t b : made.sphere_bone)
+        if (b != kMoveNone && b > made.max_bone) made.max_bone = b;
+    made.bound = true;
+    made.generation = out.generation + 1u;
+    out = std::move(made);
+    return RTX_OK;
+}
+
+void skinned_prims(const PreparedScene &s, const Skin &skin, const PoseMoves &m, float *out_v0v1v2, float *out_spheres)
+{
+    if (out_v0v1v2)
+        for (size_t c = 0; c < 3u * s.rest_tri_vec.size(); ++c)
+            skin_statement(m.moves, m.n_moves, &skin.bones[4u * c], &skin.weights[4u * c], &s.rest_v0v1v2[3u * c], out_v0v1v2 + 3u * c);
+    if (out_spheres)
+        for (size_t i = 0; i < s.rest_sphere_vec.size(); ++i)
+            move_statement(m.moves, m.radius_scale, m.n_moves, skin.sphere_bone[i], true, &s.rest_spheres[4u * i], out_spheres + 4u * i);
+}
+
+bool skinned_in_range(const PreparedScene &s, const Skin &skin, const PoseMoves &m)
+{
+    for (size_t c = 0; c < 3u * s.rest_tri_vec.size(); ++c) {
+        float out[3];
+        skin_statement(m.moves, m.n_moves, &skin.bones[4u * c], &skin.weights[4u * c], &s.rest_v0v1v2[3u * c], out);
+        for (int k = 0; k < 3; ++k)
+            if (!(std::fabs(out[k]) <= s.scene_magnitude)) return false;      // (false for a NaN)
+    }
+    for (size_t i = 0; i < s.rest_sphere_vec.size(); ++i) {
+        float out[4];
+        move_statement(m.moves, m.radius_scale, m.n_moves, skin.sphere_bone[i], true, &s.rest_spheres[4u * i], out);
+        if (!sphere_in_range(s, out)) return false;
+    }
+    return true;
+}
+
 void overlay_records(const PreparedScene &s, const PoseTables &t, const PrimsOverlay &ov, TriRec *tris, ShadeRec *shade)
 {
     const size_t n_prims = s.tris.size();

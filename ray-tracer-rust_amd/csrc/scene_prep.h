@@ -214,6 +214,25 @@ RTX_HOST_DEVICE inline void move_statement(const float *moves, const float *radi
     for (int r = 0; r < 3; ++r) out[r] = ((m[4 * r] * in[0] + m[4 * r + 1] * in[1]) + m[4 * r + 2] * in[2]) + m[4 * r + 3];
     if (sphere) out[3] = radius_scale ? in[3] * radius_scale[g] : in[3];
 }
+// A skinned pose's corner (rtx_scene_pose_skinned; the kernel: rtx_skin.hip): the rest position `in` under up to four
+// moves, blended.  All four bones not below n_moves (kMoveNone is such a value): the words are copied, no arithmetic, so a
+// -0.0 keeps its sign.  Otherwise q_k = move_statement of slot k's bone — a bone not below n_moves gives `in` itself, by that
+// statement's own rule, so `moves` is never indexed with a value that has not been compared against n_moves — and
+// out[r] = ((w0 * q0[r] + w1 * q1[r]) + w2 * q2[r]) + w3 * q3[r]: four products and three sums in this order, each rounded
+// to f32 once.  The weights are taken as given.  One text for both compilers, as move_statement is: skinned_prims on the
+// host, rtxk::skin_kernel on the device.
+RTX_HOST_DEVICE inline void skin_statement(const float *moves, uint32_t n_moves, const uint32_t bones[4], const float weights[4],
+                                           const float in[3], float out[3])
+{
+    if (bones[0] >= n_moves && bones[1] >= n_moves && bones[2] >= n_moves && bones[3] >= n_moves) {
+        for (int k = 0; k < 3; ++k) out[k] = in[k];
+        return;
+    }
+    float q[4][3];
+    for (int k = 0; k < 4; ++k) move_statement(moves, nullptr, n_moves, bones[k], false, in, q[k]);
+    for (int r = 0; r < 3; ++r)
+        out[r] = ((weights[0] * q[0][r] + weights[1] * q[1][r]) + weights[2] * q[2][r]) + weights[3] * q[3][r];
+}
 
 // Shading data of a primitive, indexed by its position in the caller's Vec<Primitive> (read once per hit).
 struct ShadeRec {
@@ -415,6 +434,26 @@ void moved_prims(const PreparedScene &s, const PoseMoves &m, float *out_v0v1v2, 
 bool moved_in_range(const PreparedScene &s, const PoseMoves &m);
 // the host variant's rule for `group`: every entry below n_moves or kMoveNone (true for a NULL array)
 bool move_groups_ok(const PreparedScene &s, const PoseMoves &m);
+// The skin of a scene (rtx_scene_skin): per triangle corner four bones and four weights — corner c of triangle t at
+// [12 t + 4 c, 12 t + 4 c + 4), the order of rest_v0v1v2's vertices — and per sphere one bone; 96 bytes per triangle and 4 per
+// sphere of host memory.  max_bone: the largest bone other than kMoveNone over both arrays (0: none).  generation: counts the
+// binds and unbinds of the scene, so that a device knows its copy is stale.
+struct Skin {
+    std::vector<uint32_t> bones;        // n_triangles x 12
+    std::vector<float>    weights;      // n_triangles x 12
+    std::vector<uint32_t> sphere_bone;  // n_spheres (kMoveNone where the bind gave no array)
+    uint32_t max_bone = 0;
+    bool bound = false;
+    uint64_t generation = 0;
+};
+// Copies the caller's arrays into `out` for scene `s` (sphere_bone may be NULL).  RTX_ERR_BAD_ARG: NULL bones or weights with
+// triangles present; RTX_ERR_UNSUPPORTED: a weight that is not finite; `out` is then left as it was.  RTX_ERR_OOM.
+int skin_bind(const PreparedScene &s, const uint32_t *bones, const float *weights, const uint32_t *sphere_bone, Skin &out);
+// The host statement of rtxk::skin_kernel: skin_statement over every corner of the rest geometry and move_statement over
+// every sphere under sphere_bone, into moved_prims' two arrays (either may be NULL).  m.group is not read: the skin names
+// the moves.  skinned_in_range: moved_in_range's rule over that output, stated without making it.
+void skinned_prims(const PreparedScene &s, const Skin &skin, const PoseMoves &m, float *out_v0v1v2, float *out_spheres);
+bool skinned_in_range(const PreparedScene &s, const Skin &skin, const PoseMoves &m);
 // The host statement of what the pose kernels make.  rank: per Vec position, or NULL for the position itself.  tris:
 // n_prims records in leaf order; shade: n_prims in Vec order; nodes: n_nodes records in NodeRec's word order, the planes
 // moved outwards by cull_delta in f32 as nodes_in_device_order moves them.  Each output may be NULL.  ov: NULL, or what

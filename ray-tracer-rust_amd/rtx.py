@@ -152,6 +152,14 @@ MOVE_NONE = 0xFFFFFFFF
 MAX_MOVES = 65536
 
 
+class RtxSkin(C.Structure):
+    """RtxSkin: the skin rtx_scene_skin binds to a scene — host pointers, copied by the call."""
+    _fields_ = [("bones", C.c_void_p), ("weights", C.c_void_p), ("sphere_bone", C.c_void_p)]
+
+
+assert C.sizeof(RtxSkin) == 24 and C.alignment(RtxSkin) == 8
+
+
 # every symbol include/rtx.h declares (tests check the export list against the header)
 _SIGS = {
     "rtx_abi_version": (C.c_int, []),
@@ -240,6 +248,11 @@ _SIGS = {
     "rtx_scene_pose_moved_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPoseMoves), C.c_uint32, C.c_void_p]),
     "rtx_scene_moved_prims": (C.c_int, [C.c_void_p, C.POINTER(RtxPoseMoves), f32p, f32p]),
     "rtx_debug_moved_prims": (C.c_int, [C.c_void_p, C.c_int, f32p, f32p]),
+    "rtx_scene_skin": (C.c_int, [C.c_void_p, C.POINTER(RtxSkin)]),
+    "rtx_scene_skin_bound": (C.c_int, [C.c_void_p, u32p]),
+    "rtx_scene_pose_skinned": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPoseMoves), C.c_uint32, C.c_uint32, C.POINTER(Stats)]),
+    "rtx_scene_pose_skinned_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPoseMoves), C.c_uint32, C.c_void_p]),
+    "rtx_scene_skinned_prims": (C.c_int, [C.c_void_p, C.POINTER(RtxPoseMoves), f32p, f32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -1098,6 +1111,59 @@ class Scene:
         """Diagnostic: the arrays the move kernel last wrote on `device`, in moved_prims' form (rtx_debug_moved_prims)."""
         v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
         _check(_lib.rtx_debug_moved_prims(self._h, device, _fp(v), _fp(sph)), "rtx_debug_moved_prims")
+        return v, sph
+
+    # -- a skin bound once, and poses that blend up to four moves per triangle corner on the device
+    def skin(self, bones=None, weights=None, sphere_bone=None):
+        """Binds a skin (rtx_scene_skin; the arrays are copied): bones uint32 [n_tris, 3, 4] and weights float32
+        [n_tris, 3, 4] per corner, sphere_bone uint32 [n_spheres] or None (every sphere MOVE_NONE).  skin() with no
+        argument unbinds.  Not re-entrant per scene."""
+        if bones is None and weights is None and sphere_bone is None:
+            _check(_lib.rtx_scene_skin(self._h, None), "rtx_scene_skin")
+            return
+        n_tris, n_spheres = len(self.tris), len(self.spheres)
+        b = np.ascontiguousarray(bones if bones is not None else np.zeros((0, 3, 4)), dtype=np.uint32).reshape(-1)
+        w = np.ascontiguousarray(weights if weights is not None else np.zeros((0, 3, 4)), dtype=np.float32).reshape(-1)
+        if len(b) != 12 * n_tris or len(w) != 12 * n_tris:
+            raise ValueError("bones and weights have 3 x 4 entries per triangle of the scene")
+        s = None if sphere_bone is None else np.ascontiguousarray(sphere_bone, dtype=np.uint32).reshape(-1)
+        if s is not None and len(s) != n_spheres:
+            raise ValueError("sphere_bone has one entry per sphere of the scene")
+        addr = lambda a: a.ctypes.data if a is not None and a.size else None
+        _check(_lib.rtx_scene_skin(self._h, C.byref(RtxSkin(addr(b), addr(w), addr(s)))), "rtx_scene_skin")
+
+    def skin_bound(self):
+        """-> (bound, the largest bone other than MOVE_NONE) (rtx_scene_skin_bound)"""
+        top = C.c_uint32(0)
+        rc = _lib.rtx_scene_skin_bound(self._h, C.byref(top))
+        if rc < 0:
+            _check(rc, "rtx_scene_skin_bound")
+        return bool(rc), int(top.value)
+
+    def pose_skinned(self, moves, radius_scale=None, rgb=None, sphere_rgb=None, device=0, tie_rank=None,
+                     reference_tree=REFTREE_NEVER, rebuilt=False, stats=False):
+        """pose_moved() with the bound skin naming the moves: every triangle corner blends up to four of them
+        (rtx_scene_pose_skinned).  stats: kernel_ms includes the skin kernel."""
+        mv, keep = self._moves_struct(moves, None, radius_scale, rgb, sphere_rgb, tie_rank)
+        st = Stats()
+        _check(_lib.rtx_scene_pose_skinned(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0, int(reference_tree),
+                                           C.byref(st) if stats else None), "rtx_scene_pose_skinned")
+        return st.asdict() if stats else None
+
+    def pose_skinned_device(self, device, n_moves, d_moves_ptr, d_radius_scale_ptr=None, d_rgb_ptr=None, d_sphere_rgb_ptr=None,
+                            d_tie_rank_ptr=None, rebuilt=False, stream=None):
+        """Asynchronous skinned pose from device arrays the caller owns (None or 0: no such array)."""
+        mv = RtxPoseMoves(int(n_moves), *[p if p else None for p in (d_moves_ptr, None, d_radius_scale_ptr, d_rgb_ptr,
+                                                                     d_sphere_rgb_ptr, d_tie_rank_ptr)])
+        _check(_lib.rtx_scene_pose_skinned_device(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0,
+                                                  C.c_void_p(stream) if stream else None), "rtx_scene_pose_skinned_device")
+
+    def skinned_prims(self, moves, radius_scale=None):
+        """Host only: the arrays such a pose makes -> (v0v1v2 float32 [n_tris, 9], spheres float32 [n_spheres, 4])
+        (rtx_scene_skinned_prims)."""
+        mv, keep = self._moves_struct(moves, None, radius_scale)
+        v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
+        _check(_lib.rtx_scene_skinned_prims(self._h, C.byref(mv), _fp(v), _fp(sph)), "rtx_scene_skinned_prims")
         return v, sph
 
 
