@@ -748,6 +748,39 @@ int rtx_scene_pose_skinned(RtxScene *scene, int device, const RtxPoseMoves *move
 int rtx_scene_pose_skinned_device(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, void *stream);
 int rtx_scene_skinned_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres);
 
+/* A resampled scene: the sample table of an existing scene replaced (the reference draws a new one for every render(),
+ * main.rs:253-265).  Every later call on the scene — render, frame, tiles, view, view rows, shade, their lit and posed forms —
+ * returns what it returns on a scene created from the same RtxSceneDesc with the new table, byte for byte and word for word.
+ * rtx_scene_resample: `samples` is n_samples interleaved pairs, as RtxSceneDesc.samples; copied before the call returns.
+ * rtx_scene_reseed: the table is rtxh_gen_samples(seed, n_pairs), word for word: draw i of 2 * n_pairs has the splitmix64
+ *   state seed + (i + 1) * 0x9E3779B97F4A7C15 mod 2^64, mixed as rtxh_gen_samples mixes it, and the value
+ *   (float)(uint32_t)(z >> 40) * 2^-24.  The table is never made on the host: the call does work proportional to nb_ray *
+ *   nb_light_sample and none proportional to n_pairs, and each device makes its copy with a kernel (rtx_samples.hip) from the
+ *   seed, so nothing of the table's size crosses the bus.
+ * Both are host only and touch no device; like rtx_scene_skin they are not re-entrant per handle: no other call on the
+ * scene may run beside them.  They re-derive what rtx_scene_create derives from the table, with create's own code: the light
+ * points, the light tour and order, the light boxes and the shaft margin (rtx_scene_light_points, rtx_scene_light_order and
+ * the _for calls answer for the new table at once).  KEPT AS CREATED: the prediction of the long primary walks
+ * (rtx_scene_probe_long, which widened its frusta by the created table's range) — an ordering hint on which no byte
+ * depends.  Not read from the table and so left alone: the gamma thresholds, the trees, the rest geometry, the skin, any pose
+ * that stands on a device and the aimed streams.
+ * RTX_ERR_BAD_ARG: a NULL scene, NULL samples, a count of 0.  RTX_ERR_UNSUPPORTED: the re-derived shaft margin is not
+ * finite — rtx_scene_create's own rule: the calls accept exactly the tables create accepts.  RTX_ERR_OOM.  On any error the
+ * scene stays exactly as it was.
+ * Each device catches up in the first call of any kind on it after a replacement (rtx_scene_upload included), before that
+ * call enqueues anything: it waits for the device (hipDeviceSynchronize: a launch on any stream may still read the old
+ * table), replaces its table — a caller's by a copy, a seeded one by the kernel — and re-uploads the small light arrays.
+ * Synchronous, as an upload is.  rtx_render_frame catches up every device it names before its first launch.
+ * rtx_scene_samples: host only; copies `count` pairs of the scene's current table from pair `first` (a seeded table's pairs
+ *   are computed, whatever its size).  RTX_ERR_BAD_ARG: a NULL scene, a NULL out with count != 0, first + count > the
+ *   table's pairs.
+ * rtx_debug_samples: the same range read back from `device`'s table, after the device caught up; blocks.
+ * RtxSceneInfo.sample_bytes is 8 * the pair count for either kind of table. */
+int rtx_scene_resample(RtxScene *scene, const float *samples, uint32_t n_samples);
+int rtx_scene_reseed(RtxScene *scene, uint64_t seed, uint32_t n_pairs);
+int rtx_scene_samples(const RtxScene *scene, uint64_t first, uint32_t count, float *out);
+int rtx_debug_samples(RtxScene *scene, int device, uint64_t first, uint32_t count, float *out);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

@@ -337,6 +337,16 @@ extern "C" {
                                          stream: *mut c_void) -> c_int;
     pub fn rtx_scene_skinned_prims(scene: *const RtxScene, moves: *const RtxPoseMoves, out_v0v1v2: *mut f32,
                                    out_spheres: *mut f32) -> c_int;
+    /// Replaces the scene's sample table by the caller's `n_samples` interleaved pairs (copied); host only, no device
+    /// touched, not re-entrant per handle.  Light points, tour, boxes and shaft margin are re-derived as `rtx_scene_create`
+    /// derives them; each device catches up in its next call.  `RTX_ERR_UNSUPPORTED`: a table `rtx_scene_create` would refuse.
+    pub fn rtx_scene_resample(scene: *mut RtxScene, samples: *const f32, n_samples: u32) -> c_int;
+    /// The same with the table `rtxh_gen_samples(seed, n_pairs)`, never made on the host: each device makes it from the seed.
+    pub fn rtx_scene_reseed(scene: *mut RtxScene, seed: u64, n_pairs: u32) -> c_int;
+    /// Host only: `count` pairs of the scene's current table from pair `first`.
+    pub fn rtx_scene_samples(scene: *const RtxScene, first: u64, count: u32, out: *mut f32) -> c_int;
+    /// Diagnostic: the same range of `device`'s table, after it caught up; blocks.
+    pub fn rtx_debug_samples(scene: *mut RtxScene, device: c_int, first: u64, count: u32, out: *mut f32) -> c_int;
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.
     pub fn rtx_debug_light_points(scene: *mut RtxScene, device: c_int, light: *const RtxLight, out: *mut f32) -> c_int;

@@ -26,6 +26,7 @@
 #include "rtx_light.h"
 #include "rtx_move.h"
 #include "rtx_skin.h"
+#include "rtx_samples.h"
 #include "rtx_planes.h"
 #include "rtx_pose.h"
 #include "rtx_prims.h"
@@ -189,6 +190,10 @@ public:
     // primary_nodes: the scene's own eye's stream, which only the calls that render the scene's own view walk
     DeviceGeometry geo;
     DeviceBuffer primary_nodes, samples, lights, light_tour, thr, light_boxes;
+    // rtx_scene_resample / rtx_scene_reseed: the generation of the scene's sample table that `samples`, `lights`, `light_tour`
+    // and `light_boxes` hold (table_upload); another one than the scene's: the first call on this device catches up
+    // (ensure_uploaded) before it enqueues anything
+    uint64_t table_generation = 0;
     // the scene's long list as probe_kernel reads it (rtx::ProbeSplit: the tiles, then the bits), uploaded with the scene
     // when it predicts any; long_all: every tile of the frame listed (rtx_debug_probe_split, mode 2), made at first use
     DeviceBuffer long_words, long_all;
@@ -385,6 +390,29 @@ uint32_t kernel_variant()
 #endif
 }
 
+// The scene's sample table and what the scene derives from it, on the device: the table — a caller's by a copy, a seeded one
+// made in place by rtxr::samples_kernel from its seed, nothing of the table's size copied — and the small light arrays
+// (points, tour, boxes).  Synchronous, on the null stream: the host arrays outlive the copies and the table stands when
+// this returns.  The buffers grow only.  Where earlier launches may still read the table it replaces, the caller waits for
+// the device first (ensure_uploaded).  The margin and n_samples travel in every call's argument block (device_scene), read
+// from the scene.
+int table_upload(const rtx::PreparedScene &p, DeviceState &st)
+{
+    st.table_generation = ~0ull;         // until every piece stands
+    if (p.seeded) {
+        RTX_TRY(st.samples.reserve(std::max<size_t>(static_cast<size_t>(p.n_samples) * sizeof(float2), 16u)));
+        RTX_HIP(rtxr::launch_samples(p.sample_seed, p.n_samples, st.samples.as<float2>(), nullptr));
+        RTX_HIP(hipStreamSynchronize(nullptr));
+    } else {
+        RTX_TRY(upload_vec(st.samples, p.samples));
+    }
+    RTX_TRY(upload_vec(st.lights, p.light_points));
+    RTX_TRY(upload_vec(st.light_tour, p.light_tour));
+    RTX_TRY(upload_vec(st.light_boxes, p.light_boxes));
+    st.table_generation = p.table_generation;
+    return RTX_OK;
+}
+
 // the uploads of ensure_uploaded; may stop half way
 int upload_all(RtxScene *scene, DeviceState &st)
 {
@@ -402,11 +430,8 @@ int upload_all(RtxScene *scene, DeviceState &st)
     // one spare record of zeros behind the primitive records (no walk requests the record after the one it tests any more)
     if ((rc = upload_vec(g.tris, p.tris, sizeof(rtx::TriRec))) != RTX_OK) return rc;
     if ((rc = upload_vec(g.shade, p.shade)) != RTX_OK) return rc;
-    if ((rc = upload_vec(st.samples, p.samples)) != RTX_OK) return rc;
-    if ((rc = upload_vec(st.lights, p.light_points)) != RTX_OK) return rc;
-    if ((rc = upload_vec(st.light_tour, p.light_tour)) != RTX_OK) return rc;
+    if ((rc = table_upload(p, st)) != RTX_OK) return rc;
     if (!p.global_planes.empty() && (rc = upload_vec(g.planes, p.global_planes)) != RTX_OK) return rc;
-    if ((rc = upload_vec(st.light_boxes, p.light_boxes)) != RTX_OK) return rc;
     if (!p.long_tiles.empty()) {
         std::vector<uint32_t> words(p.long_tiles);
         words.insert(words.end(), p.long_bits.begin(), p.long_bits.end());
@@ -426,10 +451,19 @@ int upload_all(RtxScene *scene, DeviceState &st)
 
 // Caller holds slot.mu, with a state in the slot.  An upload that fails half way takes the state out of the slot, and
 // with it everything allocated so far: nothing leaks, and the next call starts with uploaded == false.
+// A device whose table is not the scene's (rtx_scene_resample, rtx_scene_reseed) catches up here, in the first call of any
+// kind after the replacement and before that call enqueues anything: it waits for the device — a launch on any stream, the
+// caller's included, may still read the table, and rtx_render_view_device is tied to no stream the library knows — and
+// uploads as an upload does.  Geometry, pose, skin and aimed streams are not touched.  A catch-up that fails is a failed upload.
 int ensure_uploaded(RtxScene *scene, DeviceSlot &slot)
 {
-    if (slot.st->uploaded) return RTX_OK;
-    const int rc = upload_all(scene, *slot.st);
+    int rc = RTX_OK;
+    if (!slot.st->uploaded) {
+        rc = upload_all(scene, *slot.st);
+    } else if (slot.st->table_generation != scene->prep.table_generation) {
+        rc = hip_rc(hipDeviceSynchronize());
+        if (rc == RTX_OK) rc = table_upload(scene->prep, *slot.st);
+    }
     if (rc != RTX_OK) slot.st.reset();
     return rc;
 }
@@ -873,7 +907,7 @@ void light_walk_on_host(const rtx::PreparedScene &p, const Lit &lit, uint32_t *o
 {
     const size_t n = static_cast<size_t>(p.nb_ray) * lit.count;
     std::vector<float> points(3u * n), box(6u * static_cast<size_t>(p.nb_ray));
-    rtx::light_points_of(lit.tri.v, p.samples.data(), p.n_samples, p.nb_ray, lit.count, points.data());
+    rtx::light_points_of(lit.tri.v, rtx::sample_source(p), p.nb_ray, lit.count, points.data());
     rtx::light_boxes_of(points.data(), p.nb_ray, lit.count, box.data());
     if (boxes) std::memcpy(boxes, box.data(), box.size() * sizeof(float));
     if (shaft_delta) *shaft_delta = rtx::shaft_delta_of(p.scene_magnitude, box.data(), box.size());
@@ -1835,7 +1869,7 @@ int rtx_scene_info(const RtxScene *scene, RtxSceneInfo *info)
     info->node_bytes = p.nodes.size() * sizeof(rtx::NodeRec);
     info->tri_bytes = p.tris.size() * sizeof(rtx::TriRec);
     info->shade_bytes = p.shade.size() * sizeof(rtx::ShadeRec);
-    info->sample_bytes = p.samples.size() * sizeof(float);
+    info->sample_bytes = 2u * static_cast<uint64_t>(p.n_samples) * sizeof(float);
     return RTX_OK;
 }
 
@@ -1909,6 +1943,8 @@ int rtx_render_frame(RtxScene *scene, const int *devices, int n_devices, uint32_
         const auto &n = need[kv.second];
         int rc = ensure_state(*kv.second, kv.first);
         if (rc != RTX_OK) return rc;
+        // uploaded, and caught up with a replaced sample table, before any share is launched anywhere
+        if ((rc = ensure_uploaded(scene, *kv.second)) != RTX_OK) return rc;
         if ((rc = kv.second->st->d_out.reserve(n.first ? n.first : 16)) != RTX_OK) return rc;
         if ((rc = kv.second->st->h_stage.reserve(n.second ? n.second : 16)) != RTX_OK) return rc;
     }
@@ -2111,7 +2147,7 @@ int rtx_scene_light_points_for(const RtxScene *scene, const RtxLight *light, flo
     Lit lit;
     if (!lit_of(scene, light, &lit)) return RTX_ERR_BAD_ARG;
     const rtx::PreparedScene &p = scene->prep;
-    if (out) rtx::light_points_of(lit.tri.v, p.samples.data(), p.n_samples, p.nb_ray, lit.count, out);
+    if (out) rtx::light_points_of(lit.tri.v, rtx::sample_source(p), p.nb_ray, lit.count, out);
     return static_cast<int>(p.nb_ray * lit.count);      // <= 2^20
 }
 
@@ -2129,6 +2165,49 @@ int rtx_debug_light_points(RtxScene *scene, int device, const RtxLight *light, f
     const size_t bytes = static_cast<size_t>(scene->prep.nb_ray) * lit.count * 3u * sizeof(float);
     if (bytes) RTX_HIP(hipMemcpyAsync(out, st.lit.points.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
     RTX_HIP(hipStreamSynchronize(st.stream));
+    return RTX_OK;
+}
+
+// ---- the sample table replaced (rtx_scene_resample, rtx_scene_reseed; the kernel: rtx_samples.hip) -------------------------
+// Host only, and like rtx_scene_skin not re-entrant per handle: the scene is read and written without a lock.  Each device
+// catches up in its next call (ensure_uploaded).
+
+int rtx_scene_resample(RtxScene *scene, const float *samples, uint32_t n_samples)
+{
+    if (!scene || !samples || !n_samples) return RTX_ERR_BAD_ARG;
+    return rtx::resample_scene(scene->prep, rtx::SampleSource{samples, 0u, n_samples});
+}
+
+int rtx_scene_reseed(RtxScene *scene, uint64_t seed, uint32_t n_pairs)
+{
+    if (!scene || !n_pairs) return RTX_ERR_BAD_ARG;
+    return rtx::resample_scene(scene->prep, rtx::SampleSource{nullptr, seed, n_pairs});
+}
+
+// first + count within the table, or RTX_ERR_BAD_ARG
+static int sample_range_ok(const RtxScene *scene, uint64_t first, uint32_t count, const float *out)
+{
+    if (!scene || (count && !out)) return RTX_ERR_BAD_ARG;
+    const uint64_t n = scene->prep.n_samples;
+    return first <= n && count <= n - first ? RTX_OK : RTX_ERR_BAD_ARG;
+}
+
+int rtx_scene_samples(const RtxScene *scene, uint64_t first, uint32_t count, float *out)
+{
+    RTX_TRY(sample_range_ok(scene, first, count, out));
+    const rtx::SampleSource src = rtx::sample_source(scene->prep);
+    for (uint64_t k = 0; k < count; ++k) src.pair(first + k, &out[2 * k], &out[2 * k + 1]);
+    return RTX_OK;
+}
+
+int rtx_debug_samples(RtxScene *scene, int device, uint64_t first, uint32_t count, float *out)
+{
+    RTX_TRY(sample_range_ok(scene, first, count, out));
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    const DeviceState &st = e.state();
+    RTX_HIP(hipStreamSynchronize(st.stream));
+    if (count) RTX_HIP(hipMemcpy(out, st.samples.as<float>() + 2u * first, static_cast<size_t>(count) * 2u * sizeof(float), hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 

@@ -77,14 +77,14 @@ void light_sample(const float v0[3], const float v1[3], const float v2[3], float
 
 // light points: for ray r of a pixel and sample i the reference reads T[(r*NB_RAY + i) % len] (src/main.rs:194-196) —
 // the same points for every pixel
-void light_points_of(const float tri[9], const float *samples, uint32_t n_samples, uint32_t nb_ray, uint32_t nb_light,
-                     float *out)
+void light_points_of(const float tri[9], const SampleSource &samples, uint32_t nb_ray, uint32_t nb_light, float *out)
 {
     for (uint32_t r = 0; r < nb_ray; ++r)
         for (uint32_t i = 0; i < nb_light; ++i) {
-            const size_t k = (static_cast<size_t>(r) * nb_ray + i) % n_samples;
-            light_sample_point(tri, tri + 3, tri + 6, samples[2 * k], samples[2 * k + 1],
-                               &out[3 * (static_cast<size_t>(r) * nb_light + i)]);
+            const size_t k = (static_cast<size_t>(r) * nb_ray + i) % samples.n;
+            float u, v;
+            samples.pair(k, &u, &v);
+            light_sample_point(tri, tri + 3, tri + 6, u, v, &out[3 * (static_cast<size_t>(r) * nb_light + i)]);
         }
 }
 
@@ -591,6 +591,71 @@ float shaft_delta_of(float scene_magnitude, const float *light_boxes, size_t n)
     return magnitude * 0x1p-16f + 0x1p-100f;
 }
 
+void light_walk_of(const float tri[9], const SampleSource &samples, uint32_t nb_ray, uint32_t nb_light,
+                   std::vector<float> &points, std::vector<float> &tour, std::vector<uint32_t> &order_out,
+                   std::vector<float> &boxes)
+{
+    points.resize(3 * static_cast<size_t>(nb_ray) * nb_light);
+    light_points_of(tri, samples, nb_ray, nb_light, points.data());
+
+    // the order of walking them (scene_prep.h: light_tour): per primary ray, per batch of the shading pass
+    tour.resize(4 * static_cast<size_t>(nb_ray) * nb_light);
+    order_out.resize(static_cast<size_t>(nb_ray) * nb_light);
+    for (uint32_t r = 0; r < nb_ray; ++r)
+        for (uint32_t b0 = 0; b0 < nb_light; b0 += kMaxLightBatch) {
+            const uint32_t bc = std::min(nb_light - b0, kMaxLightBatch);
+            const size_t first = static_cast<size_t>(r) * nb_light + b0;
+            uint32_t order[kMaxLightBatch];
+            light_tour_order(&points[3 * first], bc, order);
+            for (uint32_t k = 0; k < bc; ++k) {
+                std::memcpy(&tour[4 * (first + k)], &points[3 * (first + order[k])], 12);
+                std::memcpy(&tour[4 * (first + k) + 3], &order[k], 4);
+                order_out[first + k] = b0 + order[k];
+            }
+        }
+
+    // bounding box of the light points of primary ray r: one end of a tile's shaft (rtx_pass_schedule.hpp: shaft_cut)
+    boxes.assign(6 * static_cast<size_t>(nb_ray), 0.0f);
+    light_boxes_of(points.data(), nb_ray, nb_light, boxes.data());
+}
+
+int resample_scene(PreparedScene &s, const SampleSource &samples)
+{
+    if (!samples.n) return RTX_ERR_BAD_ARG;
+    try {
+        std::vector<float> points, tour, boxes, grown;
+        std::vector<uint32_t> order;
+        light_walk_of(s.light_v, samples, s.nb_ray, s.nb_light_sample, points, tour, order, boxes);
+        const float shaft_delta = shaft_delta_of(s.scene_magnitude, boxes.data(), boxes.size());
+        if (!std::isfinite(shaft_delta)) return RTX_ERR_UNSUPPORTED;
+        const size_t words = 2 * static_cast<size_t>(samples.n);
+        if (samples.table && s.samples.capacity() < words) grown.reserve(words);
+        // Nothing below allocates: the scene changes whole or not at all.  A caller's table is copied into the scene's own
+        // array where it fits, so that a table per frame neither maps nor unmaps host memory: measured, giving back a 16 MB
+        // array a device has copied from stalls the process's next HIP call for milliseconds.  An
+        // insert within the capacity does not reallocate.
+        if (samples.table) {
+            if (grown.capacity()) s.samples.swap(grown);
+            s.samples.clear();
+            s.samples.insert(s.samples.end(), samples.table, samples.table + words);
+        } else {
+            std::vector<float>().swap(s.samples);
+        }
+        s.light_points.swap(points);
+        s.light_tour.swap(tour);
+        s.light_order.swap(order);
+        s.light_boxes.swap(boxes);
+        s.shaft_delta = shaft_delta;
+        s.n_samples = samples.n;
+        s.seeded = samples.table == nullptr;
+        s.sample_seed = s.seeded ? samples.seed : 0;
+        ++s.table_generation;
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
 int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
 {
     const uint64_t n_prims64 = static_cast<uint64_t>(d.n_tris) + d.n_spheres;
@@ -625,28 +690,11 @@ int prepare_scene(const RtxSceneDesc &d, PreparedScene &s)
         std::memcpy(s.light_v, d.light_v0, 12);
         std::memcpy(s.light_v + 3, d.light_v1, 12);
         std::memcpy(s.light_v + 6, d.light_v2, 12);
-        s.light_points.resize(3 * static_cast<size_t>(d.nb_ray) * d.nb_light_sample);
-        light_points_of(s.light_v, d.samples, d.n_samples, d.nb_ray, d.nb_light_sample, s.light_points.data());
-
-        // the order of walking them (scene_prep.h: light_tour): per primary ray, per batch of the shading pass
-        s.light_tour.resize(4 * static_cast<size_t>(d.nb_ray) * d.nb_light_sample);
-        s.light_order.resize(static_cast<size_t>(d.nb_ray) * d.nb_light_sample);
-        for (uint32_t r = 0; r < d.nb_ray; ++r)
-            for (uint32_t b0 = 0; b0 < d.nb_light_sample; b0 += kMaxLightBatch) {
-                const uint32_t bc = std::min(d.nb_light_sample - b0, kMaxLightBatch);
-                const size_t first = static_cast<size_t>(r) * d.nb_light_sample + b0;
-                uint32_t order[kMaxLightBatch];
-                light_tour_order(&s.light_points[3 * first], bc, order);
-                for (uint32_t k = 0; k < bc; ++k) {
-                    std::memcpy(&s.light_tour[4 * (first + k)], &s.light_points[3 * (first + order[k])], 12);
-                    std::memcpy(&s.light_tour[4 * (first + k) + 3], &order[k], 4);
-                    s.light_order[first + k] = b0 + order[k];
-                }
-            }
-
-        // bounding box of the light points of primary ray r: one end of a tile's shaft (rtx_pass_schedule.hpp: shaft_cut)
-        s.light_boxes.assign(6 * static_cast<size_t>(d.nb_ray), 0.0f);
-        light_boxes_of(s.light_points.data(), d.nb_ray, d.nb_light_sample, s.light_boxes.data());
+        s.seeded = false;
+        s.sample_seed = 0;
+        s.table_generation = 0;
+        light_walk_of(s.light_v, SampleSource{d.samples, 0, d.n_samples}, d.nb_ray, d.nb_light_sample, s.light_points,
+                      s.light_tour, s.light_order, s.light_boxes);
 
         const int grc = build_gamma_thresholds(s.gamma_thr);
         if (grc != RTX_OK) return grc;

@@ -47,6 +47,33 @@ RTX_HOST_DEVICE inline float tour_distance(const float a[3], const float b[3])
     const float e2 = a[2] - b[2];
     return sqrtf((e0 * e0 + e1 * e1) + e2 * e2);
 }
+// Draw i of a seeded sample table (rtx_scene_reseed; the kernel: rtx_samples.hip): splitmix64 in closed form.  The state of
+// draw i is seed + (i + 1) * 0x9E3779B97F4A7C15 mod 2^64 — what rtxh_gen_samples' running sum holds at its draw i — mixed by
+// the same two xor-shift-multiplies and the final shift; the value is the top 24 bits times 2^-24, a conversion and a
+// product that are both exact.  Pair k of a table is (draw 2k, draw 2k + 1).  Integer arithmetic and two exact f32 steps:
+// one text for both compilers, as light_sample_point is, and nothing for either to round differently.
+RTX_HOST_DEVICE inline float sample_statement(uint64_t seed, uint64_t i)
+{
+    uint64_t z = seed + (i + 1ull) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return static_cast<float>(static_cast<uint32_t>(z >> 40)) * 0x1p-24f;
+}
+// Where the host reads a sample table: the caller's n interleaved pairs, or — table == NULL — the seeded table of n pairs,
+// whose entries sample_statement gives.  The accessor of every host reader (light_points_of and through it the lit calls'
+// margin): a seeded table is never made on the host.
+struct SampleSource {
+    const float *table;
+    uint64_t seed;
+    uint32_t n;
+    void pair(uint64_t k, float *u, float *v) const
+    {
+        if (table) { *u = table[2 * k]; *v = table[2 * k + 1]; return; }
+        *u = sample_statement(seed, 2 * k);
+        *v = sample_statement(seed, 2 * k + 1);
+    }
+};
 // a call's light may have at most this many points (nb_ray x its sample count): rtx_*_lit, rtx_scene_light_points_for
 constexpr uint64_t kMaxCallLightPoints = 1ull << 20;
 // Triangle::new + get_bounding_box — triangle.rs:22-34, :45-56: e1 = v1 - v0, e2 = v2 - v0, normal = unit(cross(e1, e2))
@@ -261,8 +288,14 @@ struct PreparedScene {
     std::vector<NodeRec>  ref_nodes;   // the reference's own tree as a stream (empty when not built)
     std::vector<TriRec>   tris;        // primitive records (triangles and spheres) in leaf order
     std::vector<ShadeRec> shade;       // in caller order
-    std::vector<float>    samples;     // n_samples x 2
-    float light_v[9];                  // the light triangle as given: v0, v1, v2 (rtx_scene_light)
+    std::vector<float>    samples;     // n_samples x 2; empty while the table is a seeded one (rtx_scene_reseed)
+    // The table as it stands (resample_scene): seeded, its n_samples entries are sample_statement's over sample_seed and no
+    // array holds them on the host (sample_source is how the host reads either kind).  table_generation counts the accepted
+    // replacements, so that a device knows the table, the light arrays and the margin it holds are stale.
+    bool     seeded = false;
+    uint64_t sample_seed = 0;
+    uint64_t table_generation = 0;
+    float light_v[9];                // the light triangle as given: v0, v1, v2 (rtx_scene_light)
     std::vector<float>    light_points;// nb_ray x nb_light_sample x 3
     // The same points in the order the shading pass WALKS them: per primary ray and per batch of kMaxLightBatch
     // consecutive samples a short tour that starts at the batch's first sample (light_tour_order).  One 16-byte record
@@ -296,7 +329,9 @@ struct PreparedScene {
     // three are empty for a scene that does not cut per tile (more than kProbeSplitMaxNodes records) or whose camera or
     // sample table gives no proper frustum.
     std::vector<uint32_t> long_tiles, long_weights, long_bits;
-    float sample_lo[2] = {0.0f, 0.0f}, sample_hi[2] = {0.0f, 0.0f};   // range of the sample table's two columns (NaN: not finite)
+    // range of the two columns of the sample table the scene was CREATED with (NaN: not finite); like the prediction made
+    // from it, kept as created when the table is replaced
+    float sample_lo[2] = {0.0f, 0.0f}, sample_hi[2] = {0.0f, 0.0f};
     // The "rest" geometry of rtx_scene_pose_moved: RtxSceneDesc.v0v1v2 and .spheres as given (a primitive record keeps v0,
     // e1 and e2, from which v1 and v2 cannot be had exactly), and for every triangle and every sphere its position in the
     // Vec, where a pose's `group` array names its move.  No record, stream or table above is made from them.
@@ -370,9 +405,25 @@ void triangle_derive(const float v0[3], const float v1[3], const float v2[3],
                      float e1[3], float e2[3], float normal[3], float bmin[3], float bmax[3]);
 void light_sample(const float v0[3], const float v1[3], const float v2[3], float u, float v, float out[3]);
 // out[3 * (r * nb_light + i)] = light_sample(tri, T[(r * nb_ray + i) % n_samples]) for r < nb_ray, i < nb_light
-// (main.rs:194-196; samples: n_samples pairs, n_samples != 0): a scene's light points, and any other light's on it
-void light_points_of(const float tri[9], const float *samples, uint32_t n_samples, uint32_t nb_ray, uint32_t nb_light,
-                     float *out);
+// (main.rs:194-196; T: the table `samples` reads, n != 0): a scene's light points, and any other light's on it
+void light_points_of(const float tri[9], const SampleSource &samples, uint32_t nb_ray, uint32_t nb_light, float *out);
+// the scene's table as it stands, for a host reader
+inline SampleSource sample_source(const PreparedScene &s)
+{
+    return SampleSource{s.seeded ? nullptr : s.samples.data(), s.sample_seed, s.n_samples};
+}
+// What a scene derives from its sample table (prepare_scene, resample_scene — the one statement of both): the light points,
+// their tour per primary ray and batch (light_tour, light_order: PreparedScene's) and the light boxes.  The shaft margin is
+// shaft_delta_of over the boxes.  May throw std::bad_alloc.
+void light_walk_of(const float tri[9], const SampleSource &samples, uint32_t nb_ray, uint32_t nb_light,
+                   std::vector<float> &points, std::vector<float> &tour, std::vector<uint32_t> &order,
+                   std::vector<float> &boxes);
+// Replaces the scene's table by `samples` (rtx_scene_resample: a caller's table, copied; rtx_scene_reseed: table == NULL)
+// and re-derives what prepare_scene derives from it, by light_walk_of and shaft_delta_of.  RTX_ERR_BAD_ARG: n == 0;
+// RTX_ERR_UNSUPPORTED: the margin is not finite (prepare_scene's rule); RTX_ERR_OOM.  On an error the scene is as it was;
+// accepted, table_generation advances.  The prediction of the long walks and sample_lo / sample_hi stay as created.  A
+// seeded table costs work proportional to nb_ray * nb_light_sample and none proportional to n.
+int resample_scene(PreparedScene &s, const SampleSource &samples);
 // byte = (x.powf(1/2.2) * 255.0) as u8 with the host libm — color.rs:10-13,28-33
 uint8_t gamma_quantise(float linear);
 int  build_gamma_thresholds(float thr[256]);

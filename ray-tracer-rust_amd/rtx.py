@@ -253,6 +253,10 @@ _SIGS = {
     "rtx_scene_pose_skinned": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPoseMoves), C.c_uint32, C.c_uint32, C.POINTER(Stats)]),
     "rtx_scene_pose_skinned_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxPoseMoves), C.c_uint32, C.c_void_p]),
     "rtx_scene_skinned_prims": (C.c_int, [C.c_void_p, C.POINTER(RtxPoseMoves), f32p, f32p]),
+    "rtx_scene_resample": (C.c_int, [C.c_void_p, f32p, C.c_uint32]),
+    "rtx_scene_reseed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),
+    "rtx_scene_samples": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, f32p]),
+    "rtx_debug_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, f32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -1165,6 +1169,39 @@ class Scene:
         v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
         _check(_lib.rtx_scene_skinned_prims(self._h, C.byref(mv), _fp(v), _fp(sph)), "rtx_scene_skinned_prims")
         return v, sph
+
+    # -- the sample table replaced: a caller's table, or a seeded one each device makes from the seed
+    def resample(self, samples):
+        """Replaces the scene's sample table by `samples` (float32 [n, 2], copied: rtx_scene_resample).  Host only; every
+        device catches up in its next call.  Every later call answers as a scene created with this table would."""
+        t = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1, 2)
+        _check(_lib.rtx_scene_resample(self._h, _fp(t), len(t)), "rtx_scene_resample")
+        self.samples = t
+
+    def reseed(self, seed=DEFAULT_SEED, n_pairs=NB_RAND_SAMPLE):
+        """Replaces the scene's sample table by gen_samples(seed, n_pairs), which is never made on the host: each device
+        makes its copy from the seed (rtx_scene_reseed).  self.samples becomes None: read it with samples_at()."""
+        _check(_lib.rtx_scene_reseed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pairs)), "rtx_scene_reseed")
+        self.samples = None
+
+    def n_samples(self):
+        """pairs of the scene's current table"""
+        return self.info()["sample_bytes"] // 8
+
+    def samples_at(self, first=0, count=None):
+        """Host only: `count` pairs of the scene's current table from pair `first` -> float32 [count, 2]
+        (rtx_scene_samples; default: to the end)"""
+        count = self.n_samples() - first if count is None else count
+        out = np.zeros((count, 2), np.float32)
+        _check(_lib.rtx_scene_samples(self._h, int(first), int(count), _fp(out)), "rtx_scene_samples")
+        return out
+
+    def debug_samples(self, first=0, count=None, device=0):
+        """The same range of the table `device` holds, after it caught up (rtx_debug_samples; blocks)"""
+        count = self.n_samples() - first if count is None else count
+        out = np.zeros((count, 2), np.float32)
+        _check(_lib.rtx_debug_samples(self._h, device, int(first), int(count), _fp(out)), "rtx_debug_samples")
+        return out
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
