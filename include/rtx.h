@@ -781,6 +781,71 @@ int rtx_scene_reseed(RtxScene *scene, uint64_t seed, uint32_t n_pairs);
 int rtx_scene_samples(const RtxScene *scene, uint64_t first, uint32_t count, float *out);
 int rtx_debug_samples(RtxScene *scene, int device, uint64_t first, uint32_t count, float *out);
 
+/* ---- The mean of N frames, accumulated on the device ---------------------------------------------------------------------------
+ * One frame is one ray per pixel (nb_ray of them) and the table's light points: noisy and aliased, which is why the reference
+ * draws a new table for every render() (main.rs:253-265).  These calls average N frames without a byte of a frame crossing
+ * the bus and without changing the scene.
+ *
+ * THE STATEMENT.  An accumulator record is an RtxAccumPixel.  Adding frame k's RtxPixelShade record `s` to it:
+ *   first:      sum[c] = s.linear[c], copied bit for bit; hit_frames = (s.hits != 0).  The old content is not read.
+ *   otherwise:  sum[c] = sum[c] + s.linear[c], one f32 addition per channel; hit_frames += (s.hits != 0), a u32 addition.
+ * Resolving it over n_frames gives an RtxPixelShade: linear[c] = sum[c] / (float)n_frames, ONE correctly rounded f32
+ * division (not a product with a reciprocal); rgb8[c] the byte the frame's own pixel store gives that value, through the
+ * scene's 256 gamma thresholds (rtx_scene_gamma_thresholds; -inf is byte 255, a NaN and every other negative value byte 0);
+ * hits = min(hit_frames, 255): in how many frames the pixel had a hit.  Host and device compile one text (scene_prep.h:
+ * accum_add_statement, accum_resolve_statement) without contraction and agree word for word.
+ *
+ * rtxh_accum_add / rtxh_accum_resolve: the two statements over arrays, host only, no device.  RTX_ERR_BAD_ARG: a NULL array
+ * (a resolve: thr256 or accum, and both outputs NULL), n_frames == 0 or > 65,536.  n == 0: RTX_OK, nothing read or written.
+ *
+ * rtx_accum_add_device / rtx_accum_resolve_device: the same over device arrays, one kernel each (rtx_accum.hip),
+ * asynchronous on `stream`.  d_shade of an add: records from ANY call that writes RtxPixelShade (rtx_render_view_device,
+ * rtx_shade_rays_device, their lit and posed forms) — how a caller accumulates frames that differ in pose, eye or light:
+ * motion blur, depth of field.  RTX_ERR_BAD_ARG: a NULL scene or array (a resolve: d_accum, and both outputs NULL), a pointer
+ * other than d_rgb that is not 16-byte aligned (d_rgb may have any alignment), n_frames == 0 or > 65,536.  n == 0: RTX_OK,
+ * nothing launched, no device needed.  They use no library buffer: no ordering rule ties them to other calls.  A resolve
+ * reads the scene's thresholds and uploads the scene (synchronously) first if needed.
+ *
+ * rtx_render_view_mean: the mean of n_frames frames of a view, frame k rendered under the table
+ * rtxh_gen_samples(seeds[k], n_pairs).  It is rtx_render_view_lit — with RTX_MEAN_POSED rtx_render_view_posed with that
+ * light — in every respect not named here: the view and light argument checks, the empty rectangle (RTX_OK, nothing
+ * written, stats zeroed, no device needed), RTX_ERR_UNSUPPORTED for a light vertex that is not finite (decided on the host),
+ * RTX_ERR_BAD_ARG when posed and the device holds no pose.  light == NULL: the scene's own triangle and count;
+ * nb_light_sample == 0: the scene's count.  Further RTX_ERR_BAD_ARG: NULL seeds, n_frames == 0 or > 65,536, n_pairs == 0, an
+ * unknown flag, both outputs NULL (host variant), NULL or misaligned d_accum (device variant; its two outputs may both be
+ * NULL: the sums stay in d_accum for a later rtx_accum_resolve_device).  seeds is read before the call returns.
+ * Record p is the resolve of the adds, in frame order, of rtx_render_view_lit's record p on a scene created from the same
+ * RtxSceneDesc with table rtxh_gen_samples(seeds[k], n_pairs): the ordered sum of the reference's render_pixel over N
+ * scenes, divided once, then Color::to_rgba.  n_frames == 1: that frame's record, hits clipped to 0 or 1.
+ * Per frame, all on the call's stream with no host wait between frames: the seeded table made by the sample-table kernel
+ * into a library-owned scratch table (never the scene's), the light points of the call's light over that table, the view
+ * kernel with its argument block's table and light points swapped, writing library-owned scratch records, and the add;
+ * after the last frame the resolve.  THE SCENE IS NOT WRITTEN: its table, light arrays, pose, skin and aimed streams stay, and
+ * every later call returns what it returned before.  The scratch table and records and the light points are library-owned
+ * per device and grow only (growing waits for the device): device-resident launches on one device must be ordered on one
+ * stream, and the host entry points wait (by an event) for the most recent of them, as for the lit calls.
+ * stats (host variant; may be NULL): the counters are the sums over the frames, primary_rays = n_frames * nx * ny * nb_ray,
+ * kernel_ms the whole chain. */
+typedef struct RtxAccumPixel {   /* 16 bytes, 16-byte aligned on the device: one 16-byte load, one 16-byte store */
+    float    sum[3];             /* the ordered f32 sum of the frames' linear colours */
+    uint32_t hit_frames;         /* frames in which the pixel had a closest hit */
+} RtxAccumPixel;
+#define RTX_MAX_MEAN_FRAMES 65536u
+#define RTX_MEAN_POSED 1u
+int rtxh_accum_add(uint32_t n, const RtxPixelShade *shade, RtxAccumPixel *accum, uint32_t first);
+int rtxh_accum_resolve(const float thr256[256], uint32_t n, const RtxAccumPixel *accum, uint32_t n_frames,
+                       uint8_t *out_rgb /* NULL or n*3 */, RtxPixelShade *out_shade /* NULL or n */);
+int rtx_accum_add_device(RtxScene *scene, int device, uint32_t n, const void *d_shade, void *d_accum, uint32_t first,
+                         void *stream);
+int rtx_accum_resolve_device(RtxScene *scene, int device, uint32_t n, const void *d_accum, uint32_t n_frames, void *d_rgb,
+                             void *d_shade, void *stream);
+int rtx_render_view_mean(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                         uint32_t flags, const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, uint8_t *out_rgb,
+                         RtxPixelShade *out_shade, RtxStats *stats);
+int rtx_render_view_mean_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, void *d_accum, void *d_rgb,
+                                void *d_shade, void *stream);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

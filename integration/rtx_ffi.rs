@@ -101,6 +101,16 @@ pub struct RtxPixelShade {
     pub rgb8: [u8; 3],
     pub hits: u8,
 }
+/// One pixel of an accumulator of `rtx_render_view_mean` / `rtx_accum_add_device`: the ordered f32 sum of the frames'
+/// linear colours and in how many frames the pixel had a closest hit.  A device array of them must be 16-byte aligned.
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxAccumPixel {
+    pub sum: [f32; 3],
+    pub hit_frames: u32,
+}
+pub const RTX_MEAN_POSED: u32 = 1;
+pub const RTX_MAX_MEAN_FRAMES: u32 = 65536;
 /// A pinhole view of an uploaded scene for `rtx_render_view`: the frame `create_rays` sees, the `Camera` after
 /// `Camera::new` (`rtxh_camera_new` computes `u`, `v`, `w`) and the rectangle of pixels to render.
 #[repr(C)]
@@ -347,6 +357,30 @@ extern "C" {
     pub fn rtx_scene_samples(scene: *const RtxScene, first: u64, count: u32, out: *mut f32) -> c_int;
     /// Diagnostic: the same range of `device`'s table, after it caught up; blocks.
     pub fn rtx_debug_samples(scene: *mut RtxScene, device: c_int, first: u64, count: u32, out: *mut f32) -> c_int;
+    /// Host only: frame records added into accumulator records (`first != 0`: written, never read), by the statement the
+    /// device kernels compile too.
+    pub fn rtxh_accum_add(n: u32, shade: *const RtxPixelShade, accum: *mut RtxAccumPixel, first: u32) -> c_int;
+    /// Host only: accumulator records over `n_frames` frames into RGB8 (NULL or `n * 3` bytes) and records (NULL or `n`):
+    /// one correctly rounded division per channel, then the byte through the scene's 256 gamma thresholds.
+    pub fn rtxh_accum_resolve(thr256: *const f32, n: u32, accum: *const RtxAccumPixel, n_frames: u32, out_rgb: *mut u8,
+                              out_shade: *mut RtxPixelShade) -> c_int;
+    /// The add over device arrays (16-byte aligned), asynchronous on `stream`: records from any call that writes
+    /// `RtxPixelShade`, so frames may differ in pose, eye or light.
+    pub fn rtx_accum_add_device(scene: *mut RtxScene, device: c_int, n: u32, d_shade: *const c_void, d_accum: *mut c_void,
+                                first: u32, stream: *mut c_void) -> c_int;
+    /// The resolve over a device accumulator; `d_rgb` may have any alignment.
+    pub fn rtx_accum_resolve_device(scene: *mut RtxScene, device: c_int, n: u32, d_accum: *const c_void, n_frames: u32,
+                                    d_rgb: *mut c_void, d_shade: *mut c_void, stream: *mut c_void) -> c_int;
+    /// The mean of `n_frames` frames of a view, frame `k` under the table `rtxh_gen_samples(seeds[k], n_pairs)`, summed in
+    /// frame order on the device and divided once.  `light` NULL: the scene's.  `flags`: `RTX_MEAN_POSED` or 0.  The scene
+    /// is not changed.
+    pub fn rtx_render_view_mean(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight, flags: u32,
+                                seeds: *const u64, n_frames: u32, n_pairs: u32, out_rgb: *mut u8,
+                                out_shade: *mut RtxPixelShade, stats: *mut RtxStats) -> c_int;
+    /// Device-resident variant: the caller's accumulator (`nx * ny` records), outputs and stream; nothing is waited for.
+    pub fn rtx_render_view_mean_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                       flags: u32, seeds: *const u64, n_frames: u32, n_pairs: u32, d_accum: *mut c_void,
+                                       d_rgb: *mut c_void, d_shade: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn rtx_scene_light_points_for(scene: *const RtxScene, light: *const RtxLight, out: *mut f32) -> c_int;
     /// Diagnostic: the same points as the light kernel makes them on `device`.
     pub fn rtx_debug_light_points(scene: *mut RtxScene, device: c_int, light: *const RtxLight, out: *mut f32) -> c_int;

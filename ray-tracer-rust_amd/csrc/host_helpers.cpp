@@ -289,6 +289,39 @@ void rtxh_gen_samples(uint64_t seed, uint32_t n_pairs, float *out)
     }
 }
 
+// The statements of the mean of N frames over arrays (scene_prep.h: accum_add_statement, accum_resolve_statement — the text
+// rtx_accum.hip compiles for the device).  The records are copied in and out: a caller's arrays need no alignment.
+int rtxh_accum_add(uint32_t n, const RtxPixelShade *shade, RtxAccumPixel *accum, uint32_t first)
+{
+    if (!shade || !accum) return RTX_ERR_BAD_ARG;
+    const char *in = reinterpret_cast<const char *>(shade);
+    char *io = reinterpret_cast<char *>(accum);
+    for (size_t i = 0; i < n; ++i) {
+        RtxPixelShade s;
+        RtxAccumPixel a = {{0.0f, 0.0f, 0.0f}, 0u};
+        std::memcpy(&s, in + i * sizeof s, sizeof s);
+        if (!first) std::memcpy(&a, io + i * sizeof a, sizeof a);
+        rtx::accum_add_statement(first != 0u, s, &a);
+        std::memcpy(io + i * sizeof a, &a, sizeof a);
+    }
+    return RTX_OK;
+}
+
+int rtxh_accum_resolve(const float thr256[256], uint32_t n, const RtxAccumPixel *accum, uint32_t n_frames, uint8_t *out_rgb,
+                       RtxPixelShade *out_shade)
+{
+    if (!thr256 || !accum || (!out_rgb && !out_shade) || n_frames == 0u || n_frames > rtx::kMaxMeanFrames) return RTX_ERR_BAD_ARG;
+    const char *in = reinterpret_cast<const char *>(accum);
+    for (size_t i = 0; i < n; ++i) {
+        RtxAccumPixel a;
+        std::memcpy(&a, in + i * sizeof a, sizeof a);
+        const RtxPixelShade s = rtx::accum_resolve_statement(thr256, n_frames, a);
+        if (out_rgb) std::memcpy(out_rgb + 3u * i, s.rgb8, 3);
+        if (out_shade) std::memcpy(reinterpret_cast<char *>(out_shade) + i * sizeof s, &s, sizeof s);
+    }
+    return RTX_OK;
+}
+
 // Synthetic soup of BASELINE.json configs[4] (see include/rtx.h).  f32 arithmetic, one rounding per operation:
 // c = lo + f*(hi-lo) per axis, vertex = c + (2f-1).
 int rtxh_synthetic_mesh(uint64_t seed, uint32_t n_tris, float *out)

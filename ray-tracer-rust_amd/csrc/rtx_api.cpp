@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/rtx.h"
+#include "rtx_accum.h"
 #include "rtx_aim.h"
 #include "rtx_device.h"
 #include "rtx_light.h"
@@ -220,6 +221,13 @@ public:
         DeviceBuffer points, tour, boxes;
         Event used;
     } lit;
+    // rtx_render_view_mean (rtx_accum.hip): the seeded table of the frame in flight — made by rtxr::samples_kernel on the
+    // call's stream, never the scene's `samples` — and that frame's records, which the add kernel reads behind the view
+    // kernel.  The frame's light points go where a lit call's go (lit.points).  One guard: `used` (kUsesMean)
+    struct {
+        DeviceBuffer table, records;
+        Event used;
+    } mean;
     // rtx_scene_pose (rtx_pose.hip): the host tables (rtx::PoseTables, uploaded with the first pose), the host variant's
     // copies of the caller's arrays, and the one pose this device holds, as a geometry: posed primitive and shading
     // records, the refitted stream, — host variant with a reference tree — that tree's stream, the plane records of the
@@ -295,17 +303,19 @@ struct DeviceSlot {
 };
 
 // The one rule for the library-owned buffer groups an event guards.  A call states the groups it uses — the regrouping
-// buffers (q_sort), the light buffers (lit), the pose (pose: its geometry, aimed stream included) — as a set of these bits.
+// buffers (q_sort), the light buffers (lit), the pose (pose: its geometry, aimed stream included), the scratch table and records
+// of a mean call (mean) — as a set of these bits.
 // A call that uses them on the library's stream (the host bodies, the rtx_debug_* read-backs, rtx_scene_pose) waits for
 // all of them first: wait_for_uses.  A device-resident call marks all of them behind its kernels on the caller's stream:
 // mark_uses.  A new guarded group is one bit, one event and one line in each of the two.
-enum : unsigned { kUsesSort = 1u, kUsesLight = 2u, kUsesPose = 4u };
+enum : unsigned { kUsesSort = 1u, kUsesLight = 2u, kUsesPose = 4u, kUsesMean = 8u };
 
 int wait_for_uses(DeviceState &st, unsigned uses)
 {
     if (uses & kUsesSort) RTX_TRY(wait_for(st.q_sorted, st.stream));
     if (uses & kUsesLight) RTX_TRY(wait_for(st.lit.used, st.stream));
     if (uses & kUsesPose) RTX_TRY(wait_for(st.pose.used, st.stream));
+    if (uses & kUsesMean) RTX_TRY(wait_for(st.mean.used, st.stream));
     return RTX_OK;
 }
 
@@ -314,6 +324,7 @@ int mark_uses(DeviceState &st, unsigned uses, hipStream_t callers)
     if (uses & kUsesSort) RTX_TRY(mark_busy(st.q_sorted, callers));
     if (uses & kUsesLight) RTX_TRY(mark_busy(st.lit.used, callers));
     if (uses & kUsesPose) RTX_TRY(mark_busy(st.pose.used, callers));
+    if (uses & kUsesMean) RTX_TRY(mark_busy(st.mean.used, callers));
     return RTX_OK;
 }
 
@@ -1423,6 +1434,121 @@ int shade_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_o
                         {d_shade, d_hits, nullptr}, stream);
 }
 
+// ---- the mean of N frames (rtx_render_view_mean, rtx_accum_*_device; the kernels: rtx_accum.hip) ---------------------------
+
+// What a mean call is beside its view: the light (the scene's own as a Lit when the caller gave none: every frame's points
+// are made over that frame's table), whether the caller gave it (the twin's finiteness check is for a given light), the
+// geometry switch, the seeds and the table's length.
+struct MeanCall {
+    Lit lit;
+    bool given;
+    bool posed;
+    const uint64_t *seeds;
+    uint32_t n_frames, n_pairs;
+};
+
+// the argument checks the two variants share, the twin's (CallLight, view_args_ok: `out` stands for its outputs) among them
+bool mean_args_ok(const RtxScene *scene, const RtxView *view, const RtxLight *light, uint32_t flags, const uint64_t *seeds,
+                  uint32_t n_frames, uint32_t n_pairs, const void *out, MeanCall *call)
+{
+    if (!scene || !seeds || n_frames == 0u || n_frames > rtx::kMaxMeanFrames || n_pairs == 0u || (flags & ~RTX_MEAN_POSED)) return false;
+    RtxLight own;
+    if (!light && rtx_scene_light(scene, &own) != RTX_OK) return false;
+    if (!lit_of(scene, light ? light : &own, &call->lit)) return false;
+    if (!view_args_ok(scene, view, nullptr, out, nullptr)) return false;
+    call->given = light != nullptr;
+    call->posed = (flags & RTX_MEAN_POSED) != 0u;
+    call->seeds = seeds;
+    call->n_frames = n_frames;
+    call->n_pairs = n_pairs;
+    return true;
+}
+
+// The scratch table and records of a mean call, library-owned per device, grow only; growing one waits for the device
+// first, as reserve_light does: an earlier launch may still read it.
+int reserve_mean(DeviceState &st, uint32_t n_pairs, uint32_t n_pixels)
+{
+    const size_t table = std::max<size_t>(static_cast<size_t>(n_pairs) * sizeof(float2), 16u);
+    const size_t records = static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade);
+    if (st.mean.table.capacity() >= table && st.mean.records.capacity() >= records) return RTX_OK;
+    RTX_HIP(hipDeviceSynchronize());
+    return reserve_all({{st.mean.table, table}, {st.mean.records, records}});
+}
+
+// The whole chain on `stream`, nothing waited for between frames.  Per frame: the frame's table from its seed, the light's
+// points over that table, the view kernel — as it is: its argument block's table, table length, light points and count are
+// what differs — into the scratch records, the add.  Then the resolve, where an output is asked for.  The scene's own table
+// and light arrays are neither read nor written.  Caller holds the slot's lock and has the device current and the scene
+// uploaded; n_pixels > 0.
+int mean_launch(RtxScene *scene, DeviceState &st, const RtxView *view, const MeanCall &call, void *d_accum, void *d_rgb,
+                void *d_shade, unsigned long long *d_counters, hipStream_t stream)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const uint32_t n_pixels = view->nx * view->ny;
+    DeviceGeometry *geo;
+    RTX_TRY(geometry_of(st, call.posed, &geo));
+    RTX_TRY(reserve_mean(st, call.n_pairs, n_pixels));
+    RTX_TRY(reserve_light(scene, st, call.lit, false));
+    rtx::DeviceScene S = device_scene(scene, st, *geo);
+    S.samples = st.mean.table.as<const float2>();
+    S.n_samples = call.n_pairs;
+    light_swap(st, call.lit, false, 0.0f, &S);
+    rtxv::ViewBlock v;
+    std::memcpy(&v, view, sizeof v);
+    for (uint32_t k = 0; k < call.n_frames; ++k) {
+        RTX_HIP(rtxr::launch_samples(call.seeds[k], call.n_pairs, st.mean.table.as<float2>(), stream));
+        if (call.lit.count != 0u)
+            RTX_HIP(rtxl::launch_light_points(st.mean.table.as<const float2>(), call.n_pairs, call.lit.tri, p.nb_ray, call.lit.count,
+                                              st.lit.points.as<float>(), stream));
+        RTX_HIP(rtxv::launch_view(S, v, origin_bound(scene), nullptr, st.mean.records.as<void>(), nullptr, d_counters, stream));
+        RTX_HIP(rtxc::launch_accum_add(n_pixels, st.mean.records.as<const void>(), d_accum, k == 0u, stream));
+    }
+    if (d_rgb || d_shade)
+        RTX_HIP(rtxc::launch_accum_resolve(st.thr.as<const float>(), n_pixels, d_accum, call.n_frames, d_rgb, d_shade, stream));
+    return RTX_OK;
+}
+
+unsigned mean_uses(const MeanCall &call) { return kUsesLight | kUsesMean | (call.posed ? kUsesPose : 0u); }
+
+// the host entry point: the accumulator and the outputs in the library's output buffer, one behind the other (16-byte
+// records first), launch, copy out
+int mean_host(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, uint8_t *rgb, RtxPixelShade *shade,
+              RtxStats *stats)
+{
+    const Timed timed(stats);
+    const uint32_t n_pixels = view->nx * view->ny;
+    if (n_pixels == 0u) return timed.empty();
+    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const size_t records = static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade);
+    const size_t shade_bytes = shade ? records : 0u, rgb_bytes = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
+    RTX_TRY(st.q_out.reserve(records + shade_bytes + rgb_bytes));
+    uint8_t *d_accum = st.q_out.as<uint8_t>(), *d_shade = shade ? d_accum + records : nullptr;
+    uint8_t *d_rgb = rgb ? d_accum + records + shade_bytes : nullptr;
+    RTX_TRY(wait_for_uses(st, mean_uses(call)));
+    RTX_TRY(timed.begin(st));
+    RTX_TRY(mean_launch(scene, st, view, call, d_accum, d_rgb, d_shade, timed.counters(st), st.stream));
+    RTX_TRY(timed.end(st));
+    if (shade) RTX_HIP(hipMemcpyAsync(shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st.stream));
+    if (rgb) RTX_HIP(hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, st.stream));
+    return timed.gather(st, static_cast<uint64_t>(call.n_frames) * n_pixels * scene->prep.nb_ray, call.lit.count);
+}
+
+// the device-resident entry point: the caller's arrays, the caller's stream, nothing waited for
+int mean_device(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, void *d_accum, void *d_rgb, void *d_shade,
+                void *stream)
+{
+    if (view->nx * view->ny == 0u) return RTX_OK;
+    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    RTX_TRY(mean_launch(scene, st, view, call, d_accum, d_rgb, d_shade, nullptr, static_cast<hipStream_t>(stream)));
+    return mark_uses(st, mean_uses(call), static_cast<hipStream_t>(stream));
+}
+
 // ---- any view through the render pipeline (rtx_render_view_rows; the aim kernels: rtx_aim.hip) ------------------------------
 
 // the pipeline's walks start at the eye: origin_bound holds for it.  A NaN fails it.
@@ -2209,6 +2335,49 @@ int rtx_debug_samples(RtxScene *scene, int device, uint64_t first, uint32_t coun
     RTX_HIP(hipStreamSynchronize(st.stream));
     if (count) RTX_HIP(hipMemcpy(out, st.samples.as<float>() + 2u * first, static_cast<size_t>(count) * 2u * sizeof(float), hipMemcpyDeviceToHost));
     return RTX_OK;
+}
+
+// ---- the mean of N frames (the kernels: rtx_accum.hip) ---------------------------------------------------------------------
+
+int rtx_accum_add_device(RtxScene *scene, int device, uint32_t n, const void *d_shade, void *d_accum, uint32_t first, void *stream)
+{
+    if (!scene || !d_shade || !d_accum || !aligned16(d_shade, d_accum)) return RTX_ERR_BAD_ARG;
+    if (n == 0u) return RTX_OK;
+    Entry e(scene, device, Entry::kCurrent);
+    if (e.rc != RTX_OK) return e.rc;
+    return hip_rc(rtxc::launch_accum_add(n, d_shade, d_accum, first != 0u, static_cast<hipStream_t>(stream)));
+}
+
+int rtx_accum_resolve_device(RtxScene *scene, int device, uint32_t n, const void *d_accum, uint32_t n_frames, void *d_rgb,
+                             void *d_shade, void *stream)
+{
+    if (!scene || !d_accum || (!d_rgb && !d_shade) || !aligned16(d_accum, d_shade)) return RTX_ERR_BAD_ARG;
+    if (n_frames == 0u || n_frames > rtx::kMaxMeanFrames) return RTX_ERR_BAD_ARG;
+    if (n == 0u) return RTX_OK;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    return hip_rc(rtxc::launch_accum_resolve(e.state().thr.as<const float>(), n, d_accum, n_frames, d_rgb, d_shade,
+                                             static_cast<hipStream_t>(stream)));
+}
+
+int rtx_render_view_mean(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                         const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, uint8_t *out_rgb, RtxPixelShade *out_shade,
+                         RtxStats *stats)
+{
+    MeanCall call;
+    const void *out = out_rgb ? static_cast<const void *>(out_rgb) : out_shade;
+    if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, out, &call)) return RTX_ERR_BAD_ARG;
+    return mean_host(scene, device, view, call, out_rgb, out_shade, stats);
+}
+
+int rtx_render_view_mean_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, void *d_accum, void *d_rgb,
+                                void *d_shade, void *stream)
+{
+    MeanCall call;
+    if (!d_accum || !aligned16(d_accum, d_shade)) return RTX_ERR_BAD_ARG;
+    if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, d_accum, &call)) return RTX_ERR_BAD_ARG;
+    return mean_device(scene, device, view, call, d_accum, d_rgb, d_shade, stream);
 }
 
 int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats)

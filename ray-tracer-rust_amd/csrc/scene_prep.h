@@ -60,6 +60,49 @@ RTX_HOST_DEVICE inline float sample_statement(uint64_t seed, uint64_t i)
     z ^= z >> 31;
     return static_cast<float>(static_cast<uint32_t>(z >> 40)) * 0x1p-24f;
 }
+// The mean of N frames (rtx_render_view_mean, rtx_accum_*_device; the kernels: rtx_accum.hip).  Three statements, each one
+// text for both compilers, as sample_statement is: rtxh_accum_add / rtxh_accum_resolve on the host, rtxc::accum_add_kernel /
+// rtxc::accum_resolve_kernel on the device.
+// quantise_statement: the byte of a linear channel, the number of thresholds thr[1 .. 255] that are <= x by the eight
+// dependent reads of the render and view kernels' search (rtx_pass_helpers.hpp: quantise; color.rs:28-33).  -inf counts as
+// +inf (powf(-inf, 1 / 2.2) = +inf: byte 255); a NaN and every other negative value lose every comparison: byte 0.
+RTX_HOST_DEVICE inline uint32_t quantise_statement(const float *thr, float x)
+{
+    if (x == -__builtin_inff()) x = __builtin_inff();
+    uint32_t b = 0;
+    for (uint32_t step = 128; step; step >>= 1)
+        if (x >= thr[b + step]) b += step;
+    return b;
+}
+// accum_add_statement: frame k's record into the pixel's accumulator.  first: the three words of `linear` copied bit for
+// bit (a NaN keeps its payload) and hit_frames = (hits != 0); what *acc held is not read and may be anything.  Otherwise
+// sum[c] = sum[c] + linear[c], one f32 addition per channel, and hit_frames += (hits != 0), a plain u32 addition.
+RTX_HOST_DEVICE inline void accum_add_statement(bool first, const RtxPixelShade &shade, RtxAccumPixel *acc)
+{
+    const uint32_t hit = shade.hits != 0 ? 1u : 0u;
+    if (first) {
+        __builtin_memcpy(acc->sum, shade.linear, 12);
+        acc->hit_frames = hit;
+        return;
+    }
+    for (int c = 0; c < 3; ++c) acc->sum[c] = acc->sum[c] + shade.linear[c];
+    acc->hit_frames = acc->hit_frames + hit;
+}
+// accum_resolve_statement: linear[c] = sum[c] / (float)n_frames, one correctly rounded f32 division (never a product with
+// a reciprocal: sum / 3 and sum * (1 / 3) differ in the last bit for a third of all sums), rgb8[c] its byte through the
+// scene's thresholds, hits = min(hit_frames, 255).  n_frames <= 65,536 converts exactly.
+RTX_HOST_DEVICE inline RtxPixelShade accum_resolve_statement(const float *thr, uint32_t n_frames, const RtxAccumPixel &acc)
+{
+    RtxPixelShade out;
+    const float n = static_cast<float>(n_frames);
+    for (int c = 0; c < 3; ++c) {
+        out.linear[c] = acc.sum[c] / n;
+        out.rgb8[c] = static_cast<uint8_t>(quantise_statement(thr, out.linear[c]));
+    }
+    out.hits = static_cast<uint8_t>(acc.hit_frames < 255u ? acc.hit_frames : 255u);
+    return out;
+}
+constexpr uint32_t kMaxMeanFrames = 65536u;
 // Where the host reads a sample table: the caller's n interleaved pairs, or — table == NULL — the seeded table of n pairs,
 // whose entries sample_statement gives.  The accessor of every host reader (light_points_of and through it the lit calls'
 // margin): a seeded table is never made on the host.

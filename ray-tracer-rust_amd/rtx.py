@@ -111,6 +111,18 @@ PIXEL_SHADE_DTYPE = np.dtype([("linear", np.float32, 3), ("rgb8", np.uint8, 3), 
 assert PIXEL_SHADE_DTYPE.itemsize == C.sizeof(PixelShade) == 16
 
 
+class AccumPixel(C.Structure):
+    """RtxAccumPixel: a pixel's ordered sum over the frames added so far and in how many of them it had a hit."""
+    _fields_ = [("sum", C.c_float * 3), ("hit_frames", C.c_uint32)]
+
+
+# the same 16 bytes as a numpy record: what accum_add works on
+ACCUM_PIXEL_DTYPE = np.dtype([("sum", np.float32, 3), ("hit_frames", np.uint32)])
+assert ACCUM_PIXEL_DTYPE.itemsize == C.sizeof(AccumPixel) == 16
+MAX_MEAN_FRAMES = 65536
+MEAN_POSED = 1
+
+
 class RtxView(C.Structure):
     """RtxView: a pinhole view of an uploaded scene (frame, camera after Camera::new) and the rectangle of it to render."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32),
@@ -257,6 +269,15 @@ _SIGS = {
     "rtx_scene_reseed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "rtx_scene_samples": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, f32p]),
     "rtx_debug_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, f32p]),
+    "rtxh_accum_add": (C.c_int, [C.c_uint32, C.POINTER(PixelShade), C.POINTER(AccumPixel), C.c_uint32]),
+    "rtxh_accum_resolve": (C.c_int, [f32p, C.c_uint32, C.POINTER(AccumPixel), C.c_uint32, C.c_void_p, C.POINTER(PixelShade)]),
+    "rtx_accum_add_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rtx_accum_resolve_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "rtx_render_view_mean": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p, C.c_uint32,
+                                       C.c_uint32, C.c_void_p, C.POINTER(PixelShade), C.POINTER(Stats)]),
+    "rtx_render_view_mean_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
+                                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -366,6 +387,32 @@ def gen_samples(seed=DEFAULT_SEED, n_pairs=NB_RAND_SAMPLE):
     out = np.empty((n_pairs, 2), dtype=np.float32)
     _lib.rtxh_gen_samples(seed, n_pairs, _fp(out))
     return out
+
+
+def accum_add(shade, accum=None):
+    """Host only: the accumulator statement over arrays (rtxh_accum_add).  shade: PIXEL_SHADE_DTYPE records of one frame;
+    accum: ACCUM_PIXEL_DTYPE records of the same shape, updated in place and returned — None: the first frame, a new array
+    whose old content is never read."""
+    s = np.ascontiguousarray(shade, dtype=PIXEL_SHADE_DTYPE)
+    first = accum is None
+    if first:
+        accum = np.empty(s.shape, ACCUM_PIXEL_DTYPE)
+    assert accum.dtype == ACCUM_PIXEL_DTYPE and accum.flags["C_CONTIGUOUS"] and accum.size == s.size
+    _check(_lib.rtxh_accum_add(s.size, s.ctypes.data_as(C.POINTER(PixelShade)), accum.ctypes.data_as(C.POINTER(AccumPixel)),
+                               1 if first else 0), "rtxh_accum_add")
+    return accum
+
+
+def accum_resolve(thresholds, accum, n_frames):
+    """Host only: the resolve statement over arrays (rtxh_accum_resolve) -> (uint8 [..., 3], PIXEL_SHADE_DTYPE records);
+    thresholds: a scene's 256 (Scene.gamma_thresholds)."""
+    thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+    a = np.ascontiguousarray(accum, dtype=ACCUM_PIXEL_DTYPE)
+    assert thr.size == 256
+    rgb, shade = np.zeros(a.shape + (3,), np.uint8), np.zeros(a.shape, PIXEL_SHADE_DTYPE)
+    _check(_lib.rtxh_accum_resolve(_fp(thr), a.size, a.ctypes.data_as(C.POINTER(AccumPixel)), int(n_frames), rgb.ctypes.data,
+                                   shade.ctypes.data_as(C.POINTER(PixelShade))), "rtxh_accum_resolve")
+    return rgb, shade
 
 
 def write_png(path, img):
@@ -1202,6 +1249,53 @@ class Scene:
         out = np.zeros((count, 2), np.float32)
         _check(_lib.rtx_debug_samples(self._h, device, int(first), int(count), _fp(out)), "rtx_debug_samples")
         return out
+
+    # -- the mean of N frames, accumulated on the device: the scene is not changed
+    @staticmethod
+    def _seeds(seeds):
+        return np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+
+    def render_view_mean(self, view, seeds, n_pairs=NB_RAND_SAMPLE, device=0, light=None, posed=False, stats=False,
+                         want_shade=False):
+        """The mean of len(seeds) frames of the view, frame k under the table gen_samples(seeds[k], n_pairs), summed in
+        frame order and divided once (rtx_render_view_mean) -> uint8 [ny, nx, 3]; want_shade adds the records
+        (PIXEL_SHADE_DTYPE [ny, nx]: the mean's linear colour, its bytes, in how many frames the pixel had a hit), stats
+        the statistics summed over the frames, last.  light: an RtxLight, None the scene's; posed: the device's pose."""
+        sd = self._seeds(seeds)
+        out = np.zeros((view.ny, view.nx, 3), np.uint8)
+        shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
+        st = Stats()
+        _check(_lib.rtx_render_view_mean(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                         MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), out.ctypes.data,
+                                         shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
+                                         C.byref(st) if stats else None), "rtx_render_view_mean")
+        res = (out,) + ((shade,) if want_shade else ()) + ((st.asdict(),) if stats else ())
+        return res if len(res) > 1 else out
+
+    def render_view_mean_device(self, device, view, seeds, n_pairs, d_accum_ptr, d_rgb_ptr=None, d_shade_ptr=None, stream=None,
+                                light=None, posed=False):
+        """Asynchronous: the same chain on `stream` into device buffers the caller owns — ny*nx x 16 bytes of accumulator
+        (16-byte aligned), optionally ny*nx*3 bytes (any alignment) and ny*nx x 16 bytes of records."""
+        sd = self._seeds(seeds)
+        _check(_lib.rtx_render_view_mean_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                                MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs),
+                                                C.c_void_p(d_accum_ptr), C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
+                                                C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
+                                                C.c_void_p(stream) if stream else None), "rtx_render_view_mean_device")
+
+    def accum_add_device(self, device, n, d_shade_ptr, d_accum_ptr, first, stream=None):
+        """Asynchronous: adds n RtxPixelShade records — of any call that writes them — into n accumulator records
+        (rtx_accum_add_device); first: the accumulator is written, never read."""
+        _check(_lib.rtx_accum_add_device(self._h, device, int(n), C.c_void_p(d_shade_ptr), C.c_void_p(d_accum_ptr), 1 if first else 0,
+                                         C.c_void_p(stream) if stream else None), "rtx_accum_add_device")
+
+    def accum_resolve_device(self, device, n, d_accum_ptr, n_frames, d_rgb_ptr=None, d_shade_ptr=None, stream=None):
+        """Asynchronous: n accumulator records over n_frames frames into n*3 bytes (any alignment) and / or n records
+        (rtx_accum_resolve_device), through the scene's gamma thresholds."""
+        _check(_lib.rtx_accum_resolve_device(self._h, device, int(n), C.c_void_p(d_accum_ptr), int(n_frames),
+                                             C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
+                                             C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
+                                             C.c_void_p(stream) if stream else None), "rtx_accum_resolve_device")
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
