@@ -846,6 +846,53 @@ int rtx_render_view_mean_device(RtxScene *scene, int device, const RtxView *view
                                 const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, void *d_accum, void *d_rgb,
                                 void *d_shade, void *stream);
 
+/* ---- the render pipeline's linear output: RtxPixelShade records ------------------------------------------------------------
+ * rtx_render_view_rows, _lit and _posed write RGB8.  These two write, for the same rows, what rtx_render_view_lit (with
+ * RTX_ROWS_POSED: rtx_render_view_posed) writes to out_shade for the same view and light: record (y - y0) * width + x is the
+ * pixel's 16 bytes — `linear`, the three ordered f32 sums, bit for bit (a NaN stands for any NaN); `rgb8`, the bytes
+ * rtx_render_view_rows* gives; `hits`, the number of the pixel's nb_ray rays with a closest hit, saturating at 255.  One
+ * pair of functions with the light (NULL: the scene's) and the geometry (flags) as arguments.
+ * In every other respect a call is its byte twin — rtx_render_view_rows / _device for a NULL light and no flag,
+ * rtx_render_view_rows_lit / _device for a light, rtx_render_view_rows_posed / _device with RTX_ROWS_POSED: full width only,
+ * the eye's range rule and the light's rules (RTX_ERR_UNSUPPORTED) decided before a device is looked for, ny == 0 (RTX_OK,
+ * stats zeroed, no device needed), stats and kernel_ms, rtx_launch_timings and rtx_debug_tile_descs, no capture and replay,
+ * launches on one device ordered on one stream, the host variant waiting for the lit and pose uses and the device-resident one
+ * marking them, RTX_ERR_BAD_ARG when RTX_ROWS_POSED is given and `device` holds no pose.  It launches the RECORD FORMS of
+ * the three kernels that store a pixel (namespace rtxo: the same bodies, one 16-byte store per pixel in place of three byte
+ * stores) and leaves every later call on the scene unchanged.
+ * Its own rules: RTX_ERR_BAD_ARG for a flag other than RTX_ROWS_POSED, for a d_shade that is NULL or not 16-byte aligned,
+ * and for d_bytes < ny * width * 16. */
+#define RTX_ROWS_POSED 1u
+int rtx_render_view_rows_shade(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                               uint32_t flags /* RTX_ROWS_POSED or 0 */, RtxPixelShade *out_shade, RtxStats *stats);
+int rtx_render_view_rows_shade_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                      void *d_shade, size_t d_bytes, void *stream, uint64_t *d_counters);
+
+/* ---- the mean of N frames through the render pipeline ---------------------------------------------------------------------
+ * rtx_render_view_mean / _device (above) with the pipeline's record launch in the view kernel's place.  For a full-width
+ * rectangle (x0 == 0, nx == width) the outputs and the accumulator are rtx_render_view_mean's / _device's, word for word: the
+ * adds are ordered, the division is made once, the scene is not written.  Argument checks: the mean call's, then full width
+ * (RTX_ERR_BAD_ARG), then — decided on the host, before a device is looked for — the eye's range rule, a light with a
+ * vertex that is not finite, and a frame whose shaft margin is not finite (RTX_ERR_UNSUPPORTED).  Stats are the sums over the
+ * frames.  Per frame k, on the call's stream, with no host wait between frames: the sample-table kernel over (seeds[k],
+ * n_pairs) into the mean's scratch table; the light's points, tour and boxes over that table by rtx_render_view_rows_lit's
+ * kernels (light == NULL: the scene's own triangle and count, since every frame's points differ); a record launch
+ * (rtx_render_view_rows_shade's kernels) into the mean's scratch records, its argument block's table, table length and the
+ * light's five fields swapped; the add.  The aim kernels run once: there is one eye.  After the last frame the resolve.
+ * The shaft margin of a frame's light points is made on the host from the seed, in closed form over the nb_ray * count
+ * entries the points read (n_frames * nb_ray * count point statements per call); rtx_scene_light_walk_seeded reads it back,
+ * host only: its outputs are rtx_scene_light_walk_for's on a scene reseeded with (seed, n_pairs), light == NULL: the
+ * scene's own.  Ordering: the scratch buffers, the light buffers (the lit-rows buffers among them) and, when posed, the pose
+ * are guarded as rtx_render_view_mean's are. */
+int rtx_render_view_rows_mean(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                              uint32_t flags /* RTX_MEAN_POSED or 0 */, const uint64_t *seeds, uint32_t n_frames,
+                              uint32_t n_pairs, uint8_t *out_rgb, RtxPixelShade *out_shade, RtxStats *stats);
+int rtx_render_view_rows_mean_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                     const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, void *d_accum, void *d_rgb,
+                                     void *d_shade, void *stream);
+int rtx_scene_light_walk_seeded(const RtxScene *scene, const RtxLight *light /* NULL = the scene's */, uint64_t seed,
+                                uint32_t n_pairs, uint32_t *out_order, float *out_boxes, float *out_shaft_delta);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

@@ -110,6 +110,7 @@ pub struct RtxAccumPixel {
     pub hit_frames: u32,
 }
 pub const RTX_MEAN_POSED: u32 = 1;
+pub const RTX_ROWS_POSED: u32 = 1;
 pub const RTX_MAX_MEAN_FRAMES: u32 = 65536;
 /// A pinhole view of an uploaded scene for `rtx_render_view`: the frame `create_rays` sees, the `Camera` after
 /// `Camera::new` (`rtxh_camera_new` computes `u`, `v`, `w`) and the rectangle of pixels to render.
@@ -287,6 +288,25 @@ extern "C" {
     pub fn rtx_render_view_rows_posed_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
                                              d_rgb: *mut c_void, d_bytes: usize, stream: *mut c_void,
                                              d_counters: *mut u64) -> c_int;
+    /// The pipeline's linear output: the rows as `RtxPixelShade` records, `rtx_render_view_lit`'s (with `RTX_ROWS_POSED`
+    /// `rtx_render_view_posed`'s) `out_shade` bit for bit; otherwise the byte twin chosen by `light` and `flags`.
+    /// `d_shade`: 16-byte aligned, `d_bytes >= ny * width * 16`; an unknown flag is `RTX_ERR_BAD_ARG`.
+    pub fn rtx_render_view_rows_shade(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                      flags: u32, out_shade: *mut RtxPixelShade, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_rows_shade_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                             flags: u32, d_shade: *mut c_void, d_bytes: usize, stream: *mut c_void,
+                                             d_counters: *mut u64) -> c_int;
+    /// `rtx_render_view_mean` / `_device` through the render pipeline: full width only, the same outputs and accumulator word
+    /// for word; the eye's range rule and every frame's shaft margin are decided on the host (`RTX_ERR_UNSUPPORTED`).
+    pub fn rtx_render_view_rows_mean(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight, flags: u32,
+                                     seeds: *const u64, n_frames: u32, n_pairs: u32, out_rgb: *mut u8,
+                                     out_shade: *mut RtxPixelShade, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_rows_mean_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                            flags: u32, seeds: *const u64, n_frames: u32, n_pairs: u32, d_accum: *mut c_void,
+                                            d_rgb: *mut c_void, d_shade: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Host only: `rtx_scene_light_walk_for`'s outputs on a scene reseeded with (`seed`, `n_pairs`); `light` NULL: the scene's.
+    pub fn rtx_scene_light_walk_seeded(scene: *const RtxScene, light: *const RtxLight, seed: u64, n_pairs: u32,
+                                       out_order: *mut u32, out_boxes: *mut f32, out_shaft_delta: *mut f32) -> c_int;
     /// Host only: the plane records (n_global x 16 words) and the aimed stream (n_nodes x 8 words) a pose makes for the
     /// pipeline; each output may be NULL, `eye` when `out_aimed` is.  `rtx_debug_pose_pipeline` reads the device's back.
     pub fn rtx_scene_posed_pipeline_records(scene: *const RtxScene, v0v1v2: *const f32, eye: *const f32, out_planes: *mut u32,

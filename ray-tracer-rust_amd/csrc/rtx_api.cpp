@@ -210,6 +210,9 @@ public:
     PinnedBuffer h_stage;
     struct { DeviceBuffer hits, pix_slot, tiles, chunks, results, acc, ctr, buckets, cut; } ws;   // streamed pipeline:
                                                                                     // intermediate products in HBM
+    // a record launch's per-pixel hit counts between its passes, beside ws.acc (rtx_device.h: launch_trace_records); allocated
+    // by the first record launch of a scene with more than one ray per pixel, never by a byte launch
+    DeviceBuffer ws_record_hits;
     // ray queries, ray shading and views (rtx_query.hip, rtx_shade.hip, rtx_view.hip): device copies of the host entry points' arrays, the
     // regrouping pass's (key, ray number) buffers and the sort's temporary storage; none shared with the render workspace
     DeviceBuffer q_first, q_second, q_out;
@@ -651,10 +654,12 @@ struct Timed {
 // has the device current and the scene uploaded.  The redo queue is library-owned per device: launches on one device
 // must be ordered on one stream.
 // split: the long list of the scene's own view (probe_split_of), or none.
+// d_shade: NULL, or where the launch writes RtxPixelShade records in place of d_out's bytes (the record forms of the kernels
+// that store a pixel: the two-pass pipeline's alone, without a profile or a list).
 template <class Before>
 int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpec &ts, uint8_t *d_out,
                   unsigned long long *d_counters, unsigned long long *d_wave_prof, hipStream_t stream, Before before,
-                  const rtx::ProbeSplit &split = rtx::ProbeSplit{nullptr, 0u, 0u, 0u})
+                  const rtx::ProbeSplit &split = rtx::ProbeSplit{nullptr, 0u, 0u, 0u}, void *d_shade = nullptr)
 {
     int rc;
     const size_t redo_cap = st.d_redo.capacity(), buckets_cap = st.ws.buckets.capacity();
@@ -662,6 +667,11 @@ int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpe
     rtx::StreamWorkspace ws{};
     bool use_ws = false;
     if (!d_wave_prof && (rc = reserve_stream_ws(st, S, ts, &ws, &use_ws)) != RTX_OK) return rc;
+    if (d_shade) {
+        if (d_wave_prof || !use_ws || !(kernel_variant() & rtx::kVariantProbe)) return RTX_ERR_UNSUPPORTED;
+        const size_t hits_bytes = rtx::trace_record_hits_bytes(S, ts);
+        if (hits_bytes && (rc = st.ws_record_hits.reserve(hits_bytes)) != RTX_OK) return rc;
+    }
     if ((rc = before()) != RTX_OK) return rc;
     const Event *slot = st.ring[st.launches % RTX_TIMING_RING];
     hipEvent_t phases[3] = {slot[0], slot[1], slot[2]};
@@ -671,8 +681,12 @@ int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpe
         st.words_launches = st.words_passes = 0;
     }
     if (ts.local_rows) st.launch_words_ready = false;     // until this launch is known to have gone out whole
-    RTX_HIP(rtx::launch_trace_shade(S, ts, d_out, st.d_redo.as<uint32_t>(), use_ws ? &ws : nullptr, d_counters, d_wave_prof,
-                                    kernel_variant(), stream, d_wave_prof ? nullptr : phases, st.words_launches, st.words_passes, split));
+    if (d_shade)
+        RTX_HIP(rtx::launch_trace_records(S, ts, d_shade, S.nb_ray > 1u ? st.ws_record_hits.as<uint8_t>() : nullptr, st.d_redo.as<uint32_t>(),
+                                          &ws, d_counters, kernel_variant(), stream, phases, st.words_launches, st.words_passes));
+    else
+        RTX_HIP(rtx::launch_trace_shade(S, ts, d_out, st.d_redo.as<uint32_t>(), use_ws ? &ws : nullptr, d_counters, d_wave_prof,
+                                        kernel_variant(), stream, d_wave_prof ? nullptr : phases, st.words_launches, st.words_passes, split));
     if (two_pass) {
         st.launch_words_ready = true;
         ++st.words_launches;
@@ -878,12 +892,14 @@ int reserve_light(const RtxScene *scene, DeviceState &st, const Lit &lit, bool w
 }
 
 // the light kernels on `stream`, after reserve_light: the points; walk: their tour and their boxes too
-int light_launch(const RtxScene *scene, DeviceState &st, const Lit &lit, bool walk, hipStream_t stream)
+// (table / n_pairs: NULL — the scene's table — or a mean call's frame table)
+int light_launch(const RtxScene *scene, DeviceState &st, const Lit &lit, bool walk, hipStream_t stream, const float2 *table = nullptr,
+                 uint32_t n_pairs = 0u)
 {
     const rtx::PreparedScene &p = scene->prep;
     if (lit.count == 0u) return RTX_OK;      // (the scene's own count is 0 then: no kernel reads a point)
-    RTX_HIP(rtxl::launch_light_points(st.samples.as<const float2>(), p.n_samples, lit.tri, p.nb_ray, lit.count,
-                                      st.lit.points.as<float>(), stream));
+    RTX_HIP(rtxl::launch_light_points(table ? table : st.samples.as<const float2>(), table ? n_pairs : p.n_samples, lit.tri, p.nb_ray,
+                                      lit.count, st.lit.points.as<float>(), stream));
     if (!walk) return RTX_OK;
     RTX_HIP(rtxt::launch_tour(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.tour.as<float>(), stream));
     RTX_HIP(rtxt::launch_light_boxes(st.lit.points.as<const float>(), p.nb_ray, lit.count, st.lit.boxes.as<float>(), stream));
@@ -914,22 +930,16 @@ bool light_is_finite(const Lit &lit)
 // tour as sample indices (rtx_scene_light_order's form), the boxes, and the shaft margin, PreparedScene::shaft_delta's fold
 // over this light's boxes.  Each output may be NULL.  O(nb_ray * count) for the margin alone; the tour costs what
 // light_tour_order_f32 costs.  May throw std::bad_alloc.
+// samples: the table the points are made over — the scene's as it stands, or a mean call's frame (seeded: scene_prep.cpp's
+// light_walk_statement reads the nb_ray * count entries the points read and makes no table)
+void light_walk_on_host(const rtx::PreparedScene &p, const Lit &lit, const rtx::SampleSource &samples, uint32_t *order, float *boxes,
+                        float *shaft_delta)
+{
+    rtx::light_walk_statement(p, lit.tri.v, lit.count, samples, order, boxes, shaft_delta);
+}
 void light_walk_on_host(const rtx::PreparedScene &p, const Lit &lit, uint32_t *order, float *boxes, float *shaft_delta)
 {
-    const size_t n = static_cast<size_t>(p.nb_ray) * lit.count;
-    std::vector<float> points(3u * n), box(6u * static_cast<size_t>(p.nb_ray));
-    rtx::light_points_of(lit.tri.v, rtx::sample_source(p), p.nb_ray, lit.count, points.data());
-    rtx::light_boxes_of(points.data(), p.nb_ray, lit.count, box.data());
-    if (boxes) std::memcpy(boxes, box.data(), box.size() * sizeof(float));
-    if (shaft_delta) *shaft_delta = rtx::shaft_delta_of(p.scene_magnitude, box.data(), box.size());
-    if (!order) return;
-    for (uint32_t r = 0; r < p.nb_ray; ++r)
-        for (uint32_t b0 = 0; b0 < lit.count; b0 += rtx::kMaxLightBatch) {
-            const uint32_t bc = std::min(lit.count - b0, rtx::kMaxLightBatch);
-            const size_t first = static_cast<size_t>(r) * lit.count + b0;
-            rtx::light_tour_order_f32(&points[3u * first], bc, order + first);
-            for (uint32_t k = 0; k < bc; ++k) order[first + k] += b0;
-        }
+    light_walk_on_host(p, lit, rtx::sample_source(p), order, boxes, shaft_delta);
 }
 
 // The checks a lit pipeline call adds on the host, before a device is looked for, and the margin of its shaft test: the
@@ -1612,14 +1622,21 @@ int aim_at(const RtxScene *scene, DeviceGeometry &g, const float eye[3], hipStre
 // follow the aim kernels, and the pipeline's kernels are handed that light's five fields.  Whichever geometry it is, no
 // field of the block is added or moved, and the kernels are the same.  So is the shaft margin: it is folded from the bound M
 // every posed coordinate respects, not from the geometry's extent.
+// frame_of / frame (rtx_render_view_rows_mean): the launch is frame `frame` of that call — the table is the mean's scratch
+// table, made from the frame's seed ahead of the light kernels, which then read it in the scene's table's place.
 template <class Before>
 int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const RtxView &v, uint8_t *d_out,
-                     unsigned long long *d_counters, hipStream_t stream, Before before, const Lit *lit, float shaft_delta)
+                     unsigned long long *d_counters, hipStream_t stream, Before before, const Lit *lit, float shaft_delta,
+                     void *d_shade = nullptr, const MeanCall *frame_of = nullptr, uint32_t frame = 0u)
 {
     RTX_TRY(reserve_aimed(scene, g));
     if (lit) RTX_TRY(reserve_light(scene, st, *lit, true));
     rtx::DeviceScene S = device_scene(scene, st, g);
     if (lit) light_swap(st, *lit, true, shaft_delta, &S);
+    if (frame_of) {
+        S.samples = st.mean.table.as<const float2>();
+        S.n_samples = frame_of->n_pairs;
+    }
     S.width = v.width;
     S.height = v.height;
     std::memcpy(S.eye, v.eye, 12);
@@ -1633,8 +1650,12 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const 
     return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
         RTX_TRY(before());
         RTX_TRY(aim_at(scene, g, v.eye, stream));
+        if (frame_of) {
+            RTX_HIP(rtxr::launch_samples(frame_of->seeds[frame], frame_of->n_pairs, st.mean.table.as<float2>(), stream));
+            return light_launch(scene, st, *lit, true, stream, st.mean.table.as<const float2>(), frame_of->n_pairs);
+        }
         return lit ? light_launch(scene, st, *lit, true, stream) : RTX_OK;
-    });
+    }, rtx::ProbeSplit{nullptr, 0u, 0u, 0u}, d_shade);
 }
 
 // What a pipeline view with rows is checked for on the host, before a device is looked for: the eye in range, and with a
@@ -1645,12 +1666,108 @@ int view_rows_supported(const RtxScene *scene, const RtxView *view, const Lit *l
     return lit ? lit_rows_margin(scene, *lit, shaft_delta) : RTX_OK;
 }
 
+// ---- the mean of N frames through the render pipeline (rtx_render_view_rows_mean) -----------------------------------------
+
+// The shaft margin of every frame of a mean call, on the host, before a device is looked for: frame k's light points are made
+// over the seeded table (seeds[k], n_pairs), and the margin is shaft_delta_of over their boxes — light_walk_on_host's, which
+// reads the nb_ray * count entries the points read and makes no table.  n_frames * nb_ray * count point statements.
+// RTX_ERR_UNSUPPORTED when a frame's margin is not finite (prepare_scene's rule, per frame).
+int rows_mean_margins(const RtxScene *scene, const MeanCall &call, std::vector<float> *margins)
+{
+    try {
+        margins->assign(call.n_frames, scene->prep.shaft_delta);
+        if (call.lit.count == 0u) return RTX_OK;
+        for (uint32_t k = 0; k < call.n_frames; ++k) {
+            light_walk_on_host(scene->prep, call.lit, rtx::SampleSource{nullptr, call.seeds[k], call.n_pairs}, nullptr, nullptr,
+                               &(*margins)[k]);
+            if (!std::isfinite((*margins)[k])) return RTX_ERR_UNSUPPORTED;
+        }
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+// mean_launch with the pipeline's record launch in the view kernel's place.  Per frame, on `stream`, nothing waited for: the
+// frame's table from its seed, the light's points, tour and boxes over that table (the _rows_lit kernels), a record launch
+// whose argument block has the table, its length and the light's five fields swapped, the add.  The aim kernels run once:
+// there is one eye.  Then the resolve.
+int rows_mean_launch(RtxScene *scene, DeviceState &st, const RtxView *view, const MeanCall &call, const std::vector<float> &margins,
+                     void *d_accum, void *d_rgb, void *d_shade, unsigned long long *d_counters, hipStream_t stream)
+{
+    const uint32_t n_pixels = view->nx * view->ny;
+    DeviceGeometry *geo;
+    RTX_TRY(geometry_of(st, call.posed, &geo));
+    RTX_TRY(reserve_mean(st, call.n_pairs, n_pixels));
+    for (uint32_t k = 0; k < call.n_frames; ++k) {
+        RTX_TRY(view_rows_launch(scene, st, *geo, *view, nullptr, d_counters, stream, [] { return static_cast<int>(RTX_OK); }, &call.lit,
+                                 margins[k], st.mean.records.as<void>(), &call, k));
+        RTX_HIP(rtxc::launch_accum_add(n_pixels, st.mean.records.as<const void>(), d_accum, k == 0u, stream));
+    }
+    if (d_rgb || d_shade)
+        RTX_HIP(rtxc::launch_accum_resolve(st.thr.as<const float>(), n_pixels, d_accum, call.n_frames, d_rgb, d_shade, stream));
+    return RTX_OK;
+}
+
+unsigned rows_mean_uses(const MeanCall &call) { return mean_uses(call); }      // (the lit-rows buffers are the light's: kUsesLight)
+
+// the argument checks and the host-side rules the two variants share, in the mean call's order, then the pipeline's
+int rows_mean_supported(const RtxScene *scene, const RtxView *view, const MeanCall &call, std::vector<float> *margins)
+{
+    if (view->x0 != 0u || view->nx != view->width) return RTX_ERR_BAD_ARG;
+    if (view->nx * view->ny == 0u) return RTX_OK;
+    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
+    if (!light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
+    return rows_mean_margins(scene, call, margins);
+}
+
+int rows_mean_host(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, uint8_t *rgb, RtxPixelShade *shade,
+                   RtxStats *stats)
+{
+    const Timed timed(stats);
+    std::vector<float> margins;
+    RTX_TRY(rows_mean_supported(scene, view, call, &margins));
+    const uint32_t n_pixels = view->nx * view->ny;
+    if (n_pixels == 0u) return timed.empty();
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const RtxView v = *view;
+    const size_t records = static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade);
+    const size_t shade_bytes = shade ? records : 0u, rgb_bytes = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
+    RTX_TRY(st.q_out.reserve(records + shade_bytes + rgb_bytes));
+    uint8_t *d_accum = st.q_out.as<uint8_t>(), *d_shade = shade ? d_accum + records : nullptr;
+    uint8_t *d_rgb = rgb ? d_accum + records + shade_bytes : nullptr;
+    RTX_TRY(wait_for_uses(st, rows_mean_uses(call)));
+    RTX_TRY(timed.begin(st));
+    RTX_TRY(rows_mean_launch(scene, st, &v, call, margins, d_accum, d_rgb, d_shade, timed.counters(st), st.stream));
+    RTX_TRY(timed.end(st));
+    if (shade) RTX_HIP(hipMemcpyAsync(shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st.stream));
+    if (rgb) RTX_HIP(hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, st.stream));
+    return timed.gather(st, static_cast<uint64_t>(call.n_frames) * n_pixels * scene->prep.nb_ray, call.lit.count);
+}
+
+int rows_mean_device(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, void *d_accum, void *d_rgb,
+                     void *d_shade, void *stream)
+{
+    std::vector<float> margins;
+    RTX_TRY(rows_mean_supported(scene, view, call, &margins));
+    if (view->nx * view->ny == 0u) return RTX_OK;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    RTX_TRY(rows_mean_launch(scene, st, view, call, margins, d_accum, d_rgb, d_shade, nullptr, static_cast<hipStream_t>(stream)));
+    return mark_uses(st, rows_mean_uses(call), static_cast<hipStream_t>(stream));
+}
+
 // The bodies of rtx_render_view_rows and rtx_render_view_rows_device, each with its _lit twin's light as an argument (NULL:
 // the scene's, nothing swapped) and its _posed twin's switch.  The host one renders into d_out on the library's stream and
-// copies the rows back.
-int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, uint8_t *out_rgb, RtxStats *stats)
+// copies the rows back.  records (rtx_render_view_rows_shade): the output is RtxPixelShade records, 16 bytes a pixel in
+// place of 3, through the record forms of the kernels that store a pixel; everything else is the byte call's.
+int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, void *out, RtxStats *stats,
+                   bool records = false)
 {
-    if (!view_rows_args_ok(scene, view, out_rgb)) return RTX_ERR_BAD_ARG;
+    if (!view_rows_args_ok(scene, view, out)) return RTX_ERR_BAD_ARG;
     const Timed timed(stats);
     if (view->ny == 0u) return timed.empty();
     float shaft_delta = 0.0f;
@@ -1659,25 +1776,26 @@ int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
     const RtxView v = *view;                 // (the caller's may change while the call runs)
-    const size_t bytes = static_cast<size_t>(v.ny) * v.width * 3u;
+    const size_t bytes = static_cast<size_t>(v.ny) * v.width * (records ? sizeof(RtxPixelShade) : 3u);
     RTX_TRY(st.d_out.reserve(bytes));
     DeviceGeometry *geo;
     RTX_TRY(geometry_of(st, posed, &geo));
     // a device-resident call may still read its light, make the pose, or walk what was aimed over it
     RTX_TRY(wait_for_uses(st, uses_of(lit, posed)));
     RTX_TRY(view_rows_launch(scene, st, *geo, v, st.d_out.as<uint8_t>(), timed.counters(st), st.stream, [&] { return timed.begin(st); },
-                             lit, shaft_delta));
+                             lit, shaft_delta, records ? st.d_out.as<void>() : nullptr));
     RTX_TRY(timed.end(st));
-    RTX_HIP(hipMemcpyAsync(out_rgb, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
+    RTX_HIP(hipMemcpyAsync(out, st.d_out.as<void>(), bytes, hipMemcpyDeviceToHost, st.stream));
     return timed.gather(st, static_cast<uint64_t>(v.ny) * v.width * scene->prep.nb_ray, lit ? lit->count : scene->prep.nb_light_sample);
 }
 
 // ... the device-resident one into the caller's buffer on the caller's stream, nothing waited for
 int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, void *d_rgb, size_t d_bytes,
-                     void *stream, uint64_t *d_counters)
+                     void *stream, uint64_t *d_counters, bool records = false)
 {
     if (!view_rows_args_ok(scene, view, d_rgb)) return RTX_ERR_BAD_ARG;
-    if (d_bytes < static_cast<size_t>(view->ny) * view->width * 3u) return RTX_ERR_BAD_ARG;
+    if (records && reinterpret_cast<uintptr_t>(d_rgb) % sizeof(RtxPixelShade) != 0u) return RTX_ERR_BAD_ARG;
+    if (d_bytes < static_cast<size_t>(view->ny) * view->width * (records ? sizeof(RtxPixelShade) : 3u)) return RTX_ERR_BAD_ARG;
     if (view->ny == 0u) return RTX_OK;
     float shaft_delta = 0.0f;
     RTX_TRY(view_rows_supported(scene, view, lit, &shaft_delta));
@@ -1686,7 +1804,8 @@ int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit
     DeviceGeometry *geo;
     RTX_TRY(geometry_of(e.state(), posed, &geo));
     RTX_TRY(view_rows_launch(scene, e.state(), *geo, *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
-                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta));
+                             static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta,
+                             records ? d_rgb : nullptr));
     return mark_uses(e.state(), uses_of(lit, posed), static_cast<hipStream_t>(stream));
 }
 
@@ -2819,6 +2938,61 @@ int rtx_render_view_rows_posed_device(RtxScene *scene, int device, const RtxView
 {
     const CallLight l(scene, light, CallLight::kOptional);
     return l.ok ? view_rows_device(scene, device, view, l.lit, true, d_rgb, d_bytes, stream, d_counters) : RTX_ERR_BAD_ARG;
+}
+
+// The pipeline's records: view_rows_host / view_rows_device with the light (NULL: the scene's, nothing swapped) and the
+// geometry (RTX_ROWS_POSED) as arguments, as the byte calls are inside this file.
+int rtx_render_view_rows_shade(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                               RtxPixelShade *out_shade, RtxStats *stats)
+{
+    if (flags & ~RTX_ROWS_POSED) return RTX_ERR_BAD_ARG;
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? view_rows_host(scene, device, view, l.lit, (flags & RTX_ROWS_POSED) != 0u, out_shade, stats, true) : RTX_ERR_BAD_ARG;
+}
+
+int rtx_render_view_rows_shade_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                      void *d_shade, size_t d_bytes, void *stream, uint64_t *d_counters)
+{
+    if (flags & ~RTX_ROWS_POSED) return RTX_ERR_BAD_ARG;
+    const CallLight l(scene, light, CallLight::kOptional);
+    return l.ok ? view_rows_device(scene, device, view, l.lit, (flags & RTX_ROWS_POSED) != 0u, d_shade, d_bytes, stream, d_counters, true)
+                : RTX_ERR_BAD_ARG;
+}
+
+int rtx_render_view_rows_mean(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                              const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, uint8_t *out_rgb, RtxPixelShade *out_shade,
+                              RtxStats *stats)
+{
+    MeanCall call;
+    const void *out = out_rgb ? static_cast<const void *>(out_rgb) : out_shade;
+    if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, out, &call)) return RTX_ERR_BAD_ARG;
+    return rows_mean_host(scene, device, view, call, out_rgb, out_shade, stats);
+}
+
+int rtx_render_view_rows_mean_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                     const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, void *d_accum, void *d_rgb,
+                                     void *d_shade, void *stream)
+{
+    MeanCall call;
+    if (!d_accum || !aligned16(d_accum, d_shade)) return RTX_ERR_BAD_ARG;
+    if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, d_accum, &call)) return RTX_ERR_BAD_ARG;
+    return rows_mean_device(scene, device, view, call, d_accum, d_rgb, d_shade, stream);
+}
+
+int rtx_scene_light_walk_seeded(const RtxScene *scene, const RtxLight *light, uint64_t seed, uint32_t n_pairs, uint32_t *out_order,
+                                float *out_boxes, float *out_shaft_delta)
+{
+    if (!scene || n_pairs == 0u) return RTX_ERR_BAD_ARG;
+    RtxLight own;
+    if (!light && rtx_scene_light(scene, &own) != RTX_OK) return RTX_ERR_BAD_ARG;
+    Lit lit;
+    if (!lit_of(scene, light ? light : &own, &lit)) return RTX_ERR_BAD_ARG;
+    try {
+        light_walk_on_host(scene->prep, lit, rtx::SampleSource{nullptr, seed, n_pairs}, out_order, out_boxes, out_shaft_delta);
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return static_cast<int>(scene->prep.nb_ray * lit.count);      // <= 2^20
 }
 
 int rtx_scene_posed_pipeline_records(const RtxScene *scene, const float *v0v1v2, const float eye[3], uint32_t *out_planes,

@@ -206,6 +206,14 @@ hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t 
                               unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
                               hipEvent_t *phase_events = nullptr, uint32_t launch_no = 0u, uint32_t pass_no = 0u,
                               const ProbeSplit &split = ProbeSplit{nullptr, 0u, 0u, 0u});
+// The same launch through the record forms of the kernels that store a pixel (rtx_kernel.hip, namespace rtxo): d_shade takes
+// local_rows x width RtxPixelShade records, 16-byte aligned, one 16-byte store per pixel.  d_hits: trace_record_hits_bytes()
+// bytes, the per-pixel hit counts a launch's passes hand on beside StreamWorkspace::acc (0: one ray per pixel, none needed —
+// d_hits may be NULL).  The two-pass pipeline only, and never a long list.
+hipError_t launch_trace_records(const DeviceScene &S, const TileSpec &ts, void *d_shade, uint8_t *d_hits, uint32_t *d_redo,
+                                const StreamWorkspace *ws, unsigned long long *d_counters, uint32_t variant, hipStream_t stream,
+                                hipEvent_t *phase_events = nullptr, uint32_t launch_no = 0u, uint32_t pass_no = 0u);
+size_t trace_record_hits_bytes(const DeviceScene &S, const TileSpec &ts);
 // Whether a launch's tiles are tiles of the frame, so that the scene's long list names them: the share starts on a tile
 // row, and every band of it but a single one is whole tile rows.  (Otherwise a tile of the launch straddles two of the frame.)
 inline bool tiles_frame_aligned(const TileSpec &ts)

@@ -5,7 +5,8 @@
 // The traversal itself is in rtx_traverse.hpp; the passes of a launch are in rtx_pass_helpers.hpp (tile and pixel helpers),
 // rtx_pass_schedule.hpp (probe_kernel), rtx_pass_order.hpp (the counting and ordering kernels) and rtx_pass_shade.hpp
 // (shade_tiles_kernel), the timing instrumentation of tools/ in rtx_probes.hpp.  This file: reference_tiles_kernel, the
-// launcher, and the text that says what the library was built with.
+// record forms of the three kernels that store a pixel (namespace rtxo; they share the byte forms'
+// bodies), the launcher, and the text that says what the library was built with.
 //
 // A launch (launch_probe, further down) is two passes over the 8x8-pixel tiles of its rows, four dispatches:
 //   scheduling pass   probe_kernel (one wavefront per tile, one work-item per pixel: primary ray, closest hit,
@@ -33,6 +34,9 @@
 // (x.powf(1/2.2)*255) as u8 with the host libm and the kernels count thresholds <= x.
 #include <cstdlib>
 #include <type_traits>
+#if defined(RTX_RECORD_FORMS)
+#error "RTX_RECORD_FORMS is not a build switch: this file sets it around its second inclusion of the two passes' headers"
+#endif
 #include "rtx_traverse.hpp"
 // the passes, one file each (a kernel of a later one uses what the earlier ones define; one translation unit)
 #include "rtx_pass_helpers.hpp"
@@ -52,67 +56,38 @@ __global__ void __launch_bounds__(64) reference_tiles_kernel(DeviceScene S, Tile
                                                               unsigned long long *__restrict__ counters,
                                                               bool tile_blocks = false)
 {
-    const TriRec RTX_CONSTANT *tris = (const TriRec RTX_CONSTANT *)S.tris;
-    const bool have_ref = S.n_ref_nodes != 0u;
-    const NodeRec RTX_CONSTANT *stream = (const NodeRec RTX_CONSTANT *)(have_ref ? S.ref_nodes : S.nodes);
-    const uint32_t n_stream = have_ref ? S.n_ref_nodes : S.n_nodes;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t n_redo = __builtin_amdgcn_readfirstlane(redo[kQueueRedoCount]);
-    WaveCounters wc;
-    unsigned long long primary_hits = 0;
-    for (uint32_t q = blockIdx.x; q < n_redo; q += gridDim.x) {
-        const uint32_t tid = __builtin_amdgcn_readfirstlane(redo[kQueueHeader + q]);
-        uint32_t px, py, ly;
-        uint32_t tile_x, tile_y;
-        tile_xy(tid, tiles_x, tile_blocks, tile_x, tile_y);
-        const bool in_frame = tile_pixel(S, ts, tile_x, tile_y, lane, px, py, ly);
-        float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
-        const float denom = (float)(S.nb_ray * S.nb_light);
-        for (uint32_t r = 0; r < S.nb_ray; ++r) {
-            float dx, dy, dz, t;
-            uint32_t idx;
-            primary_ray(S, in_frame, px, py, r, dx, dy, dz);
-            closest_hit_reference<COUNT, SPHERES>(stream, tris, S.shade, n_stream, have_ref, in_frame, S.eye[0], S.eye[1], S.eye[2],
-                                         dx, dy, dz, t, idx, wc);
-            const bool hit = in_frame && idx != kNone;
-            const unsigned long long hit_mask = ballot(hit);
-            if (hit_mask == 0ull) continue;
-            if (COUNT) primary_hits += __popcll(hit_mask);
-            float hx = 0.0f, hy = 0.0f, hz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-            if (hit) {
-                hx = S.eye[0] + t * dx;
-                hy = S.eye[1] + t * dy;
-                hz = S.eye[2] + t * dz;
-                const ShadeRec sh = S.shade[idx];
-                hit_normal<SPHERES>(sh, hx, hy, hz, nx, ny, nz);
-                cr = sh.rgb[0]; cg = sh.rgb[1]; cb = sh.rgb[2];
-            }
-            for (uint32_t i = 0; i < S.nb_light; ++i) {
-                const float *lp = S.light_points + 3u * (r * S.nb_light + i);
-                const float vx = lp[0] - hx, vy = lp[1] - hy, vz = lp[2] - hz;
-                const float dist_light = sqrtf(vx * vx + vy * vy + vz * vz);
-                const float sx = vx / dist_light, sy = vy / dist_light, sz = vz / dist_light;
-                float st;
-                uint32_t sidx;
-                closest_hit_reference<COUNT, SPHERES>(stream, tris, S.shade, n_stream, have_ref, hit, hx, hy, hz, sx, sy, sz,
-                                             st, sidx, wc);
-                const float lnd = fabsf(nx * sx + ny * sy + nz * sz);
-                bool lit = true;
-                if (sidx != kNone) {
-                    const float qx = hx - (hx + st * sx), qy = hy - (hy + st * sy), qz = hz - (hz + st * sz);
-                    lit = sqrtf(qx * qx + qy * qy + qz * qz) > dist_light;
-                }
-                if (hit && lit) {
-                    acc_r = acc_r + ((cr * lnd) / denom);
-                    acc_g = acc_g + ((cg * lnd) / denom);
-                    acc_b = acc_b + ((cb * lnd) / denom);
-                }
-            }
-        }
-        if (in_frame) store_pixel(S, out, px, ly, acc_r, acc_g, acc_b);
-    }
-    if (COUNT && lane == 0) flush_counters<COUNT>(counters, primary_hits, wc);
+#include "rtx_reference_body.inc"
 }
+
+}  // namespace rtx
+
+// The record forms of the three kernels that store a pixel (rtx_render_view_rows_shade): the same bodies (the two passes'
+// headers included a second time, rtx_reference_body.inc) with a RecordOut —
+// one 16-byte store per pixel in place of three byte stores.  A namespace of their own: the byte forms keep their symbols.
+// Only the forms a view's launch is handed: probe_kernel's one-wavefront form (a view's launch has no long list).
+namespace rtxo {
+
+using namespace rtx;
+
+#define RTX_RECORD_FORMS 1      // probe_records_kernel and shade_records_kernel: the two headers' kernels once more
+#include "rtx_pass_schedule.hpp"
+#include "rtx_pass_shade.hpp"
+#undef RTX_RECORD_FORMS
+
+template <bool COUNT, bool SPHERES>
+__global__ void __launch_bounds__(64) reference_records_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x,
+                                                                uint4 *__restrict__ out_shade,
+                                                                const uint32_t *__restrict__ redo,
+                                                                unsigned long long *__restrict__ counters)
+{
+    constexpr bool tile_blocks = true;
+    const RecordOut out{out_shade, nullptr};
+#include "rtx_reference_body.inc"
+}
+
+}  // namespace rtxo
+
+namespace rtx {
 
 
 namespace {
@@ -143,8 +118,9 @@ float split_share()
 #endif
 }
 
-template <bool COUNT, bool FAST, bool SPHERES>
-hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
+// OUT: uint8_t * (the byte forms) or RecordOut (the record forms, rtxo)
+template <bool COUNT, bool FAST, bool SPHERES, class OUT>
+hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, OUT d_out, uint32_t *d_redo,
                         const StreamWorkspace &W, unsigned long long *d_counters, hipStream_t stream, hipEvent_t *ev,
                         uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split_in)
 {
@@ -154,7 +130,9 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
     constexpr int NW = RTX_SHADE_NW;     // wavefronts per workgroup of shade_tiles_kernel
     // the form of the two kernels that have two: per-tile cuts, or — a scene too large for them — the whole stream
     const bool whole = S.n_nodes > S.cut_max_nodes;
-    const auto shade = whole ? shade_tiles_kernel<COUNT, FAST, NW, SPHERES, true> : shade_tiles_kernel<COUNT, FAST, NW, SPHERES, false>;
+    constexpr bool kRecords = std::is_same<OUT, RecordOut>::value;
+    const auto shade_bytes = whole ? shade_tiles_kernel<COUNT, FAST, NW, SPHERES, true> : shade_tiles_kernel<COUNT, FAST, NW, SPHERES, false>;
+    const auto shade_records = whole ? rtxo::shade_records_kernel<COUNT, FAST, NW, SPHERES, true> : rtxo::shade_records_kernel<COUNT, FAST, NW, SPHERES, false>;
     const uint32_t batch = S.nb_light < kMaxLightBatch ? (S.nb_light ? S.nb_light : 1u) : kMaxLightBatch;
 #if RTX_ABLATION
     const size_t lds_bytes = (static_cast<size_t>(lds_floats(batch)) + (S.j1_mode == 1u ? kJ1WindowWords : 0u)) * sizeof(float);
@@ -169,9 +147,12 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
     const ProbeSplit split = (split_in.n_long != 0u && split_in.words && probe_split_applies(S, ts)) ? split_in : ProbeSplit{nullptr, 0u, 0u, 0u};
     const uint32_t probe_waves = split.n_long != 0u ? 4u : 1u;
     const uint32_t probe_grid = split.n_long != 0u ? ((split.n_long + 7u) & ~7u) + 128u * ((n_tiles + 511u) / 512u) : 512u * ((n_tiles + 511u) / 512u);
+    if (kRecords && split.n_long != 0u) return hipErrorInvalidValue;     // (the record forms have no four-beam probe_kernel)
     const auto probe = whole ? probe_kernel<COUNT, FAST, SPHERES, true, 1u>
                      : split.n_long != 0u ? probe_kernel<COUNT, FAST, SPHERES, false, 4u> : probe_kernel<COUNT, FAST, SPHERES, false, 1u>;
-    // persistent grid = what the device keeps resident of the form that is launched (the two forms differ in registers)
+    const auto probe_records = whole ? rtxo::probe_records_kernel<COUNT, FAST, SPHERES, true> : rtxo::probe_records_kernel<COUNT, FAST, SPHERES, false>;
+    // persistent grid = what the device keeps resident of the form that is launched (the cut and whole-stream forms differ in
+    // registers, and so may the byte and record forms: each instantiation of this launcher — one per OUT — has its own cache)
     static thread_local int cached_dev = -1, cached_blocks = 0;
     static thread_local size_t cached_lds = 0;
     static thread_local bool cached_whole = false;
@@ -180,7 +161,9 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
     if (e != hipSuccess) return e;
     if (dev != cached_dev || lds_bytes != cached_lds || whole != cached_whole) {
         int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shade, 64 * NW, lds_bytes)) != hipSuccess) return e;
+        if (kRecords) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shade_records, 64 * NW, lds_bytes);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shade_bytes, 64 * NW, lds_bytes);
+        if (e != hipSuccess) return e;
         if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
         cached_blocks = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
         cached_dev = dev;
@@ -197,17 +180,29 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out
         // one that only counts (the table in front of kOrderList)
         const uint32_t hist_set = (pass_no + r) & 1u;
         const StreamWorkspace Wp = counting_set(W, hist_set);      // what the kernels that count are handed
-        hipLaunchKernelGGL(probe, dim3(probe_grid), dim3(64 * probe_waves), 0, stream,
-                           S, ts, tiles_x, n_tiles, r, Wp, d_out, queue, d_counters, split);
+        if constexpr (kRecords)
+            hipLaunchKernelGGL(probe_records, dim3(probe_grid), dim3(64), 0, stream,
+                               S, ts, tiles_x, n_tiles, r, Wp, d_out.shade, d_out.hits, queue, d_counters);
+        else
+            hipLaunchKernelGGL(probe, dim3(probe_grid), dim3(64 * probe_waves), 0, stream,
+                               S, ts, tiles_x, n_tiles, r, Wp, d_out, queue, d_counters, split);
         if (whole) hipLaunchKernelGGL(count_classes_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, Wp);
         hipLaunchKernelGGL(order_tiles_kernel, dim3((n_tiles + 1023u) / 1024u), dim3(1024), 0, stream, n_tiles, W, grid, split_share(),
                            hist_set, whole ? 0u : grid, queue, next_redo_count);
         if (ev && r == 0u && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;   // end of the scheduling pass
-        hipLaunchKernelGGL(shade, dim3(grid), dim3(64 * NW), lds_bytes, stream, S, ts, batch, tiles_x, n_tiles, r, W, d_out, queue, d_counters);
+        if constexpr (kRecords)
+            hipLaunchKernelGGL(shade_records, dim3(grid), dim3(64 * NW), lds_bytes, stream, S, ts, batch, tiles_x, n_tiles, r, W,
+                               d_out.shade, d_out.hits, queue, d_counters);
+        else
+            hipLaunchKernelGGL(shade_bytes, dim3(grid), dim3(64 * NW), lds_bytes, stream, S, ts, batch, tiles_x, n_tiles, r, W, d_out, queue, d_counters);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((reference_tiles_kernel<COUNT, SPHERES>), dim3(n_tiles < 1024u ? n_tiles : 1024u), dim3(64), 0, stream,
-                       S, ts, tiles_x, d_out, queue, d_counters, true);
+    if constexpr (kRecords)
+        hipLaunchKernelGGL((rtxo::reference_records_kernel<COUNT, SPHERES>), dim3(n_tiles < 1024u ? n_tiles : 1024u), dim3(64), 0, stream,
+                           S, ts, tiles_x, d_out.shade, queue, d_counters);
+    else
+        hipLaunchKernelGGL((reference_tiles_kernel<COUNT, SPHERES>), dim3(n_tiles < 1024u ? n_tiles : 1024u), dim3(64), 0, stream,
+                           S, ts, tiles_x, d_out, queue, d_counters, true);
     return hipGetLastError();
 }
 
@@ -250,22 +245,25 @@ StreamWorkspaceBytes stream_workspace_bytes(const DeviceScene &S, const TileSpec
     return b;
 }
 
-static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
+template <class OUT>
+static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, OUT d_out, uint32_t *d_redo,
                                   const StreamWorkspace *ws, unsigned long long *d_counters,
                                   unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream, hipEvent_t *ev,
                                   uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split)
 {
-    // the two-pass pipeline: launch_probe<COUNT, FAST, SPHERES> for the caller's counters and the scene's primitives
+    // the two-pass pipeline: launch_probe<COUNT, FAST, SPHERES, OUT> for the caller's counters and the scene's primitives
     auto two_pass = [&](auto fast) {
         constexpr bool FAST = decltype(fast)::value;
         const bool count = d_counters != nullptr, spheres = S.n_spheres != 0u;
-        const auto launch = count ? (spheres ? launch_probe<true, FAST, true> : launch_probe<true, FAST, false>)
-                                  : (spheres ? launch_probe<false, FAST, true> : launch_probe<false, FAST, false>);
+        const auto launch = count ? (spheres ? launch_probe<true, FAST, true, OUT> : launch_probe<true, FAST, false, OUT>)
+                                  : (spheres ? launch_probe<false, FAST, true, OUT> : launch_probe<false, FAST, false, OUT>);
         return launch(S, ts, d_out, d_redo, *ws, d_counters, stream, ev, launch_no, pass_no, split);
     };
 #if RTX_ABLATION
-    if (!((variant & kVariantProbe) && ws && !d_wave_prof))
-        return launch_dispatch_ablation(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream);
+    if (!((variant & kVariantProbe) && ws && !d_wave_prof)) {
+        if constexpr (std::is_same<OUT, RecordOut>::value) return hipErrorInvalidValue;   // (records: the two-pass pipeline's alone)
+        else return launch_dispatch_ablation(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream);
+    }
     if (!(variant & 1u)) return two_pass(std::false_type{});   // with the exact (division-based) box test on inner nodes
 #else
     if (variant != kDefaultVariant || !ws || d_wave_prof) return hipErrorInvalidValue;   // one pipeline in this build
@@ -273,10 +271,11 @@ static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, uint
     return two_pass(std::true_type{});
 }
 
-hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
-                              const StreamWorkspace *ws, unsigned long long *d_counters,
-                              unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
-                              hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split)
+template <class OUT>
+static hipError_t launch_any(const DeviceScene &S, const TileSpec &ts, OUT d_out, uint32_t *d_redo,
+                             const StreamWorkspace *ws, unsigned long long *d_counters,
+                             unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
+                             hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split)
 {
     if (ts.local_rows == 0) return hipSuccess;
     hipError_t e;
@@ -287,6 +286,28 @@ hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t 
     if (e != hipSuccess) return e;
     if (phase_events && (e = hipEventRecord(phase_events[2], stream)) != hipSuccess) return e;
     return hipSuccess;
+}
+
+hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t *d_out, uint32_t *d_redo,
+                              const StreamWorkspace *ws, unsigned long long *d_counters,
+                              unsigned long long *d_wave_prof, uint32_t variant, hipStream_t stream,
+                              hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no, const ProbeSplit &split)
+{
+    return launch_any(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream, phase_events, launch_no, pass_no, split);
+}
+
+hipError_t launch_trace_records(const DeviceScene &S, const TileSpec &ts, void *d_shade, uint8_t *d_hits, uint32_t *d_redo,
+                                const StreamWorkspace *ws, unsigned long long *d_counters, uint32_t variant, hipStream_t stream,
+                                hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no)
+{
+    if (!ws || !d_shade || (S.nb_ray > 1u && !d_hits)) return hipErrorInvalidValue;
+    return launch_any(S, ts, RecordOut{static_cast<uint4 *>(d_shade), d_hits}, d_redo, ws, d_counters, nullptr, variant, stream,
+                      phase_events, launch_no, pass_no, ProbeSplit{nullptr, 0u, 0u, 0u});
+}
+
+size_t trace_record_hits_bytes(const DeviceScene &S, const TileSpec &ts)
+{
+    return S.nb_ray > 1u ? static_cast<size_t>(numbered_tiles((S.width + 7u) / 8u, (ts.local_rows + 7u) / 8u)) * 64u : 0u;
 }
 
 }  // namespace rtx

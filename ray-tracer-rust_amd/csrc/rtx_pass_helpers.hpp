@@ -187,6 +187,48 @@ __device__ __forceinline__ void store_pixel(const DeviceScene &S, uint8_t *__res
     store_pixel(S, S.gamma_thr, out, px, ly, r, g, b);
 }
 
+// Where a launch's pixels go, as the type of the kernels' bodies' `out`: uint8_t * — RGB8, three byte stores per pixel —
+// or RecordOut: one 16-byte RtxPixelShade record per pixel (the three ordered sums, their three bytes, the hit count; record
+// ly * width + px), and, for a scene with more than one ray per pixel, the per-pixel hit counts the passes of a launch
+// hand on as they hand on the sums in StreamWorkspace::acc (tiles x 64 bytes, indexed as acc's pixels; saturating at 255).
+// store_pixel with a hit count is the one store both have: the bytes ignore the count.
+struct RecordOut {
+    uint4 *shade;
+    uint8_t *hits;       // read and written only when nb_ray > 1
+};
+__device__ __forceinline__ uint32_t kept_hits(const uint8_t *, size_t) { return 0u; }
+__device__ __forceinline__ uint32_t kept_hits(const RecordOut &out, size_t pix) { return out.hits[pix]; }
+__device__ __forceinline__ void keep_hits(const uint8_t *, size_t, uint32_t) {}
+__device__ __forceinline__ void keep_hits(const RecordOut &out, size_t pix, uint32_t n) { out.hits[pix] = (uint8_t)(n < 255u ? n : 255u); }
+__device__ __forceinline__ void store_pixel(const DeviceScene &S, const float *__restrict__ thr, uint8_t *__restrict__ out,
+                                            uint32_t px, uint32_t ly, float r, float g, float b, uint32_t)
+{
+    store_pixel(S, thr, out, px, ly, r, g, b);
+}
+__device__ __forceinline__ void store_record(const DeviceScene &S, const RecordOut &out, uint32_t px, uint32_t ly, float r,
+                                             float g, float b, uint32_t qr, uint32_t qg, uint32_t qb, uint32_t n_hit)
+{
+    out.shade[(size_t)ly * S.width + px] = make_uint4(__float_as_uint(r), __float_as_uint(g), __float_as_uint(b),
+                                                      qr | (qg << 8) | (qb << 16) | ((n_hit < 255u ? n_hit : 255u) << 24));
+}
+__device__ __forceinline__ void store_pixel(const DeviceScene &S, const float *__restrict__ thr, const RecordOut &out,
+                                            uint32_t px, uint32_t ly, float r, float g, float b, uint32_t n_hit)
+{
+    store_record(S, out, px, ly, r, g, b, quantise(thr, r), quantise(thr, g), quantise(thr, b), n_hit);
+}
+// the grey-tile shortcut's store: one search has given all three bytes
+__device__ __forceinline__ void store_grey(const DeviceScene &S, uint8_t *__restrict__ out, uint32_t px, uint32_t ly, float,
+                                           float, float, uint32_t q, uint32_t)
+{
+    uint8_t *p = out + ((size_t)ly * S.width + px) * 3u;             // put_pixel, main.rs:293-294
+    p[0] = (uint8_t)q; p[1] = (uint8_t)q; p[2] = (uint8_t)q;
+}
+__device__ __forceinline__ void store_grey(const DeviceScene &S, const RecordOut &out, uint32_t px, uint32_t ly, float r,
+                                           float g, float b, uint32_t q, uint32_t n_hit)
+{
+    store_record(S, out, px, ly, r, g, b, q, q, q, n_hit);
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void flush_counters(unsigned long long *__restrict__ counters, unsigned long long primary_hits,
                                                const WaveCounters &wc)

@@ -1,7 +1,14 @@
 // rtx_pass_schedule.hpp — the render pipeline's scheduling pass (rtx_kernel.hip): probe_kernel, one wavefront per tile —
 // primary rays, hit records, the tile's cut (its shaft against the tree) and its cost estimate — with what it is made of.
 // The tiles the scene predicts long (ProbeSplit) start first, a workgroup each, their primary rays walked as four beams.
-#pragma once
+//
+// rtx_kernel.hip includes this file a second time, inside namespace rtxo with RTX_RECORD_FORMS defined: then probe_kernel's text
+// alone is compiled once more, as rtxo::probe_records_kernel — the same body with `out` a RecordOut (rtx_pass_helpers.hpp) and
+// one wavefront per tile (a view's launch has no long list).  The sky store is the one statement that differs, through
+// store_pixel's overloads.  (Why text compiled twice and not a __device__ template: rtx_pass_shade.hpp.)
+#if !defined(RTX_PASS_SCHEDULE_HPP) || defined(RTX_RECORD_FORMS)
+#if !defined(RTX_RECORD_FORMS)
+#define RTX_PASS_SCHEDULE_HPP
 #include "rtx_probes.hpp"
 #include "rtx_pass_helpers.hpp"
 
@@ -267,12 +274,26 @@ __host__ __device__ inline StreamWorkspace counting_set(StreamWorkspace W, uint3
 
 // WHOLE: the scene does not cut per tile (S.n_nodes > S.cut_max_nodes: shade_tiles_kernel's whole-stream form follows) — an
 // instantiation of its own, so that each carries one probing walk only (the kernel is short of scalar registers)
+#endif  // !RTX_RECORD_FORMS: what follows is compiled for either form
+#if !defined(RTX_RECORD_FORMS)
 template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE, uint32_t WAVES>
 __global__ void __launch_bounds__(64 * WAVES, RTX_PROBE_WAVES_PER_SIMD) probe_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
                                                    uint32_t r, StreamWorkspace W, uint8_t *__restrict__ out,
                                                    uint32_t *__restrict__ queue, unsigned long long *__restrict__ counters,
                                                    ProbeSplit split)
 {
+#else
+template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE>
+__global__ void __launch_bounds__(64, RTX_PROBE_WAVES_PER_SIMD) probe_records_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
+                                                   uint32_t r, StreamWorkspace W, uint4 *__restrict__ out_shade, uint8_t *__restrict__ out_hits,
+                                                   uint32_t *__restrict__ queue, unsigned long long *__restrict__ counters)
+{
+    // one wavefront per tile.  (Value-dependent, as probe_kernel's parameter is: the four-beam statements of the body, which
+    // this form never runs, index arrays of WAVES entries and are then not diagnosed at their definition.)
+    constexpr uint32_t WAVES = COUNT ? 1u : 1u;
+    const ProbeSplit split{nullptr, 0u, 0u, 0u};
+    const RecordOut out{out_shade, out_hits};
+#endif
     const NodeRec RTX_CONSTANT *nodes = (const NodeRec RTX_CONSTANT *)S.nodes;
     const TriRec RTX_CONSTANT *tris = (const TriRec RTX_CONSTANT *)S.tris;
     // one wavefront per tile, WAVES independent wavefronts per workgroup (no barrier; LDS only inside shaft_cut_binary
@@ -506,9 +527,11 @@ __global__ void __launch_bounds__(64 * WAVES, RTX_PROBE_WAVES_PER_SIMD) probe_ke
         if (r + 1u == S.nb_ray) {
             float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;                                   // main.rs:182
             if (r != 0u) { a0 = W.acc[3u * pix]; a1 = W.acc[3u * pix + 1u]; a2 = W.acc[3u * pix + 2u]; }
-            if (in_frame) store_pixel(S, out, px, ly, a0, a1, a2);
+            // (records: a pixel of a tile that is sky for this ray keeps the hits its earlier rays counted)
+            if (in_frame) store_pixel(S, S.gamma_thr, out, px, ly, a0, a1, a2, r != 0u ? kept_hits(out, pix) : 0u);
         } else if (r == 0u) {
             W.acc[3u * pix] = 0.0f; W.acc[3u * pix + 1u] = 0.0f; W.acc[3u * pix + 2u] = 0.0f;
+            keep_hits(out, pix, 0u);
         }
     }
     if (lane == 0) {
@@ -533,4 +556,7 @@ __global__ void __launch_bounds__(64 * WAVES, RTX_PROBE_WAVES_PER_SIMD) probe_ke
     }
 }
 
+#if !defined(RTX_RECORD_FORMS)
 }  // namespace rtx
+#endif
+#endif  // first inclusion, or the record forms'

@@ -1,6 +1,15 @@
 // rtx_pass_shade.hpp — the render pipeline's shading pass (rtx_kernel.hip): shade_tiles_kernel, persistent workgroups
 // that pull the order's jobs costliest first, and the LDS image of such a workgroup.
-#pragma once
+//
+// rtx_kernel.hip includes this file a second time, inside namespace rtxo with RTX_RECORD_FORMS defined: then the kernel's text
+// alone is compiled once more, as rtxo::shade_records_kernel — the same body with `out` a RecordOut (rtx_pass_helpers.hpp).
+// What differs is the job's last stretch: the store, and between a pixel's rays its hit count.  (Text compiled twice and not
+// a __device__ template: called through one, the byte forms came out with other instructions than the parent commit's —
+// tools/same_isa.py — and a refactoring's gate here is identical device code.)
+#if !defined(RTX_PASS_SHADE_HPP) || defined(RTX_RECORD_FORMS)
+#if !defined(RTX_RECORD_FORMS)
+#define RTX_PASS_SHADE_HPP
+#include <type_traits>
 #include "rtx_probes.hpp"
 #include "rtx_pass_order.hpp"
 
@@ -61,13 +70,25 @@ __device__ __forceinline__ void set_wave_priority(uint32_t level)
     default: __builtin_amdgcn_s_setprio(3); break;
     }
 }
+#endif  // !RTX_RECORD_FORMS: what follows is compiled for either form
 template <bool COUNT, bool FAST, int NW, bool SPHERES, bool WHOLE>
 __global__ void __launch_bounds__(64 * NW, COUNT ? 1 : (WHOLE ? RTX_SHADE_WAVES_PER_SIMD : RTX_SHADE_CUT_WAVES_PER_SIMD))
+#if !defined(RTX_RECORD_FORMS)
 shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x, uint32_t n_tiles, uint32_t r,
                    StreamWorkspace W, uint8_t *__restrict__ out, uint32_t *__restrict__ queue,
                    unsigned long long *__restrict__ counters)
 {
+#else
+shade_records_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x, uint32_t n_tiles, uint32_t r,
+                     StreamWorkspace W, uint4 *__restrict__ out_shade, uint8_t *__restrict__ out_hits, uint32_t *__restrict__ queue,
+                     unsigned long long *__restrict__ counters)
+{
+    const RecordOut out{out_shade, out_hits};
+#endif
     extern __shared__ __align__(16) float lds[];
+    constexpr bool kRecords = std::is_same<decltype(out), const RecordOut>::value;
+    // whether the lane's pixel has a hit record in this job (l_pix's fourth word: a slot, kNone or kNotMine)
+    auto pix_hit = [](const float *l_pix, uint32_t lane) { return reinterpret_cast<const uint32_t *>(l_pix)[4u * lane + 3u] < 64u; };
     float *const l_light = lds;
     float *const l_hit = l_light + kLightStride * batch;
     float *const l_res = l_hit + 64u * kHitStride;
@@ -469,17 +490,19 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
                     if (mine) {
                         W.acc[3u * pix] = l_pix[4u * lane]; W.acc[3u * pix + 1u] = l_pix[4u * lane + 1u];
                         W.acc[3u * pix + 2u] = l_pix[4u * lane + 2u];
+                        if (kRecords) keep_hits(out, pix, (r != 0u ? kept_hits(out, pix) : 0u) + (pix_hit(l_pix, lane) ? 1u : 0u));
                     }
                 } else {
                     uint32_t px, py, ly;
                     if (tile_pixel(S, ts, tile_x, tile_y, lane, px, py, ly) && mine) {
                         const float cr = l_pix[4u * lane], cg = l_pix[4u * lane + 1u], cb = l_pix[4u * lane + 2u];
+                        // (records: this ray's hit is the pixel's slot; the earlier rays' hits are where the sums were)
+                        uint32_t n_hits = 0u;
+                        if (kRecords) n_hits = (r != 0u ? kept_hits(out, (size_t)tile_id * 64u + lane) : 0u) + (pix_hit(l_pix, lane) ? 1u : 0u);
                         if (ballot(!(cr == cg && cg == cb)) == 0ull) {   // grey sums: one search of the thresholds, not three
-                            const uint8_t q = (uint8_t)quantise(l_thr, cr);
-                            uint8_t *p = out + ((size_t)ly * S.width + px) * 3u;             // put_pixel, main.rs:293-294
-                            p[0] = q; p[1] = q; p[2] = q;
+                            store_grey(S, out, px, ly, cr, cg, cb, quantise(l_thr, cr), n_hits);
                         } else {
-                            store_pixel(S, l_thr, out, px, ly, cr, cg, cb);
+                            store_pixel(S, l_thr, out, px, ly, cr, cg, cb, n_hits);
                         }
                     }
                 }
@@ -492,4 +515,7 @@ shade_tiles_kernel(DeviceScene S, TileSpec ts, uint32_t batch, uint32_t tiles_x,
     if (COUNT && lane == 0) flush_counters<COUNT>(counters, 0ull, wc);
 }
 
+#if !defined(RTX_RECORD_FORMS)
 }  // namespace rtx
+#endif
+#endif  // first inclusion, or the record forms'

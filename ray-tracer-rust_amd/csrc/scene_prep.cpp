@@ -619,6 +619,25 @@ void light_walk_of(const float tri[9], const SampleSource &samples, uint32_t nb_
     light_boxes_of(points.data(), nb_ray, nb_light, boxes.data());
 }
 
+void light_walk_statement(const PreparedScene &p, const float tri[9], uint32_t count, const SampleSource &samples, uint32_t *order,
+                          float *boxes, float *shaft_delta)
+{
+    const size_t n = static_cast<size_t>(p.nb_ray) * count;
+    std::vector<float> points(3u * n), box(6u * static_cast<size_t>(p.nb_ray));
+    light_points_of(tri, samples, p.nb_ray, count, points.data());
+    light_boxes_of(points.data(), p.nb_ray, count, box.data());
+    if (boxes) std::memcpy(boxes, box.data(), box.size() * sizeof(float));
+    if (shaft_delta) *shaft_delta = shaft_delta_of(p.scene_magnitude, box.data(), box.size());
+    if (!order) return;
+    for (uint32_t r = 0; r < p.nb_ray; ++r)
+        for (uint32_t b0 = 0; b0 < count; b0 += kMaxLightBatch) {
+            const uint32_t bc = std::min(count - b0, kMaxLightBatch);
+            const size_t first = static_cast<size_t>(r) * count + b0;
+            light_tour_order_f32(&points[3u * first], bc, order + first);
+            for (uint32_t k = 0; k < bc; ++k) order[first + k] += b0;
+        }
+}
+
 int resample_scene(PreparedScene &s, const SampleSource &samples)
 {
     if (!samples.n) return RTX_ERR_BAD_ARG;

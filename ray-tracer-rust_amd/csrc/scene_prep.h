@@ -461,6 +461,14 @@ inline SampleSource sample_source(const PreparedScene &s)
 void light_walk_of(const float tri[9], const SampleSource &samples, uint32_t nb_ray, uint32_t nb_light,
                    std::vector<float> &points, std::vector<float> &tour, std::vector<uint32_t> &order,
                    std::vector<float> &boxes);
+// What the render pipeline reads of a light over a sample table beside its points, as the host states it (a lit pipeline
+// call's light over the scene's table; a frame of rtx_render_view_rows_mean: `tri` with `count` samples over the SEEDED table
+// samples = {NULL, seed, n_pairs}, in closed form over the nb_ray * count entries the points read — no table is made):
+// order, nb_ray x count sample indices, the tour per primary ray and batch in rtx_scene_light_order's form; boxes, nb_ray x 6;
+// shaft_delta, shaft_delta_of over those boxes.  Each output may be NULL.  O(nb_ray * count) for the margin alone; the tour
+// costs what light_tour_order_f32 costs.  May throw std::bad_alloc.
+void light_walk_statement(const PreparedScene &p, const float tri[9], uint32_t count, const SampleSource &samples, uint32_t *order,
+                          float *boxes, float *shaft_delta);
 // Replaces the scene's table by `samples` (rtx_scene_resample: a caller's table, copied; rtx_scene_reseed: table == NULL)
 // and re-derives what prepare_scene derives from it, by light_walk_of and shaft_delta_of.  RTX_ERR_BAD_ARG: n == 0;
 // RTX_ERR_UNSUPPORTED: the margin is not finite (prepare_scene's rule); RTX_ERR_OOM.  On an error the scene is as it was;

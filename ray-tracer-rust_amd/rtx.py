@@ -121,6 +121,7 @@ ACCUM_PIXEL_DTYPE = np.dtype([("sum", np.float32, 3), ("hit_frames", np.uint32)]
 assert ACCUM_PIXEL_DTYPE.itemsize == C.sizeof(AccumPixel) == 16
 MAX_MEAN_FRAMES = 65536
 MEAN_POSED = 1
+ROWS_POSED = 1
 
 
 class RtxView(C.Structure):
@@ -243,6 +244,10 @@ _SIGS = {
                                              C.POINTER(Stats)]),
     "rtx_render_view_rows_posed_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_void_p,
                                                     C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rtx_render_view_rows_shade": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32,
+                                             C.POINTER(PixelShade), C.POINTER(Stats)]),
+    "rtx_render_view_rows_shade_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32,
+                                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rtx_scene_posed_pipeline_records": (C.c_int, [C.c_void_p, f32p, f32p, u32p, u32p]),
     "rtx_debug_pose_pipeline": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, u32p]),
     "rtx_scene_pose_rebuilt": (C.c_int, [C.c_void_p, C.c_int, f32p, u32p, C.c_uint32, C.POINTER(Stats)]),
@@ -278,6 +283,11 @@ _SIGS = {
                                        C.c_uint32, C.c_void_p, C.POINTER(PixelShade), C.POINTER(Stats)]),
     "rtx_render_view_mean_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_render_view_rows_mean": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p, C.c_uint32,
+                                            C.c_uint32, C.c_void_p, C.POINTER(PixelShade), C.POINTER(Stats)]),
+    "rtx_render_view_rows_mean_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
+                                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_scene_light_walk_seeded": (C.c_int, [C.c_void_p, C.POINTER(RtxLight), C.c_uint64, C.c_uint32, u32p, f32p, f32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
     "rtx_debug_tile_descs": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t]),
@@ -935,6 +945,21 @@ class Scene:
             raise RtxError(ERR_INTERNAL, "rtx_scene_light_walk_for")
         return order[:n], boxes, np.float32(delta.value)
 
+    def light_walk_seeded(self, seed, n_pairs, light=None):
+        """Host only: light_walk_for's outputs on a scene reseeded with (seed, n_pairs), this scene unchanged — what a frame of
+        render_view_mean(rows=True) walks (rtx_scene_light_walk_seeded).  light: None, the scene's."""
+        lp = C.byref(light) if light is not None else None
+        n = _lib.rtx_scene_light_walk_seeded(self._h, lp, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pairs), None, None, None)
+        if n < 0:
+            raise RtxError(n, "rtx_scene_light_walk_seeded")
+        order = np.zeros(max(n, 1), np.uint32)
+        boxes = np.zeros((self.nb_ray, 6), np.float32)
+        delta = C.c_float(0.0)
+        if _lib.rtx_scene_light_walk_seeded(self._h, lp, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_pairs), order.ctypes.data_as(u32p),
+                                            _fp(boxes), C.byref(delta)) != n:
+            raise RtxError(ERR_INTERNAL, "rtx_scene_light_walk_seeded")
+        return order[:n], boxes, np.float32(delta.value)
+
     def debug_light_walk(self, light, device=0):
         """Diagnostics: the tour records (uint32 [nb_ray * n, 4]: x, y, z bits and the index within the batch) and the boxes
         (float32 [nb_ray, 6]) as the light kernels make them on `device`, copied back."""
@@ -964,6 +989,28 @@ class Scene:
         tail = (C.c_void_p(d_rgb_ptr), d_bytes, C.c_void_p(stream) if stream else None,
                 C.c_void_p(d_counters_ptr) if d_counters_ptr else None)
         self._lit_or_posed("rtx_render_view_rows", "_device", (self._h, device, C.byref(view)), tail, light, posed)
+
+    # -- the pipeline's linear output: the RtxPixelShade records of render_view, at the pipeline's speed
+    def render_view_rows_shade(self, view, device=0, stats=False, light=None, posed=False):
+        """Rows [y0, y0 + ny) of the view's frame through the render pipeline as records -> PIXEL_SHADE_DTYPE [ny, width]:
+        render_view's `shade` (linear sums bit for bit, bytes, hit counts), light= and posed= as render_view_rows
+        (rtx_render_view_rows_shade)."""
+        out = np.zeros((view.ny, view.width), PIXEL_SHADE_DTYPE)
+        st = Stats()
+        _check(_lib.rtx_render_view_rows_shade(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                               ROWS_POSED if posed else 0, out.ctypes.data_as(C.POINTER(PixelShade)),
+                                               C.byref(st) if stats else None), "rtx_render_view_rows_shade")
+        return (out, st.asdict()) if stats else out
+
+    def render_view_rows_shade_device(self, device, view, d_shade_ptr, d_bytes, stream=None, d_counters_ptr=None, light=None,
+                                      posed=False):
+        """Asynchronous pipeline launch of the view's rows as records into a device buffer the caller owns (ny*width*16
+        bytes, 16-byte aligned)."""
+        _check(_lib.rtx_render_view_rows_shade_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                                      ROWS_POSED if posed else 0, C.c_void_p(d_shade_ptr), d_bytes,
+                                                      C.c_void_p(stream) if stream else None,
+                                                      C.c_void_p(d_counters_ptr) if d_counters_ptr else None),
+               "rtx_render_view_rows_shade_device")
 
     def aimed_nodes(self, eye):
         """Host only: records [n_nodes, 8] of the stream the primary rays of a view with this eye walk (planes moved by
@@ -1256,32 +1303,35 @@ class Scene:
         return np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
 
     def render_view_mean(self, view, seeds, n_pairs=NB_RAND_SAMPLE, device=0, light=None, posed=False, stats=False,
-                         want_shade=False):
+                         want_shade=False, rows=False):
         """The mean of len(seeds) frames of the view, frame k under the table gen_samples(seeds[k], n_pairs), summed in
         frame order and divided once (rtx_render_view_mean) -> uint8 [ny, nx, 3]; want_shade adds the records
         (PIXEL_SHADE_DTYPE [ny, nx]: the mean's linear colour, its bytes, in how many frames the pixel had a hit), stats
-        the statistics summed over the frames, last.  light: an RtxLight, None the scene's; posed: the device's pose."""
+        the statistics summed over the frames, last.  light: an RtxLight, None the scene's; posed: the device's pose.
+        rows: through the render pipeline (rtx_render_view_rows_mean: full width only, the same words)."""
         sd = self._seeds(seeds)
+        call = _lib.rtx_render_view_rows_mean if rows else _lib.rtx_render_view_mean
         out = np.zeros((view.ny, view.nx, 3), np.uint8)
         shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
         st = Stats()
-        _check(_lib.rtx_render_view_mean(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                                         MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), out.ctypes.data,
-                                         shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
-                                         C.byref(st) if stats else None), "rtx_render_view_mean")
+        _check(call(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                    MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), out.ctypes.data,
+                    shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
+                    C.byref(st) if stats else None), "rtx_render_view_rows_mean" if rows else "rtx_render_view_mean")
         res = (out,) + ((shade,) if want_shade else ()) + ((st.asdict(),) if stats else ())
         return res if len(res) > 1 else out
 
     def render_view_mean_device(self, device, view, seeds, n_pairs, d_accum_ptr, d_rgb_ptr=None, d_shade_ptr=None, stream=None,
-                                light=None, posed=False):
+                                light=None, posed=False, rows=False):
         """Asynchronous: the same chain on `stream` into device buffers the caller owns — ny*nx x 16 bytes of accumulator
         (16-byte aligned), optionally ny*nx*3 bytes (any alignment) and ny*nx x 16 bytes of records."""
         sd = self._seeds(seeds)
-        _check(_lib.rtx_render_view_mean_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                                                MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs),
-                                                C.c_void_p(d_accum_ptr), C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
-                                                C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
-                                                C.c_void_p(stream) if stream else None), "rtx_render_view_mean_device")
+        call = _lib.rtx_render_view_rows_mean_device if rows else _lib.rtx_render_view_mean_device      # (rows: through the pipeline)
+        _check(call(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                    MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs),
+                    C.c_void_p(d_accum_ptr), C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
+                    C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
+                    C.c_void_p(stream) if stream else None), "rtx_render_view_rows_mean_device" if rows else "rtx_render_view_mean_device")
 
     def accum_add_device(self, device, n, d_shade_ptr, d_accum_ptr, first, stream=None):
         """Asynchronous: adds n RtxPixelShade records — of any call that writes them — into n accumulator records

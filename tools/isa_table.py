@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Development tool: per-kernel register, scratch, spill and instruction counts of `make asm` output, and the difference
+"""Development tool: per-kernel register, scratch, spill, static LDS and instruction counts of `make asm` output, and the difference
 between two builds.
 
   tools/isa_table.py DIR                  one table: the *.gfx950.s files of DIR
@@ -13,8 +13,8 @@ import glob
 import os
 import re
 
-FIELDS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")
-HEAD = ("VGPR", "SGPR", "scratch", "vspill", "sspill", "insts")
+FIELDS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size")
+HEAD = ("VGPR", "SGPR", "scratch", "vspill", "sspill", "LDS", "insts")       # LDS: the static part, bytes
 
 
 def kernels_of(path):
@@ -39,7 +39,7 @@ def table(directory, match):
 
 
 def short(name):
-    m = re.match(r"_ZN\d+(rtx\w?)\d+(\w+_kernel)ILb([01])ELb([01])E", name)
+    m = re.match(r"_ZN\d+(rtx\w?)\d+(\w+_kernel)ILb([01])ELb([01])EEv", name)      # the kernels with exactly these two parameters
     return "%s::%s<COUNT=%s, SPHERES=%s>" % m.groups() if m else name
 
 
@@ -50,7 +50,7 @@ def main():
     a = ap.parse_args()
     after = table(a.dirs[-1], a.match)
     before = table(a.dirs[0], a.match) if len(a.dirs) == 2 else None
-    print("%-48s" % "kernel" + "".join("%16s" % h for h in HEAD))
+    print("%-56s" % "kernel" + "".join("%16s" % h for h in HEAD))
     for name in sorted(after, key=short):
         cells = []
         for k, v in enumerate(after[name]):
@@ -58,7 +58,7 @@ def main():
                 cells.append("%d" % v)
             else:
                 cells.append("%d (%+d)" % (v, v - before[name][k]) if name in before else "%d (new)" % v)
-        print("%-48s" % short(name) + "".join("%16s" % c for c in cells))
+        print("%-56s" % short(name) + "".join("%16s" % c for c in cells))
     if before is not None:
         for name in sorted(set(before) - set(after), key=short):
             print("%-48s  gone" % short(name))
