@@ -893,6 +893,93 @@ int rtx_render_view_rows_mean_device(RtxScene *scene, int device, const RtxView 
 int rtx_scene_light_walk_seeded(const RtxScene *scene, const RtxLight *light /* NULL = the scene's */, uint64_t seed,
                                 uint32_t n_pairs, uint32_t *out_order, float *out_boxes, float *out_shaft_delta);
 
+/* ---- The adaptive mean of N frames: tiles stop once their noise estimate is met ------------------------------------------------
+ * rtx_render_view_mean gives every pixel the same N frames.  These calls keep a second moment per pixel and a noise estimate
+ * per 8 x 8 tile of the RECTANGLE (tiles row by row over ceil(nx/8) x ceil(ny/8), as rtx_render_view's wavefronts: tile
+ * (tx, ty) holds pixels [8tx, 8tx+8) x [8ty, 8ty+8) of the rectangle, cut at its right and bottom edges), and a frame's
+ * launches skip the tiles whose estimate is already good enough.  Deterministic: every word below is stated.
+ *
+ * THE STATEMENT.  A moment record is an RtxMomentPixel.  Adding frame k's RtxPixelShade record `s` (l = s.linear) to it:
+ *   first:      sum[c] = l[c], copied bit for bit; sumsq[c] = l[c] * l[c]; hit_frames = (s.hits != 0); frames = 1.  The old
+ *               content is not read.
+ *   otherwise:  sum[c] = sum[c] + l[c]; sumsq[c] = sumsq[c] + (l[c] * l[c]), the product rounded to f32 first, never an
+ *               FMA; hit_frames += (s.hits != 0); frames += 1.
+ * sum and hit_frames are RtxAccumPixel's, word for word.  A pixel's error, with fn = (float)frames, per channel:
+ *   mean = sum[c] / fn;  q = sumsq[c] / fn;  v = q - (mean * mean), the product rounded first;  v = v > 0 ? v : 0 (a NaN or
+ *   a negative rounding residue becomes 0);  e_c = v / fn
+ * and the error is max(max(e_0, e_1), e_2) by `a < b ? b : a`: the (biased) variance of the mean of the noisiest channel,
+ * never NaN, never negative.  A TILE'S ERROR is the maximum of its pixels' errors over the pixels inside the rectangle,
+ * starting from +0.0; the order does not matter.  A tile's state is an RtxTileState {frames, err}, written by the add that
+ * gave the tile a frame.  A tile is STOPPED under a rule when
+ *   state.frames >= rule.min_frames && state.err <= rule.max_variance
+ * — there is no separate "stopped" word: the masked view launch and the add both evaluate this from the 8-byte state.  A
+ * stopped tile is neither rendered nor added to, its moments and its state keep their words, so within a call stopping is
+ * final; a later RTX_ADAPT_CONTINUE call with a stricter rule resumes tiles by itself.  Under `first` the state is not read:
+ * every tile is live.  Resolving a record gives an RtxPixelShade: linear[c] = sum[c] / (float)frames, ONE correctly rounded
+ * division by the pixel's OWN count; rgb8 and hits as rtx_accum_resolve's.  Host and device compile one text (scene_prep.h:
+ * moment_add_statement, moment_error_statement, tile_stopped, moment_resolve_statement) without contraction and agree word
+ * for word.  Outside the contract for the DECISION: records that are not finite or whose squares overflow (the words are
+ * still the statement's, host and device alike), frames == 0 in a resolve, more than 2^24 frames per pixel.
+ * A TRAP: after one frame v is exactly 0 (mean = l, q = l * l), so min_frames == 1 stops every tile after frame 0 for ANY
+ * max_variance.  min_frames >= 2 is the meaningful range.
+ *
+ * rtxh_moment_add / rtxh_moment_resolve: the statements over arrays, host only, no device.  An add takes the nx x ny
+ * records of a rectangle (record y * nx + x), its moments and — tiles != NULL — its ceil(nx/8) * ceil(ny/8) tile states
+ * and the rule; tiles == NULL (rule may be NULL too): every tile is live and no state is written, the plain moment
+ * accumulator.  first != 0: moments and tiles are written, never read.  RTX_ERR_BAD_ARG: a NULL shade or moments, tiles
+ * without a rule, a rule with min_frames == 0 or a max_variance that is negative or NaN, nx * ny > 2^28; a resolve: NULL
+ * thr256 or moments, both outputs NULL.  nx * ny == 0 / n == 0: RTX_OK, nothing read or written.
+ *
+ * rtx_moment_add_device / rtx_moment_resolve_device: the same over device arrays, one kernel each (rtx_adapt.hip),
+ * asynchronous on `stream`, no library buffer, no ordering rule.  d_shade: records from ANY call that writes RtxPixelShade,
+ * the pipeline's rtx_render_view_rows_shade_device included.  RTX_ERR_BAD_ARG: the host statements' and a NULL scene, d_shade,
+ * d_moments (or d_rgb and d_shade both NULL) or a pointer that is not aligned: 16 bytes for records and moments, 8 for d_tiles,
+ * any for d_rgb.  An empty rectangle: RTX_OK, nothing launched, no device needed.  A resolve reads the scene's thresholds and
+ * uploads the scene first if needed.
+ *
+ * rtx_render_view_adaptive / _device: rtx_render_view_mean / _device in every respect not named here — the argument checks,
+ * the empty rectangle, the light's rules decided on the host, RTX_MEAN_POSED, THE SCENE IS NOT WRITTEN, the mean's scratch
+ * table and records and the light buffers reused and guarded as the mean's are, seeds read before the call returns.  Further
+ * RTX_ERR_BAD_ARG: a NULL rule, min_frames == 0, max_variance negative or NaN (+infinity is allowed), NULL or misaligned
+ * d_moments or d_tiles (16 and 8 bytes; device variant).  Per frame k, on the call's stream, with no host wait between
+ * frames: the sample-table kernel, the light points, the MASKED view launch (rtx_render_view's tile body behind the stopped
+ * test, records only) into the scratch records, the moment add; after the last frame the resolve, where an output is asked
+ * for.  All n_frames frames are always enqueued: once every tile has stopped the remaining launches' wavefronts return at
+ * once.  With min_frames == n_frames no tile stops early and the outputs, sum and hit_frames are rtx_render_view_mean's.
+ * RTX_ADAPT_CONTINUE (device variant only): d_moments and d_tiles hold an earlier call's state for the same rectangle; no
+ * frame is a first one and seeds[k] are the NEXT frames' seeds — how an interactive caller refines in slices.
+ * out_tiles (host variant, may be NULL): the tile states after the last frame; a tile's `frames` is its stop frame or
+ * n_frames.  stats (host variant; it reads the tile states back): the counters are sums over the rendered tile-frames,
+ * primary_rays = the sum over tiles of frames * pixels of the tile inside the rectangle * nb_ray. */
+typedef struct RtxMomentPixel {   /* 32 bytes; 16-byte aligned on the device: two 16-byte loads, two stores */
+    float    sum[3];              /* RtxAccumPixel.sum, word for word */
+    uint32_t hit_frames;          /* RtxAccumPixel.hit_frames */
+    float    sumsq[3];            /* ordered f32 sum of the frames' squared linear colours */
+    uint32_t frames;              /* frames this pixel received */
+} RtxMomentPixel;
+typedef struct RtxTileState {     /* 8 bytes: one per 8x8 tile of the RECTANGLE, tiles row by row, as rtx_render_view's */
+    uint32_t frames;              /* frames the tile received (= each of its pixels' frames) */
+    float    err;                 /* the tile's noise estimate after its last add */
+} RtxTileState;
+typedef struct RtxAdaptRule { uint32_t min_frames; float max_variance; } RtxAdaptRule;
+#define RTX_ADAPT_CONTINUE 2u
+int rtxh_moment_add(uint32_t nx, uint32_t ny, const RtxPixelShade *shade, RtxMomentPixel *moments,
+                    RtxTileState *tiles /* NULL ok */, uint32_t first, const RtxAdaptRule *rule /* NULL when tiles is */);
+int rtxh_moment_resolve(const float thr256[256], uint32_t n, const RtxMomentPixel *moments,
+                        uint8_t *out_rgb /* NULL or n*3 */, RtxPixelShade *out_shade /* NULL or n */);
+int rtx_moment_add_device(RtxScene *scene, int device, uint32_t nx, uint32_t ny, const void *d_shade, void *d_moments,
+                          void *d_tiles, uint32_t first, const RtxAdaptRule *rule, void *stream);
+int rtx_moment_resolve_device(RtxScene *scene, int device, uint32_t n, const void *d_moments, void *d_rgb, void *d_shade,
+                              void *stream);
+int rtx_render_view_adaptive(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                             uint32_t flags /* RTX_MEAN_POSED or 0 */, const uint64_t *seeds, uint32_t n_frames,
+                             uint32_t n_pairs, const RtxAdaptRule *rule, uint8_t *out_rgb, RtxPixelShade *out_shade,
+                             RtxTileState *out_tiles /* may be NULL */, RtxStats *stats);
+int rtx_render_view_adaptive_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags
+                                    /* RTX_MEAN_POSED | RTX_ADAPT_CONTINUE */, const uint64_t *seeds, uint32_t n_frames,
+                                    uint32_t n_pairs, const RtxAdaptRule *rule, void *d_moments, void *d_tiles, void *d_rgb,
+                                    void *d_shade, void *stream);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

@@ -109,6 +109,33 @@ pub struct RtxAccumPixel {
     pub sum: [f32; 3],
     pub hit_frames: u32,
 }
+/// A pixel of the adaptive mean (`rtx_render_view_adaptive`): `RtxAccumPixel`'s words, the ordered `f32` sum of the frames'
+/// squared linear colours and the frames this pixel received.  A device array of them must be 16-byte aligned.
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxMomentPixel {
+    pub sum: [f32; 3],
+    pub hit_frames: u32,
+    pub sumsq: [f32; 3],
+    pub frames: u32,
+}
+/// An 8 x 8 tile of the rectangle: the frames it received and its noise estimate after its last add.  A device array of
+/// them must be 8-byte aligned.
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxTileState {
+    pub frames: u32,
+    pub err: f32,
+}
+/// A tile is stopped when `frames >= min_frames && err <= max_variance`.  `min_frames == 1` stops every tile after one
+/// frame, whose variance is exactly 0: `min_frames >= 2` is the meaningful range.
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct RtxAdaptRule {
+    pub min_frames: u32,
+    pub max_variance: f32,
+}
+pub const RTX_ADAPT_CONTINUE: u32 = 2;
 pub const RTX_MEAN_POSED: u32 = 1;
 pub const RTX_ROWS_POSED: u32 = 1;
 pub const RTX_MAX_MEAN_FRAMES: u32 = 65536;
@@ -304,6 +331,32 @@ extern "C" {
     pub fn rtx_render_view_rows_mean_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
                                             flags: u32, seeds: *const u64, n_frames: u32, n_pairs: u32, d_accum: *mut c_void,
                                             d_rgb: *mut c_void, d_shade: *mut c_void, stream: *mut c_void) -> c_int;
+    /// Host only: the adaptive mean's add over an `nx` x `ny` rectangle, tile by tile: the tiles that are stopped under
+    /// `rule` are skipped.  `tiles` NULL (`rule` may be too): every tile is live, no state is written.
+    pub fn rtxh_moment_add(nx: u32, ny: u32, shade: *const RtxPixelShade, moments: *mut RtxMomentPixel, tiles: *mut RtxTileState,
+                           first: u32, rule: *const RtxAdaptRule) -> c_int;
+    /// Host only: moment records into RGB8 (NULL or `n * 3` bytes) and records (NULL or `n`), each pixel divided by its own
+    /// frame count.
+    pub fn rtxh_moment_resolve(thr256: *const f32, n: u32, moments: *const RtxMomentPixel, out_rgb: *mut u8,
+                               out_shade: *mut RtxPixelShade) -> c_int;
+    /// The add over device arrays (records and moments 16-byte, tile states 8-byte aligned), asynchronous on `stream`.
+    pub fn rtx_moment_add_device(scene: *mut RtxScene, device: c_int, nx: u32, ny: u32, d_shade: *const c_void,
+                                 d_moments: *mut c_void, d_tiles: *mut c_void, first: u32, rule: *const RtxAdaptRule,
+                                 stream: *mut c_void) -> c_int;
+    /// The resolve over device moments; `d_rgb` may have any alignment.
+    pub fn rtx_moment_resolve_device(scene: *mut RtxScene, device: c_int, n: u32, d_moments: *const c_void, d_rgb: *mut c_void,
+                                     d_shade: *mut c_void, stream: *mut c_void) -> c_int;
+    /// `rtx_render_view_mean` whose 8 x 8 tiles stop receiving frames once `rule` is met; `out_tiles` (may be NULL): the
+    /// tile states after the last frame.  The scene is not changed.
+    pub fn rtx_render_view_adaptive(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight, flags: u32,
+                                    seeds: *const u64, n_frames: u32, n_pairs: u32, rule: *const RtxAdaptRule, out_rgb: *mut u8,
+                                    out_shade: *mut RtxPixelShade, out_tiles: *mut RtxTileState, stats: *mut RtxStats) -> c_int;
+    /// Device-resident variant: the caller's moments, tile states, outputs and stream.  `flags`: `RTX_MEAN_POSED |
+    /// RTX_ADAPT_CONTINUE` — continue: the moments and states are an earlier call's, `seeds` the next frames'.
+    pub fn rtx_render_view_adaptive_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                           flags: u32, seeds: *const u64, n_frames: u32, n_pairs: u32, rule: *const RtxAdaptRule,
+                                           d_moments: *mut c_void, d_tiles: *mut c_void, d_rgb: *mut c_void, d_shade: *mut c_void,
+                                           stream: *mut c_void) -> c_int;
     /// Host only: `rtx_scene_light_walk_for`'s outputs on a scene reseeded with (`seed`, `n_pairs`); `light` NULL: the scene's.
     pub fn rtx_scene_light_walk_seeded(scene: *const RtxScene, light: *const RtxLight, seed: u64, n_pairs: u32,
                                        out_order: *mut u32, out_boxes: *mut f32, out_shaft_delta: *mut f32) -> c_int;

@@ -322,6 +322,63 @@ int rtxh_accum_resolve(const float thr256[256], uint32_t n, const RtxAccumPixel 
     return RTX_OK;
 }
 
+// The statements of the adaptive mean over arrays (scene_prep.h: moment_add_statement, moment_error_statement, tile_stopped,
+// moment_resolve_statement — the text rtx_adapt.hip compiles for the device), tile by tile as the device's wavefronts take
+// them.  The records are copied in and out: a caller's arrays need no alignment.
+int rtxh_moment_add(uint32_t nx, uint32_t ny, const RtxPixelShade *shade, RtxMomentPixel *moments, RtxTileState *tiles,
+                    uint32_t first, const RtxAdaptRule *rule)
+{
+    if (!shade || !moments || (tiles && !rtx::adapt_rule_ok(rule))) return RTX_ERR_BAD_ARG;
+    if (static_cast<uint64_t>(nx) * ny > (1ull << 28)) return RTX_ERR_BAD_ARG;
+    if (nx == 0u || ny == 0u) return RTX_OK;
+    const char *in = reinterpret_cast<const char *>(shade);
+    char *io = reinterpret_cast<char *>(moments), *states = reinterpret_cast<char *>(tiles);
+    const uint32_t tiles_x = (nx - 1u) / 8u + 1u, tiles_y = (ny - 1u) / 8u + 1u;
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            const size_t tile = static_cast<size_t>(ty) * tiles_x + tx;
+            RtxTileState st = {0u, 0.0f};
+            if (tiles && !first) {
+                std::memcpy(&st, states + tile * sizeof st, sizeof st);
+                if (rtx::tile_stopped(*rule, st)) continue;
+            }
+            float err = 0.0f;
+            for (uint32_t y = ty * 8u; y < ty * 8u + 8u && y < ny; ++y)
+                for (uint32_t x = tx * 8u; x < tx * 8u + 8u && x < nx; ++x) {
+                    const size_t i = static_cast<size_t>(y) * nx + x;
+                    RtxPixelShade s;
+                    RtxMomentPixel m = {{0.0f, 0.0f, 0.0f}, 0u, {0.0f, 0.0f, 0.0f}, 0u};
+                    std::memcpy(&s, in + i * sizeof s, sizeof s);
+                    if (!first) std::memcpy(&m, io + i * sizeof m, sizeof m);
+                    rtx::moment_add_statement(first != 0u, s, &m);
+                    std::memcpy(io + i * sizeof m, &m, sizeof m);
+                    const float e = rtx::moment_error_statement(m);
+                    err = err < e ? e : err;
+                }
+            if (tiles) {
+                st.frames = st.frames + 1u;
+                st.err = err;
+                std::memcpy(states + tile * sizeof st, &st, sizeof st);
+            }
+        }
+    return RTX_OK;
+}
+
+int rtxh_moment_resolve(const float thr256[256], uint32_t n, const RtxMomentPixel *moments, uint8_t *out_rgb,
+                        RtxPixelShade *out_shade)
+{
+    if (!thr256 || !moments || (!out_rgb && !out_shade)) return RTX_ERR_BAD_ARG;
+    const char *in = reinterpret_cast<const char *>(moments);
+    for (size_t i = 0; i < n; ++i) {
+        RtxMomentPixel m;
+        std::memcpy(&m, in + i * sizeof m, sizeof m);
+        const RtxPixelShade s = rtx::moment_resolve_statement(thr256, m);
+        if (out_rgb) std::memcpy(out_rgb + 3u * i, s.rgb8, 3);
+        if (out_shade) std::memcpy(reinterpret_cast<char *>(out_shade) + i * sizeof s, &s, sizeof s);
+    }
+    return RTX_OK;
+}
+
 // Synthetic soup of BASELINE.json configs[4] (see include/rtx.h).  f32 arithmetic, one rounding per operation:
 // c = lo + f*(hi-lo) per axis, vertex = c + (2f-1).
 int rtxh_synthetic_mesh(uint64_t seed, uint32_t n_tris, float *out)

@@ -22,6 +22,7 @@
 
 #include "../../include/rtx.h"
 #include "rtx_accum.h"
+#include "rtx_adapt.h"
 #include "rtx_aim.h"
 #include "rtx_device.h"
 #include "rtx_light.h"
@@ -1559,6 +1560,100 @@ int mean_device(RtxScene *scene, int device, const RtxView *view, const MeanCall
     return mark_uses(st, mean_uses(call), static_cast<hipStream_t>(stream));
 }
 
+// ---- the adaptive mean of N frames (rtx_render_view_adaptive, rtx_moment_*_device; the kernels: rtx_adapt.hip) ---------------
+
+// the mean's chain with the masked view launch and the moment add in the view kernel's and the add's places: a tile that
+// tile_stopped(rule, its state) names is neither rendered nor added to.  resume: no frame is a first one (d_moments and
+// d_tiles hold an earlier call's state).  Caller holds the slot's lock and has the device current and the scene uploaded;
+// the rectangle is not empty.
+int adaptive_launch(RtxScene *scene, DeviceState &st, const RtxView *view, const MeanCall &call, const RtxAdaptRule &rule, bool resume,
+                    void *d_moments, void *d_tiles, void *d_rgb, void *d_shade, unsigned long long *d_counters, hipStream_t stream)
+{
+    const rtx::PreparedScene &p = scene->prep;
+    const uint32_t n_pixels = view->nx * view->ny;
+    DeviceGeometry *geo;
+    RTX_TRY(geometry_of(st, call.posed, &geo));
+    RTX_TRY(reserve_mean(st, call.n_pairs, n_pixels));
+    RTX_TRY(reserve_light(scene, st, call.lit, false));
+    rtx::DeviceScene S = device_scene(scene, st, *geo);
+    S.samples = st.mean.table.as<const float2>();
+    S.n_samples = call.n_pairs;
+    light_swap(st, call.lit, false, 0.0f, &S);
+    rtxv::ViewBlock v;
+    std::memcpy(&v, view, sizeof v);
+    for (uint32_t k = 0; k < call.n_frames; ++k) {
+        const bool first = k == 0u && !resume;
+        RTX_HIP(rtxr::launch_samples(call.seeds[k], call.n_pairs, st.mean.table.as<float2>(), stream));
+        if (call.lit.count != 0u)
+            RTX_HIP(rtxl::launch_light_points(st.mean.table.as<const float2>(), call.n_pairs, call.lit.tri, p.nb_ray, call.lit.count,
+                                              st.lit.points.as<float>(), stream));
+        RTX_HIP(rtxe::launch_view_masked(S, v, origin_bound(scene), st.mean.records.as<void>(), d_counters, d_tiles, first, rule, stream));
+        RTX_HIP(rtxe::launch_moment_add(view->nx, view->ny, st.mean.records.as<const void>(), d_moments, d_tiles, first, rule, stream));
+    }
+    if (d_rgb || d_shade)
+        RTX_HIP(rtxe::launch_moment_resolve(st.thr.as<const float>(), n_pixels, d_moments, d_rgb, d_shade, stream));
+    return RTX_OK;
+}
+
+// the host entry point: the moments, the tile states and the outputs in the library's output buffer, one behind the other
+// (every part a multiple of 16 bytes but the last), launch, copy out.  The statistics need the tile states: they are read
+// back whether or not the caller asked for them.
+int adaptive_host(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, const RtxAdaptRule &rule, uint8_t *rgb,
+                  RtxPixelShade *shade, RtxTileState *tiles, RtxStats *stats)
+{
+    const Timed timed(stats);
+    const uint32_t n_pixels = view->nx * view->ny;
+    if (n_pixels == 0u) return timed.empty();
+    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    const size_t n_tiles = static_cast<size_t>(rtxe::tile_count(view->nx, view->ny));
+    const size_t moments = static_cast<size_t>(n_pixels) * sizeof(RtxMomentPixel);
+    const size_t states = (n_tiles * sizeof(RtxTileState) + 15u) & ~static_cast<size_t>(15u);
+    const size_t shade_bytes = shade ? static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade) : 0u;
+    const size_t rgb_bytes = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
+    RTX_TRY(st.q_out.reserve(moments + states + shade_bytes + rgb_bytes));
+    uint8_t *d_moments = st.q_out.as<uint8_t>(), *d_tiles = d_moments + moments;
+    uint8_t *d_shade = shade ? d_tiles + states : nullptr, *d_rgb = rgb ? d_tiles + states + shade_bytes : nullptr;
+    RTX_TRY(wait_for_uses(st, mean_uses(call)));
+    RTX_TRY(timed.begin(st));
+    RTX_TRY(adaptive_launch(scene, st, view, call, rule, false, d_moments, d_tiles, d_rgb, d_shade, timed.counters(st), st.stream));
+    RTX_TRY(timed.end(st));
+    std::vector<RtxTileState> own;
+    if (!tiles && stats) {
+        own.resize(n_tiles);
+        tiles = own.data();
+    }
+    if (shade) RTX_HIP(hipMemcpyAsync(shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st.stream));
+    if (rgb) RTX_HIP(hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, st.stream));
+    if (tiles) RTX_HIP(hipMemcpyAsync(tiles, d_tiles, n_tiles * sizeof(RtxTileState), hipMemcpyDeviceToHost, st.stream));
+    uint64_t pixel_frames = 0;
+    if (stats) {
+        RTX_HIP(hipStreamSynchronize(st.stream));
+        const uint32_t tiles_x = (view->nx + 7u) / 8u;
+        for (size_t t = 0; t < n_tiles; ++t) {
+            const uint32_t x = static_cast<uint32_t>(t % tiles_x) * 8u, y = static_cast<uint32_t>(t / tiles_x) * 8u;
+            const uint64_t inside = static_cast<uint64_t>(std::min(8u, view->nx - x)) * std::min(8u, view->ny - y);
+            pixel_frames += inside * tiles[t].frames;
+        }
+    }
+    return timed.gather(st, pixel_frames * scene->prep.nb_ray, call.lit.count);
+}
+
+// the device-resident entry point: the caller's arrays, the caller's stream, nothing waited for
+int adaptive_device(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, const RtxAdaptRule &rule, bool resume,
+                    void *d_moments, void *d_tiles, void *d_rgb, void *d_shade, void *stream)
+{
+    if (view->nx * view->ny == 0u) return RTX_OK;
+    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    RTX_TRY(adaptive_launch(scene, st, view, call, rule, resume, d_moments, d_tiles, d_rgb, d_shade, nullptr, static_cast<hipStream_t>(stream)));
+    return mark_uses(st, mean_uses(call), static_cast<hipStream_t>(stream));
+}
+
 // ---- any view through the render pipeline (rtx_render_view_rows; the aim kernels: rtx_aim.hip) ------------------------------
 
 // the pipeline's walks start at the eye: origin_bound holds for it.  A NaN fails it.
@@ -2497,6 +2592,51 @@ int rtx_render_view_mean_device(RtxScene *scene, int device, const RtxView *view
     if (!d_accum || !aligned16(d_accum, d_shade)) return RTX_ERR_BAD_ARG;
     if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, d_accum, &call)) return RTX_ERR_BAD_ARG;
     return mean_device(scene, device, view, call, d_accum, d_rgb, d_shade, stream);
+}
+
+// ---- the adaptive mean of N frames (the kernels: rtx_adapt.hip) -----------------------------------------------------------------
+
+int rtx_moment_add_device(RtxScene *scene, int device, uint32_t nx, uint32_t ny, const void *d_shade, void *d_moments, void *d_tiles,
+                          uint32_t first, const RtxAdaptRule *rule, void *stream)
+{
+    if (!scene || !d_shade || !d_moments || !aligned16(d_shade, d_moments) || (reinterpret_cast<uintptr_t>(d_tiles) & 7u)) return RTX_ERR_BAD_ARG;
+    if ((d_tiles && !rtx::adapt_rule_ok(rule)) || static_cast<uint64_t>(nx) * ny > rtxe::kMaxPixels) return RTX_ERR_BAD_ARG;
+    if (nx == 0u || ny == 0u) return RTX_OK;
+    Entry e(scene, device, Entry::kCurrent);
+    if (e.rc != RTX_OK) return e.rc;
+    return hip_rc(rtxe::launch_moment_add(nx, ny, d_shade, d_moments, d_tiles, first != 0u, d_tiles ? *rule : RtxAdaptRule{1u, 0.0f},
+                                          static_cast<hipStream_t>(stream)));
+}
+
+int rtx_moment_resolve_device(RtxScene *scene, int device, uint32_t n, const void *d_moments, void *d_rgb, void *d_shade, void *stream)
+{
+    if (!scene || !d_moments || (!d_rgb && !d_shade) || !aligned16(d_moments, d_shade)) return RTX_ERR_BAD_ARG;
+    if (n == 0u) return RTX_OK;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    return hip_rc(rtxe::launch_moment_resolve(e.state().thr.as<const float>(), n, d_moments, d_rgb, d_shade, static_cast<hipStream_t>(stream)));
+}
+
+int rtx_render_view_adaptive(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                             const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, const RtxAdaptRule *rule, uint8_t *out_rgb,
+                             RtxPixelShade *out_shade, RtxTileState *out_tiles, RtxStats *stats)
+{
+    MeanCall call;
+    const void *out = out_rgb ? static_cast<const void *>(out_rgb) : out_shade;
+    if (!rtx::adapt_rule_ok(rule)) return RTX_ERR_BAD_ARG;
+    if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, out, &call)) return RTX_ERR_BAD_ARG;
+    return adaptive_host(scene, device, view, call, *rule, out_rgb, out_shade, out_tiles, stats);
+}
+
+int rtx_render_view_adaptive_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                    const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, const RtxAdaptRule *rule,
+                                    void *d_moments, void *d_tiles, void *d_rgb, void *d_shade, void *stream)
+{
+    MeanCall call;
+    if (!rtx::adapt_rule_ok(rule) || !d_moments || !d_tiles || !aligned16(d_moments, d_shade) || (reinterpret_cast<uintptr_t>(d_tiles) & 7u))
+        return RTX_ERR_BAD_ARG;
+    if (!mean_args_ok(scene, view, light, flags & ~RTX_ADAPT_CONTINUE, seeds, n_frames, n_pairs, d_moments, &call)) return RTX_ERR_BAD_ARG;
+    return adaptive_device(scene, device, view, call, *rule, (flags & RTX_ADAPT_CONTINUE) != 0u, d_moments, d_tiles, d_rgb, d_shade, stream);
 }
 
 int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats)

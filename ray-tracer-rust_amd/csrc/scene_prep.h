@@ -103,6 +103,69 @@ RTX_HOST_DEVICE inline RtxPixelShade accum_resolve_statement(const float *thr, u
     return out;
 }
 constexpr uint32_t kMaxMeanFrames = 65536u;
+// The adaptive mean of N frames (rtx_render_view_adaptive, rtx_moment_*_device; the kernels: rtx_adapt.hip).  Four
+// statements, each one text for both compilers: rtxh_moment_add / rtxh_moment_resolve on the host, rtxe::moment_add_kernel /
+// rtxe::moment_resolve_kernel and the masked view launch on the device.
+// moment_add_statement: accum_add_statement's sum and hit_frames, word for word, beside the ordered f32 sum of the squares
+// and the pixel's own frame count.  The square is a product rounded to f32 BEFORE it is added (two statements, and
+// -ffp-contract=off on both sides: never an FMA).  first: what *m held is not read and may be anything.
+RTX_HOST_DEVICE inline void moment_add_statement(bool first, const RtxPixelShade &shade, RtxMomentPixel *m)
+{
+    const uint32_t hit = shade.hits != 0 ? 1u : 0u;
+    if (first) {
+        __builtin_memcpy(m->sum, shade.linear, 12);
+        for (int c = 0; c < 3; ++c) m->sumsq[c] = shade.linear[c] * shade.linear[c];
+        m->hit_frames = hit;
+        m->frames = 1u;
+        return;
+    }
+    for (int c = 0; c < 3; ++c) {
+        const float sq = shade.linear[c] * shade.linear[c];
+        m->sum[c] = m->sum[c] + shade.linear[c];
+        m->sumsq[c] = m->sumsq[c] + sq;
+    }
+    m->hit_frames = m->hit_frames + hit;
+    m->frames = m->frames + 1u;
+}
+// moment_error_statement: the (biased) variance of the mean of the pixel's noisiest channel.  Per channel two correctly
+// rounded divisions by (float)frames, a product rounded first, a subtraction, `v > 0 ? v : 0` — a NaN and a negative
+// rounding residue both become +0 — and a third division; the maximum by `a < b ? b : a`.  Never NaN, never negative.
+// frames <= 2^24 converts exactly.
+RTX_HOST_DEVICE inline float moment_error_statement(const RtxMomentPixel &m)
+{
+    const float fn = static_cast<float>(m.frames);
+    float e[3];
+    for (int c = 0; c < 3; ++c) {
+        const float mean = m.sum[c] / fn;
+        const float q = m.sumsq[c] / fn;
+        const float sq = mean * mean;
+        float v = q - sq;
+        v = v > 0.0f ? v : 0.0f;
+        e[c] = v / fn;
+    }
+    const float worst = e[0] < e[1] ? e[1] : e[0];
+    return worst < e[2] ? e[2] : worst;
+}
+// tile_stopped: the one predicate the masked view launch and the add both evaluate from a tile's 8-byte state; there is no
+// separate "stopped" word.  A stopped tile's state is no longer written, so within a call stopping is final.
+RTX_HOST_DEVICE inline bool tile_stopped(const RtxAdaptRule &rule, const RtxTileState &state)
+{
+    return state.frames >= rule.min_frames && state.err <= rule.max_variance;
+}
+// a rule a call accepts: min_frames >= 1, max_variance >= 0 (+infinity included; a NaN fails the comparison)
+inline bool adapt_rule_ok(const RtxAdaptRule *rule) { return rule && rule->min_frames != 0u && rule->max_variance >= 0.0f; }
+// moment_resolve_statement: accum_resolve_statement with the pixel's OWN frame count as the divisor.
+RTX_HOST_DEVICE inline RtxPixelShade moment_resolve_statement(const float *thr, const RtxMomentPixel &m)
+{
+    RtxPixelShade out;
+    const float n = static_cast<float>(m.frames);
+    for (int c = 0; c < 3; ++c) {
+        out.linear[c] = m.sum[c] / n;
+        out.rgb8[c] = static_cast<uint8_t>(quantise_statement(thr, out.linear[c]));
+    }
+    out.hits = static_cast<uint8_t>(m.hit_frames < 255u ? m.hit_frames : 255u);
+    return out;
+}
 // Where the host reads a sample table: the caller's n interleaved pairs, or — table == NULL — the seeded table of n pairs,
 // whose entries sample_statement gives.  The accessor of every host reader (light_points_of and through it the lit calls'
 // margin): a seeded table is never made on the host.

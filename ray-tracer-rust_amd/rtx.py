@@ -121,6 +121,28 @@ ACCUM_PIXEL_DTYPE = np.dtype([("sum", np.float32, 3), ("hit_frames", np.uint32)]
 assert ACCUM_PIXEL_DTYPE.itemsize == C.sizeof(AccumPixel) == 16
 MAX_MEAN_FRAMES = 65536
 MEAN_POSED = 1
+ADAPT_CONTINUE = 2
+
+
+class MomentPixel(C.Structure):
+    """RtxMomentPixel: RtxAccumPixel's words, the ordered sum of the frames' squared linear colours and the pixel's own count."""
+    _fields_ = [("sum", C.c_float * 3), ("hit_frames", C.c_uint32), ("sumsq", C.c_float * 3), ("frames", C.c_uint32)]
+
+
+class TileState(C.Structure):
+    """RtxTileState: the frames an 8 x 8 tile of the rectangle received and its noise estimate after its last add."""
+    _fields_ = [("frames", C.c_uint32), ("err", C.c_float)]
+
+
+class AdaptRule(C.Structure):
+    """RtxAdaptRule: a tile is stopped when frames >= min_frames and err <= max_variance."""
+    _fields_ = [("min_frames", C.c_uint32), ("max_variance", C.c_float)]
+
+
+# the same bytes as numpy records: what moment_add works on
+MOMENT_PIXEL_DTYPE = np.dtype([("sum", np.float32, 3), ("hit_frames", np.uint32), ("sumsq", np.float32, 3), ("frames", np.uint32)])
+TILE_STATE_DTYPE = np.dtype([("frames", np.uint32), ("err", np.float32)])
+assert MOMENT_PIXEL_DTYPE.itemsize == C.sizeof(MomentPixel) == 32 and TILE_STATE_DTYPE.itemsize == C.sizeof(TileState) == 8
 ROWS_POSED = 1
 
 
@@ -283,6 +305,18 @@ _SIGS = {
                                        C.c_uint32, C.c_void_p, C.POINTER(PixelShade), C.POINTER(Stats)]),
     "rtx_render_view_mean_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtxh_moment_add": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(PixelShade), C.POINTER(MomentPixel), C.POINTER(TileState), C.c_uint32,
+                                  C.POINTER(AdaptRule)]),
+    "rtxh_moment_resolve": (C.c_int, [f32p, C.c_uint32, C.POINTER(MomentPixel), C.c_void_p, C.POINTER(PixelShade)]),
+    "rtx_moment_add_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.POINTER(AdaptRule), C.c_void_p]),
+    "rtx_moment_resolve_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_render_view_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p, C.c_uint32,
+                                           C.c_uint32, C.POINTER(AdaptRule), C.c_void_p, C.POINTER(PixelShade), C.POINTER(TileState),
+                                           C.POINTER(Stats)]),
+    "rtx_render_view_adaptive_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
+                                                  C.c_uint32, C.c_uint32, C.POINTER(AdaptRule), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
     "rtx_render_view_rows_mean": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p, C.c_uint32,
                                             C.c_uint32, C.c_void_p, C.POINTER(PixelShade), C.POINTER(Stats)]),
     "rtx_render_view_rows_mean_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
@@ -422,6 +456,49 @@ def accum_resolve(thresholds, accum, n_frames):
     rgb, shade = np.zeros(a.shape + (3,), np.uint8), np.zeros(a.shape, PIXEL_SHADE_DTYPE)
     _check(_lib.rtxh_accum_resolve(_fp(thr), a.size, a.ctypes.data_as(C.POINTER(AccumPixel)), int(n_frames), rgb.ctypes.data,
                                    shade.ctypes.data_as(C.POINTER(PixelShade))), "rtxh_accum_resolve")
+    return rgb, shade
+
+
+def tile_grid(nx, ny):
+    """(tiles_x, tiles_y) of an nx x ny rectangle: its 8 x 8 tiles, row by row"""
+    return (nx + 7) // 8, (ny + 7) // 8
+
+
+def moment_add(shade, moments=None, tiles=None, rule=None):
+    """Host only: the adaptive mean's add over a rectangle (rtxh_moment_add).  shade: PIXEL_SHADE_DTYPE records [ny, nx] of one
+    frame; moments: MOMENT_PIXEL_DTYPE [ny, nx], updated in place and returned — None: the first frame, new arrays whose old
+    content is never read.  rule: None (no tile states: the plain moment accumulator -> moments) or (min_frames,
+    max_variance) -> (moments, tiles), tiles TILE_STATE_DTYPE [tiles_y, tiles_x], updated in place when given."""
+    s = np.ascontiguousarray(shade, dtype=PIXEL_SHADE_DTYPE)
+    assert s.ndim == 2
+    ny, nx = s.shape
+    first = moments is None
+    if first:
+        moments = np.empty(s.shape, MOMENT_PIXEL_DTYPE)
+        assert tiles is None
+    assert moments.dtype == MOMENT_PIXEL_DTYPE and moments.flags["C_CONTIGUOUS"] and moments.shape == s.shape
+    r = None
+    if rule is not None:
+        r = AdaptRule(int(rule[0]), float(rule[1]))
+        if tiles is None:
+            assert first
+            tiles = np.empty(tile_grid(nx, ny)[::-1], TILE_STATE_DTYPE)
+        assert tiles.dtype == TILE_STATE_DTYPE and tiles.flags["C_CONTIGUOUS"] and tiles.shape == tile_grid(nx, ny)[::-1]
+    _check(_lib.rtxh_moment_add(nx, ny, s.ctypes.data_as(C.POINTER(PixelShade)), moments.ctypes.data_as(C.POINTER(MomentPixel)),
+                                tiles.ctypes.data_as(C.POINTER(TileState)) if rule is not None else None, 1 if first else 0,
+                                C.byref(r) if r is not None else None), "rtxh_moment_add")
+    return moments if rule is None else (moments, tiles)
+
+
+def moment_resolve(thresholds, moments):
+    """Host only: the adaptive mean's resolve over arrays (rtxh_moment_resolve) -> (uint8 [..., 3], PIXEL_SHADE_DTYPE records):
+    every pixel divided by its own frame count; thresholds: a scene's 256 (Scene.gamma_thresholds)."""
+    thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+    m = np.ascontiguousarray(moments, dtype=MOMENT_PIXEL_DTYPE)
+    assert thr.size == 256
+    rgb, shade = np.zeros(m.shape + (3,), np.uint8), np.zeros(m.shape, PIXEL_SHADE_DTYPE)
+    _check(_lib.rtxh_moment_resolve(_fp(thr), m.size, m.ctypes.data_as(C.POINTER(MomentPixel)), rgb.ctypes.data,
+                                    shade.ctypes.data_as(C.POINTER(PixelShade))), "rtxh_moment_resolve")
     return rgb, shade
 
 
@@ -1346,6 +1423,61 @@ class Scene:
                                              C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
                                              C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
                                              C.c_void_p(stream) if stream else None), "rtx_accum_resolve_device")
+
+    # -- the adaptive mean of N frames: tiles stop once their noise estimate is met; the scene is not changed
+    def render_view_adaptive(self, view, seeds, rule, n_pairs=NB_RAND_SAMPLE, device=0, light=None, posed=False, stats=False,
+                             want_shade=False, want_tiles=False):
+        """The mean of up to len(seeds) frames of the view (rtx_render_view_adaptive): an 8 x 8 tile of the rectangle stops
+        receiving frames once it has rule[0] = min_frames of them and its noise estimate is <= rule[1] = max_variance
+        -> uint8 [ny, nx, 3]; want_shade adds the records, want_tiles the tile states (TILE_STATE_DTYPE [tiles_y, tiles_x]:
+        the frames each tile received and its estimate), stats the statistics summed over the rendered tile-frames, last."""
+        sd = self._seeds(seeds)
+        r = AdaptRule(int(rule[0]), float(rule[1]))
+        out = np.zeros((view.ny, view.nx, 3), np.uint8)
+        shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
+        tiles = np.zeros(tile_grid(view.nx, view.ny)[::-1], TILE_STATE_DTYPE) if want_tiles else None
+        st = Stats()
+        _check(_lib.rtx_render_view_adaptive(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                             MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), C.byref(r),
+                                             out.ctypes.data, shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
+                                             tiles.ctypes.data_as(C.POINTER(TileState)) if want_tiles else None,
+                                             C.byref(st) if stats else None), "rtx_render_view_adaptive")
+        res = (out,) + ((shade,) if want_shade else ()) + ((tiles,) if want_tiles else ()) + ((st.asdict(),) if stats else ())
+        return res if len(res) > 1 else out
+
+    def render_view_adaptive_device(self, device, view, seeds, rule, n_pairs, d_moments_ptr, d_tiles_ptr, d_rgb_ptr=None,
+                                    d_shade_ptr=None, stream=None, light=None, posed=False, resume=False):
+        """Asynchronous: the same chain on `stream` into device buffers the caller owns — ny*nx x 32 bytes of moments (16-byte
+        aligned), tiles_y*tiles_x x 8 bytes of tile states (8-byte aligned), optionally ny*nx*3 bytes (any alignment) and
+        ny*nx x 16 bytes of records.  resume (RTX_ADAPT_CONTINUE): the moments and the states are an earlier call's, the
+        seeds the next frames'."""
+        sd = self._seeds(seeds)
+        r = AdaptRule(int(rule[0]), float(rule[1]))
+        flags = (MEAN_POSED if posed else 0) | (ADAPT_CONTINUE if resume else 0)
+        _check(_lib.rtx_render_view_adaptive_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                                    flags, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), C.byref(r),
+                                                    C.c_void_p(d_moments_ptr), C.c_void_p(d_tiles_ptr),
+                                                    C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
+                                                    C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
+                                                    C.c_void_p(stream) if stream else None), "rtx_render_view_adaptive_device")
+
+    def moment_add_device(self, device, nx, ny, d_shade_ptr, d_moments_ptr, d_tiles_ptr, first, rule=None, stream=None):
+        """Asynchronous: adds the nx x ny RtxPixelShade records of a rectangle — of any call that writes them — into its moment
+        records, tile by tile, skipping the tiles that are stopped under `rule` (rtx_moment_add_device).  d_tiles_ptr None:
+        every tile is live and no state is written.  first: moments and states are written, never read."""
+        r = AdaptRule(int(rule[0]), float(rule[1])) if rule is not None else None
+        _check(_lib.rtx_moment_add_device(self._h, device, int(nx), int(ny), C.c_void_p(d_shade_ptr), C.c_void_p(d_moments_ptr),
+                                          C.c_void_p(d_tiles_ptr) if d_tiles_ptr else None, 1 if first else 0,
+                                          C.byref(r) if r is not None else None,
+                                          C.c_void_p(stream) if stream else None), "rtx_moment_add_device")
+
+    def moment_resolve_device(self, device, n, d_moments_ptr, d_rgb_ptr=None, d_shade_ptr=None, stream=None):
+        """Asynchronous: n moment records into n*3 bytes (any alignment) and / or n records (rtx_moment_resolve_device), each
+        divided by its own frame count, through the scene's gamma thresholds."""
+        _check(_lib.rtx_moment_resolve_device(self._h, device, int(n), C.c_void_p(d_moments_ptr),
+                                              C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
+                                              C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
+                                              C.c_void_p(stream) if stream else None), "rtx_moment_resolve_device")
 
 
 def default_scene(obj_paths, width=DEFAULT_WIDTH, height=DEFAULT_HEIGHT, samples=None, **kw):
