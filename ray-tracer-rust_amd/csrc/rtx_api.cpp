@@ -1445,7 +1445,7 @@ int shade_device(RtxScene *scene, int device, uint32_t n_pixels, const void *d_o
                         {d_shade, d_hits, nullptr}, stream);
 }
 
-// ---- the mean of N frames (rtx_render_view_mean, rtx_accum_*_device; the kernels: rtx_accum.hip) ---------------------------
+// ---- the mean of N frames: what a call is and what it reserves (the one path: below, behind the pipeline's view launch) ------
 
 // What a mean call is beside its view: the light (the scene's own as a Lit when the caller gave none: every frame's points
 // are made over that frame's table), whether the caller gave it (the twin's finiteness check is for a given light), the
@@ -1458,7 +1458,7 @@ struct MeanCall {
     uint32_t n_frames, n_pairs;
 };
 
-// the argument checks the two variants share, the twin's (CallLight, view_args_ok: `out` stands for its outputs) among them
+// the argument checks every mean call shares, the twin's (CallLight, view_args_ok: `out` stands for its outputs) among them
 bool mean_args_ok(const RtxScene *scene, const RtxView *view, const RtxLight *light, uint32_t flags, const uint64_t *seeds,
                   uint32_t n_frames, uint32_t n_pairs, const void *out, MeanCall *call)
 {
@@ -1486,173 +1486,8 @@ int reserve_mean(DeviceState &st, uint32_t n_pairs, uint32_t n_pixels)
     return reserve_all({{st.mean.table, table}, {st.mean.records, records}});
 }
 
-// The whole chain on `stream`, nothing waited for between frames.  Per frame: the frame's table from its seed, the light's
-// points over that table, the view kernel — as it is: its argument block's table, table length, light points and count are
-// what differs — into the scratch records, the add.  Then the resolve, where an output is asked for.  The scene's own table
-// and light arrays are neither read nor written.  Caller holds the slot's lock and has the device current and the scene
-// uploaded; n_pixels > 0.
-int mean_launch(RtxScene *scene, DeviceState &st, const RtxView *view, const MeanCall &call, void *d_accum, void *d_rgb,
-                void *d_shade, unsigned long long *d_counters, hipStream_t stream)
-{
-    const rtx::PreparedScene &p = scene->prep;
-    const uint32_t n_pixels = view->nx * view->ny;
-    DeviceGeometry *geo;
-    RTX_TRY(geometry_of(st, call.posed, &geo));
-    RTX_TRY(reserve_mean(st, call.n_pairs, n_pixels));
-    RTX_TRY(reserve_light(scene, st, call.lit, false));
-    rtx::DeviceScene S = device_scene(scene, st, *geo);
-    S.samples = st.mean.table.as<const float2>();
-    S.n_samples = call.n_pairs;
-    light_swap(st, call.lit, false, 0.0f, &S);
-    rtxv::ViewBlock v;
-    std::memcpy(&v, view, sizeof v);
-    for (uint32_t k = 0; k < call.n_frames; ++k) {
-        RTX_HIP(rtxr::launch_samples(call.seeds[k], call.n_pairs, st.mean.table.as<float2>(), stream));
-        if (call.lit.count != 0u)
-            RTX_HIP(rtxl::launch_light_points(st.mean.table.as<const float2>(), call.n_pairs, call.lit.tri, p.nb_ray, call.lit.count,
-                                              st.lit.points.as<float>(), stream));
-        RTX_HIP(rtxv::launch_view(S, v, origin_bound(scene), nullptr, st.mean.records.as<void>(), nullptr, d_counters, stream));
-        RTX_HIP(rtxc::launch_accum_add(n_pixels, st.mean.records.as<const void>(), d_accum, k == 0u, stream));
-    }
-    if (d_rgb || d_shade)
-        RTX_HIP(rtxc::launch_accum_resolve(st.thr.as<const float>(), n_pixels, d_accum, call.n_frames, d_rgb, d_shade, stream));
-    return RTX_OK;
-}
-
+// the guarded groups every mean call uses (the pipeline's tour and boxes are the light's: kUsesLight)
 unsigned mean_uses(const MeanCall &call) { return kUsesLight | kUsesMean | (call.posed ? kUsesPose : 0u); }
-
-// the host entry point: the accumulator and the outputs in the library's output buffer, one behind the other (16-byte
-// records first), launch, copy out
-int mean_host(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, uint8_t *rgb, RtxPixelShade *shade,
-              RtxStats *stats)
-{
-    const Timed timed(stats);
-    const uint32_t n_pixels = view->nx * view->ny;
-    if (n_pixels == 0u) return timed.empty();
-    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    const size_t records = static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade);
-    const size_t shade_bytes = shade ? records : 0u, rgb_bytes = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
-    RTX_TRY(st.q_out.reserve(records + shade_bytes + rgb_bytes));
-    uint8_t *d_accum = st.q_out.as<uint8_t>(), *d_shade = shade ? d_accum + records : nullptr;
-    uint8_t *d_rgb = rgb ? d_accum + records + shade_bytes : nullptr;
-    RTX_TRY(wait_for_uses(st, mean_uses(call)));
-    RTX_TRY(timed.begin(st));
-    RTX_TRY(mean_launch(scene, st, view, call, d_accum, d_rgb, d_shade, timed.counters(st), st.stream));
-    RTX_TRY(timed.end(st));
-    if (shade) RTX_HIP(hipMemcpyAsync(shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st.stream));
-    if (rgb) RTX_HIP(hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, st.stream));
-    return timed.gather(st, static_cast<uint64_t>(call.n_frames) * n_pixels * scene->prep.nb_ray, call.lit.count);
-}
-
-// the device-resident entry point: the caller's arrays, the caller's stream, nothing waited for
-int mean_device(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, void *d_accum, void *d_rgb, void *d_shade,
-                void *stream)
-{
-    if (view->nx * view->ny == 0u) return RTX_OK;
-    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    RTX_TRY(mean_launch(scene, st, view, call, d_accum, d_rgb, d_shade, nullptr, static_cast<hipStream_t>(stream)));
-    return mark_uses(st, mean_uses(call), static_cast<hipStream_t>(stream));
-}
-
-// ---- the adaptive mean of N frames (rtx_render_view_adaptive, rtx_moment_*_device; the kernels: rtx_adapt.hip) ---------------
-
-// the mean's chain with the masked view launch and the moment add in the view kernel's and the add's places: a tile that
-// tile_stopped(rule, its state) names is neither rendered nor added to.  resume: no frame is a first one (d_moments and
-// d_tiles hold an earlier call's state).  Caller holds the slot's lock and has the device current and the scene uploaded;
-// the rectangle is not empty.
-int adaptive_launch(RtxScene *scene, DeviceState &st, const RtxView *view, const MeanCall &call, const RtxAdaptRule &rule, bool resume,
-                    void *d_moments, void *d_tiles, void *d_rgb, void *d_shade, unsigned long long *d_counters, hipStream_t stream)
-{
-    const rtx::PreparedScene &p = scene->prep;
-    const uint32_t n_pixels = view->nx * view->ny;
-    DeviceGeometry *geo;
-    RTX_TRY(geometry_of(st, call.posed, &geo));
-    RTX_TRY(reserve_mean(st, call.n_pairs, n_pixels));
-    RTX_TRY(reserve_light(scene, st, call.lit, false));
-    rtx::DeviceScene S = device_scene(scene, st, *geo);
-    S.samples = st.mean.table.as<const float2>();
-    S.n_samples = call.n_pairs;
-    light_swap(st, call.lit, false, 0.0f, &S);
-    rtxv::ViewBlock v;
-    std::memcpy(&v, view, sizeof v);
-    for (uint32_t k = 0; k < call.n_frames; ++k) {
-        const bool first = k == 0u && !resume;
-        RTX_HIP(rtxr::launch_samples(call.seeds[k], call.n_pairs, st.mean.table.as<float2>(), stream));
-        if (call.lit.count != 0u)
-            RTX_HIP(rtxl::launch_light_points(st.mean.table.as<const float2>(), call.n_pairs, call.lit.tri, p.nb_ray, call.lit.count,
-                                              st.lit.points.as<float>(), stream));
-        RTX_HIP(rtxe::launch_view_masked(S, v, origin_bound(scene), st.mean.records.as<void>(), d_counters, d_tiles, first, rule, stream));
-        RTX_HIP(rtxe::launch_moment_add(view->nx, view->ny, st.mean.records.as<const void>(), d_moments, d_tiles, first, rule, stream));
-    }
-    if (d_rgb || d_shade)
-        RTX_HIP(rtxe::launch_moment_resolve(st.thr.as<const float>(), n_pixels, d_moments, d_rgb, d_shade, stream));
-    return RTX_OK;
-}
-
-// the host entry point: the moments, the tile states and the outputs in the library's output buffer, one behind the other
-// (every part a multiple of 16 bytes but the last), launch, copy out.  The statistics need the tile states: they are read
-// back whether or not the caller asked for them.
-int adaptive_host(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, const RtxAdaptRule &rule, uint8_t *rgb,
-                  RtxPixelShade *shade, RtxTileState *tiles, RtxStats *stats)
-{
-    const Timed timed(stats);
-    const uint32_t n_pixels = view->nx * view->ny;
-    if (n_pixels == 0u) return timed.empty();
-    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    const size_t n_tiles = static_cast<size_t>(rtxe::tile_count(view->nx, view->ny));
-    const size_t moments = static_cast<size_t>(n_pixels) * sizeof(RtxMomentPixel);
-    const size_t states = (n_tiles * sizeof(RtxTileState) + 15u) & ~static_cast<size_t>(15u);
-    const size_t shade_bytes = shade ? static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade) : 0u;
-    const size_t rgb_bytes = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
-    RTX_TRY(st.q_out.reserve(moments + states + shade_bytes + rgb_bytes));
-    uint8_t *d_moments = st.q_out.as<uint8_t>(), *d_tiles = d_moments + moments;
-    uint8_t *d_shade = shade ? d_tiles + states : nullptr, *d_rgb = rgb ? d_tiles + states + shade_bytes : nullptr;
-    RTX_TRY(wait_for_uses(st, mean_uses(call)));
-    RTX_TRY(timed.begin(st));
-    RTX_TRY(adaptive_launch(scene, st, view, call, rule, false, d_moments, d_tiles, d_rgb, d_shade, timed.counters(st), st.stream));
-    RTX_TRY(timed.end(st));
-    std::vector<RtxTileState> own;
-    if (!tiles && stats) {
-        own.resize(n_tiles);
-        tiles = own.data();
-    }
-    if (shade) RTX_HIP(hipMemcpyAsync(shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st.stream));
-    if (rgb) RTX_HIP(hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, st.stream));
-    if (tiles) RTX_HIP(hipMemcpyAsync(tiles, d_tiles, n_tiles * sizeof(RtxTileState), hipMemcpyDeviceToHost, st.stream));
-    uint64_t pixel_frames = 0;
-    if (stats) {
-        RTX_HIP(hipStreamSynchronize(st.stream));
-        const uint32_t tiles_x = (view->nx + 7u) / 8u;
-        for (size_t t = 0; t < n_tiles; ++t) {
-            const uint32_t x = static_cast<uint32_t>(t % tiles_x) * 8u, y = static_cast<uint32_t>(t / tiles_x) * 8u;
-            const uint64_t inside = static_cast<uint64_t>(std::min(8u, view->nx - x)) * std::min(8u, view->ny - y);
-            pixel_frames += inside * tiles[t].frames;
-        }
-    }
-    return timed.gather(st, pixel_frames * scene->prep.nb_ray, call.lit.count);
-}
-
-// the device-resident entry point: the caller's arrays, the caller's stream, nothing waited for
-int adaptive_device(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, const RtxAdaptRule &rule, bool resume,
-                    void *d_moments, void *d_tiles, void *d_rgb, void *d_shade, void *stream)
-{
-    if (view->nx * view->ny == 0u) return RTX_OK;
-    if (call.given && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    RTX_TRY(adaptive_launch(scene, st, view, call, rule, resume, d_moments, d_tiles, d_rgb, d_shade, nullptr, static_cast<hipStream_t>(stream)));
-    return mark_uses(st, mean_uses(call), static_cast<hipStream_t>(stream));
-}
 
 // ---- any view through the render pipeline (rtx_render_view_rows; the aim kernels: rtx_aim.hip) ------------------------------
 
@@ -1717,20 +1552,20 @@ int aim_at(const RtxScene *scene, DeviceGeometry &g, const float eye[3], hipStre
 // follow the aim kernels, and the pipeline's kernels are handed that light's five fields.  Whichever geometry it is, no
 // field of the block is added or moved, and the kernels are the same.  So is the shaft margin: it is folded from the bound M
 // every posed coordinate respects, not from the geometry's extent.
-// frame_of / frame (rtx_render_view_rows_mean): the launch is frame `frame` of that call — the table is the mean's scratch
-// table, made from the frame's seed ahead of the light kernels, which then read it in the scene's table's place.
+// table / n_pairs: NULL, or a table on the device that stands in for the scene's: the light kernels and the pipeline's read
+// it.  Whoever hands one in makes it on the stream in `before`.
 template <class Before>
 int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const RtxView &v, uint8_t *d_out,
                      unsigned long long *d_counters, hipStream_t stream, Before before, const Lit *lit, float shaft_delta,
-                     void *d_shade = nullptr, const MeanCall *frame_of = nullptr, uint32_t frame = 0u)
+                     void *d_shade = nullptr, const float2 *table = nullptr, uint32_t n_pairs = 0u)
 {
     RTX_TRY(reserve_aimed(scene, g));
     if (lit) RTX_TRY(reserve_light(scene, st, *lit, true));
     rtx::DeviceScene S = device_scene(scene, st, g);
     if (lit) light_swap(st, *lit, true, shaft_delta, &S);
-    if (frame_of) {
-        S.samples = st.mean.table.as<const float2>();
-        S.n_samples = frame_of->n_pairs;
+    if (table) {
+        S.samples = table;
+        S.n_samples = n_pairs;
     }
     S.width = v.width;
     S.height = v.height;
@@ -1745,11 +1580,7 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const 
     return render_launch(st, S, ts, d_out, d_counters, nullptr, stream, [&]() -> int {
         RTX_TRY(before());
         RTX_TRY(aim_at(scene, g, v.eye, stream));
-        if (frame_of) {
-            RTX_HIP(rtxr::launch_samples(frame_of->seeds[frame], frame_of->n_pairs, st.mean.table.as<float2>(), stream));
-            return light_launch(scene, st, *lit, true, stream, st.mean.table.as<const float2>(), frame_of->n_pairs);
-        }
-        return lit ? light_launch(scene, st, *lit, true, stream) : RTX_OK;
+        return lit ? light_launch(scene, st, *lit, true, stream, table, n_pairs) : RTX_OK;
     }, rtx::ProbeSplit{nullptr, 0u, 0u, 0u}, d_shade);
 }
 
@@ -1761,7 +1592,8 @@ int view_rows_supported(const RtxScene *scene, const RtxView *view, const Lit *l
     return lit ? lit_rows_margin(scene, *lit, shaft_delta) : RTX_OK;
 }
 
-// ---- the mean of N frames through the render pipeline (rtx_render_view_rows_mean) -----------------------------------------
+// ---- the mean of N frames, one path: a renderer and the sums as arguments (rtx_render_view_mean, rtx_render_view_rows_mean,
+// ---- rtx_render_view_adaptive and their _device twins; the kernels: rtx_accum.hip, rtx_adapt.hip) -------------------------------
 
 // The shaft margin of every frame of a mean call, on the host, before a device is looked for: frame k's light points are made
 // over the seeded table (seeds[k], n_pairs), and the margin is shaft_delta_of over their boxes — light_walk_on_host's, which
@@ -1783,76 +1615,161 @@ int rows_mean_margins(const RtxScene *scene, const MeanCall &call, std::vector<f
     return RTX_OK;
 }
 
-// mean_launch with the pipeline's record launch in the view kernel's place.  Per frame, on `stream`, nothing waited for: the
-// frame's table from its seed, the light's points, tour and boxes over that table (the _rows_lit kernels), a record launch
-// whose argument block has the table, its length and the light's five fields swapped, the add.  The aim kernels run once:
-// there is one eye.  Then the resolve.
-int rows_mean_launch(RtxScene *scene, DeviceState &st, const RtxView *view, const MeanCall &call, const std::vector<float> &margins,
-                     void *d_accum, void *d_rgb, void *d_shade, unsigned long long *d_counters, hipStream_t stream)
+// What renders a frame of a mean call into the scratch records: the view kernel as it is; the masked view kernel, which
+// skips the tiles the sums' rule has stopped (it reads the sums' tile states: moments only); or the pipeline's record
+// launch (full width, a shaft margin per frame: rows_mean_margins).
+enum class Renderer { kView, kMasked, kRows };
+
+// What a frame's records are summed into and resolved from.  rule == NULL: the plain sum (rtx_accum.hip), d_state one
+// 16-byte accumulator per pixel.  Else the moments (rtx_adapt.hip): d_state 32-byte moments, d_tiles a state per 8 x 8 tile;
+// resume: no frame is a first one (both hold an earlier call's state).  A host call lays state_bytes() out with place().
+struct Sums {
+    const RtxAdaptRule *rule = nullptr;
+    bool resume = false;
+    void *d_state = nullptr, *d_tiles = nullptr;
+
+    size_t tiles_bytes(const RtxView &v) const { return rule ? static_cast<size_t>(rtxe::tile_count(v.nx, v.ny)) * sizeof(RtxTileState) : 0u; }
+    size_t pixels_bytes(const RtxView &v) const { return static_cast<size_t>(v.nx) * v.ny * (rule ? sizeof(RtxMomentPixel) : sizeof(RtxPixelShade)); }
+    size_t state_bytes(const RtxView &v) const { return pixels_bytes(v) + ((tiles_bytes(v) + 15u) & ~static_cast<size_t>(15u)); }
+    void place(const RtxView &v, uint8_t *d)
+    {
+        d_state = d;
+        d_tiles = rule ? d + pixels_bytes(v) : nullptr;
+    }
+    hipError_t add(const RtxView &v, const void *records, bool first, hipStream_t stream) const
+    {
+        return rule ? rtxe::launch_moment_add(v.nx, v.ny, records, d_state, d_tiles, first, *rule, stream)
+                    : rtxc::launch_accum_add(v.nx * v.ny, records, d_state, first, stream);
+    }
+    hipError_t resolve(const float *thr, const RtxView &v, uint32_t n_frames, void *d_rgb, void *d_shade, hipStream_t stream) const
+    {
+        return rule ? rtxe::launch_moment_resolve(thr, v.nx * v.ny, d_state, d_rgb, d_shade, stream)
+                    : rtxc::launch_accum_resolve(thr, v.nx * v.ny, d_state, n_frames, d_rgb, d_shade, stream);
+    }
+    // What a host call copies out beside records and bytes, and *pixel_frames, the pixels it rendered over all frames (its
+    // statistics' primary rays, per ray of a pixel).  The plain sum: nothing, every pixel of every frame.  The moments: the
+    // tile states, for the caller or for the count (`count`: read back whether asked for or not, and the stream is waited
+    // for), and a tile's pixels inside the rectangle times its frames.
+    int copy_out(const RtxView &v, uint32_t n_frames, RtxTileState *tiles, bool count, hipStream_t stream, uint64_t *pixel_frames) const
+    {
+        *pixel_frames = static_cast<uint64_t>(n_frames) * v.nx * v.ny;
+        if (!rule || (!tiles && !count)) return RTX_OK;
+        const size_t n_tiles = tiles_bytes(v) / sizeof(RtxTileState);
+        std::vector<RtxTileState> own(tiles ? 0u : n_tiles);
+        if (!tiles) tiles = own.data();
+        RTX_HIP(hipMemcpyAsync(tiles, d_tiles, tiles_bytes(v), hipMemcpyDeviceToHost, stream));
+        if (!count) return RTX_OK;
+        RTX_HIP(hipStreamSynchronize(stream));
+        *pixel_frames = 0;
+        const uint32_t tiles_x = (v.nx + 7u) / 8u;
+        for (size_t t = 0; t < n_tiles; ++t) {
+            const uint32_t x = static_cast<uint32_t>(t % tiles_x) * 8u, y = static_cast<uint32_t>(t / tiles_x) * 8u;
+            *pixel_frames += static_cast<uint64_t>(std::min(8u, v.nx - x)) * std::min(8u, v.ny - y) * tiles[t].frames;
+        }
+        return RTX_OK;
+    }
+};
+
+// Every mean call's chain on `stream`, nothing waited for between frames.  Per frame: the frame's table from its seed into
+// the scratch table, the light's arrays over that table (the points; for the pipeline their tour and boxes too), the
+// renderer into the scratch records — its argument block's table, table length and light fields are what differs from the
+// twin's — and the add.  Then the resolve, where an output is asked for.  The pipeline launch puts the first two on the
+// stream itself, once its buffers stand; its aim kernels run once, there is one eye.  The scene's own table and light
+// arrays are neither read nor written.  margins: kRows only.  Caller holds the slot's lock and has the device current and
+// the scene uploaded; the rectangle is not empty.
+int frames_launch(RtxScene *scene, DeviceState &st, const RtxView &view, const MeanCall &call, Renderer renderer, const float *margins,
+                  const Sums &sums, void *d_rgb, void *d_shade, unsigned long long *d_counters, hipStream_t stream)
 {
-    const uint32_t n_pixels = view->nx * view->ny;
+    const bool rows = renderer == Renderer::kRows;
     DeviceGeometry *geo;
     RTX_TRY(geometry_of(st, call.posed, &geo));
-    RTX_TRY(reserve_mean(st, call.n_pairs, n_pixels));
+    RTX_TRY(reserve_mean(st, call.n_pairs, view.nx * view.ny));
+    RTX_TRY(reserve_light(scene, st, call.lit, rows));
+    const float2 *table = st.mean.table.as<const float2>();
+    void *records = st.mean.records.as<void>();
+    rtx::DeviceScene S = device_scene(scene, st, *geo);      // (the view kernels': the pipeline launch makes its own)
+    S.samples = table;
+    S.n_samples = call.n_pairs;
+    light_swap(st, call.lit, false, 0.0f, &S);
+    rtxv::ViewBlock v;
+    std::memcpy(&v, &view, sizeof v);
     for (uint32_t k = 0; k < call.n_frames; ++k) {
-        RTX_TRY(view_rows_launch(scene, st, *geo, *view, nullptr, d_counters, stream, [] { return static_cast<int>(RTX_OK); }, &call.lit,
-                                 margins[k], st.mean.records.as<void>(), &call, k));
-        RTX_HIP(rtxc::launch_accum_add(n_pixels, st.mean.records.as<const void>(), d_accum, k == 0u, stream));
+        const bool first = k == 0u && !sums.resume;
+        const auto seed = [&] { return hip_rc(rtxr::launch_samples(call.seeds[k], call.n_pairs, st.mean.table.as<float2>(), stream)); };
+        if (rows) {
+            RTX_TRY(view_rows_launch(scene, st, *geo, view, nullptr, d_counters, stream, seed, &call.lit, margins[k], records, table,
+                                     call.n_pairs));
+        } else {
+            RTX_TRY(seed());
+            RTX_TRY(light_launch(scene, st, call.lit, false, stream, table, call.n_pairs));
+            RTX_HIP(renderer == Renderer::kMasked
+                        ? rtxe::launch_view_masked(S, v, origin_bound(scene), records, d_counters, sums.d_tiles, first, *sums.rule, stream)
+                        : rtxv::launch_view(S, v, origin_bound(scene), nullptr, records, nullptr, d_counters, stream));
+        }
+        RTX_HIP(sums.add(view, records, first, stream));
     }
-    if (d_rgb || d_shade)
-        RTX_HIP(rtxc::launch_accum_resolve(st.thr.as<const float>(), n_pixels, d_accum, call.n_frames, d_rgb, d_shade, stream));
+    if (d_rgb || d_shade) RTX_HIP(sums.resolve(st.thr.as<const float>(), view, call.n_frames, d_rgb, d_shade, stream));
     return RTX_OK;
 }
 
-unsigned rows_mean_uses(const MeanCall &call) { return mean_uses(call); }      // (the lit-rows buffers are the light's: kUsesLight)
-
-// the argument checks and the host-side rules the two variants share, in the mean call's order, then the pipeline's
-int rows_mean_supported(const RtxScene *scene, const RtxView *view, const MeanCall &call, std::vector<float> *margins)
+// What a mean call is refused for on the host, before a device is looked for, in each family's own order (the host tests pin
+// them).  The view kernels: a given light that is not finite (the scene's own is not checked).  The pipeline: not full
+// width, even for an eye out of range; then the eye, the light, given or not, and the frames' margins.  An empty rectangle
+// answers RTX_OK ahead of everything but the width: the caller returns its empty answer.
+int frames_refused(const RtxScene *scene, const RtxView *view, const MeanCall &call, Renderer renderer, std::vector<float> *margins)
 {
-    if (view->x0 != 0u || view->nx != view->width) return RTX_ERR_BAD_ARG;
+    const bool rows = renderer == Renderer::kRows;
+    if (rows && (view->x0 != 0u || view->nx != view->width)) return RTX_ERR_BAD_ARG;
     if (view->nx * view->ny == 0u) return RTX_OK;
-    if (!eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
-    if (!light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
-    return rows_mean_margins(scene, call, margins);
+    if (rows && !eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
+    if ((rows || call.given) && !light_is_finite(call.lit)) return RTX_ERR_UNSUPPORTED;
+    return rows ? rows_mean_margins(scene, call, margins) : RTX_OK;
 }
 
-int rows_mean_host(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, uint8_t *rgb, RtxPixelShade *shade,
-                   RtxStats *stats)
+// the host entry points: the sums' state and the outputs in the library's output buffer, one behind the other (every part
+// a multiple of 16 bytes but the last), launch on the library's stream, copy out.  A host call never resumes.
+int frames_host(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, Renderer renderer, const RtxAdaptRule *rule,
+                uint8_t *rgb, RtxPixelShade *shade, RtxTileState *tiles, RtxStats *stats)
 {
     const Timed timed(stats);
     std::vector<float> margins;
-    RTX_TRY(rows_mean_supported(scene, view, call, &margins));
-    const uint32_t n_pixels = view->nx * view->ny;
-    if (n_pixels == 0u) return timed.empty();
+    RTX_TRY(frames_refused(scene, view, call, renderer, &margins));
+    if (view->nx * view->ny == 0u) return timed.empty();
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    const RtxView v = *view;
-    const size_t records = static_cast<size_t>(n_pixels) * sizeof(RtxPixelShade);
-    const size_t shade_bytes = shade ? records : 0u, rgb_bytes = rgb ? static_cast<size_t>(n_pixels) * 3u : 0u;
-    RTX_TRY(st.q_out.reserve(records + shade_bytes + rgb_bytes));
-    uint8_t *d_accum = st.q_out.as<uint8_t>(), *d_shade = shade ? d_accum + records : nullptr;
-    uint8_t *d_rgb = rgb ? d_accum + records + shade_bytes : nullptr;
-    RTX_TRY(wait_for_uses(st, rows_mean_uses(call)));
+    const RtxView v = *view;                 // (the caller's may change while the call runs)
+    Sums sums{rule};
+    const size_t state = sums.state_bytes(v);
+    const size_t shade_bytes = shade ? static_cast<size_t>(v.nx) * v.ny * sizeof(RtxPixelShade) : 0u;
+    const size_t rgb_bytes = rgb ? static_cast<size_t>(v.nx) * v.ny * 3u : 0u;
+    RTX_TRY(st.q_out.reserve(state + shade_bytes + rgb_bytes));
+    uint8_t *d_shade = shade ? st.q_out.as<uint8_t>() + state : nullptr, *d_rgb = rgb ? st.q_out.as<uint8_t>() + state + shade_bytes : nullptr;
+    sums.place(v, st.q_out.as<uint8_t>());
+    RTX_TRY(wait_for_uses(st, mean_uses(call)));
     RTX_TRY(timed.begin(st));
-    RTX_TRY(rows_mean_launch(scene, st, &v, call, margins, d_accum, d_rgb, d_shade, timed.counters(st), st.stream));
+    RTX_TRY(frames_launch(scene, st, v, call, renderer, margins.data(), sums, d_rgb, d_shade, timed.counters(st), st.stream));
     RTX_TRY(timed.end(st));
     if (shade) RTX_HIP(hipMemcpyAsync(shade, d_shade, shade_bytes, hipMemcpyDeviceToHost, st.stream));
     if (rgb) RTX_HIP(hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, st.stream));
-    return timed.gather(st, static_cast<uint64_t>(call.n_frames) * n_pixels * scene->prep.nb_ray, call.lit.count);
+    uint64_t pixel_frames = 0;
+    RTX_TRY(sums.copy_out(v, call.n_frames, tiles, stats != nullptr, st.stream, &pixel_frames));
+    return timed.gather(st, pixel_frames * scene->prep.nb_ray, call.lit.count);
 }
 
-int rows_mean_device(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, void *d_accum, void *d_rgb,
-                     void *d_shade, void *stream)
+// the device-resident entry points: the caller's arrays (in `sums` and d_rgb, d_shade), the caller's stream, no counters,
+// nothing waited for
+int frames_device(RtxScene *scene, int device, const RtxView *view, const MeanCall &call, Renderer renderer, const Sums &sums,
+                  void *d_rgb, void *d_shade, void *stream)
 {
     std::vector<float> margins;
-    RTX_TRY(rows_mean_supported(scene, view, call, &margins));
+    RTX_TRY(frames_refused(scene, view, call, renderer, &margins));
     if (view->nx * view->ny == 0u) return RTX_OK;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    RTX_TRY(rows_mean_launch(scene, st, view, call, margins, d_accum, d_rgb, d_shade, nullptr, static_cast<hipStream_t>(stream)));
-    return mark_uses(st, rows_mean_uses(call), static_cast<hipStream_t>(stream));
+    RTX_TRY(frames_launch(scene, st, *view, call, renderer, margins.data(), sums, d_rgb, d_shade, nullptr, static_cast<hipStream_t>(stream)));
+    return mark_uses(st, mean_uses(call), static_cast<hipStream_t>(stream));
 }
 
 // The bodies of rtx_render_view_rows and rtx_render_view_rows_device, each with its _lit twin's light as an argument (NULL:
@@ -2581,7 +2498,7 @@ int rtx_render_view_mean(RtxScene *scene, int device, const RtxView *view, const
     MeanCall call;
     const void *out = out_rgb ? static_cast<const void *>(out_rgb) : out_shade;
     if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, out, &call)) return RTX_ERR_BAD_ARG;
-    return mean_host(scene, device, view, call, out_rgb, out_shade, stats);
+    return frames_host(scene, device, view, call, Renderer::kView, nullptr, out_rgb, out_shade, nullptr, stats);
 }
 
 int rtx_render_view_mean_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
@@ -2591,7 +2508,7 @@ int rtx_render_view_mean_device(RtxScene *scene, int device, const RtxView *view
     MeanCall call;
     if (!d_accum || !aligned16(d_accum, d_shade)) return RTX_ERR_BAD_ARG;
     if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, d_accum, &call)) return RTX_ERR_BAD_ARG;
-    return mean_device(scene, device, view, call, d_accum, d_rgb, d_shade, stream);
+    return frames_device(scene, device, view, call, Renderer::kView, Sums{nullptr, false, d_accum, nullptr}, d_rgb, d_shade, stream);
 }
 
 // ---- the adaptive mean of N frames (the kernels: rtx_adapt.hip) -----------------------------------------------------------------
@@ -2625,7 +2542,7 @@ int rtx_render_view_adaptive(RtxScene *scene, int device, const RtxView *view, c
     const void *out = out_rgb ? static_cast<const void *>(out_rgb) : out_shade;
     if (!rtx::adapt_rule_ok(rule)) return RTX_ERR_BAD_ARG;
     if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, out, &call)) return RTX_ERR_BAD_ARG;
-    return adaptive_host(scene, device, view, call, *rule, out_rgb, out_shade, out_tiles, stats);
+    return frames_host(scene, device, view, call, Renderer::kMasked, rule, out_rgb, out_shade, out_tiles, stats);
 }
 
 int rtx_render_view_adaptive_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
@@ -2636,7 +2553,8 @@ int rtx_render_view_adaptive_device(RtxScene *scene, int device, const RtxView *
     if (!rtx::adapt_rule_ok(rule) || !d_moments || !d_tiles || !aligned16(d_moments, d_shade) || (reinterpret_cast<uintptr_t>(d_tiles) & 7u))
         return RTX_ERR_BAD_ARG;
     if (!mean_args_ok(scene, view, light, flags & ~RTX_ADAPT_CONTINUE, seeds, n_frames, n_pairs, d_moments, &call)) return RTX_ERR_BAD_ARG;
-    return adaptive_device(scene, device, view, call, *rule, (flags & RTX_ADAPT_CONTINUE) != 0u, d_moments, d_tiles, d_rgb, d_shade, stream);
+    return frames_device(scene, device, view, call, Renderer::kMasked, Sums{rule, (flags & RTX_ADAPT_CONTINUE) != 0u, d_moments, d_tiles},
+                         d_rgb, d_shade, stream);
 }
 
 int rtx_render_view_rows(RtxScene *scene, int device, const RtxView *view, uint8_t *out_rgb, RtxStats *stats)
@@ -3106,7 +3024,7 @@ int rtx_render_view_rows_mean(RtxScene *scene, int device, const RtxView *view, 
     MeanCall call;
     const void *out = out_rgb ? static_cast<const void *>(out_rgb) : out_shade;
     if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, out, &call)) return RTX_ERR_BAD_ARG;
-    return rows_mean_host(scene, device, view, call, out_rgb, out_shade, stats);
+    return frames_host(scene, device, view, call, Renderer::kRows, nullptr, out_rgb, out_shade, nullptr, stats);
 }
 
 int rtx_render_view_rows_mean_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
@@ -3116,7 +3034,7 @@ int rtx_render_view_rows_mean_device(RtxScene *scene, int device, const RtxView 
     MeanCall call;
     if (!d_accum || !aligned16(d_accum, d_shade)) return RTX_ERR_BAD_ARG;
     if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, d_accum, &call)) return RTX_ERR_BAD_ARG;
-    return rows_mean_device(scene, device, view, call, d_accum, d_rgb, d_shade, stream);
+    return frames_device(scene, device, view, call, Renderer::kRows, Sums{nullptr, false, d_accum, nullptr}, d_rgb, d_shade, stream);
 }
 
 int rtx_scene_light_walk_seeded(const RtxScene *scene, const RtxLight *light, uint64_t seed, uint32_t n_pairs, uint32_t *out_order,

@@ -1379,6 +1379,33 @@ class Scene:
     def _seeds(seeds):
         return np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
 
+    def _mean_call(self, name, device, view, light, flags, seeds, n_pairs, rule=None, tail=(), want=None):
+        """One call of the mean family: the argument head all of them share (view, light, flags, seeds, n_frames, n_pairs;
+        `rule`: the adaptive calls' RtxAdaptRule behind it), then `tail`, a device-resident call's pointers (None or 0:
+        NULL), or with want = (shade, tiles, stats) a host call's outputs, made here and answered as (out, shade, tiles,
+        stats) without the unwanted ones, `out` alone when nothing else is wanted."""
+        sd = self._seeds(seeds)
+        args = [self._h, device, C.byref(view), C.byref(light) if light is not None else None, flags, sd.ctypes.data_as(u64p),
+                len(sd), int(n_pairs)]
+        if rule is not None:
+            args.append(C.byref(AdaptRule(int(rule[0]), float(rule[1]))))
+        args += [C.c_void_p(p) if p else None for p in tail]
+        if want is not None:
+            want_shade, want_tiles, stats = want
+            out = np.zeros((view.ny, view.nx, 3), np.uint8)
+            shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
+            tiles = np.zeros(tile_grid(view.nx, view.ny)[::-1], TILE_STATE_DTYPE) if want_tiles else None
+            st = Stats()
+            args += [out.ctypes.data, shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None]
+            if rule is not None:
+                args.append(tiles.ctypes.data_as(C.POINTER(TileState)) if want_tiles else None)
+            args.append(C.byref(st) if stats else None)
+        _check(getattr(_lib, name)(*args), name)
+        if want is None:
+            return None
+        res = tuple(x for x in (out, shade, tiles) if x is not None) + ((st.asdict(),) if stats else ())
+        return res if len(res) > 1 else out
+
     def render_view_mean(self, view, seeds, n_pairs=NB_RAND_SAMPLE, device=0, light=None, posed=False, stats=False,
                          want_shade=False, rows=False):
         """The mean of len(seeds) frames of the view, frame k under the table gen_samples(seeds[k], n_pairs), summed in
@@ -1386,29 +1413,15 @@ class Scene:
         (PIXEL_SHADE_DTYPE [ny, nx]: the mean's linear colour, its bytes, in how many frames the pixel had a hit), stats
         the statistics summed over the frames, last.  light: an RtxLight, None the scene's; posed: the device's pose.
         rows: through the render pipeline (rtx_render_view_rows_mean: full width only, the same words)."""
-        sd = self._seeds(seeds)
-        call = _lib.rtx_render_view_rows_mean if rows else _lib.rtx_render_view_mean
-        out = np.zeros((view.ny, view.nx, 3), np.uint8)
-        shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
-        st = Stats()
-        _check(call(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                    MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), out.ctypes.data,
-                    shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
-                    C.byref(st) if stats else None), "rtx_render_view_rows_mean" if rows else "rtx_render_view_mean")
-        res = (out,) + ((shade,) if want_shade else ()) + ((st.asdict(),) if stats else ())
-        return res if len(res) > 1 else out
+        return self._mean_call("rtx_render_view_rows_mean" if rows else "rtx_render_view_mean", device, view, light,
+                               MEAN_POSED if posed else 0, seeds, n_pairs, want=(want_shade, False, stats))
 
     def render_view_mean_device(self, device, view, seeds, n_pairs, d_accum_ptr, d_rgb_ptr=None, d_shade_ptr=None, stream=None,
                                 light=None, posed=False, rows=False):
         """Asynchronous: the same chain on `stream` into device buffers the caller owns — ny*nx x 16 bytes of accumulator
         (16-byte aligned), optionally ny*nx*3 bytes (any alignment) and ny*nx x 16 bytes of records."""
-        sd = self._seeds(seeds)
-        call = _lib.rtx_render_view_rows_mean_device if rows else _lib.rtx_render_view_mean_device      # (rows: through the pipeline)
-        _check(call(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                    MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs),
-                    C.c_void_p(d_accum_ptr), C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
-                    C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
-                    C.c_void_p(stream) if stream else None), "rtx_render_view_rows_mean_device" if rows else "rtx_render_view_mean_device")
+        self._mean_call("rtx_render_view_rows_mean_device" if rows else "rtx_render_view_mean_device",      # (rows: through the pipeline)
+                        device, view, light, MEAN_POSED if posed else 0, seeds, n_pairs, tail=(d_accum_ptr, d_rgb_ptr, d_shade_ptr, stream))
 
     def accum_add_device(self, device, n, d_shade_ptr, d_accum_ptr, first, stream=None):
         """Asynchronous: adds n RtxPixelShade records — of any call that writes them — into n accumulator records
@@ -1431,19 +1444,8 @@ class Scene:
         receiving frames once it has rule[0] = min_frames of them and its noise estimate is <= rule[1] = max_variance
         -> uint8 [ny, nx, 3]; want_shade adds the records, want_tiles the tile states (TILE_STATE_DTYPE [tiles_y, tiles_x]:
         the frames each tile received and its estimate), stats the statistics summed over the rendered tile-frames, last."""
-        sd = self._seeds(seeds)
-        r = AdaptRule(int(rule[0]), float(rule[1]))
-        out = np.zeros((view.ny, view.nx, 3), np.uint8)
-        shade = np.zeros((view.ny, view.nx), PIXEL_SHADE_DTYPE) if want_shade else None
-        tiles = np.zeros(tile_grid(view.nx, view.ny)[::-1], TILE_STATE_DTYPE) if want_tiles else None
-        st = Stats()
-        _check(_lib.rtx_render_view_adaptive(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                                             MEAN_POSED if posed else 0, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), C.byref(r),
-                                             out.ctypes.data, shade.ctypes.data_as(C.POINTER(PixelShade)) if want_shade else None,
-                                             tiles.ctypes.data_as(C.POINTER(TileState)) if want_tiles else None,
-                                             C.byref(st) if stats else None), "rtx_render_view_adaptive")
-        res = (out,) + ((shade,) if want_shade else ()) + ((tiles,) if want_tiles else ()) + ((st.asdict(),) if stats else ())
-        return res if len(res) > 1 else out
+        return self._mean_call("rtx_render_view_adaptive", device, view, light, MEAN_POSED if posed else 0, seeds, n_pairs, rule=rule,
+                               want=(want_shade, want_tiles, stats))
 
     def render_view_adaptive_device(self, device, view, seeds, rule, n_pairs, d_moments_ptr, d_tiles_ptr, d_rgb_ptr=None,
                                     d_shade_ptr=None, stream=None, light=None, posed=False, resume=False):
@@ -1451,15 +1453,9 @@ class Scene:
         aligned), tiles_y*tiles_x x 8 bytes of tile states (8-byte aligned), optionally ny*nx*3 bytes (any alignment) and
         ny*nx x 16 bytes of records.  resume (RTX_ADAPT_CONTINUE): the moments and the states are an earlier call's, the
         seeds the next frames'."""
-        sd = self._seeds(seeds)
-        r = AdaptRule(int(rule[0]), float(rule[1]))
         flags = (MEAN_POSED if posed else 0) | (ADAPT_CONTINUE if resume else 0)
-        _check(_lib.rtx_render_view_adaptive_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
-                                                    flags, sd.ctypes.data_as(u64p), len(sd), int(n_pairs), C.byref(r),
-                                                    C.c_void_p(d_moments_ptr), C.c_void_p(d_tiles_ptr),
-                                                    C.c_void_p(d_rgb_ptr) if d_rgb_ptr else None,
-                                                    C.c_void_p(d_shade_ptr) if d_shade_ptr else None,
-                                                    C.c_void_p(stream) if stream else None), "rtx_render_view_adaptive_device")
+        self._mean_call("rtx_render_view_adaptive_device", device, view, light, flags, seeds, n_pairs, rule=rule,
+                        tail=(d_moments_ptr, d_tiles_ptr, d_rgb_ptr, d_shade_ptr, stream))
 
     def moment_add_device(self, device, nx, ny, d_shade_ptr, d_moments_ptr, d_tiles_ptr, first, rule=None, stream=None):
         """Asynchronous: adds the nx x ny RtxPixelShade records of a rectangle — of any call that writes them — into its moment

@@ -1,6 +1,7 @@
 """GPU parity of rtx_render_view_rows_mean (and its device-resident variant): the mean of N seeded frames through the render
 pipeline against accum_sets' expected records (the oracle's frames, added in numpy) and against rtx_render_view_mean on the
-same arguments — linear words, bytes, hits and the accumulator, word for word — and the scene untouched afterwards."""
+same arguments — linear words, bytes, hits and the accumulator, word for word — the scene untouched afterwards, and the
+three families of mean calls back to back on the scratch they share."""
 import importlib
 
 import numpy as np
@@ -10,7 +11,7 @@ import accum_sets as ac
 import light_sets as ls
 import prims_sets as pm
 import resample_sets as rs
-from query_sets import bits
+from query_sets import NO_HIT, bits
 
 pytestmark = pytest.mark.gpu
 GUARD = 64
@@ -170,3 +171,58 @@ def test_two_device_resident_rows_means_back_to_back_and_a_host_one_behind_them(
     for (d_acc, d_shade, d_rgb), e in zip(bufs, (e7, e3)):
         check_mean(d_rgb.get().reshape(h, w, 3), d_shade.get(rtx.PIXEL_SHADE_DTYPE).reshape(h, w), e, "device-resident, side stream")
         assert ac.same_accum(d_acc.get(rtx.ACCUM_PIXEL_DTYPE).reshape(h, w), e["sum"], e["hit_frames"])
+
+
+def expected_in(orc, frame, n_pairs, n):
+    """accum_sets.expected's statement for the bunny in another frame under tables of another length: the oracle scene created
+    with that frame (the same field of view) and the table gen_samples(SEEDS[k], n_pairs), frame by frame through the numpy
+    statements"""
+    w, h = frame
+    acc = None
+    for seed in ac.SEEDS[:n]:
+        osc = orc.default_scene(["bunny.obj"], w, h, orc.gen_samples(seed, n_pairs), nb_light_sample=ac.BUNNY_LIGHT_SAMPLES, distance=6.0 * w)
+        _, _, tri, lin = osc.render_rows(mode=orc.MODE_BVH, nthreads=4, want_tri=True, want_lin=True)
+        osc.close()
+        acc = ac.np_add(lin, tri != NO_HIT, acc)
+    linear = ac.np_divide(acc[0], n)
+    return dict(linear=linear, rgb8=ac.oracle_bytes(orc, linear), hits=np.minimum(acc[1], 255).astype(np.uint8), sum=acc[0], hit_frames=acc[1])
+
+
+def test_the_three_mean_calls_share_a_scratch_that_grows_and_is_reused_smaller(rtx, torch, orc):
+    """All three go through one path and share the scratch table and records.  On one side stream, nothing waited for: a
+    view-kernel mean, a pipeline mean in a larger frame under a longer table (both scratch buffers grow), an adaptive mean
+    under a rule that never stops and the view-kernel mean again, both back in the small frame under the short table; behind
+    them a host pipeline mean.  The scene's own table (1000 pairs) lies between the two lengths."""
+    n, small, large = 3, ((16, 12), 701), ((24, 16), 5003)
+    seeds = ac.SEEDS[:n]
+    e = {shape: expected_in(orc, *shape, n) for shape in (small, large)}
+    for x in e.values():
+        assert (x["hits"] == 0).any() and (x["hits"] == n).any()
+    side = torch.cuda.Stream()
+    s = side.cuda_stream
+    with ac.open_bunny(rtx, ac.table(orc, 0)[:1000]) as scene:
+        view = {shape: rtx.Scene.view(*shape[0], rtx.DEFAULT_EYE, rtx.DEFAULT_LOOK_AT, distance=6.0 * shape[0][0]) for shape in (small, large)}
+
+        def buffers(shape, state_bytes):
+            w, h = shape[0]
+            return Guarded(torch, state_bytes * w * h), Guarded(torch, 16 * w * h), Guarded(torch, 3 * w * h, 1)
+
+        calls = [("view", small, buffers(small, 16)), ("rows", large, buffers(large, 16)), ("adaptive", small, buffers(small, 32)),
+                 ("view", small, buffers(small, 16))]
+        d_tiles = Guarded(torch, 8 * 2 * 2)
+        torch.cuda.synchronize()
+        for how, shape, (d_state, d_shade, d_rgb) in calls:
+            if how == "adaptive":
+                scene.render_view_adaptive_device(0, view[shape], seeds, (n, 0.0), shape[1], d_state.ptr, d_tiles.ptr, d_rgb.ptr, d_shade.ptr, s)
+            else:
+                scene.render_view_mean_device(0, view[shape], seeds, shape[1], d_state.ptr, d_rgb.ptr, d_shade.ptr, s, rows=how == "rows")
+        rgb, shade = scene.render_view_mean(view[small], seeds, small[1], want_shade=True, rows=True)
+        side.synchronize()
+        check_mean(rgb, shade, e[small], "host pipeline mean behind the four")
+        for k, (how, shape, (d_state, d_shade, d_rgb)) in enumerate(calls):
+            w, h = shape[0]
+            check_mean(d_rgb.get().reshape(h, w, 3), d_shade.get(rtx.PIXEL_SHADE_DTYPE).reshape(h, w), e[shape], "call %d, %s" % (k, how))
+            state = d_state.get(rtx.MOMENT_PIXEL_DTYPE if how == "adaptive" else rtx.ACCUM_PIXEL_DTYPE).reshape(h, w)
+            assert ac.same_accum(state, e[shape]["sum"], e[shape]["hit_frames"]), "call %d, %s: the sums" % (k, how)
+            if how == "adaptive":
+                assert (state["frames"] == n).all() and (d_tiles.get(rtx.TILE_STATE_DTYPE)["frames"] == n).all()

@@ -17,6 +17,11 @@ batch; call times are the host's clock around the calls, the stream waited for.
   (4) --parent DIR [--parent2 DIR] --bench: bench.py --gpus 1 --steps 20 --warmup 3 of the builds under DIR (the parent
       commit's tree, built; a second copy of it shows the spread of two identical builds) and of this one, alternated
       --rounds times (bench.py does not reach the new code).
+  (5) --mean-path --parent DIR --parent2 DIR [--bench]: in place of (1) to (3), the host-side cost of every mean call —
+      through the view kernel, through the pipeline, adaptive under a rule that never stops; device-resident and host —
+      at 1, 4, 16 and 64 frames, of the three builds (each tree's own binding and library, a child process each),
+      alternated --rounds times; per case, whether this build's median is as near a parent's as the two parents' are to
+      each other.
 
 --repeats interleaved rounds after --warmup rounds; reported are the minimum, the median and the spread (max - min) / min.
 One JSON document on stdout, and in --out.
@@ -191,8 +196,74 @@ def kernels_doc(args, resolve_only):
     return doc
 
 
+MEAN_CALL_REPEATS = {1: 41, 4: 15, 16: 5, 64: 3}
+
+
+def mean_calls(root):
+    """(5)'s child: the build under `root` (its binding and its library), every mean call at every frame count, the host's
+    clock around the call and the wait for the stream; the samples of every case"""
+    import torch  # before librtx.so: one HIP runtime per process (tests/conftest.py)
+    sys.path.insert(0, root)
+    rtx = importlib.import_module("ray-tracer-rust_amd")
+    tris, rgb = rtx.default_primitives([os.path.join(root, "models", "big_bunny.obj")])
+    sc = rtx.Scene(W, H, tris, rgb, rtx.gen_samples())
+    sc.upload(0)
+    view, n, n_pairs = sc.own_view(), W * H, sc.n_samples()
+    stream = torch.cuda.Stream(device="cuda:0")
+    s = stream.cuda_stream
+    state, tiles, d_rgb = (torch.empty(b, dtype=torch.uint8, device="cuda:0").data_ptr() for b in (32 * n, 8 * ((W + 7) // 8) * ((H + 7) // 8), 3 * n))
+    calls = {
+        "view_mean_device": lambda sd: sc.render_view_mean_device(0, view, sd, n_pairs, state, d_rgb, None, s),
+        "rows_mean_device": lambda sd: sc.render_view_mean_device(0, view, sd, n_pairs, state, d_rgb, None, s, rows=True),
+        "never_stops_device": lambda sd: sc.render_view_adaptive_device(0, view, sd, (len(sd), 0.0), n_pairs, state, tiles, d_rgb, None, s),
+        "view_mean_host": lambda sd: sc.render_view_mean(view, sd, n_pairs),
+        "rows_mean_host": lambda sd: sc.render_view_mean(view, sd, n_pairs, rows=True),
+        "never_stops_host": lambda sd: sc.render_view_adaptive(view, sd, (len(sd), 0.0), n_pairs),
+    }
+    ms = {}
+    for count in FRAME_COUNTS:
+        seeds = [1000 + k for k in range(count)]
+        for i in range(1 + MEAN_CALL_REPEATS[count]):
+            for name in list(calls)[::-1] if i % 2 else list(calls):
+                stream.synchronize()
+                t0 = time.perf_counter()
+                calls[name](seeds)
+                stream.synchronize()
+                if i >= 1:
+                    ms.setdefault("%s_%d_frames" % (name, count), []).append(1e3 * (time.perf_counter() - t0))
+    sc.close()
+    return {"lib": rtx.rtx.LIB_PATH, "ms": ms}
+
+
+def mean_path(args, roots):
+    """(5): mean_calls of every build in a child process each, --rounds times, who goes first rotating; per case the pooled
+    samples' summary per build and whether this build's median is as near a parent's as the two parents' are to each other"""
+    pooled = {who: {} for who, _ in roots}
+    for k in range(args.rounds):
+        for who, root in roots[k % len(roots):] + roots[:k % len(roots)]:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--mean-calls", root], capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                raise SystemExit("child for %s failed (%d):\n%s" % (who, r.returncode, (r.stdout + r.stderr)[-3000:]))
+            child = json.loads(r.stdout.splitlines()[-1])
+            assert child["lib"].startswith(root + os.sep), child["lib"]
+            for case, v in child["ms"].items():
+                pooled[who].setdefault(case, []).extend(v)
+            print("round %d, %s: done" % (k, who), file=sys.stderr, flush=True)
+    out = {}
+    for case in pooled["this"]:
+        med = {who: float(np.median(v[case])) for who, v in pooled.items()}
+        out[case] = {who: summary(v[case]) for who, v in pooled.items()}
+        if "parent2" in med:
+            between = abs(med["parent"] - med["parent2"])
+            away = min(abs(med["this"] - med["parent"]), abs(med["this"] - med["parent2"]))
+            out[case].update(parents_apart_ms=round(between, 5), this_from_nearer_parent_ms=round(away, 5), within=bool(away <= between))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--mean-calls", default=None, metavar="ROOT", help="(5)'s child: the mean calls of the build under ROOT")
+    ap.add_argument("--mean-path", action="store_true", help="(5) and, with --bench, (4) alone")
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=20)
@@ -207,8 +278,31 @@ def main():
     if args.resolve_only:
         print(json.dumps(kernels_doc(args, True)))
         return
+    if args.mean_calls:
+        print(json.dumps(mean_calls(os.path.abspath(args.mean_calls))))
+        return
+    roots = [(who, os.path.abspath(root)) for who, root in (("parent", args.parent), ("this", HERE), ("parent2", args.parent2)) if root]
     doc = {"frame": [W, H], "repeats": args.repeats, "warmup": args.warmup, "batch": args.batch}
-    if args.other_lib:                                                    # before this process opens the device
+    if args.mean_path:
+        doc = {"frame": [W, H], "rounds": args.rounds, "samples_per_round": MEAN_CALL_REPEATS, "mean_calls": mean_path(args, roots)}
+    else:
+        measure_this_build(args, doc)
+    if args.parent and args.bench:                                        # (4); who goes first alternates too
+        lines = {who: [] for who, _ in roots}
+        for k in range(args.rounds):
+            for who, root in roots[::-1] if k % 2 else roots:
+                lines[who].append(bench_line(root))
+        doc["bench"] = {"command": "bench.py --gpus 1 --steps 20 --warmup 3", **lines}
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+def measure_this_build(args, doc):
+    """(1), (2), (3)"""
+    if args.other_lib:                                                   # before this process opens the device
         forms = {"this_build": None, "other_form": os.path.abspath(args.other_lib)}
         doc["resolve_forms"] = {who: [] for who in forms}
         for k in range(args.rounds):
@@ -240,20 +334,6 @@ def main():
         doc["differences_of_medians"]["parents_way_over_mean_device_%d_frames" % count] = round(
             med["parents_way_%d_frames_ms" % count] / med["mean_device_%d_frames_ms" % count], 2)
     b.scene.close()
-    if args.parent and args.bench:                                        # (4); who goes first alternates too
-        roots = [("parent", os.path.abspath(args.parent)), ("this", HERE)]
-        if args.parent2:
-            roots.append(("parent2", os.path.abspath(args.parent2)))
-        lines = {who: [] for who, _ in roots}
-        for k in range(args.rounds):
-            for who, root in roots[::-1] if k % 2 else roots:
-                lines[who].append(bench_line(root))
-        doc["bench"] = {"command": "bench.py --gpus 1 --steps 20 --warmup 3", **lines}
-    text = json.dumps(doc, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
 
 
 if __name__ == "__main__":
