@@ -18,6 +18,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rtx.h"
@@ -985,11 +986,44 @@ const rtx::RebuildTables &rebuild_tables_of(RtxScene *scene)
     return scene->rebuild_tables;
 }
 
-// The pose's buffers, library-owned per device and grow-only, and the tables' upload with the first pose.  Growing a buffer
-// waits for the device first, since an earlier launch may still read it.  n_ref: records of the reference tree's stream that
-// goes beside the pose (host variant), or 0.  rebuilt: the node records are sized for the rebuilt stream, and the sort's
-// buffers and the rebuilt stream's tables come with them (uploaded with the first rebuilt pose).  Caller holds the slot's
-// lock and has the device current and the scene uploaded.
+// What a pose states (the ten rtx_scene_pose* entry points), as host pointers for a host call and as device pointers for a
+// device-resident one: the vertices (NULL: the scene has no triangle, or the device makes them), the tie ranks (NULL:
+// none), what it states beside the vertices, the moves the device makes the vertices and the spheres from (n_moves == 0:
+// none), the skin that blends them (NULL: every primitive follows its group's move) and whether the tree is rebuilt.
+// spheres: the pose states spheres — ov.spheres, or the device's own output for a moved pose of a scene that has some.
+struct PoseCall {
+    const float *v = nullptr;
+    const uint32_t *tie_rank = nullptr;
+    rtx::PrimsOverlay ov;
+    rtx::PoseMoves moves;
+    const rtx::Skin *skin = nullptr;
+    bool rebuilt = false;
+    bool spheres = false;
+    bool moved() const { return moves.n_moves != 0u; }
+    bool overlaid() const { return spheres || ov.rgb || ov.sphere_rgb; }      // the overlay kernel runs, its buffers are used
+};
+
+// a pose that states its vertices alone
+PoseCall vertices_alone(const float *v, const uint32_t *tie_rank, bool rebuilt) { return {v, tie_rank, {}, {}, nullptr, rebuilt, false}; }
+
+// The one rule for growing the pose's buffers, library-owned per device and grow-only: when one of `list` is too small the
+// pose is marked invalid, the device is waited for — an earlier launch may still read what is freed — and all are reserved;
+// otherwise nothing happens.  moved_list: the list is the moved pose's own, and what the move kernel last wrote
+// (rtx_debug_moved_prims) goes with it; no other growth takes that away.
+int grow_pose(DeviceState &st, std::initializer_list<Sized> list, bool moved_list)
+{
+    if (std::all_of(list.begin(), list.end(), [](const Sized &s) { return s.buffer.capacity() >= s.bytes; })) return RTX_OK;
+    st.pose.valid = false;
+    if (moved_list) st.pose.f.ran = false;
+    RTX_HIP(hipDeviceSynchronize());
+    return reserve_all(list);
+}
+
+// Every pose's buffers (grow_pose), and the tables' upload with the first pose.  host_copies: room for the host variant's
+// copies of the vertices and the ranks.  n_ref: records of the reference tree's stream that goes beside the pose (host
+// variant), or 0.  rebuilt: the node records are sized for the rebuilt stream, and the sort's buffers and the rebuilt
+// stream's tables come with them (uploaded with the first rebuilt pose).  Caller holds the slot's lock and has the device
+// current and the scene uploaded, here and in the three below.
 int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_ref, bool rebuilt)
 {
     const rtx::PreparedScene &p = scene->prep;
@@ -1000,11 +1034,6 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
         return RTX_ERR_OOM;
     }
     const size_t n_prims = p.tris.size(), n_nodes = bt ? bt->nodes.size() : p.nodes.size();
-    const size_t tris = (n_prims + 1u) * sizeof(rtx::TriRec), shade = std::max<size_t>(n_prims * sizeof(rtx::ShadeRec), 16u);
-    const size_t nodes = (n_nodes + 1u) * sizeof(rtx::NodeDev), ref = n_ref ? (n_ref + 1u) * sizeof(rtx::NodeDev) : 0u;
-    const size_t v = host_copies ? std::max<size_t>(static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float), 16u) : 0u;
-    const size_t rank = host_copies ? std::max<size_t>(n_prims * sizeof(uint32_t), 16u) : 0u;
-    const size_t planes = static_cast<size_t>(p.n_global) * sizeof(rtx::TriRec);      // (no global triangle: no buffer)
     const size_t n_tree = n_prims - p.n_global;
     const size_t keys = rebuilt ? std::max<size_t>(n_tree * sizeof(uint64_t), 16u) : 0u;
     const size_t index = rebuilt ? std::max<size_t>(n_tree * sizeof(uint32_t), 16u) : 0u;
@@ -1015,16 +1044,15 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
     }
     auto &q = st.pose;
     DeviceGeometry &g = q.geo;
-    if (g.tris.capacity() < tris || g.shade.capacity() < shade || g.nodes.capacity() < nodes || g.ref_nodes.capacity() < ref ||
-        q.v.capacity() < v || q.rank.capacity() < rank || g.planes.capacity() < planes || q.b.keys.capacity() < keys ||
-        q.b.keys_sorted.capacity() < keys || q.b.index.capacity() < index || q.b.perm.capacity() < index ||
-        q.b.temp.capacity() < temp) {
-        q.valid = false;
-        RTX_HIP(hipDeviceSynchronize());
-        RTX_TRY(reserve_all({{g.tris, tris}, {g.shade, shade}, {g.nodes, nodes}, {g.ref_nodes, ref}, {q.v, v}, {q.rank, rank},
-                             {g.planes, planes}, {q.b.keys, keys}, {q.b.keys_sorted, keys}, {q.b.index, index},
-                             {q.b.perm, index}, {q.b.temp, temp}}));
-    }
+    RTX_TRY(grow_pose(st, {{g.tris, (n_prims + 1u) * sizeof(rtx::TriRec)},
+                           {g.shade, std::max<size_t>(n_prims * sizeof(rtx::ShadeRec), 16u)},
+                           {g.nodes, (n_nodes + 1u) * sizeof(rtx::NodeDev)},
+                           {g.ref_nodes, n_ref ? (n_ref + 1u) * sizeof(rtx::NodeDev) : 0u},
+                           {q.v, host_copies ? std::max<size_t>(static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float), 16u) : 0u},
+                           {q.rank, host_copies ? std::max<size_t>(n_prims * sizeof(uint32_t), 16u) : 0u},
+                           {g.planes, static_cast<size_t>(p.n_global) * sizeof(rtx::TriRec)},      // (no global triangle: no buffer)
+                           {q.b.keys, keys}, {q.b.keys_sorted, keys}, {q.b.index, index}, {q.b.perm, index}, {q.b.temp, temp}},
+                      false));
     try {
         if (!q.tables) {
             const rtx::PoseTables &t = pose_tables_of(scene);
@@ -1045,26 +1073,20 @@ int reserve_pose(RtxScene *scene, DeviceState &st, bool host_copies, size_t n_re
     return RTX_OK;
 }
 
-// The overlay's buffers of a pose that states spheres or colours (rtx_scene_pose_prims), beside reserve_pose's and by its
-// rule: library-owned per device, grow-only, growing waits for the device; sphere_of is uploaded with the first such pose.
-// host_copies: room for the host variant's copies of the arrays `ov` gives.  Caller holds the slot's lock and has the
-// device current and the scene uploaded.
-int reserve_prims(RtxScene *scene, DeviceState &st, bool host_copies, const rtx::PrimsOverlay &ov)
+// The overlay's buffers of a pose that states spheres or colours, beside reserve_pose's: the overlay's records — the
+// primitive records only where spheres are stated — and, host_copies, room for the host variant's copies of the arrays the
+// call gives (the spheres' also where the device makes them); sphere_of is uploaded with the first such pose.
+int reserve_prims(RtxScene *scene, DeviceState &st, bool host_copies, const PoseCall &c)
 {
     const rtx::PreparedScene &p = scene->prep;
     const size_t n_prims = p.tris.size(), n_spheres = p.n_spheres, n_triangles = posed_triangles(scene);
-    const size_t tris = ov.spheres ? std::max<size_t>(n_prims * sizeof(rtx::TriRec), 16u) : 0u;
-    const size_t shade = std::max<size_t>(n_prims * sizeof(rtx::ShadeRec), 16u);
-    const size_t spheres = host_copies && ov.spheres ? std::max<size_t>(n_spheres * 4u * sizeof(float), 16u) : 0u;
-    const size_t rgb = host_copies && ov.rgb ? std::max<size_t>(n_triangles * 3u * sizeof(float), 16u) : 0u;
-    const size_t sphere_rgb = host_copies && ov.sphere_rgb ? std::max<size_t>(n_spheres * 3u * sizeof(float), 16u) : 0u;
     auto &m = st.pose.m;
-    if (m.tris.capacity() < tris || m.shade.capacity() < shade || m.spheres.capacity() < spheres || m.rgb.capacity() < rgb ||
-        m.sphere_rgb.capacity() < sphere_rgb) {
-        st.pose.valid = false;
-        RTX_HIP(hipDeviceSynchronize());
-        RTX_TRY(reserve_all({{m.tris, tris}, {m.shade, shade}, {m.spheres, spheres}, {m.rgb, rgb}, {m.sphere_rgb, sphere_rgb}}));
-    }
+    RTX_TRY(grow_pose(st, {{m.tris, c.spheres ? std::max<size_t>(n_prims * sizeof(rtx::TriRec), 16u) : 0u},
+                           {m.shade, std::max<size_t>(n_prims * sizeof(rtx::ShadeRec), 16u)},
+                           {m.spheres, host_copies && c.spheres ? std::max<size_t>(n_spheres * 4u * sizeof(float), 16u) : 0u},
+                           {m.rgb, host_copies && c.ov.rgb ? std::max<size_t>(n_triangles * 3u * sizeof(float), 16u) : 0u},
+                           {m.sphere_rgb, host_copies && c.ov.sphere_rgb ? std::max<size_t>(n_spheres * 3u * sizeof(float), 16u) : 0u}},
+                      false));
     try {
         if (!m.tables) {
             RTX_TRY(upload_vec(m.sphere_of, pose_tables_of(scene).sphere_of));
@@ -1076,25 +1098,18 @@ int reserve_prims(RtxScene *scene, DeviceState &st, bool host_copies, const rtx:
     return RTX_OK;
 }
 
-// The buffers of a moved pose (rtx_scene_pose_moved), beside reserve_pose's and by its rule: the rest geometry, uploaded with
-// the first such pose, the two arrays the move kernel writes (pose.v, pose.m.spheres) and, host_copies, room for the host
-// variant's copies of what `mv` gives.  Caller holds the slot's lock and has the device current and the scene uploaded.
+// The buffers of a moved pose, beside reserve_pose's: the two arrays the move kernel writes (pose.v, pose.m.spheres) and,
+// host_copies, room for the host variant's copies of what `mv` gives; the rest geometry is uploaded with the first such pose.
 int reserve_moves(RtxScene *scene, DeviceState &st, bool host_copies, const rtx::PoseMoves &mv)
 {
     const rtx::PreparedScene &p = scene->prep;
-    const size_t v = std::max<size_t>(p.rest_v0v1v2.size() * sizeof(float), 16u);
-    const size_t spheres = std::max<size_t>(p.rest_spheres.size() * sizeof(float), 16u);
-    const size_t moves = host_copies ? static_cast<size_t>(mv.n_moves) * 12u * sizeof(float) : 0u;
-    const size_t group = host_copies && mv.group ? std::max<size_t>(p.tris.size() * sizeof(uint32_t), 16u) : 0u;
-    const size_t scale = host_copies && mv.radius_scale ? static_cast<size_t>(mv.n_moves) * sizeof(float) : 0u;
     auto &q = st.pose;
-    if (q.v.capacity() < v || q.m.spheres.capacity() < spheres || q.f.moves.capacity() < moves || q.f.group.capacity() < group ||
-        q.f.radius_scale.capacity() < scale) {
-        q.valid = false;
-        q.f.ran = false;
-        RTX_HIP(hipDeviceSynchronize());
-        RTX_TRY(reserve_all({{q.v, v}, {q.m.spheres, spheres}, {q.f.moves, moves}, {q.f.group, group}, {q.f.radius_scale, scale}}));
-    }
+    RTX_TRY(grow_pose(st, {{q.v, std::max<size_t>(p.rest_v0v1v2.size() * sizeof(float), 16u)},
+                           {q.m.spheres, std::max<size_t>(p.rest_spheres.size() * sizeof(float), 16u)},
+                           {q.f.moves, host_copies ? static_cast<size_t>(mv.n_moves) * 12u * sizeof(float) : 0u},
+                           {q.f.group, host_copies && mv.group ? std::max<size_t>(p.tris.size() * sizeof(uint32_t), 16u) : 0u},
+                           {q.f.radius_scale, host_copies && mv.radius_scale ? static_cast<size_t>(mv.n_moves) * sizeof(float) : 0u}},
+                      true));
     if (!q.f.tables) {
         RTX_TRY(upload_vec(q.f.rest_v, p.rest_v0v1v2));
         RTX_TRY(upload_vec(q.f.rest_spheres, p.rest_spheres));
@@ -1105,9 +1120,9 @@ int reserve_moves(RtxScene *scene, DeviceState &st, bool host_copies, const rtx:
     return RTX_OK;
 }
 
-// This device's copy of the scene's skin (rtx_scene_pose_skinned), after reserve_moves and by its rule: library-owned,
-// grow-only, uploaded when the scene's generation is not the copy's.  A device-resident skinned pose may still read the
-// copy a re-bind replaces, so the upload waits for the device; it happens once per bind.  No pose is touched.
+// This device's copy of the scene's skin (rtx_scene_pose_skinned), after reserve_moves: library-owned, grow-only, uploaded
+// when the scene's generation is not the copy's.  A device-resident skinned pose may still read the copy a re-bind
+// replaces, so the upload waits for the device; it happens once per bind.  No pose is touched.
 int reserve_skin(RtxScene *scene, DeviceState &st)
 {
     const rtx::Skin &k = scene->skin;
@@ -1122,23 +1137,19 @@ int reserve_skin(RtxScene *scene, DeviceState &st)
     return RTX_OK;
 }
 
-// the pose kernels on `stream`, after reserve_pose: d_pose and d_rank (or NULL) are the caller's arrays or the library's
-// copies of them; ov_in: the sphere and colour arrays of a pose that states them (after reserve_prims), in the same sense:
-// the overlay kernel then runs ahead of the others, which read its records where they read the uploaded ones — the primitive
-// records only with spheres given; nothing given: no launch, no buffer of the overlay's touched.  The records behind the
-// last one (upload_all pads the scene's with the same) are zeroed on the same stream.
-// rebuilt: the rebuild kernels and the sort make the records in sorted order, and the refit runs alone over the rebuilt
-// stream's tables; the geometry's node count becomes that stream's.
-// The plane kernel follows them over the posed global triangles (none: no launch).  This is the only writer of the pose's
-// nodes, and it takes the aimed stream's validity away before anything is launched (AimedStream).
-// d_moves: a moved pose (after reserve_moves; its arrays on the device): the move kernel runs ahead of all of them and
-// writes pose.v and pose.m.spheres, which then stand where d_pose and d_ov.spheres stand.  skinned (after reserve_skin): the
-// skin kernel runs in the move kernel's place and writes the same two buffers.
-int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uint32_t *d_rank, const rtx::PrimsOverlay &ov_in,
-                hipStream_t stream, bool rebuilt, const rtx::PoseMoves *d_moves = nullptr, bool skinned = false)
+// The pose kernels on `stream`, after the reservations; `d` is the call over device arrays, the caller's or the library's
+// copies of them.  In this order: the move kernel, or with a skin the skin kernel, makes pose.v and pose.m.spheres, which
+// then stand for the call's vertices and spheres; the overlay kernel restates what the call states beside the vertices, and
+// the others read its records where they read the uploaded ones (nothing stated: no launch, none of its buffers touched);
+// the pose kernels refit the uploaded stream or — rebuilt — the rebuild kernels and the sort make the records in sorted
+// order and the refit runs alone over the rebuilt stream's tables, whose node count becomes the geometry's; the plane kernel
+// runs over the posed global triangles (none: no launch).  The records behind the last one (upload_all pads the scene's
+// with the same) are zeroed on the same stream.  This is the only writer of the pose's nodes, and it takes the aimed
+// stream's validity away before anything is launched (AimedStream).
+int pose_launch(RtxScene *scene, DeviceState &st, const PoseCall &d, hipStream_t stream)
 {
-    rtx::PrimsOverlay d_ov = ov_in;
     const rtx::PreparedScene &p = scene->prep;
+    const bool rebuilt = d.rebuilt;
     const uint32_t n_prims = static_cast<uint32_t>(p.tris.size());
     const uint32_t n_nodes = static_cast<uint32_t>(rebuilt ? scene->rebuild_tables.nodes.size() : p.nodes.size());   // (made: reserve_pose)
     DeviceGeometry &q = st.pose.geo;
@@ -1148,44 +1159,40 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
     st.pose.rebuilt = rebuilt;
     RTX_HIP(hipMemsetAsync(q.tris.as<rtx::TriRec>() + n_prims, 0, sizeof(rtx::TriRec), stream));
     RTX_HIP(hipMemsetAsync(q.nodes.as<rtx::NodeDev>() + n_nodes, 0, sizeof(rtx::NodeDev), stream));
-    if (d_moves && skinned) {
-        rtxk::SkinArgs k{};
-        k.rest_v = st.pose.f.rest_v.as<const float>();
-        k.rest_spheres = st.pose.f.rest_spheres.as<const float>();
-        k.bones = st.pose.k.bones.as<const uint4>();
-        k.weights = st.pose.k.weights.as<const float4>();
-        k.sphere_bone = st.pose.k.sphere_bone.as<const uint32_t>();
-        k.n_triangles = posed_triangles(scene);
-        k.n_spheres = p.n_spheres;
-        k.n_moves = d_moves->n_moves;
-        k.moves = d_moves->moves;
-        k.radius_scale = d_moves->radius_scale;
-        k.out_v = st.pose.v.as<float>();
-        k.out_spheres = st.pose.m.spheres.as<float>();
-        st.pose.f.ran = false;
-        RTX_HIP(rtxk::launch_skin(k, stream));
-        st.pose.f.ran = true;
-        d_pose = k.n_triangles ? k.out_v : nullptr;
-        d_ov.spheres = k.n_spheres ? k.out_spheres : nullptr;
-    } else if (d_moves) {
-        rtxf::MoveArgs f{};
-        f.rest_v = st.pose.f.rest_v.as<const float>();
-        f.rest_spheres = st.pose.f.rest_spheres.as<const float>();
-        f.tri_vec = st.pose.f.tri_vec.as<const uint32_t>();
-        f.sphere_vec = st.pose.f.sphere_vec.as<const uint32_t>();
-        f.n_triangles = posed_triangles(scene);
-        f.n_spheres = p.n_spheres;
-        f.n_moves = d_moves->n_moves;
-        f.moves = d_moves->moves;
-        f.group = d_moves->group;
-        f.radius_scale = d_moves->radius_scale;
-        f.out_v = st.pose.v.as<float>();
-        f.out_spheres = st.pose.m.spheres.as<float>();
-        st.pose.f.ran = false;
-        RTX_HIP(rtxf::launch_move(f, stream));
-        st.pose.f.ran = true;
-        d_pose = f.n_triangles ? f.out_v : nullptr;
-        d_ov.spheres = f.n_spheres ? f.out_spheres : nullptr;
+    const float *d_pose = d.v;
+    rtx::PrimsOverlay d_ov = d.ov;
+    if (d.moved()) {
+        auto &f = st.pose.f;
+        auto common = [&](auto &a) {
+            a.rest_v = f.rest_v.as<const float>();
+            a.rest_spheres = f.rest_spheres.as<const float>();
+            a.n_triangles = posed_triangles(scene);
+            a.n_spheres = p.n_spheres;
+            a.n_moves = d.moves.n_moves;
+            a.moves = d.moves.moves;
+            a.radius_scale = d.moves.radius_scale;
+            a.out_v = st.pose.v.as<float>();
+            a.out_spheres = st.pose.m.spheres.as<float>();
+        };
+        f.ran = false;
+        if (d.skin) {
+            rtxk::SkinArgs k{};
+            common(k);
+            k.bones = st.pose.k.bones.as<const uint4>();
+            k.weights = st.pose.k.weights.as<const float4>();
+            k.sphere_bone = st.pose.k.sphere_bone.as<const uint32_t>();
+            RTX_HIP(rtxk::launch_skin(k, stream));
+        } else {
+            rtxf::MoveArgs m{};
+            common(m);
+            m.tri_vec = f.tri_vec.as<const uint32_t>();
+            m.sphere_vec = f.sphere_vec.as<const uint32_t>();
+            m.group = d.moves.group;
+            RTX_HIP(rtxf::launch_move(m, stream));
+        }
+        f.ran = true;
+        d_pose = posed_triangles(scene) ? st.pose.v.as<const float>() : nullptr;
+        d_ov.spheres = p.n_spheres ? st.pose.m.spheres.as<const float>() : nullptr;
     }
     rtxp::PoseArgs a{};
     a.tris = st.geo.tris.as<const rtx::TriRec>();
@@ -1217,7 +1224,7 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
     a.n_long = rebuilt ? scene->rebuild_tables.n_long : scene->pose_tables.n_long;      // (made: reserve_pose)
     a.cull_delta = p.cull_delta;
     a.pose = d_pose;
-    a.rank = d_rank;
+    a.rank = d.tie_rank;
     a.out_tris = q.tris.as<rtx::TriRec>();
     a.out_shade = q.shade.as<rtx::ShadeRec>();
     a.out_nodes = q.nodes.as<rtx::NodeDev>();
@@ -1231,7 +1238,7 @@ int pose_launch(RtxScene *scene, DeviceState &st, const float *d_pose, const uin
         r.bound = p.scene_magnitude;
         r.scale = rtx::rebuild_key_scale(p.scene_magnitude);
         r.pose = d_pose;
-        r.rank = d_rank;
+        r.rank = d.tie_rank;
         r.keys = st.pose.b.keys.as<uint64_t>();
         r.keys_sorted = st.pose.b.keys_sorted.as<uint64_t>();
         r.index = st.pose.b.index.as<uint32_t>();
@@ -1821,46 +1828,52 @@ int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit
     return mark_uses(e.state(), uses_of(lit, posed), static_cast<hipStream_t>(stream));
 }
 
-// host statement of the plane kernel and of the aim kernels over a pose: global_plane_statement over the posed records of
-// the global triangles; stream_nearest_first over posed_records' node words, whose planes cull_delta has moved already
-// (a scene without a primary stream of its own: those words as they are).  Each output may be NULL.  May throw.
-void posed_pipeline_on_host(RtxScene *scene, const float *pose, const float *eye, rtx::TriRec *planes, rtx::NodeRec *aimed,
-                            const rtx::PrimsOverlay *ov = nullptr)
+// Host statement of the pose kernels for what `c` states in host arrays (the overlay's with it): posed_records, or for a
+// rebuilt pose rebuilt_records, which alone gives keys and perm.  The records are stated as the words the entry points give.
+// Each output may be NULL.  May throw.
+void records_on_host(const RtxScene *scene, const PoseCall &c, uint64_t *keys, uint32_t *perm, uint32_t *out_tris, uint32_t *out_shade,
+                     uint32_t *out_nodes)
+{
+    RtxScene *sc = const_cast<RtxScene *>(scene);      // (the tables are caches under the scene's lock)
+    const rtx::PoseTables &t = pose_tables_of(sc);
+    rtx::TriRec *tris = reinterpret_cast<rtx::TriRec *>(out_tris);
+    rtx::ShadeRec *shade = reinterpret_cast<rtx::ShadeRec *>(out_shade);
+    rtx::NodeRec *nodes = reinterpret_cast<rtx::NodeRec *>(out_nodes);
+    if (c.rebuilt) rtx::rebuilt_records(scene->prep, t, rebuild_tables_of(sc), c.v, c.tie_rank, keys, perm, tris, shade, nodes, &c.ov);
+    else rtx::posed_records(scene->prep, t, c.v, c.tie_rank, tris, shade, nodes, &c.ov);
+}
+
+// host statement of the aim kernels over `nodes`, the scene's stream or a pose's, in place: stream_nearest_first from the
+// tree proper's root; a scene without a primary stream of its own aims nothing, and the stream stays as it is
+void nearest_first_on_host(const rtx::PreparedScene &p, std::vector<rtx::NodeRec> &nodes, const float eye[3])
+{
+    if (p.primary_nodes.empty()) return;
+    std::vector<rtx::NodeRec> out;
+    rtx::stream_nearest_first(nodes, tree_root(p, nodes.size()), eye, out);
+    nodes.swap(out);
+}
+
+// host statement of the plane kernel and of the aim kernels over the pose `c` states: global_plane_statement over the posed
+// records of the global triangles; nearest_first_on_host over the pose's node words, whose planes cull_delta has moved
+// already (aimed: the uploaded stream's count of records, a rebuilt pose: the rebuilt stream's).  Each output may be NULL.
+// May throw.
+void posed_pipeline_on_host(const RtxScene *scene, const PoseCall &c, const float *eye, uint32_t *out_planes, uint32_t *aimed)
 {
     const rtx::PreparedScene &p = scene->prep;
-    const rtx::PoseTables &t = pose_tables_of(scene);
     std::vector<rtx::TriRec> tris(p.tris.size());
-    std::vector<rtx::NodeRec> nodes(aimed ? p.nodes.size() : 0u);
-    rtx::posed_records(p, t, pose, nullptr, tris.data(), nullptr, aimed ? nodes.data() : nullptr, ov);
+    std::vector<rtx::NodeRec> nodes(!aimed ? 0u : c.rebuilt ? rebuild_tables_of(const_cast<RtxScene *>(scene)).nodes.size() : p.nodes.size());
+    records_on_host(scene, c, nullptr, nullptr, reinterpret_cast<uint32_t *>(tris.data()), nullptr,
+                    aimed ? reinterpret_cast<uint32_t *>(nodes.data()) : nullptr);
+    rtx::TriRec *planes = reinterpret_cast<rtx::TriRec *>(out_planes);
     if (planes)
         for (uint32_t i = 0; i < p.n_global; ++i) rtx::global_plane_statement(tris[i], planes + i);
     if (!aimed) return;
-    if (!p.primary_nodes.empty()) {
-        std::vector<rtx::NodeRec> out;
-        rtx::stream_nearest_first(nodes, tree_root(p), eye, out);
-        nodes.swap(out);
-    }
+    nearest_first_on_host(p, nodes, eye);
     std::memcpy(aimed, nodes.data(), nodes.size() * sizeof(rtx::NodeRec));
 }
 
-// the same over a rebuilt pose: rebuilt_records' node words in rtx_scene_aimed_nodes' order (a scene that aims nothing: the
-// pose's stream as it is).  aimed: the rebuilt stream's count of records.  May throw.
-void rebuilt_aimed_on_host(RtxScene *scene, const float *pose, const float *eye, rtx::NodeRec *aimed, const rtx::PrimsOverlay *ov)
-{
-    const rtx::PreparedScene &p = scene->prep;
-    const rtx::RebuildTables &b = rebuild_tables_of(scene);
-    std::vector<rtx::NodeRec> nodes(b.nodes.size());
-    rtx::rebuilt_records(p, pose_tables_of(scene), b, pose, nullptr, nullptr, nullptr, nullptr, nullptr, nodes.data(), ov);
-    if (!p.primary_nodes.empty()) {
-        std::vector<rtx::NodeRec> out;
-        rtx::stream_nearest_first(nodes, tree_root(p, nodes.size()), eye, out);
-        nodes.swap(out);
-    }
-    std::memcpy(aimed, nodes.data(), nodes.size() * sizeof(rtx::NodeRec));
-}
-
-// host statement of the aim kernels: stream_nearest_first over the shadow stream with its planes moved as
-// nodes_in_device_order moves them (f32); a scene without a primary stream of its own: that stream as it is
+// host statement of the aim kernels: the shadow stream with its planes moved as nodes_in_device_order moves them (f32),
+// nearest first
 std::vector<rtx::NodeRec> aimed_on_host(const rtx::PreparedScene &p, const float eye[3])
 {
     std::vector<rtx::NodeRec> moved(p.nodes);
@@ -1870,10 +1883,8 @@ std::vector<rtx::NodeRec> aimed_on_host(const rtx::PreparedScene &p, const float
             n.bmin[k] = n.bmin[k] - inflate;
             n.bmax[k] = n.bmax[k] + inflate;
         }
-    if (p.primary_nodes.empty()) return moved;
-    std::vector<rtx::NodeRec> out;
-    rtx::stream_nearest_first(moved, tree_root(p), eye, out);
-    return out;
+    nearest_first_on_host(p, moved, eye);
+    return moved;
 }
 
 // The end of a read-back on the library's stream: n records of a node stream on the device (a geometry's nodes or its
@@ -1898,124 +1909,167 @@ int read_back_nodes(const DeviceState &st, const void *d_nodes, size_t n, uint32
     return RTX_OK;
 }
 
+// ---- what a pose call is: one maker per family, each with all of that family's refusals in the order they apply --------
+// host: the pointers are the host's, and reference_tree and the range rules apply; otherwise they are the device's, and the
+// 4-byte alignment applies.  The flag word and the struct are looked at first, as every entry point did.
+
+bool pose_head_ok(const RtxScene *scene, const void *in, uint32_t flags) { return scene && in && !(flags & ~RTX_POSE_REBUILT); }
+
+// The refusals a maker ends with, over the arrays the call states itself: host form, pose_in_range and spheres_in_range;
+// device form, every pointer of the call a multiple of 4.  (The device form looked at the moves' three pointers in a second
+// condition with the same answer: one condition here, nothing to observe.)
+int stated_arrays_ok(const RtxScene *scene, const PoseCall &c, bool host)
+{
+    if (host) {
+        if (c.v && !rtx::pose_in_range(scene->prep, c.v)) return RTX_ERR_UNSUPPORTED;
+        if (c.ov.spheres && !rtx::spheres_in_range(scene->prep, c.ov.spheres)) return RTX_ERR_UNSUPPORTED;
+        return RTX_OK;
+    }
+    auto low_bits = [](auto... ptr) { return (reinterpret_cast<uintptr_t>(ptr) | ...); };
+    return (low_bits(c.v, c.tie_rank, c.ov.spheres, c.ov.rgb, c.ov.sphere_rgb, c.moves.moves, c.moves.group, c.moves.radius_scale) & 3u)
+               ? RTX_ERR_BAD_ARG : RTX_OK;
+}
+
+// rtx_scene_pose, rtx_scene_pose_rebuilt and their _device twins
+int vertices_call(const RtxScene *scene, const void *v0v1v2, const void *tie_rank, bool rebuilt, bool host, uint32_t reference_tree,
+                  PoseCall *call)
+{
+    if (!scene || !v0v1v2 || (host && reference_tree > RTX_REFTREE_NEVER)) return RTX_ERR_BAD_ARG;
+    *call = vertices_alone(static_cast<const float *>(v0v1v2), static_cast<const uint32_t *>(tie_rank), rebuilt);
+    return stated_arrays_ok(scene, *call, host);
+}
+
 // What rtx_scene_pose_prims reads of its struct for `scene`: the arrays of an arm the scene does not have are not read.
 // RTX_ERR_BAD_ARG for vertices missing with triangles present.
-int prims_of(const RtxScene *scene, const RtxPosePrims *in, const float **v0v1v2, rtx::PrimsOverlay *ov)
+int prims_of(const RtxScene *scene, const RtxPosePrims *in, uint32_t flags, PoseCall *call)
 {
     const bool triangles = posed_triangles(scene) != 0u, spheres = scene->prep.n_spheres != 0u;
     if (triangles && !in->v0v1v2) return RTX_ERR_BAD_ARG;
-    *v0v1v2 = triangles ? in->v0v1v2 : nullptr;
-    ov->rgb = triangles ? in->rgb : nullptr;
-    ov->spheres = spheres ? in->spheres : nullptr;
-    ov->sphere_rgb = spheres ? in->sphere_rgb : nullptr;
+    call->v = triangles ? in->v0v1v2 : nullptr;
+    call->tie_rank = in->tie_rank;
+    call->ov.rgb = triangles ? in->rgb : nullptr;
+    call->ov.spheres = spheres ? in->spheres : nullptr;
+    call->ov.sphere_rgb = spheres ? in->sphere_rgb : nullptr;
+    call->spheres = call->ov.spheres != nullptr;
+    call->rebuilt = (flags & RTX_POSE_REBUILT) != 0u;
     return RTX_OK;
+}
+
+// rtx_scene_pose_prims and its _device twin
+int prims_call(const RtxScene *scene, const RtxPosePrims *in, uint32_t flags, bool host, uint32_t reference_tree, PoseCall *call)
+{
+    if (!pose_head_ok(scene, in, flags)) return RTX_ERR_BAD_ARG;
+    RTX_TRY(prims_of(scene, in, flags, call));
+    if (host && reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
+    return stated_arrays_ok(scene, *call, host);
 }
 
 // What rtx_scene_pose_moved reads of its struct for `scene`, as prims_of: the colours of an arm the scene does not have are
-// not read.  RTX_ERR_BAD_ARG for a NULL `moves` or a count outside 1 ... 65,536.
-int moves_of(const RtxScene *scene, const RtxPoseMoves *in, rtx::PoseMoves *mv, rtx::PrimsOverlay *ov)
+// not read, and the pose states spheres where the scene has some.  RTX_ERR_BAD_ARG for a NULL `moves` or a count outside
+// 1 ... 65,536.
+int moves_of(const RtxScene *scene, const RtxPoseMoves *in, uint32_t flags, PoseCall *call)
 {
     if (!in->moves || in->n_moves == 0u || in->n_moves > rtx::kMaxMoves) return RTX_ERR_BAD_ARG;
-    mv->n_moves = in->n_moves;
-    mv->moves = in->moves;
-    mv->group = in->group;
-    mv->radius_scale = in->radius_scale;
-    ov->rgb = posed_triangles(scene) != 0u ? in->rgb : nullptr;
-    ov->sphere_rgb = scene->prep.n_spheres != 0u ? in->sphere_rgb : nullptr;
+    call->moves.n_moves = in->n_moves;
+    call->moves.moves = in->moves;
+    call->moves.group = in->group;
+    call->moves.radius_scale = in->radius_scale;
+    call->tie_rank = in->tie_rank;
+    call->ov.rgb = posed_triangles(scene) != 0u ? in->rgb : nullptr;
+    call->ov.sphere_rgb = scene->prep.n_spheres != 0u ? in->sphere_rgb : nullptr;
+    call->spheres = scene->prep.n_spheres != 0u;
+    call->rebuilt = (flags & RTX_POSE_REBUILT) != 0u;
     return RTX_OK;
 }
 
-// The bodies of rtx_scene_pose / rtx_scene_pose_device and of their _rebuilt twins: everything but the tree is the same.
-// prims: rtx_scene_pose_prims' bodies — v0v1v2 may be NULL for a scene without triangles, and ov is what the call states
-// beside the vertices; the other entry points give none, and nothing of the overlay's is then reserved, copied or launched.
-// moves: rtx_scene_pose_moved's bodies — v0v1v2 is NULL and ov_in states no spheres: the device makes both from the moves,
-// the caller has applied the range rule to the host statement (rtx::moved_in_range), and only the reference's own tree has
-// the statement's output made on the host.  skin: rtx_scene_pose_skinned's — the moves are blended per corner by the scene's
-// skin (rtx::skinned_in_range applied by the caller), everything else as for moves.
-int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
-              RtxStats *stats, bool rebuilt, bool prims = false, const rtx::PrimsOverlay &ov_in = rtx::PrimsOverlay(),
-              const rtx::PoseMoves *moves = nullptr, const rtx::Skin *skin = nullptr)
+// rtx_scene_pose_moved and its _device twin.  The host form applies the range rule to the statement (rtx::moved_in_range),
+// nothing stored.  rtx_scene_moved_prims does not look at the groups; neither does the device form.
+int moved_call(const RtxScene *scene, const RtxPoseMoves *in, uint32_t flags, bool host, uint32_t reference_tree, PoseCall *call)
 {
-    if (!scene || (!v0v1v2 && !moves && (!prims || posed_triangles(scene) != 0u)) || reference_tree > RTX_REFTREE_NEVER)
-        return RTX_ERR_BAD_ARG;
+    if (!pose_head_ok(scene, in, flags) || (host && reference_tree > RTX_REFTREE_NEVER)) return RTX_ERR_BAD_ARG;
+    RTX_TRY(moves_of(scene, in, flags, call));
+    if (!host) return stated_arrays_ok(scene, *call, false);
+    if (!rtx::move_groups_ok(scene->prep, call->moves)) return RTX_ERR_BAD_ARG;
+    return rtx::moved_in_range(scene->prep, call->moves) ? RTX_OK : RTX_ERR_UNSUPPORTED;
+}
+
+// rtx_scene_pose_skinned and its _device twin: the moves are blended per corner by the scene's skin.  n_moves against the
+// bind's largest bone is O(1), what the bind recorded, and the host form's alone: the kernel takes a bone at or above the
+// count as RTX_MOVE_NONE.
+int skinned_call(const RtxScene *scene, const RtxPoseMoves *in, uint32_t flags, bool host, uint32_t reference_tree, PoseCall *call)
+{
+    if (!pose_head_ok(scene, in, flags) || (host && reference_tree > RTX_REFTREE_NEVER)) return RTX_ERR_BAD_ARG;
+    RTX_TRY(moves_of(scene, in, flags, call));
+    const rtx::Skin &skin = scene->skin;
+    if (call->moves.group || !skin.bound || (host && call->moves.n_moves <= skin.max_bone)) return RTX_ERR_BAD_ARG;
+    call->skin = &skin;
+    if (!host) return stated_arrays_ok(scene, *call, false);
+    return rtx::skinned_in_range(scene->prep, skin, call->moves) ? RTX_OK : RTX_ERR_UNSUPPORTED;
+}
+
+// The body of the five host entry points, `c` made by its family's maker: the reference's own tree where reference_tree asks
+// for one — over the call's arrays, a moved pose's made by the host statement for this alone —, the reservations, the
+// copies onto the library's stream, and pose_launch over the copies.
+int pose_host(RtxScene *scene, int device, const PoseCall &c, uint32_t reference_tree, RtxStats *stats)
+{
     const rtx::PreparedScene &p = scene->prep;
-    if (v0v1v2 && !rtx::pose_in_range(p, v0v1v2)) return RTX_ERR_UNSUPPORTED;
-    if (ov_in.spheres && !rtx::spheres_in_range(p, ov_in.spheres)) return RTX_ERR_UNSUPPORTED;
-    rtx::PrimsOverlay ov = ov_in;
-    // a moved pose states spheres wherever the scene has some: the rest array stands for "given" (it is never copied)
-    if (moves && p.n_spheres) ov.spheres = p.rest_spheres.data();
-    const rtx::PrimsOverlay *pov = ov.any() ? &ov : nullptr;
     const Timed timed(stats);
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    const size_t n_prims = p.tris.size();
+    const size_t n_prims = p.tris.size(), n_triangles = posed_triangles(scene);
     const bool want_ref = reference_tree == RTX_REFTREE_ALWAYS || (reference_tree == RTX_REFTREE_AUTO && n_prims <= rtx::kRefTreeAutoMax);
     std::vector<uint32_t> ref_rank;
     std::vector<rtx::NodeDev> ref_stream;
-    std::vector<float> moved_v, moved_spheres;
     try {
-        if (want_ref && moves) {      // the reference's own tree is built from the statement's output
-            moved_v.resize(p.rest_v0v1v2.size());
-            moved_spheres.resize(p.rest_spheres.size());
-            if (skin) rtx::skinned_prims(p, *skin, *moves, moved_v.data(), moved_spheres.data());
-            else rtx::moved_prims(p, *moves, moved_v.data(), moved_spheres.data());
-            v0v1v2 = moved_v.data();
-            if (p.n_spheres) ov.spheres = moved_spheres.data();
-        }
         if (want_ref) {
+            std::vector<float> moved_v(c.moved() ? p.rest_v0v1v2.size() : 0u), moved_spheres(c.moved() ? p.rest_spheres.size() : 0u);
+            PoseCall stated = c;      // the call in host arrays
+            if (c.skin) rtx::skinned_prims(p, *c.skin, c.moves, moved_v.data(), moved_spheres.data());
+            else if (c.moved()) rtx::moved_prims(p, c.moves, moved_v.data(), moved_spheres.data());
+            if (c.moved()) {
+                stated.v = moved_v.data();
+                if (p.n_spheres) stated.ov.spheres = moved_spheres.data();
+            }
+            const rtx::PrimsOverlay *ov = c.overlaid() ? &stated.ov : nullptr;
             std::vector<rtx::NodeRec> stream;
-            if (rebuilt) {      // the leaves name positions of the sorted array: through the host statement's permutation
+            if (c.rebuilt) {      // the leaves name positions of the sorted array: through the host statement's permutation
                 std::vector<uint32_t> perm(n_prims - p.n_global);
-                rtx::rebuilt_records(p, pose_tables_of(scene), rebuild_tables_of(scene), v0v1v2, nullptr, nullptr, perm.data(),
-                                     nullptr, nullptr, nullptr, pov);
-                RTX_TRY(rtx::rebuilt_ref_tree(p, pose_tables_of(scene), v0v1v2, perm.data(), ref_rank, stream, pov));
+                rtx::rebuilt_records(p, pose_tables_of(scene), rebuild_tables_of(scene), stated.v, nullptr, nullptr, perm.data(), nullptr,
+                                     nullptr, nullptr, ov);
+                RTX_TRY(rtx::rebuilt_ref_tree(p, pose_tables_of(scene), stated.v, perm.data(), ref_rank, stream, ov));
             } else {
-                RTX_TRY(rtx::posed_ref_tree(p, pose_tables_of(scene), v0v1v2, ref_rank, stream, pov));
+                RTX_TRY(rtx::posed_ref_tree(p, pose_tables_of(scene), stated.v, ref_rank, stream, ov));
             }
             ref_stream = rtx::nodes_in_device_order(stream);
         }
     } catch (...) {
         return RTX_ERR_OOM;
     }
-    const uint32_t *rank = tie_rank ? tie_rank : (want_ref ? ref_rank.data() : nullptr);
-    RTX_TRY(reserve_pose(scene, st, true, ref_stream.size(), rebuilt));
-    if (pov) RTX_TRY(reserve_prims(scene, st, true, ov));
-    if (moves) RTX_TRY(reserve_moves(scene, st, true, *moves));
-    if (skin) RTX_TRY(reserve_skin(scene, st));
+    const uint32_t *rank = c.tie_rank ? c.tie_rank : (want_ref ? ref_rank.data() : nullptr);
+    RTX_TRY(reserve_pose(scene, st, true, ref_stream.size(), c.rebuilt));
+    if (c.overlaid()) RTX_TRY(reserve_prims(scene, st, true, c));
+    if (c.moved()) RTX_TRY(reserve_moves(scene, st, true, c.moves));
+    if (c.skin) RTX_TRY(reserve_skin(scene, st));
     RTX_TRY(wait_for_uses(st, kUsesPose));      // a device-resident call may still read the pose this one replaces
-    const size_t v_bytes = moves ? 0u : static_cast<size_t>(posed_triangles(scene)) * 9u * sizeof(float);
+    if (!c.moved()) st.pose.f.ran = false;      // (the copies below overwrite what the move kernel wrote)
     hipError_t he = hipSuccess;
-    if (!moves) st.pose.f.ran = false;      // (the copies below overwrite what the move kernel wrote)
-    if (v_bytes) he = hipMemcpyAsync(st.pose.v.as<void>(), v0v1v2, v_bytes, hipMemcpyHostToDevice, st.stream);
-    rtx::PrimsOverlay d_ov;
-    rtx::PoseMoves d_moves;
-    if (moves) {
-        auto &f = st.pose.f;
-        d_moves.n_moves = moves->n_moves;
-        he = hipMemcpyAsync(f.moves.as<void>(), moves->moves, static_cast<size_t>(moves->n_moves) * 12u * sizeof(float),
-                            hipMemcpyHostToDevice, st.stream);
-        d_moves.moves = f.moves.as<const float>();
-        if (he == hipSuccess && moves->group) {
-            he = hipMemcpyAsync(f.group.as<void>(), moves->group, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
-            d_moves.group = f.group.as<const uint32_t>();
-        }
-        if (he == hipSuccess && moves->radius_scale) {
-            he = hipMemcpyAsync(f.radius_scale.as<void>(), moves->radius_scale, static_cast<size_t>(moves->n_moves) * sizeof(float),
-                                hipMemcpyHostToDevice, st.stream);
-            d_moves.radius_scale = f.radius_scale.as<const float>();
-        }
-    }
-    auto copy_in = [&](const float *from, DeviceBuffer &to, size_t floats, const float *&d) {      // (an array not given: nothing)
-        if (he != hipSuccess || !from) return;
-        he = hipMemcpyAsync(to.as<void>(), from, floats * sizeof(float), hipMemcpyHostToDevice, st.stream);
-        d = to.as<const float>();
+    auto copy_in = [&](const auto *from, DeviceBuffer &to, size_t n) {      // -> the copy (an array not given: nothing, NULL)
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(from)>>;
+        if (!from) return static_cast<const T *>(nullptr);
+        if (he == hipSuccess && n) he = hipMemcpyAsync(to.as<void>(), from, n * sizeof(T), hipMemcpyHostToDevice, st.stream);
+        return to.as<const T>();
     };
-    copy_in(moves ? nullptr : ov.spheres, st.pose.m.spheres, static_cast<size_t>(p.n_spheres) * 4u, d_ov.spheres);
-    copy_in(ov.rgb, st.pose.m.rgb, static_cast<size_t>(posed_triangles(scene)) * 3u, d_ov.rgb);
-    copy_in(ov.sphere_rgb, st.pose.m.sphere_rgb, static_cast<size_t>(p.n_spheres) * 3u, d_ov.sphere_rgb);
-    if (he == hipSuccess && rank)
-        he = hipMemcpyAsync(st.pose.rank.as<void>(), rank, n_prims * sizeof(uint32_t), hipMemcpyHostToDevice, st.stream);
+    PoseCall d = c;      // the call over the library's copies
+    copy_in(c.v, st.pose.v, n_triangles * 9u);
+    d.v = st.pose.v.as<const float>();
+    d.moves.moves = copy_in(c.moves.moves, st.pose.f.moves, static_cast<size_t>(c.moves.n_moves) * 12u);
+    d.moves.group = copy_in(c.moves.group, st.pose.f.group, n_prims);
+    d.moves.radius_scale = copy_in(c.moves.radius_scale, st.pose.f.radius_scale, c.moves.n_moves);
+    d.ov.spheres = copy_in(c.ov.spheres, st.pose.m.spheres, static_cast<size_t>(p.n_spheres) * 4u);
+    d.ov.rgb = copy_in(c.ov.rgb, st.pose.m.rgb, n_triangles * 3u);
+    d.ov.sphere_rgb = copy_in(c.ov.sphere_rgb, st.pose.m.sphere_rgb, static_cast<size_t>(p.n_spheres) * 3u);
+    d.tie_rank = copy_in(rank, st.pose.rank, n_prims);
     if (he == hipSuccess && !ref_stream.empty()) {
         he = hipMemcpyAsync(st.pose.geo.ref_nodes.as<void>(), ref_stream.data(), ref_stream.size() * sizeof(rtx::NodeDev),
                             hipMemcpyHostToDevice, st.stream);
@@ -2024,9 +2078,7 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     }
     int rc = hip_rc(he);
     if (rc == RTX_OK) rc = timed.begin(st);
-    if (rc == RTX_OK)
-        rc = pose_launch(scene, st, st.pose.v.as<const float>(), rank ? st.pose.rank.as<const uint32_t>() : nullptr, d_ov, st.stream,
-                         rebuilt, moves ? &d_moves : nullptr, skin != nullptr);
+    if (rc == RTX_OK) rc = pose_launch(scene, st, d, st.stream);
     if (rc == RTX_OK) rc = timed.end(st);
     if (rc != RTX_OK) {
         st.pose.valid = false;
@@ -2037,31 +2089,69 @@ int pose_host(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *
     return timed.gather(st, 0u, 0u);
 }
 
-int pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream, bool rebuilt,
-                bool prims = false, const rtx::PrimsOverlay &ov_in = rtx::PrimsOverlay(), const rtx::PoseMoves *d_moves = nullptr,
-                bool skinned = false)
+// ... of the five device-resident ones: the reservations and pose_launch over the caller's arrays on the caller's stream,
+// nothing waited for.  (The overlay's primitive records are reserved where spheres are stated, the move kernel's too.)
+int pose_device(RtxScene *scene, int device, const PoseCall &d, void *stream)
 {
-    rtx::PrimsOverlay d_ov = ov_in;
-    if (!scene || (!d_v0v1v2 && !d_moves && (!prims || posed_triangles(scene) != 0u))) return RTX_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_v0v1v2) | reinterpret_cast<uintptr_t>(d_tie_rank) | reinterpret_cast<uintptr_t>(d_ov.spheres) |
-         reinterpret_cast<uintptr_t>(d_ov.rgb) | reinterpret_cast<uintptr_t>(d_ov.sphere_rgb)) & 3u)
-        return RTX_ERR_BAD_ARG;
-    if (d_moves && ((reinterpret_cast<uintptr_t>(d_moves->moves) | reinterpret_cast<uintptr_t>(d_moves->group) |
-                     reinterpret_cast<uintptr_t>(d_moves->radius_scale)) & 3u))
-        return RTX_ERR_BAD_ARG;
     Entry e(scene, device, Entry::kUploaded);
     if (e.rc != RTX_OK) return e.rc;
     DeviceState &st = e.state();
-    RTX_TRY(reserve_pose(scene, st, false, 0u, rebuilt));
-    if (d_moves) {      // (the overlay's primitive records are reserved where spheres are stated: the move kernel's)
-        RTX_TRY(reserve_moves(scene, st, false, *d_moves));
-        if (scene->prep.n_spheres) d_ov.spheres = st.pose.m.spheres.as<const float>();
-        if (skinned) RTX_TRY(reserve_skin(scene, st));
-    }
-    if (d_ov.any()) RTX_TRY(reserve_prims(scene, st, false, d_ov));
-    RTX_TRY(pose_launch(scene, st, static_cast<const float *>(d_v0v1v2), static_cast<const uint32_t *>(d_tie_rank), d_ov,
-                        static_cast<hipStream_t>(stream), rebuilt, d_moves, skinned));
+    RTX_TRY(reserve_pose(scene, st, false, 0u, d.rebuilt));
+    if (d.moved()) RTX_TRY(reserve_moves(scene, st, false, d.moves));
+    if (d.skin) RTX_TRY(reserve_skin(scene, st));
+    if (d.overlaid()) RTX_TRY(reserve_prims(scene, st, false, d));
+    RTX_TRY(pose_launch(scene, st, d, static_cast<hipStream_t>(stream)));
     return mark_uses(st, kUsesPose, static_cast<hipStream_t>(stream));
+}
+
+// The end of a pose's read-back with an aimed stream: the aim kernels run over `g` for `eye`, whatever the buffer holds, and
+// the n records of their stream are read back (read_back_nodes; out == NULL: nothing is aimed, the stream is drained)
+int read_back_aimed(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const float eye[3], size_t n, uint32_t *out)
+{
+    if (out && n) {
+        RTX_TRY(reserve_aimed(scene, g));
+        g.aimed.valid = false;
+        RTX_TRY(aim_at(scene, g, eye, st.stream));
+    }
+    return read_back_nodes(st, aimed_stream(scene, g), n, out);
+}
+
+// a host statement, which may throw std::bad_alloc, as a return code
+template <class Statement>
+int on_host(Statement statement)
+{
+    try {
+        statement();
+    } catch (...) {
+        return RTX_ERR_OOM;
+    }
+    return RTX_OK;
+}
+
+// The body of rtx_debug_pose and of rtx_debug_pose_rebuilt (for_rebuilt), each with its own refusal: the first states its
+// nodes by the uploaded count and so gives none of a rebuilt pose, the second reads a rebuilt pose alone.  The records of
+// the pose the device holds are copied back behind what a device-resident pose has enqueued; the second then runs the aim
+// kernels over the pose for `eye` and reads their stream.  Each output may be NULL.
+int debug_pose(RtxScene *scene, int device, bool for_rebuilt, const float *eye, uint32_t *out_perm, uint32_t *out_tris,
+               uint32_t *out_shade, uint32_t *out_nodes, uint32_t *out_aimed)
+{
+    if (!scene || (out_aimed && !eye)) return RTX_ERR_BAD_ARG;
+    Entry e(scene, device, Entry::kUploaded);
+    if (e.rc != RTX_OK) return e.rc;
+    DeviceState &st = e.state();
+    DeviceGeometry *g;
+    RTX_TRY(geometry_of(st, true, &g));
+    if (for_rebuilt ? !st.pose.rebuilt : (st.pose.rebuilt && out_nodes)) return RTX_ERR_BAD_ARG;
+    const size_t n_prims = scene->prep.tris.size(), n_tree = n_prims - scene->prep.n_global, n = g->n_nodes;
+    RTX_TRY(wait_for_uses(st, kUsesPose));
+    if (out_perm && n_tree)
+        RTX_HIP(hipMemcpyAsync(out_perm, st.pose.b.perm.as<void>(), n_tree * sizeof(uint32_t), hipMemcpyDeviceToHost, st.stream));
+    if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, g->tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
+    if (out_shade)
+        RTX_HIP(hipMemcpyAsync(out_shade, g->shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
+    if (!for_rebuilt) return read_back_nodes(st, g->nodes.as<void>(), n, out_nodes);      // (refitted: n is the uploaded count)
+    RTX_TRY(read_back_nodes(st, g->nodes.as<void>(), n, out_nodes));
+    return read_back_aimed(scene, st, *g, eye, n, out_aimed);
 }
 
 }  // namespace
@@ -2627,168 +2717,115 @@ int rtx_scene_posed_records(const RtxScene *scene, const float *v0v1v2, const ui
                             uint32_t *out_shade, uint32_t *out_nodes)
 {
     if (!scene || !v0v1v2) return RTX_ERR_BAD_ARG;
-    try {
-        const rtx::PoseTables &t = pose_tables_of(const_cast<RtxScene *>(scene));      // (the tables are a cache under the scene's lock)
-        rtx::posed_records(scene->prep, t, v0v1v2, tie_rank, reinterpret_cast<rtx::TriRec *>(out_tris),
-                           reinterpret_cast<rtx::ShadeRec *>(out_shade), reinterpret_cast<rtx::NodeRec *>(out_nodes));
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    return RTX_OK;
+    return on_host([&] { records_on_host(scene, vertices_alone(v0v1v2, tie_rank, false), nullptr, nullptr, out_tris, out_shade, out_nodes); });
 }
 
 int rtx_scene_pose(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
                    RtxStats *stats)
 {
-    return pose_host(scene, device, v0v1v2, tie_rank, reference_tree, stats, false);
+    PoseCall call;
+    RTX_TRY(vertices_call(scene, v0v1v2, tie_rank, false, true, reference_tree, &call));
+    return pose_host(scene, device, call, reference_tree, stats);
 }
 
 int rtx_scene_pose_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream)
 {
-    return pose_device(scene, device, d_v0v1v2, d_tie_rank, stream, false);
+    PoseCall d;
+    RTX_TRY(vertices_call(scene, d_v0v1v2, d_tie_rank, false, false, RTX_REFTREE_NEVER, &d));
+    return pose_device(scene, device, d, stream);
 }
 
 int rtx_scene_pose_rebuilt(RtxScene *scene, int device, const float *v0v1v2, const uint32_t *tie_rank, uint32_t reference_tree,
                            RtxStats *stats)
 {
-    return pose_host(scene, device, v0v1v2, tie_rank, reference_tree, stats, true);
+    PoseCall call;
+    RTX_TRY(vertices_call(scene, v0v1v2, tie_rank, true, true, reference_tree, &call));
+    return pose_host(scene, device, call, reference_tree, stats);
 }
 
 int rtx_scene_pose_rebuilt_device(RtxScene *scene, int device, const void *d_v0v1v2, const void *d_tie_rank, void *stream)
 {
-    return pose_device(scene, device, d_v0v1v2, d_tie_rank, stream, true);
+    PoseCall d;
+    RTX_TRY(vertices_call(scene, d_v0v1v2, d_tie_rank, true, false, RTX_REFTREE_NEVER, &d));
+    return pose_device(scene, device, d, stream);
 }
 
 int rtx_scene_rebuilt_counts(const RtxScene *scene, uint32_t *out_n_nodes)
 {
-    if (!scene || !out_n_nodes) return RTX_ERR_BAD_ARG;
-    try {
-        *out_n_nodes = static_cast<uint32_t>(rebuild_tables_of(const_cast<RtxScene *>(scene)).nodes.size());   // (a cache under the scene's lock)
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    return RTX_OK;
+    if (!scene || !out_n_nodes) return RTX_ERR_BAD_ARG;      // (the tables are a cache under the scene's lock)
+    return on_host([&] { *out_n_nodes = static_cast<uint32_t>(rebuild_tables_of(const_cast<RtxScene *>(scene)).nodes.size()); });
 }
 
 int rtx_scene_rebuilt_records(const RtxScene *scene, const float *v0v1v2, const uint32_t *tie_rank, uint64_t *out_keys,
                               uint32_t *out_perm, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
 {
     if (!scene || !v0v1v2) return RTX_ERR_BAD_ARG;
-    try {
-        RtxScene *sc = const_cast<RtxScene *>(scene);      // (the tables are caches under the scene's lock)
-        const rtx::PoseTables &t = pose_tables_of(sc);
-        rtx::rebuilt_records(scene->prep, t, rebuild_tables_of(sc), v0v1v2, tie_rank, out_keys, out_perm,
-                             reinterpret_cast<rtx::TriRec *>(out_tris), reinterpret_cast<rtx::ShadeRec *>(out_shade),
-                             reinterpret_cast<rtx::NodeRec *>(out_nodes));
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    return RTX_OK;
+    return on_host([&] { records_on_host(scene, vertices_alone(v0v1v2, tie_rank, true), out_keys, out_perm, out_tris, out_shade, out_nodes); });
 }
 
 int rtx_scene_rebuilt_aimed(const RtxScene *scene, const float *v0v1v2, const float eye[3], uint32_t *out_aimed)
 {
     if (!scene || !v0v1v2 || !eye || !out_aimed) return RTX_ERR_BAD_ARG;
-    try {
-        rebuilt_aimed_on_host(const_cast<RtxScene *>(scene), v0v1v2, eye, reinterpret_cast<rtx::NodeRec *>(out_aimed), nullptr);
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    return RTX_OK;
+    return on_host([&] { posed_pipeline_on_host(scene, vertices_alone(v0v1v2, nullptr, true), eye, nullptr, out_aimed); });
 }
 
 int rtx_scene_pose_prims(RtxScene *scene, int device, const RtxPosePrims *prims, uint32_t flags, uint32_t reference_tree,
                          RtxStats *stats)
 {
-    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
-    const float *v0v1v2;
-    rtx::PrimsOverlay ov;
-    RTX_TRY(prims_of(scene, prims, &v0v1v2, &ov));
-    return pose_host(scene, device, v0v1v2, prims->tie_rank, reference_tree, stats, (flags & RTX_POSE_REBUILT) != 0u, true, ov);
+    PoseCall call;
+    RTX_TRY(prims_call(scene, prims, flags, true, reference_tree, &call));
+    return pose_host(scene, device, call, reference_tree, stats);
 }
 
 int rtx_scene_pose_prims_device(RtxScene *scene, int device, const RtxPosePrims *prims, uint32_t flags, void *stream)
 {
-    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
-    const float *d_v0v1v2;
-    rtx::PrimsOverlay d_ov;
-    RTX_TRY(prims_of(scene, prims, &d_v0v1v2, &d_ov));
-    return pose_device(scene, device, d_v0v1v2, prims->tie_rank, stream, (flags & RTX_POSE_REBUILT) != 0u, true, d_ov);
+    PoseCall d;
+    RTX_TRY(prims_call(scene, prims, flags, false, RTX_REFTREE_NEVER, &d));
+    return pose_device(scene, device, d, stream);
 }
 
 int rtx_scene_pose_prims_records(const RtxScene *scene, const RtxPosePrims *prims, uint32_t flags, uint64_t *out_keys,
                                  uint32_t *out_perm, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
 {
-    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
-    const bool rebuilt = (flags & RTX_POSE_REBUILT) != 0u;
-    if (!rebuilt && (out_keys || out_perm)) return RTX_ERR_BAD_ARG;
-    const float *v0v1v2;
-    rtx::PrimsOverlay ov;
-    RTX_TRY(prims_of(scene, prims, &v0v1v2, &ov));
-    try {
-        RtxScene *sc = const_cast<RtxScene *>(scene);      // (the tables are caches under the scene's lock)
-        const rtx::PoseTables &t = pose_tables_of(sc);
-        rtx::TriRec *tris = reinterpret_cast<rtx::TriRec *>(out_tris);
-        rtx::ShadeRec *shade = reinterpret_cast<rtx::ShadeRec *>(out_shade);
-        rtx::NodeRec *nodes = reinterpret_cast<rtx::NodeRec *>(out_nodes);
-        if (rebuilt)
-            rtx::rebuilt_records(scene->prep, t, rebuild_tables_of(sc), v0v1v2, prims->tie_rank, out_keys, out_perm, tris, shade,
-                                 nodes, &ov);
-        else
-            rtx::posed_records(scene->prep, t, v0v1v2, prims->tie_rank, tris, shade, nodes, &ov);
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    return RTX_OK;
+    if (!pose_head_ok(scene, prims, flags)) return RTX_ERR_BAD_ARG;
+    if (!(flags & RTX_POSE_REBUILT) && (out_keys || out_perm)) return RTX_ERR_BAD_ARG;
+    PoseCall call;
+    RTX_TRY(prims_of(scene, prims, flags, &call));
+    return on_host([&] { records_on_host(scene, call, out_keys, out_perm, out_tris, out_shade, out_nodes); });
 }
 
 int rtx_scene_pose_prims_aimed(const RtxScene *scene, const RtxPosePrims *prims, uint32_t flags, const float eye[3],
                                uint32_t *out_aimed)
 {
-    if (!scene || !prims || (flags & ~RTX_POSE_REBUILT) || !eye || !out_aimed) return RTX_ERR_BAD_ARG;
-    const float *v0v1v2;
-    rtx::PrimsOverlay ov;
-    RTX_TRY(prims_of(scene, prims, &v0v1v2, &ov));
-    try {
-        RtxScene *sc = const_cast<RtxScene *>(scene);
-        rtx::NodeRec *aimed = reinterpret_cast<rtx::NodeRec *>(out_aimed);
-        if (flags & RTX_POSE_REBUILT) rebuilt_aimed_on_host(sc, v0v1v2, eye, aimed, &ov);
-        else posed_pipeline_on_host(sc, v0v1v2, eye, nullptr, aimed, &ov);
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    return RTX_OK;
+    if (!pose_head_ok(scene, prims, flags) || !eye || !out_aimed) return RTX_ERR_BAD_ARG;
+    PoseCall call;
+    RTX_TRY(prims_of(scene, prims, flags, &call));
+    call.tie_rank = nullptr;      // (the node words do not depend on it)
+    return on_host([&] { posed_pipeline_on_host(scene, call, eye, nullptr, out_aimed); });
 }
 
 int rtx_scene_moved_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres)
 {
     if (!scene || !moves) return RTX_ERR_BAD_ARG;
-    rtx::PoseMoves mv;
-    rtx::PrimsOverlay ov;
-    RTX_TRY(moves_of(scene, moves, &mv, &ov));
-    rtx::moved_prims(scene->prep, mv, out_v0v1v2, out_spheres);
+    PoseCall call;
+    RTX_TRY(moves_of(scene, moves, 0u, &call));
+    rtx::moved_prims(scene->prep, call.moves, out_v0v1v2, out_spheres);
     return RTX_OK;
 }
 
 int rtx_scene_pose_moved(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, uint32_t reference_tree,
                          RtxStats *stats)
 {
-    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT) || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
-    rtx::PoseMoves mv;
-    rtx::PrimsOverlay ov;
-    RTX_TRY(moves_of(scene, moves, &mv, &ov));
-    if (!rtx::move_groups_ok(scene->prep, mv)) return RTX_ERR_BAD_ARG;
-    if (!rtx::moved_in_range(scene->prep, mv)) return RTX_ERR_UNSUPPORTED;      // the statement on the host, nothing stored
-    return pose_host(scene, device, nullptr, moves->tie_rank, reference_tree, stats, (flags & RTX_POSE_REBUILT) != 0u, true, ov, &mv);
+    PoseCall call;
+    RTX_TRY(moved_call(scene, moves, flags, true, reference_tree, &call));
+    return pose_host(scene, device, call, reference_tree, stats);
 }
 
 int rtx_scene_pose_moved_device(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, void *stream)
 {
-    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
-    rtx::PoseMoves d_mv;
-    rtx::PrimsOverlay d_ov;
-    RTX_TRY(moves_of(scene, moves, &d_mv, &d_ov));
-    return pose_device(scene, device, nullptr, moves->tie_rank, stream, (flags & RTX_POSE_REBUILT) != 0u, true, d_ov, &d_mv);
+    PoseCall d;
+    RTX_TRY(moved_call(scene, moves, flags, false, RTX_REFTREE_NEVER, &d));
+    return pose_device(scene, device, d, stream);
 }
 
 int rtx_scene_skin(RtxScene *scene, const RtxSkin *skin)
@@ -2813,36 +2850,26 @@ int rtx_scene_skin_bound(const RtxScene *scene, uint32_t *out_max_bone)
 int rtx_scene_skinned_prims(const RtxScene *scene, const RtxPoseMoves *moves, float *out_v0v1v2, float *out_spheres)
 {
     if (!scene || !moves) return RTX_ERR_BAD_ARG;
-    rtx::PoseMoves mv;
-    rtx::PrimsOverlay ov;
-    RTX_TRY(moves_of(scene, moves, &mv, &ov));
-    if (mv.group || !scene->skin.bound) return RTX_ERR_BAD_ARG;
-    rtx::skinned_prims(scene->prep, scene->skin, mv, out_v0v1v2, out_spheres);
+    PoseCall call;
+    RTX_TRY(moves_of(scene, moves, 0u, &call));
+    if (call.moves.group || !scene->skin.bound) return RTX_ERR_BAD_ARG;
+    rtx::skinned_prims(scene->prep, scene->skin, call.moves, out_v0v1v2, out_spheres);
     return RTX_OK;
 }
 
 int rtx_scene_pose_skinned(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, uint32_t reference_tree,
                            RtxStats *stats)
 {
-    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT) || reference_tree > RTX_REFTREE_NEVER) return RTX_ERR_BAD_ARG;
-    rtx::PoseMoves mv;
-    rtx::PrimsOverlay ov;
-    RTX_TRY(moves_of(scene, moves, &mv, &ov));
-    const rtx::Skin &skin = scene->skin;
-    if (mv.group || !skin.bound || mv.n_moves <= skin.max_bone) return RTX_ERR_BAD_ARG;      // (O(1): what the bind recorded)
-    if (!rtx::skinned_in_range(scene->prep, skin, mv)) return RTX_ERR_UNSUPPORTED;      // the statement on the host, nothing stored
-    return pose_host(scene, device, nullptr, moves->tie_rank, reference_tree, stats, (flags & RTX_POSE_REBUILT) != 0u, true, ov, &mv,
-                     &skin);
+    PoseCall call;
+    RTX_TRY(skinned_call(scene, moves, flags, true, reference_tree, &call));
+    return pose_host(scene, device, call, reference_tree, stats);
 }
 
 int rtx_scene_pose_skinned_device(RtxScene *scene, int device, const RtxPoseMoves *moves, uint32_t flags, void *stream)
 {
-    if (!scene || !moves || (flags & ~RTX_POSE_REBUILT)) return RTX_ERR_BAD_ARG;
-    rtx::PoseMoves d_mv;
-    rtx::PrimsOverlay d_ov;
-    RTX_TRY(moves_of(scene, moves, &d_mv, &d_ov));
-    if (d_mv.group || !scene->skin.bound) return RTX_ERR_BAD_ARG;
-    return pose_device(scene, device, nullptr, moves->tie_rank, stream, (flags & RTX_POSE_REBUILT) != 0u, true, d_ov, &d_mv, true);
+    PoseCall d;
+    RTX_TRY(skinned_call(scene, moves, flags, false, RTX_REFTREE_NEVER, &d));
+    return pose_device(scene, device, d, stream);
 }
 
 int rtx_debug_moved_prims(RtxScene *scene, int device, float *out_v0v1v2, float *out_spheres)
@@ -2863,44 +2890,12 @@ int rtx_debug_moved_prims(RtxScene *scene, int device, float *out_v0v1v2, float 
 int rtx_debug_pose_rebuilt(RtxScene *scene, int device, const float eye[3], uint32_t *out_perm, uint32_t *out_tris,
                            uint32_t *out_shade, uint32_t *out_nodes, uint32_t *out_aimed)
 {
-    if (!scene || (out_aimed && !eye)) return RTX_ERR_BAD_ARG;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    DeviceGeometry *g;
-    RTX_TRY(geometry_of(st, true, &g));
-    if (!st.pose.rebuilt) return RTX_ERR_BAD_ARG;
-    const size_t n_prims = scene->prep.tris.size(), n_tree = n_prims - scene->prep.n_global, n = g->n_nodes;
-    RTX_TRY(wait_for_uses(st, kUsesPose));
-    if (out_perm && n_tree)
-        RTX_HIP(hipMemcpyAsync(out_perm, st.pose.b.perm.as<void>(), n_tree * sizeof(uint32_t), hipMemcpyDeviceToHost, st.stream));
-    if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, g->tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
-    if (out_shade)
-        RTX_HIP(hipMemcpyAsync(out_shade, g->shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
-    RTX_TRY(read_back_nodes(st, g->nodes.as<void>(), n, out_nodes));
-    if (out_aimed && n) {
-        RTX_TRY(reserve_aimed(scene, *g));
-        g->aimed.valid = false;              // the kernels run whatever the buffer holds
-        RTX_TRY(aim_at(scene, *g, eye, st.stream));
-    }
-    return read_back_nodes(st, aimed_stream(scene, *g), n, out_aimed);
+    return debug_pose(scene, device, true, eye, out_perm, out_tris, out_shade, out_nodes, out_aimed);
 }
 
 int rtx_debug_pose(RtxScene *scene, int device, uint32_t *out_tris, uint32_t *out_shade, uint32_t *out_nodes)
 {
-    if (!scene) return RTX_ERR_BAD_ARG;
-    Entry e(scene, device, Entry::kUploaded);
-    if (e.rc != RTX_OK) return e.rc;
-    DeviceState &st = e.state();
-    DeviceGeometry *g;
-    RTX_TRY(geometry_of(st, true, &g));
-    if (st.pose.rebuilt && out_nodes) return RTX_ERR_BAD_ARG;      // sized by the uploaded node count: rtx_debug_pose_rebuilt
-    const size_t n_prims = scene->prep.tris.size();
-    RTX_TRY(wait_for_uses(st, kUsesPose));
-    if (out_tris) RTX_HIP(hipMemcpyAsync(out_tris, g->tris.as<void>(), n_prims * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
-    if (out_shade)
-        RTX_HIP(hipMemcpyAsync(out_shade, g->shade.as<void>(), n_prims * sizeof(rtx::ShadeRec), hipMemcpyDeviceToHost, st.stream));
-    return read_back_nodes(st, g->nodes.as<void>(), out_nodes ? scene->prep.nodes.size() : 0u, out_nodes);
+    return debug_pose(scene, device, false, nullptr, nullptr, out_tris, out_shade, out_nodes, nullptr);
 }
 
 int rtx_trace_rays_posed(RtxScene *scene, int device, uint32_t n_rays, const float *origins, const float *directions,
@@ -3057,13 +3052,7 @@ int rtx_scene_posed_pipeline_records(const RtxScene *scene, const float *v0v1v2,
                                      uint32_t *out_aimed)
 {
     if (!scene || !v0v1v2 || (out_aimed && !eye)) return RTX_ERR_BAD_ARG;
-    try {
-        posed_pipeline_on_host(const_cast<RtxScene *>(scene), v0v1v2, eye, reinterpret_cast<rtx::TriRec *>(out_planes),
-                               reinterpret_cast<rtx::NodeRec *>(out_aimed));      // (the tables are a cache under the scene's lock)
-    } catch (...) {
-        return RTX_ERR_OOM;
-    }
-    return RTX_OK;
+    return on_host([&] { posed_pipeline_on_host(scene, vertices_alone(v0v1v2, nullptr, false), eye, out_planes, out_aimed); });
 }
 
 int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uint32_t *out_planes, uint32_t *out_aimed)
@@ -3079,12 +3068,7 @@ int rtx_debug_pose_pipeline(RtxScene *scene, int device, const float eye[3], uin
     RTX_TRY(wait_for_uses(st, kUsesPose));
     if (out_planes && n_global)
         RTX_HIP(hipMemcpyAsync(out_planes, g->planes.as<void>(), n_global * sizeof(rtx::TriRec), hipMemcpyDeviceToHost, st.stream));
-    if (out_aimed && n) {
-        RTX_TRY(reserve_aimed(scene, *g));
-        g->aimed.valid = false;              // the kernels run whatever the buffer holds
-        RTX_TRY(aim_at(scene, *g, eye, st.stream));
-    }
-    return read_back_nodes(st, aimed_stream(scene, *g), n, out_aimed);
+    return read_back_aimed(scene, st, *g, eye, n, out_aimed);
 }
 
 int rtx_debug_wave_profile(RtxScene *scene, int device, uint32_t row0, uint32_t nrows, uint64_t *out,

@@ -372,6 +372,11 @@ def _fp(a):
     return a.ctypes.data_as(f32p)
 
 
+def _up(a):
+    """uint32 words of an array, None: NULL"""
+    return a.ctypes.data_as(u32p) if a is not None else None
+
+
 def _f3(x):
     return np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(3))
 
@@ -939,40 +944,53 @@ class Scene:
             raise ValueError("tie_rank must have one entry per primitive")
         return v, rank
 
+    def _pose(self, name, device, head, rebuilt=None, reference_tree=None, stats=False, stream=None):
+        """One pose entry point: `head` (the arrays, or the struct), the flag word where the entry point has one (rebuilt is
+        not None), then reference_tree and stats (a host form: reference_tree is not None) or the stream -> the stats dict
+        or None"""
+        st = Stats()
+        args = list(head) + ([POSE_REBUILT if rebuilt else 0] if rebuilt is not None else [])
+        if reference_tree is not None:
+            args += [int(reference_tree), C.byref(st) if stats else None]
+        else:
+            args.append(C.c_void_p(stream) if stream else None)
+        _check(getattr(_lib, name)(self._h, device, *args), name)
+        return st.asdict() if stats else None
+
     def pose(self, v0v1v2, device=0, tie_rank=None, reference_tree=REFTREE_NEVER, stats=False):
         """Moves the scene's triangles on `device` to v0v1v2 (float32 [n_tris, 9], Vec order, spheres skipped): one pose per
         scene and device, replaced by the next (rtx_scene_pose).  stats: kernel_ms is the pose kernels' time."""
         v, rank = self._pose_arrays(v0v1v2, tie_rank)
-        st = Stats()
-        _check(_lib.rtx_scene_pose(self._h, device, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
-                                   int(reference_tree), C.byref(st) if stats else None), "rtx_scene_pose")
-        return st.asdict() if stats else None
+        return self._pose("rtx_scene_pose", device, (_fp(v), _up(rank)), None, reference_tree, stats)
 
     def pose_device(self, device, d_v0v1v2_ptr, d_tie_rank_ptr=None, stream=None):
         """Asynchronous pose from device arrays the caller owns (n_tris x 9 float32; n_prims uint32 or None)."""
-        _check(_lib.rtx_scene_pose_device(self._h, device, C.c_void_p(d_v0v1v2_ptr),
-                                          C.c_void_p(d_tie_rank_ptr) if d_tie_rank_ptr else None,
-                                          C.c_void_p(stream) if stream else None), "rtx_scene_pose_device")
+        self._pose("rtx_scene_pose_device", device, (C.c_void_p(d_v0v1v2_ptr), C.c_void_p(d_tie_rank_ptr) if d_tie_rank_ptr else None),
+                   stream=stream)
 
-    def _pose_outputs(self):
-        i = self.info()
-        return np.zeros((self.n_prims, 16), np.uint32), np.zeros((self.n_prims, 8), np.uint32), np.zeros((i["n_nodes"], 8), np.uint32)
+    def _pose_outputs(self, rebuilt=False):
+        """-> zeroed (tris, shade, nodes), a rebuilt pose's: (perm, tris, shade, nodes)"""
+        t, s = np.zeros((self.n_prims, 16), np.uint32), np.zeros((self.n_prims, 8), np.uint32)
+        if rebuilt:
+            return np.zeros(self.n_prims - self.info()["n_global"], np.uint32), t, s, np.zeros((self.rebuilt_counts(), 8), np.uint32)
+        return t, s, np.zeros((self.info()["n_nodes"], 8), np.uint32)
+
+    def _prim_outputs(self):
+        """-> zeroed (v0v1v2 [n_tris, 9], spheres [n_spheres, 4])"""
+        return np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
 
     def posed_records(self, v0v1v2, tie_rank=None):
         """Host only: the words the pose kernels make -> (tris uint32 [n_prims, 16] in leaf order, shade uint32 [n_prims, 8]
         in Vec order, nodes uint32 [n_nodes, 8] in nodes()' word order with the planes moved by cull_delta)."""
         v, rank = self._pose_arrays(v0v1v2, tie_rank)
         t, s, n = self._pose_outputs()
-        _check(_lib.rtx_scene_posed_records(self._h, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
-                                            t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)),
-               "rtx_scene_posed_records")
+        _check(_lib.rtx_scene_posed_records(self._h, _fp(v), _up(rank), _up(t), _up(s), _up(n)), "rtx_scene_posed_records")
         return t, s, n
 
     def debug_pose(self, device=0):
         """Diagnostics: the pose `device` holds, copied back, in posed_records' layout."""
         t, s, n = self._pose_outputs()
-        _check(_lib.rtx_debug_pose(self._h, device, t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)),
-               "rtx_debug_pose")
+        _check(_lib.rtx_debug_pose(self._h, device, _up(t), _up(s), _up(n)), "rtx_debug_pose")
         return t, s, n
 
     # -- another light for views and shaded rays: the light= keyword of render_view* and shade_rays*
@@ -1132,16 +1150,12 @@ class Scene:
         """pose() with the tree rebuilt on the device: the tree proper's records sorted by Morton key, a balanced tree over
         the sorted runs, boxes by the refit kernels (rtx_scene_pose_rebuilt).  stats: kernel_ms is the kernels' time."""
         v, rank = self._pose_arrays(v0v1v2, tie_rank)
-        st = Stats()
-        _check(_lib.rtx_scene_pose_rebuilt(self._h, device, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
-                                           int(reference_tree), C.byref(st) if stats else None), "rtx_scene_pose_rebuilt")
-        return st.asdict() if stats else None
+        return self._pose("rtx_scene_pose_rebuilt", device, (_fp(v), _up(rank)), None, reference_tree, stats)
 
     def pose_rebuilt_device(self, device, d_v0v1v2_ptr, d_tie_rank_ptr=None, stream=None):
         """Asynchronous rebuilt pose from device arrays the caller owns (n_tris x 9 float32; n_prims uint32 or None)."""
-        _check(_lib.rtx_scene_pose_rebuilt_device(self._h, device, C.c_void_p(d_v0v1v2_ptr),
-                                                  C.c_void_p(d_tie_rank_ptr) if d_tie_rank_ptr else None,
-                                                  C.c_void_p(stream) if stream else None), "rtx_scene_pose_rebuilt_device")
+        self._pose("rtx_scene_pose_rebuilt_device", device,
+                   (C.c_void_p(d_v0v1v2_ptr), C.c_void_p(d_tie_rank_ptr) if d_tie_rank_ptr else None), stream=stream)
 
     def rebuilt_counts(self):
         """Node records of the rebuilt stream (rtx_scene_rebuilt_counts)."""
@@ -1149,40 +1163,32 @@ class Scene:
         _check(_lib.rtx_scene_rebuilt_counts(self._h, C.byref(out)), "rtx_scene_rebuilt_counts")
         return int(out.value)
 
-    def _rebuilt_outputs(self):
-        n_tree = self.n_prims - self.info()["n_global"]
-        return (np.zeros(n_tree, np.uint32), np.zeros((self.n_prims, 16), np.uint32), np.zeros((self.n_prims, 8), np.uint32),
-                np.zeros((self.rebuilt_counts(), 8), np.uint32))
-
     def rebuilt_records(self, v0v1v2, tie_rank=None):
         """Host only: the words a rebuilt pose makes -> (keys uint64 [n_tree], perm uint32 [n_tree] — positions of the
         uploaded primitive array in sorted order —, tris uint32 [n_prims, 16] in sorted order, shade uint32 [n_prims, 8] in
         Vec order, nodes uint32 [rebuilt_counts(), 8] with the planes moved by cull_delta)."""
         v, rank = self._pose_arrays(v0v1v2, tie_rank)
-        perm, t, s, n = self._rebuilt_outputs()
+        perm, t, s, n = self._pose_outputs(rebuilt=True)
         keys = np.zeros(len(perm), np.uint64)
-        _check(_lib.rtx_scene_rebuilt_records(self._h, _fp(v), rank.ctypes.data_as(u32p) if rank is not None else None,
-                                              keys.ctypes.data_as(C.POINTER(C.c_uint64)), perm.ctypes.data_as(u32p),
-                                              t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)),
-               "rtx_scene_rebuilt_records")
+        _check(_lib.rtx_scene_rebuilt_records(self._h, _fp(v), _up(rank), keys.ctypes.data_as(C.POINTER(C.c_uint64)), _up(perm),
+                                              _up(t), _up(s), _up(n)), "rtx_scene_rebuilt_records")
         return keys, perm, t, s, n
 
     def rebuilt_aimed(self, v0v1v2, eye):
         """Host only: the aim kernels' output over the rebuilt pose for `eye` -> uint32 [rebuilt_counts(), 8]."""
         v, _ = self._pose_arrays(v0v1v2, None)
         aimed = np.zeros((self.rebuilt_counts(), 8), np.uint32)
-        _check(_lib.rtx_scene_rebuilt_aimed(self._h, _fp(v), _fp(_f3(eye)), aimed.ctypes.data_as(u32p)), "rtx_scene_rebuilt_aimed")
+        _check(_lib.rtx_scene_rebuilt_aimed(self._h, _fp(v), _fp(_f3(eye)), _up(aimed)), "rtx_scene_rebuilt_aimed")
         return aimed
 
     def debug_pose_rebuilt(self, eye=None, device=0):
         """Diagnostics: the rebuilt pose `device` holds, copied back -> (perm, tris, shade, nodes, aimed or None without an
         eye), in rebuilt_records' layout; aimed: the aim kernels run over it for `eye`."""
-        perm, t, s, n = self._rebuilt_outputs()
-        aimed = np.zeros_like(n)
-        _check(_lib.rtx_debug_pose_rebuilt(self._h, device, _fp(_f3(eye)) if eye is not None else None, perm.ctypes.data_as(u32p),
-                                           t.ctypes.data_as(u32p), s.ctypes.data_as(u32p), n.ctypes.data_as(u32p),
-                                           aimed.ctypes.data_as(u32p) if eye is not None else None), "rtx_debug_pose_rebuilt")
-        return perm, t, s, n, (aimed if eye is not None else None)
+        perm, t, s, n = self._pose_outputs(rebuilt=True)
+        aimed = np.zeros_like(n) if eye is not None else None
+        _check(_lib.rtx_debug_pose_rebuilt(self._h, device, _fp(_f3(eye)) if eye is not None else None, _up(perm), _up(t), _up(s),
+                                           _up(n), _up(aimed)), "rtx_debug_pose_rebuilt")
+        return perm, t, s, n, aimed
 
     # -- a pose that states every field of a primitive: spheres move, colours change.  None = as uploaded
     def _prims_struct(self, v0v1v2, spheres, rgb, sphere_rgb, tie_rank):
@@ -1205,39 +1211,31 @@ class Scene:
         (float32 [n_tris, 3], [n_spheres, 3]) stated too; None: as uploaded (v0v1v2: the scene's own vertices)
         (rtx_scene_pose_prims).  stats: kernel_ms is the kernels' time, the overlay kernel's included."""
         prims, keep = self._prims_struct(v0v1v2, spheres, rgb, sphere_rgb, tie_rank)
-        st = Stats()
-        _check(_lib.rtx_scene_pose_prims(self._h, device, C.byref(prims), POSE_REBUILT if rebuilt else 0, int(reference_tree),
-                                         C.byref(st) if stats else None), "rtx_scene_pose_prims")
-        return st.asdict() if stats else None
+        return self._pose("rtx_scene_pose_prims", device, (C.byref(prims),), rebuilt, reference_tree, stats)
 
     def pose_prims_device(self, device, d_v0v1v2_ptr, d_spheres_ptr=None, d_rgb_ptr=None, d_sphere_rgb_ptr=None,
                           d_tie_rank_ptr=None, rebuilt=False, stream=None):
         """Asynchronous pose of every field from device arrays the caller owns (None or 0: as uploaded)."""
         prims = RtxPosePrims(*[p if p else None for p in (d_v0v1v2_ptr, d_spheres_ptr, d_rgb_ptr, d_sphere_rgb_ptr, d_tie_rank_ptr)])
-        _check(_lib.rtx_scene_pose_prims_device(self._h, device, C.byref(prims), POSE_REBUILT if rebuilt else 0,
-                                                C.c_void_p(stream) if stream else None), "rtx_scene_pose_prims_device")
+        self._pose("rtx_scene_pose_prims_device", device, (C.byref(prims),), rebuilt, stream=stream)
 
     def pose_prims_records(self, v0v1v2=None, spheres=None, rgb=None, sphere_rgb=None, tie_rank=None, rebuilt=False):
         """Host only: the words such a pose makes -> posed_records' (tris, shade, nodes), or with rebuilt=True
         rebuilt_records' (keys, perm, tris, shade, nodes)."""
         prims, keep = self._prims_struct(v0v1v2, spheres, rgb, sphere_rgb, tie_rank)
-        if rebuilt:
-            perm, t, s, n = self._rebuilt_outputs()
-            keys = np.zeros(len(perm), np.uint64)
-        else:
-            t, s, n = self._pose_outputs()
+        perm, t, s, n = self._pose_outputs(rebuilt=True) if rebuilt else (None,) + self._pose_outputs()
+        keys = np.zeros(len(perm), np.uint64) if rebuilt else None
         _check(_lib.rtx_scene_pose_prims_records(self._h, C.byref(prims), POSE_REBUILT if rebuilt else 0,
-                                                 keys.ctypes.data_as(C.POINTER(C.c_uint64)) if rebuilt else None,
-                                                 perm.ctypes.data_as(u32p) if rebuilt else None, t.ctypes.data_as(u32p),
-                                                 s.ctypes.data_as(u32p), n.ctypes.data_as(u32p)), "rtx_scene_pose_prims_records")
+                                                 keys.ctypes.data_as(C.POINTER(C.c_uint64)) if rebuilt else None, _up(perm), _up(t),
+                                                 _up(s), _up(n)), "rtx_scene_pose_prims_records")
         return (keys, perm, t, s, n) if rebuilt else (t, s, n)
 
     def pose_prims_aimed(self, eye, v0v1v2=None, spheres=None, rgb=None, sphere_rgb=None, rebuilt=False):
         """Host only: the aim kernels' output over such a pose for `eye` -> uint32 [n_nodes or rebuilt_counts(), 8]."""
         prims, keep = self._prims_struct(v0v1v2, spheres, rgb, sphere_rgb, None)
         aimed = np.zeros((self.rebuilt_counts() if rebuilt else self.info()["n_nodes"], 8), np.uint32)
-        _check(_lib.rtx_scene_pose_prims_aimed(self._h, C.byref(prims), POSE_REBUILT if rebuilt else 0, _fp(_f3(eye)),
-                                               aimed.ctypes.data_as(u32p)), "rtx_scene_pose_prims_aimed")
+        _check(_lib.rtx_scene_pose_prims_aimed(self._h, C.byref(prims), POSE_REBUILT if rebuilt else 0, _fp(_f3(eye)), _up(aimed)),
+               "rtx_scene_pose_prims_aimed")
         return aimed
 
     # -- a pose the device makes from the scene's geometry as created and a set of affine moves
@@ -1261,30 +1259,26 @@ class Scene:
         major), group uint32 [n_prims] (the move each Vec position follows, MOVE_NONE: none; None: all follow move 0),
         radius_scale float32 [n_moves] or None (rtx_scene_pose_moved).  stats: kernel_ms includes the move kernel."""
         mv, keep = self._moves_struct(moves, group, radius_scale, rgb, sphere_rgb, tie_rank)
-        st = Stats()
-        _check(_lib.rtx_scene_pose_moved(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0, int(reference_tree),
-                                         C.byref(st) if stats else None), "rtx_scene_pose_moved")
-        return st.asdict() if stats else None
+        return self._pose("rtx_scene_pose_moved", device, (C.byref(mv),), rebuilt, reference_tree, stats)
 
     def pose_moved_device(self, device, n_moves, d_moves_ptr, d_group_ptr=None, d_radius_scale_ptr=None, d_rgb_ptr=None,
                           d_sphere_rgb_ptr=None, d_tie_rank_ptr=None, rebuilt=False, stream=None):
         """Asynchronous moved pose from device arrays the caller owns (None or 0: no such array)."""
         mv = RtxPoseMoves(int(n_moves), *[p if p else None for p in (d_moves_ptr, d_group_ptr, d_radius_scale_ptr, d_rgb_ptr,
                                                                      d_sphere_rgb_ptr, d_tie_rank_ptr)])
-        _check(_lib.rtx_scene_pose_moved_device(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0,
-                                                C.c_void_p(stream) if stream else None), "rtx_scene_pose_moved_device")
+        self._pose("rtx_scene_pose_moved_device", device, (C.byref(mv),), rebuilt, stream=stream)
 
     def moved_prims(self, moves, group=None, radius_scale=None):
         """Host only: the arrays such a pose makes -> (v0v1v2 float32 [n_tris, 9], spheres float32 [n_spheres, 4])
         (rtx_scene_moved_prims)."""
         mv, keep = self._moves_struct(moves, group, radius_scale)
-        v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
+        v, sph = self._prim_outputs()
         _check(_lib.rtx_scene_moved_prims(self._h, C.byref(mv), _fp(v), _fp(sph)), "rtx_scene_moved_prims")
         return v, sph
 
     def debug_moved_prims(self, device=0):
         """Diagnostic: the arrays the move kernel last wrote on `device`, in moved_prims' form (rtx_debug_moved_prims)."""
-        v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
+        v, sph = self._prim_outputs()
         _check(_lib.rtx_debug_moved_prims(self._h, device, _fp(v), _fp(sph)), "rtx_debug_moved_prims")
         return v, sph
 
@@ -1320,24 +1314,20 @@ class Scene:
         """pose_moved() with the bound skin naming the moves: every triangle corner blends up to four of them
         (rtx_scene_pose_skinned).  stats: kernel_ms includes the skin kernel."""
         mv, keep = self._moves_struct(moves, None, radius_scale, rgb, sphere_rgb, tie_rank)
-        st = Stats()
-        _check(_lib.rtx_scene_pose_skinned(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0, int(reference_tree),
-                                           C.byref(st) if stats else None), "rtx_scene_pose_skinned")
-        return st.asdict() if stats else None
+        return self._pose("rtx_scene_pose_skinned", device, (C.byref(mv),), rebuilt, reference_tree, stats)
 
     def pose_skinned_device(self, device, n_moves, d_moves_ptr, d_radius_scale_ptr=None, d_rgb_ptr=None, d_sphere_rgb_ptr=None,
                             d_tie_rank_ptr=None, rebuilt=False, stream=None):
         """Asynchronous skinned pose from device arrays the caller owns (None or 0: no such array)."""
         mv = RtxPoseMoves(int(n_moves), *[p if p else None for p in (d_moves_ptr, None, d_radius_scale_ptr, d_rgb_ptr,
                                                                      d_sphere_rgb_ptr, d_tie_rank_ptr)])
-        _check(_lib.rtx_scene_pose_skinned_device(self._h, device, C.byref(mv), POSE_REBUILT if rebuilt else 0,
-                                                  C.c_void_p(stream) if stream else None), "rtx_scene_pose_skinned_device")
+        self._pose("rtx_scene_pose_skinned_device", device, (C.byref(mv),), rebuilt, stream=stream)
 
     def skinned_prims(self, moves, radius_scale=None):
         """Host only: the arrays such a pose makes -> (v0v1v2 float32 [n_tris, 9], spheres float32 [n_spheres, 4])
         (rtx_scene_skinned_prims)."""
         mv, keep = self._moves_struct(moves, None, radius_scale)
-        v, sph = np.zeros((len(self.tris), 9), np.float32), np.zeros((len(self.spheres), 4), np.float32)
+        v, sph = self._prim_outputs()
         _check(_lib.rtx_scene_skinned_prims(self._h, C.byref(mv), _fp(v), _fp(sph)), "rtx_scene_skinned_prims")
         return v, sph
 

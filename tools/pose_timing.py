@@ -18,11 +18,22 @@ view_posed_identity must give view_unposed's bytes and every posed_turn_K its fr
 One JSON document on stdout, and in --out when given.
 
     python tools/pose_timing.py --out profiles/pose_timing.json
+
+--pose-path --parent DIR --parent2 DIR [--bench]: in place of the above, the cost of every pose entry point on big_bunny +
+ground in the 1920 x 1080 frame, of this build beside two separate builds of the parent commit under DIR.  The ten entry
+points refitted, and rebuilt where they take the flag; a host call as the host's clock around it (wall) and as
+RtxStats.total_ms (total), a device-resident call between two events on its stream.  Every build runs in a child process
+of its own, --rounds times, who goes first rotating; in a child --repeats rounds of one call per case follow --warmup
+rounds.  Per case: the pooled samples' summary per build, and whether this build's median is no further from the nearer
+parent's than the two parents' medians are apart.  --bench adds bench.py --gpus 1 --steps 20 --warmup 3 of the three.
+
+    python tools/pose_timing.py --pose-path --parent build_ab/parent --parent2 build_ab/parent2 --bench --out run_1.json
 """
 import argparse
 import importlib
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -43,13 +54,140 @@ def turned(tris, n_mesh, degrees):
     return np.ascontiguousarray(out.reshape(-1, 9).astype(np.float32))
 
 
+def summary(v):
+    return {"min_ms": round(min(v), 5), "median_ms": round(float(np.median(v)), 5), "spread": round((max(v) - min(v)) / min(v), 4)}
+
+
+def pose_calls(root, warmup, repeats):
+    """--pose-path's child: the build under `root` (its binding and its library) -> the samples of every case"""
+    import torch  # before librtx.so: one HIP runtime per process (tests/conftest.py)
+    sys.path.insert(0, root)
+    rtx = importlib.import_module("ray-tracer-rust_amd")
+    tris, rgb = rtx.default_primitives([os.path.join(root, "models", "big_bunny.obj")])
+    n_mesh = len(tris) - 1
+    sc = rtx.Scene(rtx.DEFAULT_WIDTH, rtx.DEFAULT_HEIGHT, tris, rgb, rtx.gen_samples())
+    sc.upload(0)
+    v = turned(tris, n_mesh, TURN_DEGREES[0])
+    mesh = np.array(tris, np.float64).reshape(-1, 3, 3)[:n_mesh].reshape(-1, 3)
+    c, a = 0.5 * (mesh.min(axis=0) + mesh.max(axis=0)), np.deg2rad(TURN_DEGREES[0])
+    lin = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    turn = np.concatenate([lin, (c - lin @ c).reshape(3, 1)], axis=1).reshape(12)
+    moves = np.stack([np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0.0]), turn]).astype(np.float32)
+    group = np.full(len(tris), 0xFFFFFFFF, np.uint32)      # the mesh follows move 1, the ground none
+    group[:n_mesh] = 1
+    bones = np.full((len(tris), 3, 4), 0xFFFFFFFF, np.uint32)
+    bones[:n_mesh, :, 0], bones[:n_mesh, :, 1] = 0, 1
+    weights = np.zeros((len(tris), 3, 4), np.float32)
+    weights[:n_mesh, :, 0], weights[:n_mesh, :, 1] = 0.25, 0.75
+    sc.skin(bones, weights)
+    stream = torch.cuda.Stream(device="cuda:0")
+    s = stream.cuda_stream
+    dev = {k: torch.from_numpy(x.view(np.int32) if x.dtype == np.uint32 else x).to("cuda:0") for k, x in
+           dict(v=v, rgb=np.ascontiguousarray(rgb, np.float32), moves=moves, group=group).items()}
+    torch.cuda.synchronize()
+    d = {k: t.data_ptr() for k, t in dev.items()}
+    host = {"pose": lambda r, **kw: (sc.pose_rebuilt if r else sc.pose)(v, **kw),
+            "pose_prims": lambda r, **kw: sc.pose_prims(v, rgb=rgb, rebuilt=r, **kw),
+            "pose_moved": lambda r, **kw: sc.pose_moved(moves, group, rebuilt=r, **kw),
+            "pose_skinned": lambda r, **kw: sc.pose_skinned(moves, rebuilt=r, **kw)}
+    device = {"pose_device": lambda r: (sc.pose_rebuilt_device if r else sc.pose_device)(0, d["v"], None, s),
+              "pose_prims_device": lambda r: sc.pose_prims_device(0, d["v"], d_rgb_ptr=d["rgb"], rebuilt=r, stream=s),
+              "pose_moved_device": lambda r: sc.pose_moved_device(0, 2, d["moves"], d["group"], rebuilt=r, stream=s),
+              "pose_skinned_device": lambda r: sc.pose_skinned_device(0, 2, d["moves"], rebuilt=r, stream=s)}
+    ms = {}
+    for i in range(warmup + repeats):
+        keep = ms if i >= warmup else {}
+        for r in (False, True):
+            tree = "rebuilt" if r else "refitted"
+            for name, f in host.items():
+                stream.synchronize()
+                t0 = time.perf_counter()
+                f(r)
+                keep.setdefault("%s_%s_wall" % (name, tree), []).append(1e3 * (time.perf_counter() - t0))
+                keep.setdefault("%s_%s_total" % (name, tree), []).append(f(r, stats=True)["total_ms"])
+            for name, f in device.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                f(r)
+                e1.record(stream)
+                e1.synchronize()
+                keep.setdefault("%s_%s" % (name, tree), []).append(e0.elapsed_time(e1))
+    sc.close()
+    return {"lib": rtx.rtx.LIB_PATH, "ms": ms}
+
+
+def pose_path(args, roots):
+    """--pose-path: pose_calls of every build in a child process each, --rounds times -> per case the summaries and the verdict"""
+    pooled = {who: {} for who, _ in roots}
+    for k in range(args.rounds):
+        for who, root in roots[k % len(roots):] + roots[:k % len(roots)]:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--pose-calls", root, "--repeats", str(args.repeats), "--warmup",
+                                str(args.warmup)], capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                raise SystemExit("child for %s failed (%d):\n%s" % (who, r.returncode, (r.stdout + r.stderr)[-3000:]))
+            child = json.loads(r.stdout.splitlines()[-1])
+            assert child["lib"].startswith(root + os.sep), child["lib"]
+            for case, v in child["ms"].items():
+                pooled[who].setdefault(case, []).extend(v)
+            print("round %d, %s: done" % (k, who), file=sys.stderr, flush=True)
+    out = {}
+    for case in pooled["this"]:
+        med = {who: float(np.median(v[case])) for who, v in pooled.items()}
+        out[case] = {who: summary(v[case]) for who, v in pooled.items()}
+        between = abs(med["parent"] - med["parent2"])
+        nearer = min(("parent", "parent2"), key=lambda who: abs(med["this"] - med[who]))
+        out[case].update(parents_apart_ms=round(between, 5), this_minus_nearer_parent_ms=round(med["this"] - med[nearer], 5),
+                         within=bool(abs(med["this"] - med[nearer]) <= between))
+    return out
+
+
+def bench_line(root):
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3"],
+                       capture_output=True, text=True, cwd=root, timeout=900)
+    if r.returncode != 0:
+        raise SystemExit("bench.py under %s failed (%d):\n%s" % (root, r.returncode, (r.stdout + r.stderr)[-3000:]))
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    return {k: v for k, v in line.items() if not isinstance(v, (dict, list))}      # (the scalars)
+
+
+def pose_path_doc(args):
+    if not (args.parent and args.parent2):
+        raise SystemExit("--pose-path needs --parent and --parent2: two builds of the parent commit")
+    roots = [(who, os.path.abspath(root)) for who, root in (("parent", args.parent), ("this", ROOT), ("parent2", args.parent2))]
+    doc = {"frame": [1920, 1080], "rounds": args.rounds, "repeats": args.repeats, "warmup": args.warmup, "pose_calls": pose_path(args, roots)}
+    doc["not_within"] = sorted(case for case, row in doc["pose_calls"].items() if not row["within"])
+    if args.bench:
+        lines = {who: [] for who, _ in roots}
+        for k in range(args.rounds):
+            for who, root in roots[::-1] if k % 2 else roots:
+                lines[who].append(bench_line(root))
+        doc["bench"] = {"command": "bench.py --gpus 1 --steps 20 --warmup 3", **lines}
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-1m", action="store_true")
+    ap.add_argument("--pose-path", action="store_true", help="the ten entry points of this build beside two builds of the parent")
+    ap.add_argument("--pose-calls", default=None, metavar="ROOT", help="--pose-path's child: the pose calls of the build under ROOT")
+    ap.add_argument("--parent", default=None, help="--pose-path: the parent commit's tree, built")
+    ap.add_argument("--parent2", default=None, help="--pose-path: a second copy of it")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--bench", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.pose_calls:
+        print(json.dumps(pose_calls(os.path.abspath(args.pose_calls), args.warmup, args.repeats)))
+        return
+    if args.pose_path:
+        text = json.dumps(pose_path_doc(args), indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
 
     import torch  # before librtx.so: one HIP runtime per process (tests/conftest.py)
     sys.path.insert(0, ROOT)
