@@ -103,6 +103,21 @@ __device__ __forceinline__ bool slab_fast_fma(float lox, float loy, float loz, f
     return !(t_in - t_out > slack) && !(t_out < behind);   // written so that a NaN can only accept
 }
 
+// The same test as a lane mask, each comparison voted on its own and the votes combined by the scalar unit: ANDed as a
+// bool the pair is first turned into a value per lane and compared again, two vector instructions more.
+__device__ __forceinline__ unsigned long long slab_fast_fma_mask(float lox, float loy, float loz, float hix, float hiy, float hiz,
+                                                                 float ix, float iy, float iz, float nx, float ny, float nz,
+                                                                 float slack0, float behind)
+{
+    const float ax = __builtin_fmaf(lox, ix, nx), bx = __builtin_fmaf(hix, ix, nx);
+    const float ay = __builtin_fmaf(loy, iy, ny), by = __builtin_fmaf(hiy, iy, ny);
+    const float az = __builtin_fmaf(loz, iz, nz), bz = __builtin_fmaf(hiz, iz, nz);
+    const float t_in = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+    const float t_out = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+    const float slack = __builtin_fmaf(fabsf(t_in) + fabsf(t_out), 0x1p-20f, slack0);
+    return ballot(!(t_in - t_out > slack)) & ballot(!(t_out < behind));
+}
+
 // a node record through the constant address space (scalar loads); field-wise because a struct copy
 // across address spaces has no implicit constructor
 // (the stream in HBM is in NodeDev order, see scene_prep.h; the pointer type only carries the record size)
@@ -286,6 +301,7 @@ struct LaneRay {
     float ix, iy, iz;     // 1/d, used by the multiply-based culling only
     float nx, ny, nz;     // -(o * 1/d)                       "
     float slack0, behind; // E and -1.00001 E of slab_fast_fma "
+    float cs;             // 2^-22 (|ox| + |oy| + |oz|): the origin's part of candidate_occludes_voted's margin "
     float best_t;         // minimum accepted distance so far
     uint32_t best_idx;    // caller-order index of its triangle, kNone = no hit
     bool active;          // lanes without a ray never vote
@@ -305,6 +321,31 @@ __device__ __forceinline__ bool candidate_occludes(const LaneRay &r, float t)
     return !(sqrtf(qx * qx + qy * qy + qz * qz) > r.limit);                                                     // main.rs:221
 }
 
+// The same answer from t alone, where t and the light's distance do not nearly coincide.  f(t) above is a rounding of
+// t |d|: per component fl(o - fl(o + fl(t d))) is off from -t d by at most 3u |t d| + u |o| (u = 2^-24: the product, the
+// sum, the difference), the sum of squares and the square root add 2.5u relative, and |d| is within 2u of 1 (Ray::new), so
+//     |f(t) - t| <= 8u t + 1.0001u (|ox| + |oy| + |oz|)          for t >= 1 (the leaf rule) and finite operands.
+// With twice that in t and four times that in the origin (cs, ray_cull_constants), each side one fused multiply-add:
+//     fma(t, 1 + 2^-20, cs) <= limit   =>   f(t) <= limit: the candidate occludes
+//     fma(t, 1 - 2^-20, -cs) > limit   =>   f(t) >  limit: it does not
+// (the fma's own rounding, u of its value, is inside the spare half).  Culling arithmetic: no pixel value is made of
+// these numbers.  A NaN in t, the origin or the limit fails both comparisons, and so does an infinite origin (cs is
+// infinite: inf <= limit only for an infinite limit, which f(t) never exceeds either; inf - inf is a NaN).  An overflowed
+// t = +inf certifies "does not occlude" against a finite limit, which is f's answer too WHEN every direction component
+// is non-zero (t d is infinite in each, f = inf) — with a zero component f is a NaN and the reference's comparison says
+// "occludes": the short way is taken by walks of regular directions only (FAST_OK, leaf_triangles).
+// DESIGN.md section 2; tests/test_occluder_certificate.py restates both sides in float32.  The wavefront evaluates the
+// reference's expression only when some lane that holds a candidate is left undecided: t within a few ulp of the
+// light's distance, or an origin whose coordinates dwarf t.
+__device__ __forceinline__ bool candidate_occludes_voted(const LaneRay &r, float t)
+{
+    const bool yes = __builtin_fmaf(t, 1.0f + 0x1p-20f, r.cs) <= r.limit;
+    const bool no = __builtin_fmaf(t, 1.0f - 0x1p-20f, -r.cs) > r.limit;
+    // (called by the lanes that hold a candidate: the votes are theirs alone)
+    if ((ballot(yes) | ballot(no)) == ballot(true)) return yes;
+    return candidate_occludes(r, t);
+}
+
 // origin, direction and the result fields; the constants of the multiply-based culling are added by ray_cull_constants
 // (a chunk that has nothing to walk never needs them)
 __device__ __forceinline__ LaneRay make_ray_bare(bool active, float ox, float oy, float oz, float dx, float dy, float dz)
@@ -313,6 +354,7 @@ __device__ __forceinline__ LaneRay make_ray_bare(bool active, float ox, float oy
     r.ox = ox; r.oy = oy; r.oz = oz;
     r.dx = dx; r.dy = dy; r.dz = dz;
     r.ix = r.iy = r.iz = r.nx = r.ny = r.nz = r.slack0 = r.behind = 0.0f;
+    r.cs = __builtin_nanf("");     // without the constants no candidate is settled by candidate_occludes_voted's short way
     r.best_t = __builtin_inff();
     r.best_idx = kNone;
     r.active = active;
@@ -330,6 +372,7 @@ __device__ __forceinline__ void ray_cull_constants(LaneRay &r)
     r.nx = -px; r.ny = -py; r.nz = -pz;
     r.slack0 = __builtin_fmaf(fabsf(px) + fabsf(py) + fabsf(pz), 0x1p-21f, 0x1p-100f);
     r.behind = -1.00001f * r.slack0;
+    r.cs = 0x1p-22f * (fabsf(r.ox) + fabsf(r.oy) + fabsf(r.oz));
 }
 
 __device__ __forceinline__ LaneRay make_ray(bool active, float ox, float oy, float oz, float dx, float dy, float dz)
@@ -545,8 +588,8 @@ __device__ __forceinline__ void leaf_triangles(const TriRec RTX_CONSTANT *__rest
         // stream's.  Only when few rays are left: the count and its branch cost more than the test saves.)
         if (ANYHIT && FAST_OK && !VEC) {   // shadow walks only
             // (the record's box is the exact one, not moved outwards like the stream's: the test widens itself, slab_fast_fma)
-            if ((ballot(slab_fast_fma(tr->bmin[0], tr->bmin[1], tr->bmin[2], tr->bmax[0], tr->bmax[1], tr->bmax[2], r.ix, r.iy, r.iz,
-                                      r.nx, r.ny, r.nz, r.slack0, r.behind)) & alive) == 0ull) continue;
+            if ((slab_fast_fma_mask(tr->bmin[0], tr->bmin[1], tr->bmin[2], tr->bmax[0], tr->bmax[1], tr->bmax[2], r.ix, r.iy, r.iz,
+                                    r.nx, r.ny, r.nz, r.slack0, r.behind) & alive) == 0ull) continue;
         }
         const float pvx = r.dy * e2z - r.dz * e2y;                                   // :69
         const float pvy = r.dz * e2x - r.dx * e2z;
@@ -575,7 +618,7 @@ __device__ __forceinline__ void leaf_triangles(const TriRec RTX_CONSTANT *__rest
             if (own_box_passes<FAST_OK>(tr->bmin[0], tr->bmin[1], tr->bmin[2], tr->bmax[0], tr->bmax[1], tr->bmax[2], r)) {
                 const uint32_t idx = tr->idx;
                 if (ANYHIT) {
-                    if (candidate_occludes(r, t)) { r.best_t = t; r.best_idx = idx; }
+                    if (FAST_OK ? candidate_occludes_voted(r, t) : candidate_occludes(r, t)) { r.best_t = t; r.best_idx = idx; }
                 } else {
                     bool take = t < r.best_t;
                     if (!take && t == r.best_t && r.best_idx != kNone)   // exact tie: right-most reference leaf wins (bvh.rs:123-130)
@@ -841,12 +884,12 @@ __device__ __forceinline__ void advance_to_leaf(const NodeRec RTX_CONSTANT *__re
                      : "vcc", "scc", "s64", "s65", "s66", "s67", "s68", "s69"
     if (COUNT) {
         asm volatile(RTX_ADVANCE_BODY("s_add_u32 %[n], %[n], 1\n\t")
-                     : [off] "+s"(o), [n] "+s"(n), [nxt] "=&s"(nxt), [skip] "=&s"(skip), [m] "=&s"(m), "={s70}"(w6), "={s71}"(w7),
+                     : [off] "+s"(o), [n] "+s"(n), [nxt] "=&s"(nxt), [skip] "=&s"(skip), [m] "=&s"(m), "=&{s70}"(w6), "=&{s71}"(w7),
                        [a] "=&v"(a), [b] "=&v"(b), [c] "=&v"(c), [d] "=&v"(d), [e] "=&v"(e), [f] "=&v"(f), [g] "=&v"(g)
                      RTX_ADVANCE_OPERANDS);
     } else {
         asm volatile(RTX_ADVANCE_BODY("")
-                     : [off] "+s"(o), [nxt] "=&s"(nxt), [skip] "=&s"(skip), [m] "=&s"(m), "={s70}"(w6), "={s71}"(w7),
+                     : [off] "+s"(o), [nxt] "=&s"(nxt), [skip] "=&s"(skip), [m] "=&s"(m), "=&{s70}"(w6), "=&{s71}"(w7),
                        [a] "=&v"(a), [b] "=&v"(b), [c] "=&v"(c), [d] "=&v"(d), [e] "=&v"(e), [f] "=&v"(f), [g] "=&v"(g)
                      RTX_ADVANCE_OPERANDS);
     }
