@@ -980,6 +980,44 @@ int rtx_render_view_adaptive_device(RtxScene *scene, int device, const RtxView *
                                     uint32_t n_pairs, const RtxAdaptRule *rule, void *d_moments, void *d_tiles, void *d_rgb,
                                     void *d_shade, void *stream);
 
+/* ---- The adaptive mean through the render pipeline: a stopped tile is not scheduled ------------------------------------------
+ * rtx_render_view_rows_adaptive / _device: rtx_render_view_adaptive / _device (above) in every respect, with the pipeline's
+ * MASKED record launch in the masked view kernel's place.  For a full-width rectangle (x0 == 0, nx == width) every output is
+ * the view-kernel call's, word for word: moments, tile states with their stop frames, records and bytes.  Argument checks,
+ * in this order: the adaptive call's; full width (RTX_ERR_BAD_ARG); then — decided on the host before a device is looked for,
+ * as rtx_render_view_rows_mean does — the eye's range rule, a light with a vertex that is not finite, and a frame whose
+ * shaft margin is not finite (RTX_ERR_UNSUPPORTED).  Per frame k, on the call's stream, with no host wait between frames: the
+ * sample-table kernel; the light's points, tour and boxes; the masked record launch into the mean's scratch records (a first
+ * frame: the unmasked record launch, rtx_render_view_rows_shade's); the moment add.  After the last frame the resolve.  The
+ * aim kernels run once.  The masked launch is the record launch whose scheduling pass (namespace rtxn) reads, per 8 x 8 tile
+ * of the rectangle, the tile's RtxTileState — tiles row by row, as everywhere above — and evaluates the stopped test: a
+ * stopped tile gets a descriptor that schedules nothing (rtx_debug_tile_descs: class 0xFFFFFFFF, no hits, no flags, nothing
+ * counted), makes no ray, stores no pixel, queues nothing and touches no counter, and so never reaches the shading pass or
+ * the reference pass.  All n_frames frames are always enqueued; a frame in which every tile has stopped still runs the
+ * light's kernels and the pipeline's four dispatches over empty lists.  The scene is not written; the scratch buffers, the
+ * light buffers and, when posed, the pose are guarded as rtx_render_view_rows_mean's are; rtx_launch_timings and
+ * rtx_debug_tile_descs see the frames' launches; no capture and replay.  stats (host variant): as rtx_render_view_adaptive's.
+ *
+ * rtx_render_view_rows_shade_masked_device: the building block, device-resident only — rtx_render_view_rows_shade_device
+ * behind the mask.  d_tiles: ceil(width/8) * ceil(ny/8) RtxTileState written by an earlier launch on the stream (or by the
+ * caller), 8-byte aligned.  A tile stopped under `rule` keeps the words its records in d_shade held; a live tile's records
+ * are the unmasked call's, and d_counters receives the live tiles' counts alone.  A caller whose frames differ in pose, eye
+ * or light pairs it with rtx_moment_add_device under the same states and rule: adaptive motion blur.  Further
+ * RTX_ERR_BAD_ARG beyond the unmasked call's: a NULL d_tiles or one that is not 8-byte aligned, a NULL rule,
+ * min_frames == 0, a max_variance that is negative or NaN. */
+int rtx_render_view_rows_adaptive(RtxScene *scene, int device, const RtxView *view, const RtxLight *light /* NULL = the scene's */,
+                                  uint32_t flags /* RTX_MEAN_POSED or 0 */, const uint64_t *seeds, uint32_t n_frames,
+                                  uint32_t n_pairs, const RtxAdaptRule *rule, uint8_t *out_rgb, RtxPixelShade *out_shade,
+                                  RtxTileState *out_tiles /* may be NULL */, RtxStats *stats);
+int rtx_render_view_rows_adaptive_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags
+                                         /* RTX_MEAN_POSED | RTX_ADAPT_CONTINUE */, const uint64_t *seeds, uint32_t n_frames,
+                                         uint32_t n_pairs, const RtxAdaptRule *rule, void *d_moments, void *d_tiles, void *d_rgb,
+                                         void *d_shade, void *stream);
+int rtx_render_view_rows_shade_masked_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light,
+                                             uint32_t flags /* RTX_ROWS_POSED or 0 */, const void *d_tiles,
+                                             const RtxAdaptRule *rule, void *d_shade, size_t d_bytes, void *stream,
+                                             uint64_t *d_counters);
+
 /* Diagnostics: per 8x8 pixel tile of rows [row0,row0+nrows), RTX_WAVE_PROFILE_WORDS uint64 {node records
  * fetched, triangle records fetched, start, end, primary phase, shadow phase (slowest wavefront),
  * accumulation phase, reserved}, times in ticks of the 100 MHz device wall clock.  Call with

@@ -357,6 +357,20 @@ extern "C" {
                                            flags: u32, seeds: *const u64, n_frames: u32, n_pairs: u32, rule: *const RtxAdaptRule,
                                            d_moments: *mut c_void, d_tiles: *mut c_void, d_rgb: *mut c_void, d_shade: *mut c_void,
                                            stream: *mut c_void) -> c_int;
+    /// `rtx_render_view_adaptive` / `_device` through the render pipeline: full width only, every output word for word; a
+    /// stopped tile is not scheduled.  The eye's range rule and every frame's shaft margin are decided on the host.
+    pub fn rtx_render_view_rows_adaptive(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight, flags: u32,
+                                         seeds: *const u64, n_frames: u32, n_pairs: u32, rule: *const RtxAdaptRule, out_rgb: *mut u8,
+                                         out_shade: *mut RtxPixelShade, out_tiles: *mut RtxTileState, stats: *mut RtxStats) -> c_int;
+    pub fn rtx_render_view_rows_adaptive_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                                flags: u32, seeds: *const u64, n_frames: u32, n_pairs: u32, rule: *const RtxAdaptRule,
+                                                d_moments: *mut c_void, d_tiles: *mut c_void, d_rgb: *mut c_void, d_shade: *mut c_void,
+                                                stream: *mut c_void) -> c_int;
+    /// `rtx_render_view_rows_shade_device` behind a tile mask: a tile stopped under `rule` by its state in `d_tiles` (8-byte
+    /// aligned, tiles row by row) is not scheduled and its records in `d_shade` keep their words.
+    pub fn rtx_render_view_rows_shade_masked_device(scene: *mut RtxScene, device: c_int, view: *const RtxView, light: *const RtxLight,
+                                                    flags: u32, d_tiles: *const c_void, rule: *const RtxAdaptRule, d_shade: *mut c_void,
+                                                    d_bytes: usize, stream: *mut c_void, d_counters: *mut u64) -> c_int;
     /// Host only: `rtx_scene_light_walk_for`'s outputs on a scene reseeded with (`seed`, `n_pairs`); `light` NULL: the scene's.
     pub fn rtx_scene_light_walk_seeded(scene: *const RtxScene, light: *const RtxLight, seed: u64, n_pairs: u32,
                                        out_order: *mut u32, out_boxes: *mut f32, out_shaft_delta: *mut f32) -> c_int;

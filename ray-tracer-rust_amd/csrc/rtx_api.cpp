@@ -658,10 +658,17 @@ struct Timed {
 // split: the long list of the scene's own view (probe_split_of), or none.
 // d_shade: NULL, or where the launch writes RtxPixelShade records in place of d_out's bytes (the record forms of the kernels
 // that store a pixel: the two-pass pipeline's alone, without a profile or a list).
+// mask (with d_shade): NULL, or the tile states and the rule behind which the record launch schedules its tiles
+// (rtx_device.h: launch_trace_records_masked).
+struct TileMask {
+    const void *d_tiles;
+    RtxAdaptRule rule;
+};
 template <class Before>
 int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpec &ts, uint8_t *d_out,
                   unsigned long long *d_counters, unsigned long long *d_wave_prof, hipStream_t stream, Before before,
-                  const rtx::ProbeSplit &split = rtx::ProbeSplit{nullptr, 0u, 0u, 0u}, void *d_shade = nullptr)
+                  const rtx::ProbeSplit &split = rtx::ProbeSplit{nullptr, 0u, 0u, 0u}, void *d_shade = nullptr,
+                  const TileMask *mask = nullptr)
 {
     int rc;
     const size_t redo_cap = st.d_redo.capacity(), buckets_cap = st.ws.buckets.capacity();
@@ -683,7 +690,11 @@ int render_launch(DeviceState &st, const rtx::DeviceScene &S, const rtx::TileSpe
         st.words_launches = st.words_passes = 0;
     }
     if (ts.local_rows) st.launch_words_ready = false;     // until this launch is known to have gone out whole
-    if (d_shade)
+    if (d_shade && mask)
+        RTX_HIP(rtx::launch_trace_records_masked(S, ts, d_shade, S.nb_ray > 1u ? st.ws_record_hits.as<uint8_t>() : nullptr,
+                                                 st.d_redo.as<uint32_t>(), &ws, d_counters, kernel_variant(), stream, phases,
+                                                 st.words_launches, st.words_passes, mask->d_tiles, mask->rule));
+    else if (d_shade)
         RTX_HIP(rtx::launch_trace_records(S, ts, d_shade, S.nb_ray > 1u ? st.ws_record_hits.as<uint8_t>() : nullptr, st.d_redo.as<uint32_t>(),
                                           &ws, d_counters, kernel_variant(), stream, phases, st.words_launches, st.words_passes));
     else
@@ -1561,10 +1572,11 @@ int aim_at(const RtxScene *scene, DeviceGeometry &g, const float eye[3], hipStre
 // every posed coordinate respects, not from the geometry's extent.
 // table / n_pairs: NULL, or a table on the device that stands in for the scene's: the light kernels and the pipeline's read
 // it.  Whoever hands one in makes it on the stream in `before`.
+// mask (with d_shade): NULL, or the tile mask of the record launch (render_launch).
 template <class Before>
 int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const RtxView &v, uint8_t *d_out,
                      unsigned long long *d_counters, hipStream_t stream, Before before, const Lit *lit, float shaft_delta,
-                     void *d_shade = nullptr, const float2 *table = nullptr, uint32_t n_pairs = 0u)
+                     void *d_shade = nullptr, const float2 *table = nullptr, uint32_t n_pairs = 0u, const TileMask *mask = nullptr)
 {
     RTX_TRY(reserve_aimed(scene, g));
     if (lit) RTX_TRY(reserve_light(scene, st, *lit, true));
@@ -1588,7 +1600,7 @@ int view_rows_launch(RtxScene *scene, DeviceState &st, DeviceGeometry &g, const 
         RTX_TRY(before());
         RTX_TRY(aim_at(scene, g, v.eye, stream));
         return lit ? light_launch(scene, st, *lit, true, stream, table, n_pairs) : RTX_OK;
-    }, rtx::ProbeSplit{nullptr, 0u, 0u, 0u}, d_shade);
+    }, rtx::ProbeSplit{nullptr, 0u, 0u, 0u}, d_shade, mask);
 }
 
 // What a pipeline view with rows is checked for on the host, before a device is looked for: the eye in range, and with a
@@ -1624,8 +1636,10 @@ int rows_mean_margins(const RtxScene *scene, const MeanCall &call, std::vector<f
 
 // What renders a frame of a mean call into the scratch records: the view kernel as it is; the masked view kernel, which
 // skips the tiles the sums' rule has stopped (it reads the sums' tile states: moments only); or the pipeline's record
-// launch (full width, a shaft margin per frame: rows_mean_margins).
-enum class Renderer { kView, kMasked, kRows };
+// launch (full width, a shaft margin per frame: rows_mean_margins); or that launch behind the sums' tile states (a first
+// frame: the unmasked one), which does not schedule the stopped tiles.
+enum class Renderer { kView, kMasked, kRows, kRowsMasked };
+bool through_pipeline(Renderer renderer) { return renderer == Renderer::kRows || renderer == Renderer::kRowsMasked; }
 
 // What a frame's records are summed into and resolved from.  rule == NULL: the plain sum (rtx_accum.hip), d_state one
 // 16-byte accumulator per pixel.  Else the moments (rtx_adapt.hip): d_state 32-byte moments, d_tiles a state per 8 x 8 tile;
@@ -1682,12 +1696,12 @@ struct Sums {
 // renderer into the scratch records — its argument block's table, table length and light fields are what differs from the
 // twin's — and the add.  Then the resolve, where an output is asked for.  The pipeline launch puts the first two on the
 // stream itself, once its buffers stand; its aim kernels run once, there is one eye.  The scene's own table and light
-// arrays are neither read nor written.  margins: kRows only.  Caller holds the slot's lock and has the device current and
+// arrays are neither read nor written.  margins: the pipeline's renderers only.  Caller holds the slot's lock and has the device current and
 // the scene uploaded; the rectangle is not empty.
 int frames_launch(RtxScene *scene, DeviceState &st, const RtxView &view, const MeanCall &call, Renderer renderer, const float *margins,
                   const Sums &sums, void *d_rgb, void *d_shade, unsigned long long *d_counters, hipStream_t stream)
 {
-    const bool rows = renderer == Renderer::kRows;
+    const bool rows = through_pipeline(renderer);
     DeviceGeometry *geo;
     RTX_TRY(geometry_of(st, call.posed, &geo));
     RTX_TRY(reserve_mean(st, call.n_pairs, view.nx * view.ny));
@@ -1704,8 +1718,9 @@ int frames_launch(RtxScene *scene, DeviceState &st, const RtxView &view, const M
         const bool first = k == 0u && !sums.resume;
         const auto seed = [&] { return hip_rc(rtxr::launch_samples(call.seeds[k], call.n_pairs, st.mean.table.as<float2>(), stream)); };
         if (rows) {
+            const TileMask mask{sums.d_tiles, sums.rule ? *sums.rule : RtxAdaptRule{1u, 0.0f}};
             RTX_TRY(view_rows_launch(scene, st, *geo, view, nullptr, d_counters, stream, seed, &call.lit, margins[k], records, table,
-                                     call.n_pairs));
+                                     call.n_pairs, renderer == Renderer::kRowsMasked && !first ? &mask : nullptr));
         } else {
             RTX_TRY(seed());
             RTX_TRY(light_launch(scene, st, call.lit, false, stream, table, call.n_pairs));
@@ -1725,7 +1740,7 @@ int frames_launch(RtxScene *scene, DeviceState &st, const RtxView &view, const M
 // answers RTX_OK ahead of everything but the width: the caller returns its empty answer.
 int frames_refused(const RtxScene *scene, const RtxView *view, const MeanCall &call, Renderer renderer, std::vector<float> *margins)
 {
-    const bool rows = renderer == Renderer::kRows;
+    const bool rows = through_pipeline(renderer);
     if (rows && (view->x0 != 0u || view->nx != view->width)) return RTX_ERR_BAD_ARG;
     if (view->nx * view->ny == 0u) return RTX_OK;
     if (rows && !eye_in_pipeline_range(scene, view->eye)) return RTX_ERR_UNSUPPORTED;
@@ -1810,11 +1825,12 @@ int view_rows_host(RtxScene *scene, int device, const RtxView *view, const Lit *
 
 // ... the device-resident one into the caller's buffer on the caller's stream, nothing waited for
 int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit *lit, bool posed, void *d_rgb, size_t d_bytes,
-                     void *stream, uint64_t *d_counters, bool records = false)
+                     void *stream, uint64_t *d_counters, bool records = false, const TileMask *mask = nullptr)
 {
     if (!view_rows_args_ok(scene, view, d_rgb)) return RTX_ERR_BAD_ARG;
     if (records && reinterpret_cast<uintptr_t>(d_rgb) % sizeof(RtxPixelShade) != 0u) return RTX_ERR_BAD_ARG;
     if (d_bytes < static_cast<size_t>(view->ny) * view->width * (records ? sizeof(RtxPixelShade) : 3u)) return RTX_ERR_BAD_ARG;
+    if (mask && (!records || !mask->d_tiles || (reinterpret_cast<uintptr_t>(mask->d_tiles) & 7u))) return RTX_ERR_BAD_ARG;
     if (view->ny == 0u) return RTX_OK;
     float shaft_delta = 0.0f;
     RTX_TRY(view_rows_supported(scene, view, lit, &shaft_delta));
@@ -1824,7 +1840,7 @@ int view_rows_device(RtxScene *scene, int device, const RtxView *view, const Lit
     RTX_TRY(geometry_of(e.state(), posed, &geo));
     RTX_TRY(view_rows_launch(scene, e.state(), *geo, *view, static_cast<uint8_t *>(d_rgb), reinterpret_cast<unsigned long long *>(d_counters),
                              static_cast<hipStream_t>(stream), [] { return static_cast<int>(RTX_OK); }, lit, shaft_delta,
-                             records ? d_rgb : nullptr));
+                             records ? d_rgb : nullptr, nullptr, 0u, mask));
     return mark_uses(e.state(), uses_of(lit, posed), static_cast<hipStream_t>(stream));
 }
 
@@ -3012,6 +3028,18 @@ int rtx_render_view_rows_shade_device(RtxScene *scene, int device, const RtxView
                 : RTX_ERR_BAD_ARG;
 }
 
+// The pipeline's records behind a tile mask: rtx_render_view_rows_shade_device with the states and the rule as arguments.
+int rtx_render_view_rows_shade_masked_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                             const void *d_tiles, const RtxAdaptRule *rule, void *d_shade, size_t d_bytes, void *stream,
+                                             uint64_t *d_counters)
+{
+    if (flags & ~RTX_ROWS_POSED) return RTX_ERR_BAD_ARG;
+    const CallLight l(scene, light, CallLight::kOptional);
+    if (!l.ok || !d_tiles || (reinterpret_cast<uintptr_t>(d_tiles) & 7u) || !rtx::adapt_rule_ok(rule)) return RTX_ERR_BAD_ARG;
+    const TileMask mask{d_tiles, *rule};
+    return view_rows_device(scene, device, view, l.lit, (flags & RTX_ROWS_POSED) != 0u, d_shade, d_bytes, stream, d_counters, true, &mask);
+}
+
 int rtx_render_view_rows_mean(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
                               const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, uint8_t *out_rgb, RtxPixelShade *out_shade,
                               RtxStats *stats)
@@ -3030,6 +3058,30 @@ int rtx_render_view_rows_mean_device(RtxScene *scene, int device, const RtxView 
     if (!d_accum || !aligned16(d_accum, d_shade)) return RTX_ERR_BAD_ARG;
     if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, d_accum, &call)) return RTX_ERR_BAD_ARG;
     return frames_device(scene, device, view, call, Renderer::kRows, Sums{nullptr, false, d_accum, nullptr}, d_rgb, d_shade, stream);
+}
+
+// The adaptive mean through the pipeline: rtx_render_view_adaptive's checks, then the pipeline's (frames_refused).
+int rtx_render_view_rows_adaptive(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                  const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, const RtxAdaptRule *rule, uint8_t *out_rgb,
+                                  RtxPixelShade *out_shade, RtxTileState *out_tiles, RtxStats *stats)
+{
+    MeanCall call;
+    const void *out = out_rgb ? static_cast<const void *>(out_rgb) : out_shade;
+    if (!rtx::adapt_rule_ok(rule)) return RTX_ERR_BAD_ARG;
+    if (!mean_args_ok(scene, view, light, flags, seeds, n_frames, n_pairs, out, &call)) return RTX_ERR_BAD_ARG;
+    return frames_host(scene, device, view, call, Renderer::kRowsMasked, rule, out_rgb, out_shade, out_tiles, stats);
+}
+
+int rtx_render_view_rows_adaptive_device(RtxScene *scene, int device, const RtxView *view, const RtxLight *light, uint32_t flags,
+                                         const uint64_t *seeds, uint32_t n_frames, uint32_t n_pairs, const RtxAdaptRule *rule,
+                                         void *d_moments, void *d_tiles, void *d_rgb, void *d_shade, void *stream)
+{
+    MeanCall call;
+    if (!rtx::adapt_rule_ok(rule) || !d_moments || !d_tiles || !aligned16(d_moments, d_shade) || (reinterpret_cast<uintptr_t>(d_tiles) & 7u))
+        return RTX_ERR_BAD_ARG;
+    if (!mean_args_ok(scene, view, light, flags & ~RTX_ADAPT_CONTINUE, seeds, n_frames, n_pairs, d_moments, &call)) return RTX_ERR_BAD_ARG;
+    return frames_device(scene, device, view, call, Renderer::kRowsMasked, Sums{rule, (flags & RTX_ADAPT_CONTINUE) != 0u, d_moments, d_tiles},
+                         d_rgb, d_shade, stream);
 }
 
 int rtx_scene_light_walk_seeded(const RtxScene *scene, const RtxLight *light, uint64_t seed, uint32_t n_pairs, uint32_t *out_order,

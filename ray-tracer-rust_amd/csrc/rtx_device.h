@@ -213,6 +213,14 @@ hipError_t launch_trace_shade(const DeviceScene &S, const TileSpec &ts, uint8_t 
 hipError_t launch_trace_records(const DeviceScene &S, const TileSpec &ts, void *d_shade, uint8_t *d_hits, uint32_t *d_redo,
                                 const StreamWorkspace *ws, unsigned long long *d_counters, uint32_t variant, hipStream_t stream,
                                 hipEvent_t *phase_events = nullptr, uint32_t launch_no = 0u, uint32_t pass_no = 0u);
+// The record launch behind the adaptive mean's tile mask (namespace rtxn: the scheduling pass's masked form): d_tiles holds an
+// RtxTileState per 8 x 8 tile of the launch's rows, row by row, 8-byte aligned, written by an earlier launch on the stream; a
+// tile that tile_stopped(rule, state) names is not scheduled and its records keep their words.  One band of rows (a view's
+// launch), so that the launch's tile rows are the rectangle's.
+hipError_t launch_trace_records_masked(const DeviceScene &S, const TileSpec &ts, void *d_shade, uint8_t *d_hits, uint32_t *d_redo,
+                                       const StreamWorkspace *ws, unsigned long long *d_counters, uint32_t variant, hipStream_t stream,
+                                       hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no, const void *d_tiles,
+                                       const RtxAdaptRule &rule);
 size_t trace_record_hits_bytes(const DeviceScene &S, const TileSpec &ts);
 // Whether a launch's tiles are tiles of the frame, so that the scene's long list names them: the share starts on a tile
 // row, and every band of it but a single one is whole tile rows.  (Otherwise a tile of the launch straddles two of the frame.)

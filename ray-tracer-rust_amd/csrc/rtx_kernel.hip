@@ -6,7 +6,8 @@
 // rtx_pass_schedule.hpp (probe_kernel), rtx_pass_order.hpp (the counting and ordering kernels) and rtx_pass_shade.hpp
 // (shade_tiles_kernel), the timing instrumentation of tools/ in rtx_probes.hpp.  This file: reference_tiles_kernel, the
 // record forms of the three kernels that store a pixel (namespace rtxo; they share the byte forms'
-// bodies), the launcher, and the text that says what the library was built with.
+// bodies), the masked form of the scheduling pass (namespace rtxn: the record form behind the adaptive mean's tile mask), the
+// launcher, and the text that says what the library was built with.
 //
 // A launch (launch_probe, further down) is two passes over the 8x8-pixel tiles of its rows, four dispatches:
 //   scheduling pass   probe_kernel (one wavefront per tile, one work-item per pixel: primary ray, closest hit,
@@ -34,8 +35,8 @@
 // (x.powf(1/2.2)*255) as u8 with the host libm and the kernels count thresholds <= x.
 #include <cstdlib>
 #include <type_traits>
-#if defined(RTX_RECORD_FORMS)
-#error "RTX_RECORD_FORMS is not a build switch: this file sets it around its second inclusion of the two passes' headers"
+#if defined(RTX_RECORD_FORMS) || defined(RTX_MASKED_FORMS)
+#error "RTX_RECORD_FORMS and RTX_MASKED_FORMS are not build switches: this file sets them around its further inclusions of the passes' headers"
 #endif
 #include "rtx_traverse.hpp"
 // the passes, one file each (a kernel of a later one uses what the earlier ones define; one translation unit)
@@ -87,6 +88,22 @@ __global__ void __launch_bounds__(64) reference_records_kernel(DeviceScene S, Ti
 
 }  // namespace rtxo
 
+// The masked form of the scheduling pass (rtx_render_view_rows_adaptive, rtx_render_view_rows_shade_masked_device):
+// probe_records_kernel's text a third time, behind the adaptive mean's tile mask — a stopped tile is not scheduled, so the
+// shading pass and the reference pass are rtxo's, unchanged.  A top-level namespace of its own: every other kernel set keeps
+// its symbols.
+namespace rtxn {
+
+using namespace rtx;
+
+#define RTX_RECORD_FORMS 1
+#define RTX_MASKED_FORMS 1      // probe_masked_kernel
+#include "rtx_pass_schedule.hpp"
+#undef RTX_MASKED_FORMS
+#undef RTX_RECORD_FORMS
+
+}  // namespace rtxn
+
 namespace rtx {
 
 
@@ -118,7 +135,19 @@ float split_share()
 #endif
 }
 
-// OUT: uint8_t * (the byte forms) or RecordOut (the record forms, rtxo)
+// The record output behind the adaptive mean's tile mask: rtxn::probe_masked_kernel's three further arguments
+struct MaskedOut {
+    RecordOut records;
+    const RtxTileState *tiles;       // one per 8 x 8 tile of the rectangle, row by row; 8-byte aligned
+    uint32_t min_frames;
+    float max_variance;
+};
+inline uint8_t *records_of(uint8_t *out) { return out; }
+inline RecordOut records_of(const RecordOut &out) { return out; }
+inline RecordOut records_of(const MaskedOut &out) { return out.records; }
+
+// OUT: uint8_t * (the byte forms), RecordOut (the record forms, rtxo) or MaskedOut (the record forms, their scheduling pass
+// masked: rtxn)
 template <bool COUNT, bool FAST, bool SPHERES, class OUT>
 hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, OUT d_out, uint32_t *d_redo,
                         const StreamWorkspace &W, unsigned long long *d_counters, hipStream_t stream, hipEvent_t *ev,
@@ -130,7 +159,9 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, OUT d_out, uin
     constexpr int NW = RTX_SHADE_NW;     // wavefronts per workgroup of shade_tiles_kernel
     // the form of the two kernels that have two: per-tile cuts, or — a scene too large for them — the whole stream
     const bool whole = S.n_nodes > S.cut_max_nodes;
-    constexpr bool kRecords = std::is_same<OUT, RecordOut>::value;
+    constexpr bool kMasked = std::is_same<OUT, MaskedOut>::value;
+    constexpr bool kRecords = std::is_same<OUT, RecordOut>::value || kMasked;
+    const auto d_rec = records_of(d_out);     // (the byte forms: d_out itself)
     const auto shade_bytes = whole ? shade_tiles_kernel<COUNT, FAST, NW, SPHERES, true> : shade_tiles_kernel<COUNT, FAST, NW, SPHERES, false>;
     const auto shade_records = whole ? rtxo::shade_records_kernel<COUNT, FAST, NW, SPHERES, true> : rtxo::shade_records_kernel<COUNT, FAST, NW, SPHERES, false>;
     const uint32_t batch = S.nb_light < kMaxLightBatch ? (S.nb_light ? S.nb_light : 1u) : kMaxLightBatch;
@@ -148,9 +179,12 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, OUT d_out, uin
     const uint32_t probe_waves = split.n_long != 0u ? 4u : 1u;
     const uint32_t probe_grid = split.n_long != 0u ? ((split.n_long + 7u) & ~7u) + 128u * ((n_tiles + 511u) / 512u) : 512u * ((n_tiles + 511u) / 512u);
     if (kRecords && split.n_long != 0u) return hipErrorInvalidValue;     // (the record forms have no four-beam probe_kernel)
+    if constexpr (kMasked)
+        if (!d_out.tiles || (reinterpret_cast<uintptr_t>(d_out.tiles) & 7u)) return hipErrorInvalidValue;
     const auto probe = whole ? probe_kernel<COUNT, FAST, SPHERES, true, 1u>
                      : split.n_long != 0u ? probe_kernel<COUNT, FAST, SPHERES, false, 4u> : probe_kernel<COUNT, FAST, SPHERES, false, 1u>;
     const auto probe_records = whole ? rtxo::probe_records_kernel<COUNT, FAST, SPHERES, true> : rtxo::probe_records_kernel<COUNT, FAST, SPHERES, false>;
+    const auto probe_masked = whole ? rtxn::probe_masked_kernel<COUNT, FAST, SPHERES, true> : rtxn::probe_masked_kernel<COUNT, FAST, SPHERES, false>;
     // persistent grid = what the device keeps resident of the form that is launched (the cut and whole-stream forms differ in
     // registers, and so may the byte and record forms: each instantiation of this launcher — one per OUT — has its own cache)
     static thread_local int cached_dev = -1, cached_blocks = 0;
@@ -180,9 +214,13 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, OUT d_out, uin
         // one that only counts (the table in front of kOrderList)
         const uint32_t hist_set = (pass_no + r) & 1u;
         const StreamWorkspace Wp = counting_set(W, hist_set);      // what the kernels that count are handed
-        if constexpr (kRecords)
+        if constexpr (kMasked)
+            hipLaunchKernelGGL(probe_masked, dim3(probe_grid), dim3(64), 0, stream,
+                               S, ts, tiles_x, n_tiles, r, Wp, d_rec.shade, d_rec.hits, queue, d_counters, d_out.tiles, d_out.min_frames,
+                               d_out.max_variance);
+        else if constexpr (kRecords)
             hipLaunchKernelGGL(probe_records, dim3(probe_grid), dim3(64), 0, stream,
-                               S, ts, tiles_x, n_tiles, r, Wp, d_out.shade, d_out.hits, queue, d_counters);
+                               S, ts, tiles_x, n_tiles, r, Wp, d_rec.shade, d_rec.hits, queue, d_counters);
         else
             hipLaunchKernelGGL(probe, dim3(probe_grid), dim3(64 * probe_waves), 0, stream,
                                S, ts, tiles_x, n_tiles, r, Wp, d_out, queue, d_counters, split);
@@ -192,14 +230,14 @@ hipError_t launch_probe(const DeviceScene &S, const TileSpec &ts, OUT d_out, uin
         if (ev && r == 0u && (e = hipEventRecord(ev[1], stream)) != hipSuccess) return e;   // end of the scheduling pass
         if constexpr (kRecords)
             hipLaunchKernelGGL(shade_records, dim3(grid), dim3(64 * NW), lds_bytes, stream, S, ts, batch, tiles_x, n_tiles, r, W,
-                               d_out.shade, d_out.hits, queue, d_counters);
+                               d_rec.shade, d_rec.hits, queue, d_counters);
         else
             hipLaunchKernelGGL(shade_bytes, dim3(grid), dim3(64 * NW), lds_bytes, stream, S, ts, batch, tiles_x, n_tiles, r, W, d_out, queue, d_counters);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if constexpr (kRecords)
         hipLaunchKernelGGL((rtxo::reference_records_kernel<COUNT, SPHERES>), dim3(n_tiles < 1024u ? n_tiles : 1024u), dim3(64), 0, stream,
-                           S, ts, tiles_x, d_out.shade, queue, d_counters);
+                           S, ts, tiles_x, d_rec.shade, queue, d_counters);
     else
         hipLaunchKernelGGL((reference_tiles_kernel<COUNT, SPHERES>), dim3(n_tiles < 1024u ? n_tiles : 1024u), dim3(64), 0, stream,
                            S, ts, tiles_x, d_out, queue, d_counters, true);
@@ -261,7 +299,7 @@ static hipError_t launch_dispatch(const DeviceScene &S, const TileSpec &ts, OUT 
     };
 #if RTX_ABLATION
     if (!((variant & kVariantProbe) && ws && !d_wave_prof)) {
-        if constexpr (std::is_same<OUT, RecordOut>::value) return hipErrorInvalidValue;   // (records: the two-pass pipeline's alone)
+        if constexpr (!std::is_same<OUT, uint8_t *>::value) return hipErrorInvalidValue;   // (records: the two-pass pipeline's alone)
         else return launch_dispatch_ablation(S, ts, d_out, d_redo, ws, d_counters, d_wave_prof, variant, stream);
     }
     if (!(variant & 1u)) return two_pass(std::false_type{});   // with the exact (division-based) box test on inner nodes
@@ -303,6 +341,19 @@ hipError_t launch_trace_records(const DeviceScene &S, const TileSpec &ts, void *
     if (!ws || !d_shade || (S.nb_ray > 1u && !d_hits)) return hipErrorInvalidValue;
     return launch_any(S, ts, RecordOut{static_cast<uint4 *>(d_shade), d_hits}, d_redo, ws, d_counters, nullptr, variant, stream,
                       phase_events, launch_no, pass_no, ProbeSplit{nullptr, 0u, 0u, 0u});
+}
+
+hipError_t launch_trace_records_masked(const DeviceScene &S, const TileSpec &ts, void *d_shade, uint8_t *d_hits, uint32_t *d_redo,
+                                       const StreamWorkspace *ws, unsigned long long *d_counters, uint32_t variant, hipStream_t stream,
+                                       hipEvent_t *phase_events, uint32_t launch_no, uint32_t pass_no, const void *d_tiles,
+                                       const RtxAdaptRule &rule)
+{
+    if (!ws || !d_shade || (S.nb_ray > 1u && !d_hits) || !d_tiles || (reinterpret_cast<uintptr_t>(d_tiles) & 7u)) return hipErrorInvalidValue;
+    if (ts.first_row + ts.local_rows > S.height || ts.tile_rows != ts.local_rows) return hipErrorInvalidValue;   // one band: a view's rows
+    const MaskedOut out{RecordOut{static_cast<uint4 *>(d_shade), d_hits}, static_cast<const RtxTileState *>(d_tiles), rule.min_frames,
+                        rule.max_variance};
+    return launch_any(S, ts, out, d_redo, ws, d_counters, nullptr, variant, stream, phase_events, launch_no, pass_no,
+                      ProbeSplit{nullptr, 0u, 0u, 0u});
 }
 
 size_t trace_record_hits_bytes(const DeviceScene &S, const TileSpec &ts)

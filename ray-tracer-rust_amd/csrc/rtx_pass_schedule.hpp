@@ -6,6 +6,12 @@
 // alone is compiled once more, as rtxo::probe_records_kernel — the same body with `out` a RecordOut (rtx_pass_helpers.hpp) and
 // one wavefront per tile (a view's launch has no long list).  The sky store is the one statement that differs, through
 // store_pixel's overloads.  (Why text compiled twice and not a __device__ template: rtx_pass_shade.hpp.)
+//
+// ... and a third time, inside namespace rtxn with RTX_MASKED_FORMS defined beside RTX_RECORD_FORMS: the record form behind the
+// adaptive mean's tile mask, rtxn::probe_masked_kernel.  Once the wavefront knows its tile it reads the tile's 8-byte state
+// (RtxTileState, numbered row by row over the rectangle: NOT tile_id, which is swizzled), makes the two words scalars and
+// evaluates scene_prep.h's tile_stopped: a stopped tile gets a descriptor that schedules nothing and the wavefront returns;
+// a live tile runs the record form's body, token for token.
 #if !defined(RTX_PASS_SCHEDULE_HPP) || defined(RTX_RECORD_FORMS)
 #if !defined(RTX_RECORD_FORMS)
 #define RTX_PASS_SCHEDULE_HPP
@@ -283,10 +289,18 @@ __global__ void __launch_bounds__(64 * WAVES, RTX_PROBE_WAVES_PER_SIMD) probe_ke
                                                    ProbeSplit split)
 {
 #else
+#if defined(RTX_MASKED_FORMS)
+template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE>
+__global__ void __launch_bounds__(64, RTX_PROBE_WAVES_PER_SIMD) probe_masked_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
+                                                   uint32_t r, StreamWorkspace W, uint4 *__restrict__ out_shade, uint8_t *__restrict__ out_hits,
+                                                   uint32_t *__restrict__ queue, unsigned long long *__restrict__ counters,
+                                                   const RtxTileState *__restrict__ tile_states, uint32_t min_frames, float max_variance)
+#else
 template <bool COUNT, bool FAST, bool SPHERES, bool WHOLE>
 __global__ void __launch_bounds__(64, RTX_PROBE_WAVES_PER_SIMD) probe_records_kernel(DeviceScene S, TileSpec ts, uint32_t tiles_x, uint32_t n_tiles,
                                                    uint32_t r, StreamWorkspace W, uint4 *__restrict__ out_shade, uint8_t *__restrict__ out_hits,
                                                    uint32_t *__restrict__ queue, unsigned long long *__restrict__ counters)
+#endif
 {
     // one wavefront per tile.  (Value-dependent, as probe_kernel's parameter is: the four-beam statements of the body, which
     // this form never runs, index arrays of WAVES entries and are then not diagnosed at their definition.)
@@ -359,6 +373,23 @@ __global__ void __launch_bounds__(64, RTX_PROBE_WAVES_PER_SIMD) probe_records_ke
             }
         }
     }
+#if defined(RTX_MASKED_FORMS)
+    // The mask.  A tile of the rectangle (the padding of the numbering's blocks has no state and no pixel: it goes on and ends
+    // as a tile without a hit) reads its state by its ROW-MAJOR number — a view's launch is TileSpec{y0, ny, ny, ny}, so the
+    // local tile rows are the rectangle's — as two scalars, the states being an earlier launch's words.  Stopped: a descriptor
+    // that schedules nothing (no class, no hits, no redo flag, nothing counted) and the wavefront leaves — no ray, no walk,
+    // no pixel, no word of acc or hits, no histogram add, no queue entry, no counter; the same in every pass of a frame.
+    if (tile_x < tiles_x && tile_y * 8u < ts.local_rows) {
+        const uint2 w = *reinterpret_cast<const uint2 *>(tile_states + (tile_y * tiles_x + tile_x));
+        RtxTileState state;
+        state.frames = __builtin_amdgcn_readfirstlane(w.x);
+        state.err = __uint_as_float(__builtin_amdgcn_readfirstlane(w.y));
+        if (tile_stopped(RtxAdaptRule{min_frames, max_variance}, state)) {
+            if (lane == 0) W.tiles[tile_id] = TileDesc{kNone, 0u, 0u, 0u};
+            return;
+        }
+    }
+#endif
     uint32_t px, py, ly;
     const bool in_frame = tile_pixel(S, ts, tile_x, tile_y, lane, px, py, ly);
     WaveCounters wc;

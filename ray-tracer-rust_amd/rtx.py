@@ -321,6 +321,15 @@ _SIGS = {
                                             C.c_uint32, C.c_void_p, C.POINTER(PixelShade), C.POINTER(Stats)]),
     "rtx_render_view_rows_mean_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
                                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtx_render_view_rows_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
+                                                C.c_uint32, C.c_uint32, C.POINTER(AdaptRule), C.c_void_p, C.POINTER(PixelShade),
+                                                C.POINTER(TileState), C.POINTER(Stats)]),
+    "rtx_render_view_rows_adaptive_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32, u64p,
+                                                       C.c_uint32, C.c_uint32, C.POINTER(AdaptRule), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]),
+    "rtx_render_view_rows_shade_masked_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RtxView), C.POINTER(RtxLight), C.c_uint32,
+                                                           C.c_void_p, C.POINTER(AdaptRule), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                           C.c_void_p]),
     "rtx_scene_light_walk_seeded": (C.c_int, [C.c_void_p, C.POINTER(RtxLight), C.c_uint64, C.c_uint32, u32p, f32p, f32p]),
     "rtx_debug_wave_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u32p, u32p]),
     "rtx_launch_timings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p, f32p]),
@@ -1446,6 +1455,36 @@ class Scene:
         flags = (MEAN_POSED if posed else 0) | (ADAPT_CONTINUE if resume else 0)
         self._mean_call("rtx_render_view_adaptive_device", device, view, light, flags, seeds, n_pairs, rule=rule,
                         tail=(d_moments_ptr, d_tiles_ptr, d_rgb_ptr, d_shade_ptr, stream))
+
+    # -- the adaptive mean through the render pipeline: a stopped tile is not scheduled (full width only, the same words)
+    def render_view_rows_adaptive(self, view, seeds, rule, n_pairs=NB_RAND_SAMPLE, device=0, light=None, posed=False, stats=False,
+                                  want_shade=False, want_tiles=False):
+        """render_view_adaptive through the render pipeline (rtx_render_view_rows_adaptive): the view's full-width rows, the
+        pipeline's record launch behind the tile states in the masked view kernel's place; every output is
+        render_view_adaptive's, word for word."""
+        return self._mean_call("rtx_render_view_rows_adaptive", device, view, light, MEAN_POSED if posed else 0, seeds, n_pairs,
+                               rule=rule, want=(want_shade, want_tiles, stats))
+
+    def render_view_rows_adaptive_device(self, device, view, seeds, rule, n_pairs, d_moments_ptr, d_tiles_ptr, d_rgb_ptr=None,
+                                         d_shade_ptr=None, stream=None, light=None, posed=False, resume=False):
+        """Asynchronous: render_view_adaptive_device through the render pipeline (rtx_render_view_rows_adaptive_device), the
+        same buffers and the same words."""
+        flags = (MEAN_POSED if posed else 0) | (ADAPT_CONTINUE if resume else 0)
+        self._mean_call("rtx_render_view_rows_adaptive_device", device, view, light, flags, seeds, n_pairs, rule=rule,
+                        tail=(d_moments_ptr, d_tiles_ptr, d_rgb_ptr, d_shade_ptr, stream))
+
+    def render_view_rows_shade_masked_device(self, device, view, d_tiles_ptr, rule, d_shade_ptr, d_bytes, stream=None,
+                                             d_counters_ptr=None, light=None, posed=False):
+        """Asynchronous: render_view_rows_shade_device behind a tile mask (rtx_render_view_rows_shade_masked_device) — d_tiles_ptr:
+        tiles_y*tiles_x x 8 bytes of tile states (8-byte aligned); a tile stopped under `rule` is not scheduled and its
+        records in d_shade keep their words, a live tile's records are the unmasked launch's."""
+        r = AdaptRule(int(rule[0]), float(rule[1])) if rule is not None else None
+        _check(_lib.rtx_render_view_rows_shade_masked_device(self._h, device, C.byref(view), C.byref(light) if light is not None else None,
+                                                             ROWS_POSED if posed else 0, C.c_void_p(d_tiles_ptr) if d_tiles_ptr else None,
+                                                             C.byref(r) if r is not None else None, C.c_void_p(d_shade_ptr), d_bytes,
+                                                             C.c_void_p(stream) if stream else None,
+                                                             C.c_void_p(d_counters_ptr) if d_counters_ptr else None),
+               "rtx_render_view_rows_shade_masked_device")
 
     def moment_add_device(self, device, nx, ny, d_shade_ptr, d_moments_ptr, d_tiles_ptr, first, rule=None, stream=None):
         """Asynchronous: adds the nx x ny RtxPixelShade records of a rectangle — of any call that writes them — into its moment
